@@ -2,7 +2,7 @@
 """bench.py -- Mreads/s of HARC reorder+encode (100 bp) on 1/2/4/8 MI355X, with the roofline of the dominant kernel and
 the reference's CPU path timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1|c2r|c2d|mini ...] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1|c2r|c2d|mini ...] [--dump-outputs DIR] [--full [--no-cpu]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one pass of the hot path over the synthetic batch: index build + chaining (reorder.cpp:277-703) + encoding
@@ -12,6 +12,12 @@ N>1: every rank owns a batch of the same size drawn from a genome N times larger
 are sharded by a canonical-minimizer bucket with ONE all-to-all over xGMI -- harc_amd_shard_exchange: RCCL send/recv inside
 libharc_amd.so, packed read + u32 global id per read -- then each GPU chains and encodes its shard independently
 (BASELINE.json north_star; DESIGN.md "Multi-GPU").  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step, with the
+chain kernel's roofline from the counters of the timed steps).  Everything else it can measure or check -- the round trip of the last step's
+streams, the reference's CPU baseline, exact mode, the compressed size against the reference, the other BASELINE configurations, the
+end-to-end leg and the N>1 side legs -- runs only with --full (which --no-cpu / --no-other-configs / --no-side-legs then trim as before).
+--dump-outputs DIR writes the streams of the last timed step as .npy files (see dump_outputs).
 """
 import argparse
 import json
@@ -338,10 +344,11 @@ def scale_spike(spike, f):
     return out
 
 
-def install_synthetic(h, n, L, G, err, seed, dev, spike=None):
+def install_synthetic(h, n, L, G, err, seed, dev, spike=None, signature=True):
     """the synthetic workload -> the context h, 4 M reads at a time so that config-3/4-sized sets never exist as ASCII: clean reads are
     packed to 2 bits per base (k_pack2) as they are made, reads with N are kept as text for stage II.  Returns the order-independent
-    signature [count, sum, xor of 64-bit read hashes] of all reads, taken on the way (for the round-trip check after a run)."""
+    signature [count, sum, xor of 64-bit read hashes] of all reads, taken on the way (for the round-trip check after a run; [0, 0, 0]
+    with signature=False)."""
     _need_torch()
     Wd = (2 * L + 63) // 64
     packed = torch.empty((n, Wd), dtype=torch.int64, device=dev)
@@ -349,6 +356,8 @@ def install_synthetic(h, n, L, G, err, seed, dev, spike=None):
     sig = [0, 0, 0]
 
     def acc(t):
+        if not signature:
+            return
         c3 = h.reads_signature_device(t.data_ptr(), t.shape[0], L)
         sig[0] += c3[0]; sig[1] = (sig[1] + c3[1]) % (1 << 64); sig[2] ^= c3[2]
     for r in synth_chunks(n, L, G, err, seed, dev, spike):
@@ -468,6 +477,63 @@ def stage2_blobs(h, shards):
     for sid in ("S2_SINGLETON", "S2_SINGLETON_TAIL", "S2_INPUT_N", "S2_META"):
         out.append(h.stream(sid))
     return out
+
+
+DUMP_BUDGET = 48 << 20     # bytes of sampled stream elements written by --dump-outputs (float64 at most: the files stay below 64 MB)
+
+
+def dump_stream_names(shards, with_pack_order):
+    """(stream id, shard, file stem) of every stream --dump-outputs writes, in the order of the rows of streams.npy"""
+    names = [(sid, e, f"{sid}_{e}") for e in range(shards) for sid in ("S2_SEQ", "S2_SEQ_TAIL", "S2_POS", "S2_NOISE", "S2_NOISEPOS", "S2_REV", "S2_REV_TAIL")]
+    names += [(sid, 0, sid) for sid in ("S2_ORDER", "S2_ORDER_N_PE", "S2_SINGLETON", "S2_SINGLETON_TAIL", "S2_INPUT_N", "S2_META")]
+    if with_pack_order:
+        names += [(sid, 0, sid) for sid in ("P_ORDER", "P_ORDER_TAIL")]
+    return names
+
+
+def dump_outputs(harc_amd, h, shards, with_pack_order, d):
+    """--dump-outputs: what the last timed step handed its caller -- the stage-II streams in host memory (and the packed order with -p) --
+    as d/<stream>.npy (d/<stream>_<shard>.npy for the per-shard ones).  Bytes as float32; read_order.bin and read_order_N_pe.bin as u32
+    values in float64.  A stream of more than `per` elements is sampled: `per` positions, one drawn in each of `per` equal strides by a
+    generator seeded with the crc32 of the file stem, so that two builds given the same arguments write the same positions.  An empty stream
+    (no reads with N on an error-free workload, no noise positions, ...) gets no file.  d/streams.npy (float64, one row per stream, empty
+    ones included, in the order of dump_stream_names) holds the byte length and the crc32 of every WHOLE stream.  With N GPUs, rank 0
+    writes the streams of its own shard only."""
+    import ctypes as C
+    import zlib
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    names = dump_stream_names(shards, with_pack_order)
+    per = min(1 << 17, DUMP_BUDGET // (8 * len(names)))
+    os.makedirs(d, exist_ok=True)
+    # the library is called from this thread only (one context per host thread: the first request of a stream may copy it to the host);
+    # the pool below works on the host memory the calls returned, which stays valid until the context's next reorder / encode
+    views = []
+    for sid, e, fname in names:
+        ptr, ln = C.c_void_p(), C.c_size_t()
+        rc = harc_amd.lib().harc_amd_get_stream(h._ctx, harc_amd.STREAMS[sid], e, C.byref(ptr), C.byref(ln))
+        if rc != 0:
+            raise harc_amd.HarcAmdError(rc, f"harc_amd_get_stream({sid}, {e})")
+        raw = np.ctypeslib.as_array((C.c_uint8 * ln.value).from_address(ptr.value)) if ln.value else np.zeros(0, np.uint8)   # library-owned, not copied
+        views.append((sid, fname, raw))
+
+    def one(item):
+        sid, fname, raw = item
+        as_u32 = sid in ("S2_ORDER", "S2_ORDER_N_PE") and raw.shape[0] % 4 == 0
+        a = raw.view(np.uint32) if as_u32 else raw
+        if a.shape[0] > per:
+            rng = np.random.default_rng(zlib.crc32(fname.encode()))
+            stride = a.shape[0] // per
+            a = a[np.arange(per, dtype=np.int64) * stride + rng.integers(0, stride, per)]
+        path = os.path.join(d, fname + ".npy")
+        if a.shape[0]:
+            np.save(path, a.astype(np.float64 if as_u32 else np.float32))
+        elif os.path.exists(path):
+            os.remove(path)                                       # left by an earlier dump into the same directory
+        return [float(raw.shape[0]), float(zlib.crc32(raw))]
+    with ThreadPoolExecutor(8) as ex:                             # numpy and zlib.crc32 only (they let go of the GIL): the large streams side by side
+        rows = list(ex.map(one, views))
+    np.save(os.path.join(d, "streams.npy"), np.array(rows, dtype=np.float64))
 
 
 L2_PEAK_GBS = 34500.0     # MI355X_MICROARCH.md "L2 (per XCD)": 8 x 4 MiB, ~34.5 TB/s aggregate
@@ -626,12 +692,15 @@ def main():
     ap.add_argument("--chains", type=int, default=0)
     ap.add_argument("--super-steps", type=int, default=0, help="steps per super-round (num_steps; 0 = the library's choice: 16; 64 for one chain; 32 from 16 385 chains on, and from 2048 chains on inputs that are not low-coverage ones, where the index holds next to no large bins)")
     ap.add_argument("--shards", type=int, default=8, help="num_thr of the reference = encoder shards per GPU (harc:195 default 8)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU legs (reference baseline, size comparison) and the exact-mode sample")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run what the headline does not need: the round trip of the last step's streams, "
+                                                         "the CPU legs, the other BASELINE configurations, the end-to-end leg (default workload) and the N>1 side legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the streams of the last timed step to DIR/*.npy (a fixed sample of the large ones; with N GPUs rank 0's shard only; see dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU legs (reference baseline, size comparison) and the exact-mode sample")
     ap.add_argument("--no-prime", action="store_true", help="with --warmup 0: do NOT make the untimed pass that allocates the context's device pool and pinned buffers (the first timed step then pays for them: cold-start numbers)")
-    ap.add_argument("--no-side-legs", action="store_true", help="N>1: skip rank 0's GPU side legs after the timed region (n1_equivalent, size_vs_1gpu) -- the peers wait for them in the final barrier")
+    ap.add_argument("--no-side-legs", action="store_true", help="with --full, N>1: skip rank 0's GPU side legs after the timed region (n1_equivalent, size_vs_1gpu) -- the peers wait for them in the final barrier")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the bucket exchange even at world size 1 (exercises the N>1 path on one GPU)")
     ap.add_argument("--cpu-sample", type=int, default=0)
-    ap.add_argument("--no-other-configs", action="store_true", help="default workload on one GPU: skip the side lines for configs[2] with repeats (c3r, 1 timed step), configs[3] (c4) and configs[4]'s share (c5g), 2 timed steps each, after the main line's timed region")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full, default workload on one GPU: skip the side lines for configs[2] with repeats (c3r, 1 timed step), configs[3] (c4) and configs[4]'s share (c5g), 2 timed steps each, after the main line's timed region")
     ap.add_argument("--end-to-end", type=int, default=0, help="run the end-to-end leg (FASTQ file in /dev/shm -> stream files -> output.dna) on this many reads whatever the workload (default: 100 M reads with the default workload)")
     ap.add_argument("--mg-mode", default="bucket", choices=["bucket", "replicate"],
                     help="N>1: bucket = minimizer-bucket shard + one all-to-all, independent shards (north_star; larger archives); replicate = design (R): "
@@ -691,12 +760,13 @@ def main():
     p = harc_amd.default_params(L, num_thr=args.shards, num_chains=args.chains, device=local, profile=1, num_steps=args.super_steps, reads_per_chain=rpc)
     h = harc_amd.HarcAmd(p)
     Wd = (2 * L + 63) // 64
-    sig_in = install_synthetic(h, n, L, G * world, err, 1000 + rank, dev, spike)
+    sig_in = install_synthetic(h, n, L, G * world, err, 1000 + rank, dev, spike, signature=args.full)     # the input signature is for the round trip
     if dist is not None:
         from harc_amd import multigpu
         with wd.phase("communicator bootstrap", args.watchdog):
             multigpu.init_comm(h, dist, dev)                      # ncclUniqueId from the library, broadcast over the process group
-            sig_in = list(multigpu.allreduce_signature(dist, tuple(sig_in), dev))    # the whole job's reads, BEFORE any exchange
+            if args.full:
+                sig_in = list(multigpu.allreduce_signature(dist, tuple(sig_in), dev))    # the whole job's reads, BEFORE any exchange
     with_pack_order = args.workload in ("c5s", "c5g")
 
     replicate = dist is not None and args.mg_mode == "replicate"
@@ -751,24 +821,28 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
     c = h.counters()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(harc_amd, h, args.shards, with_pack_order, args.dump_outputs)
     # round trip at full size, outside the timed region: decode the streams of the last step on the GPU (decoder.cpp:90-169
     # restated in verify.hip) and compare the multiset signature (count, sum, xor of 64-bit read hashes) with the inputs'.  N GPUs:
     # the signatures of all ranks' INPUT slices (taken before the first exchange) against the signatures of all ranks' decoded
-    # shards -- a read lost, duplicated or altered anywhere between the slice and the streams (the all-to-all included) shows.
-    dsig = h.decode_signature()
+    # shards -- a read lost, duplicated or altered anywhere between the slice and the streams (the all-to-all included) shows.  --full only.
     seq_bases_total, reads_total = int(c.seq_bases), n
     s2_env = os.environ.get("HARC_AMD_S2_PART", "1")
     s2_part = (world > 1 and s2_env != "0") or (replicate and s2_env == "2")      # design (R): stage II partitioned over the ranks by encoder shard (the default from two ranks on; 2: also at world 1, so that its collectives run)
-    if replicate and not s2_part:
-        reads_total = n * world                                   # every rank decoded the WHOLE job: its signature alone must equal all ranks' inputs
-    elif dist is not None:
-        with wd.phase("round-trip signature", args.watchdog):
-            dsig = multigpu.allreduce_signature(dist, dsig, dev)
-            sb = torch.tensor([int(c.seq_bases)], dtype=torch.int64, device=dev)
-            dist.all_reduce(sb)
-            seq_bases_total, reads_total = int(sb.item()), n * world
-    roundtrip = {"ok": bool(tuple(dsig) == tuple(sig_in)), "reads_decoded": int(dsig[0]), "reads_in": int(sig_in[0]),
-                 "check": "multiset signature (count, sum, xor of 64-bit read hashes) of the GPU-decoded streams of all ranks == the input reads of all ranks"}
+    roundtrip = None
+    if args.full:
+        dsig = h.decode_signature()
+        if replicate and not s2_part:
+            reads_total = n * world                               # every rank decoded the WHOLE job: its signature alone must equal all ranks' inputs
+        elif dist is not None:
+            with wd.phase("round-trip signature", args.watchdog):
+                dsig = multigpu.allreduce_signature(dist, dsig, dev)
+                sb = torch.tensor([int(c.seq_bases)], dtype=torch.int64, device=dev)
+                dist.all_reduce(sb)
+                seq_bases_total, reads_total = int(sb.item()), n * world
+        roundtrip = {"ok": bool(tuple(dsig) == tuple(sig_in)), "reads_decoded": int(dsig[0]), "reads_in": int(sig_in[0]),
+                     "check": "multiset signature (count, sum, xor of 64-bit read hashes) of the GPU-decoded streams of all ranks == the input reads of all ranks"}
     total_reads = n * world * args.steps
     value = total_reads / dt / 1e6
 
@@ -838,17 +912,18 @@ def main():
         "roofline": roofline,
         "stage2_mode": ("partitioned by encoder shard over the ranks, one all-reduce(min) of the claims" if (replicate and s2_part) else "replicated on every rank" if replicate else "independent per shard" if dist is not None else "single GPU"),
         "build_id": harc_amd.build_id(),
-        "roundtrip": roundtrip,
         "phases_ms_last_step": {"index": round(c.index_ms, 2), "chain": round(c.chain_ms, 2), "encode": round(c.encode_ms, 2)},
         "counters_last_step": {"unmatched": int(c.unmatched), "singletons_aligned": int(c.aligned_singletons), "N_aligned": int(c.aligned_N),
                                "rounds": int(c.rounds), "conflicts": int(c.conflicts), "contigs": int(c.contigs),
                                "seq_bases": int(c.seq_bases), "device_bytes_peak": int(c.device_bytes_peak)},
     }
+    if roundtrip is not None:
+        out["roundtrip"] = roundtrip
     if dist is not None:
         # every N>1 line carries what ONE GPU does with its own batch, unsharded (no exchange, the single-GPU schedule): the N = 1 equivalent
         # measured in this very run on rank 0, outside the timed region
         out["per_gpu_value"] = round(value / world, 3)
-        if rank == 0 and not args.no_side_legs:
+        if rank == 0 and args.full and not args.no_side_legs:
             h.shard_reset()
             h.reorder(); h.encode()                               # warm-up at the unsharded size (pool growth)
             t1 = time.perf_counter()
@@ -861,7 +936,7 @@ def main():
     h.close()
     del h
     # ---- bounded side legs on rank 0 (outside the timed region): a sample of the same generator at the same coverage and error rate
-    if rank == 0 and (not args.no_cpu or (dist is not None and not args.no_side_legs)):
+    if rank == 0 and args.full and (not args.no_cpu or (dist is not None and not args.no_side_legs)):
         ns = args.cpu_sample or min(n, 3_300_000 if err > 0 or G // max(1, n) < 10 else 1_000_000)
         if isinstance(spike, dict):                               # the BASELINE-sized repeat workloads: a sample genome with the same SHARES of every kind of repeat
             ns = args.cpu_sample or 3_300_000
@@ -936,7 +1011,7 @@ def main():
     # ---- the other BASELINE configurations that fit one GPU, on the same line (outside the timed region, after the context of the main
     #      workload is gone): configs[3] on ONE GPU (c4: 810 M x 101 bp, 1 % errors) and one GPU's share of configs[4] (c5g: 500 M x 150 bp, 31 %
     #      of the reads with N, pack_order inside the step) -- one warm-up + 2 timed steps each, round trip checked on all reads; bounded in wall time
-    if rank == 0 and world == 1 and dist is None and args.workload == "c3" and not args.no_other_configs and not args.no_cpu:
+    if rank == 0 and world == 1 and dist is None and args.workload == "c3" and args.full and not args.no_other_configs and not args.no_cpu:
         out["other_configs"] = {}
         t_other = time.perf_counter()
         # (round 6: c3r first -- configs[2] on a genome with a human-like repeat content, the input shape of the real configs[1] / [3]; one warm-up + ONE timed
@@ -953,7 +1028,7 @@ def main():
             torch.cuda.empty_cache()
         out["other_configs"]["wall_s"] = round(time.perf_counter() - t_other, 1)
     # ---- end to end, FASTQ file -> stream files (and back), on the same line, outside the timed region
-    if rank == 0 and world == 1 and dist is None and ((args.workload == "c3" and not args.no_cpu and not args.no_other_configs) or args.end_to_end):
+    if rank == 0 and world == 1 and dist is None and ((args.workload == "c3" and args.full and not args.no_cpu and not args.no_other_configs) or args.end_to_end):
         t_e = time.perf_counter()
         try:
             out["end_to_end"] = end_to_end_leg(harc_amd, local, dev, args.shards, n=args.end_to_end or 100_000_000)

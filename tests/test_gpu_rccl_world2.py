@@ -36,7 +36,7 @@ needs2 = pytest.mark.skipif(_ngpu() < WORLD, reason="needs two GPUs (RCCL refuse
 @pytest.mark.parametrize("mode", ["bucket", "replicate"])
 def test_bench_two_gpus_round_trip(mode):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(WORLD), "--workload", "c3m", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-side-legs",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(WORLD), "--workload", "c3m", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-side-legs",
                         "--mg-mode", mode, "--launch-timeout", "600", "--watchdog", "240"] + (["--via-launcher", "--force-dist"] if WORLD == 1 else []), cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

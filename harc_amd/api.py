@@ -158,7 +158,7 @@ def compress_fastq(fastq, basedir, readlen, num_thr=1, num_chains=1, preserve_or
 
 
 def build_has(feature):
-    """True when the loaded library was built with the optional part `feature` ("grp", "test_transport", "experiments")"""
+    """True when the loaded library was built with the optional part `feature` ("test_transport", "experiments")"""
     return bool(lib().harc_amd_build_has(feature.encode()))
 
 

@@ -488,9 +488,6 @@ extern "C" const char *harc_amd_build_id(void) { return HARC_AMD_BUILD_ID; }
 extern "C" int harc_amd_build_has(const char *feature)
 {
     if (!feature) return 0;
-#ifdef HARC_AMD_WITH_GRP
-    if (!strcmp(feature, "grp")) return 1;
-#endif
 #ifdef HARC_AMD_TEST_TRANSPORT
     if (!strcmp(feature, "test_transport")) return 1;
 #endif

@@ -87,7 +87,7 @@ typedef struct harc_amd_counters {
     uint64_t probes;                  /* hash-table slots inspected by the chain kernel */
     uint64_t candidates;              /* candidate reads fetched + Hamming-tested by the chain kernel */
     uint64_t conflicts;               /* proposals that lost arbitration */
-    uint64_t propose_launches;        /* launches of the dominant kernel (k_propose) */
+    uint64_t propose_launches;        /* launches of k_steps' main form (the cooperative kernel not included) */
     double propose_ms;                /* sum of their HIP-event durations (params.profile=1), else 0 */
     double index_ms, chain_ms, encode_ms, total_ms;   /* host wall-clock of the phases, stream-synchronised */
     uint64_t contigs, seq_bases;      /* stage II */
@@ -234,8 +234,7 @@ int harc_amd_input_signature(harc_amd_ctx *ctx, uint64_t sig[3]);           /* o
 int harc_amd_stream_digest(harc_amd_ctx *ctx, uint64_t out[4]);
 /* sha256 (hex) of the kernel sources this library was built from: ties a committed profile (profiles/k_steps_traffic.json) to a build */
 const char *harc_amd_build_id(void);
-/* 1 when this library was built with the named optional part: "grp" (make GRP=1: k_steps_grp, the walk with several chains per wave), "test_transport"
- * (the file-mailbox transport of the one-GPU multi-rank tests), "experiments" (schedule constants from the environment); 0 otherwise */
+/* 1 when this library was built with the named optional part: "test_transport" (the file-mailbox transport of the one-GPU multi-rank tests), "experiments" (schedule constants from the environment); 0 otherwise */
 int harc_amd_build_has(const char *feature);
 /* Self-test of the library's launch geometry (one thread per item over n items through harc_gid / harc_gid32, and four lanes per item in folded workgroups, n beyond 2^32 included: a one-dimensional grid of 2^32 and more
  * work-items is cut short without an error on this platform).  *visited == n and *index_sum == n (n - 1) / 2 mod 2^64 when every item was visited once. */

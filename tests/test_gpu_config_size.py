@@ -37,18 +37,12 @@ def _synth_text(n, L, G, err, seed):
     ("configs1", 3_300_000, 100, 6_300_000, 0.005, 8, False, {}),
     # the kernels a 350 M-read run takes, forced at a size the oracle can follow: dense launch with the wave-uniform scan (8 waves per SIMD),
     # k_reseed by 64 workgroups -- with 3.3 M reads its later rounds need more than one pass of a million bitmap bits to find their seeds
-    ("configs1", 3_300_000, 100, 6_300_000, 0.005, 8, False, {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_RESEED_MG": "1"}),
+    ("configs1", 3_300_000, 100, 6_300_000, 0.005, 8, False, {"HARC_AMD_QUAD": "0", "HARC_AMD_SEQ": "1", "HARC_AMD_RESEED_MG": "1"}),
     # ... in its specialised form (SPEC: needs the bitmap lines by minimizer, which a 3.3 M-read bitmap gets only when told so)
-    ("configs1", 3_300_000, 100, 6_300_000, 0.005, 8, False, {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0"}),
-    # ... and with two chains per wave (k_steps_grp; HARC_AMD_GRP=2 fails the run if that kernel cannot be the one that walks)
-    ("configs1", 3_300_000, 100, 6_300_000, 0.005, 8, False, {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_GRP": "2"}),
-    ("configs0", 1_000_000, 100, 35_000_000, 0.0, 8, True, {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_GRP": "2", "HARC_AMD_RESEED_MG": "1"}),
-    ("configs1", 3_300_000, 100, 6_300_000, 0.005, 8, False, {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_GRP": "2", "HARC_AMD_GRP_WIDE": "1", "HARC_AMD_GRP_WIDE_LIMIT": "40"}),      # at 52x half of the chains are beyond 40 in some column
-    ("configs0", 1_000_000, 100, 35_000_000, 0.0, 8, True, {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_RESEED_MG": "1", "HARC_AMD_S1BLOOM_TILED": "1", "HARC_AMD_S1BLOOM_VERIFY": "1"})])
+    ("configs1", 3_300_000, 100, 6_300_000, 0.005, 8, False, {"HARC_AMD_QUAD": "0", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0"}),
+    ("configs0", 1_000_000, 100, 35_000_000, 0.0, 8, True, {"HARC_AMD_QUAD": "0", "HARC_AMD_RESEED_MG": "1", "HARC_AMD_S1BLOOM_TILED": "1", "HARC_AMD_S1BLOOM_VERIFY": "1"})])
 def test_config_size_matches_oracle(name, n, L, G, err, E, expect_lowcov, env, oracle, tmp_path, monkeypatch):
     import harc_amd
-    if "HARC_AMD_GRP" in env and not harc_amd.build_has("grp"):
-        pytest.skip("k_steps_grp is not in this build (make -C harc_amd/csrc GRP=1)")
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     (tmp_path / "g").mkdir()
@@ -94,9 +88,8 @@ def test_parity_fuzz_bounded(it, oracle, tmp_path, monkeypatch):
     import harc_amd
     if it % 2:
         monkeypatch.setenv("HARC_AMD_SUCC", "1")
-    if it % 3 == 0:      # ... and every third with the kernels of a large run forced, the walk by several chains per wave (k_steps_grp) where it can run (L >= 100, S <= 16)
-        for k, v in {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_GRP": "1", "HARC_AMD_GRP_WIDE": "1",
-                     "HARC_AMD_GRP_WIDE_LIMIT": str(3 + it)}.items():
+    if it % 3 == 0:      # ... and every third with the kernels of a large run forced
+        for k, v in {"HARC_AMD_QUAD": "0", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0"}.items():
             monkeypatch.setenv(k, v)
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import fuzz_parity as fz

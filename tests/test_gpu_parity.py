@@ -37,8 +37,6 @@ def assert_same(got, want, files, what):
 def test_stage1_K1_matches_reference(case, env, tmp_path, monkeypatch):
     """exact mode: by default through the successor lists (k_succ) and with k_resolve + k_reseed in one launch; without the lists; with two launches"""
     import harc_amd
-    if "HARC_AMD_GRP" in env and not harc_amd.build_has("grp"):
-        pytest.skip("k_steps_grp is not in this build (make -C harc_amd/csrc GRP=1)")
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     g = ol.load_golden(case)
@@ -326,35 +324,31 @@ def test_steps_per_super_round_chosen_from_the_index(oracle, tmp_path):
     assert differ          # (the two schedules do differ on at least one of the inputs: the test can tell them apart)
 
 
-@pytest.mark.parametrize("env", [{"HARC_AMD_QUAD": "0"}, {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1"},
-                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_S1BLOOM_MZMB": "0"}, {"HARC_AMD_S1BLOOM_MZMB": "0"},
+# a case's id is its position in the list as it stood before env1 (a duplicate of env0) and env22-27 (a kernel since removed) left it: every case keeps its id
+_VARIANT_IDS = ["env0"] + ["env%d" % i for i in range(2, 22)] + ["env%d" % i for i in range(28, 39)]
+
+
+@pytest.mark.parametrize("env", [{"HARC_AMD_QUAD": "0"},
+                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_S1BLOOM_MZMB": "0"}, {"HARC_AMD_S1BLOOM_MZMB": "0"},
                                  {"HARC_AMD_S1BLOOM": "0"}, {"HARC_AMD_BLOOM4_HASHED": "1"}, {"HARC_AMD_BLOOM1": "1"}, {"HARC_AMD_CAPMULT": "2"},
                                  {"HARC_AMD_COOP_WAVES": "1"}, {"HARC_AMD_COOP_WAVES": "2"}, {"HARC_AMD_RESEED_MG": "1"},
-                                 {"HARC_AMD_RESEED_MG": "1", "HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1"},
-                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1"}, {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "0"},
-                                 {"HARC_AMD_LAZY": "0"}, {"HARC_AMD_LAZY": "0", "HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1"},
+                                 {"HARC_AMD_RESEED_MG": "1", "HARC_AMD_QUAD": "0"},
+                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_SEQ": "1"}, {"HARC_AMD_QUAD": "0", "HARC_AMD_SEQ": "0"},
+                                 {"HARC_AMD_LAZY": "0"}, {"HARC_AMD_LAZY": "0", "HARC_AMD_QUAD": "0", "HARC_AMD_SEQ": "1"},
                                  {"HARC_AMD_SUCC": "1"}, {"HARC_AMD_SUCC": "1", "HARC_AMD_S1BLOOM": "0"}, {"HARC_AMD_SUCC": "1", "HARC_AMD_S1BLOOM_MZMB": "0"},      # steps by successor list (k_succ), with chains that lose bids and are rolled back
-                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0"},      # the specialised dense kernel (k_steps' SPEC) ...
-                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_SPEC": "0"},      # ... and the general one under the same conditions
-                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_LAZY": "0"},
-                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_GRP": "2"},      # two chains per wave (k_steps_grp; 2 = fail if it cannot run)
-                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_GRP": "2", "HARC_AMD_LAZY": "0"},
-                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_GRP": "2", "HARC_AMD_RESEED_MG": "1", "HARC_AMD_WEEDMIN": "1"},
-                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_GRP": "2", "HARC_AMD_GRP_G": "32"},      # two chains per wave instead of four
-                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_GRP": "2", "HARC_AMD_GRP_WIDE": "1", "HARC_AMD_GRP_WIDE_LIMIT": "6"},      # chains with a count above 6 change to the u32 form of the kernel
-                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_GRP": "2", "HARC_AMD_GRP_G": "32", "HARC_AMD_GRP_WIDE": "1", "HARC_AMD_GRP_WIDE_LIMIT": "2", "HARC_AMD_LAZY": "0"},
+                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0"},      # the specialised dense kernel (k_steps' SPEC) ...
+                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_SPEC": "0"},      # ... and the general one under the same conditions
+                                 {"HARC_AMD_QUAD": "0", "HARC_AMD_SEQ": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_LAZY": "0"},
                                  {"HARC_AMD_LEFT_ALL": "1"},      # the leftover reads emitted by a pass over all candidates instead of over their list
                                  {"HARC_AMD_TABLE_FILL": "0"}, {"HARC_AMD_TABLE_FILL": "1"}, {"HARC_AMD_SORT_BITS": "8"}, {"HARC_AMD_SORT_BITS": "13"}, {"HARC_AMD_SORT_BITS": "1"}, {"HARC_AMD_SORT_BITS": "64"},
                                  {"HARC_AMD_S2BLOOM_TILED": "1", "HARC_AMD_S2BLOOM_VERIFY": "1"}, {"HARC_AMD_S2BLOOM_TILED": "1", "HARC_AMD_S2BLOOM_VERIFY": "1", "HARC_AMD_BLOOM4_HASHED": "1"},
                                  {"HARC_AMD_S1BLOOM_TILED": "1", "HARC_AMD_S1BLOOM_VERIFY": "1"},
-                                 {"HARC_AMD_S1BLOOM_TILED": "1", "HARC_AMD_S1BLOOM_VERIFY": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1"}])
+                                 {"HARC_AMD_S1BLOOM_TILED": "1", "HARC_AMD_S1BLOOM_VERIFY": "1", "HARC_AMD_S1BLOOM_MZMB": "0", "HARC_AMD_QUAD": "0"}], ids=_VARIANT_IDS)
 def test_kernel_variants_same_bytes(env, oracle, tmp_path, monkeypatch):
-    """the variants the library picks by problem size (two-slot vs whole-bucket fetches, 5 vs 6 waves per SIMD, bitmap lines hashed vs by
+    """the variants the library picks by problem size (two-slot vs whole-bucket fetches, the dense kernels with the wave-uniform scan of the small bins or the lanes' own, specialised or general, bitmap lines hashed vs by
     minimizer, with / without the bitmaps, the table cleared by a memset or by the placement itself, the index sorted on its top 8 / 13 bits with the mixed stretches fixed up, on 1 bit (stretches too long: falls back to all 64) and on all bits, the stage-I bitmap built tile by tile from sorted keys instead of with atomics (and compared with it word for word), the column counts applied step by step instead of a run of agreeing steps at once (HARC_AMD_LAZY=0), stage-II bitmap kinds, a fuller table, 1 / 2 / 4 waves per cooperative workgroup) are execution details: forced on a small repeat-rich
     input, every stage-I and stage-II file is the oracle's"""
     import harc_amd
-    if "HARC_AMD_GRP" in env and not harc_amd.build_has("grp"):
-        pytest.skip("k_steps_grp is not in this build (make -C harc_amd/csrc GRP=1)")
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     txt = gen.reads_text_lowcomplexity(99, 20000, 100, 50000, err=0.004)

@@ -115,7 +115,7 @@ def test_replicated_ranks_large_run_kernels(tmp_path, monkeypatch):
     os.environ["HARC_AMD_MAILBOX_TIMEOUT"] = "180"
     arr = gen.reads_array(411, 300000, 100, 1200000, err=0.01)
     want, cw = _one_gpu(arr, 100, 2, 6000, 16)
-    for k, v in {"HARC_AMD_QUAD": "0", "HARC_AMD_DENSE": "1", "HARC_AMD_SEQ": "1", "HARC_AMD_RESEED_MG": "1", "HARC_AMD_RESEED_WIN": "256", "HARC_AMD_RESEED_STRESS": "3"}.items():
+    for k, v in {"HARC_AMD_QUAD": "0", "HARC_AMD_SEQ": "1", "HARC_AMD_RESEED_MG": "1", "HARC_AMD_RESEED_WIN": "256", "HARC_AMD_RESEED_STRESS": "3"}.items():
         monkeypatch.setenv(k, v)
     res = _ranks(3, shard_model.slices_of(arr, 3), 100, 2, 6000, 16, str(tmp_path))
     got = _assemble(res, 2, 100)                                   # stage II partitioned over the three ranks (two shards: one rank has none)

@@ -86,6 +86,8 @@ def lib():
     l.harc_amd_decoder_preserve_files.argtypes = [PP, C.c_char_p, C.c_int32]
     l.harc_amd_compress_fastq_files.argtypes = [PP, C.c_char_p, C.c_char_p]
     l.harc_amd_set_fastq_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_bgzf_inflate_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_set_fastq_bgzf_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     l.harc_amd_decode_signature.argtypes = [ctx, C.POINTER(C.c_uint64)]
     l.harc_amd_input_signature.argtypes = [ctx, C.POINTER(C.c_uint64)]
     l.harc_amd_reads_signature_device.argtypes = [ctx, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
@@ -162,11 +164,13 @@ def build_has(feature):
     return bool(lib().harc_amd_build_has(feature.encode()))
 
 
-def last_fastq_timing():
-    """seconds of the last compress_fastq of this process, by phase (include/harc_amd.h: harc_amd_last_fastq_timing)"""
-    t = (C.c_double * 8)()
-    _check(lib().harc_amd_last_fastq_timing(t, 8))
-    names = ("context_and_pool", "ingest", "ingest_waiting_for_file_readers", "ingest_device_passes", "reorder", "encode", "stream_files", "total")
+def last_fastq_timing(n=8):
+    """seconds of the last compress_fastq of this process, by phase (include/harc_amd.h: harc_amd_last_fastq_timing); n=9 adds the
+    BGZF member scan and inflate"""
+    t = (C.c_double * n)()
+    _check(lib().harc_amd_last_fastq_timing(t, n))
+    names = ("context_and_pool", "ingest", "ingest_waiting_for_file_readers", "ingest_device_passes", "reorder", "encode", "stream_files", "total",
+             "ingest_bgzf_inflate")
     return {k: float(v) for k, v in zip(names, t)}
 
 
@@ -243,6 +247,18 @@ class HarcAmd:
     def set_fastq_device(self, dptr, nbytes):
         nrec = C.c_uint64(0)
         _check(lib().harc_amd_set_fastq_device(self._ctx, C.c_void_p(dptr), nbytes, C.byref(nrec)))
+        return nrec.value
+
+    def bgzf_inflate_device(self, dptr, nbytes, out_ptr=None, out_capacity=0):
+        """BGZF bytes in device memory -> their text at out_ptr (device memory); without out_ptr only the text size. -> text bytes"""
+        n = C.c_uint64(0)
+        _check(lib().harc_amd_bgzf_inflate_device(self._ctx, C.c_void_p(dptr), nbytes, C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
+        return n.value
+
+    def set_fastq_bgzf_device(self, dptr, nbytes):
+        """set_fastq_device for a BGZF-compressed FASTQ in device memory (inflated on the GPU) -> complete records"""
+        nrec = C.c_uint64(0)
+        _check(lib().harc_amd_set_fastq_bgzf_device(self._ctx, C.c_void_p(dptr), nbytes, C.byref(nrec)))
         return nrec.value
 
     def set_reads_packed_device(self, dptr, n):

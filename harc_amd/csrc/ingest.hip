@@ -4,6 +4,7 @@
 // input_clean.dna round trip: the whole file is staged in HBM, a prefix sum over the newline flags gives the line index, one thread
 // per record classifies, two compactions pack the reads straight into the 2-bit / 3-bit stores of the context.
 #include "devutil.h"
+#include "inflate_member.h"
 #include <string>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -470,6 +471,16 @@ __global__ __launch_bounds__(256) void k_q_place(const char *txt, const uint64_t
 }
 static int load_file_range(harc_amd_ctx *c, FILE *f, const char *name, uint64_t lo, uint64_t hi, char **d_txt);
 static int record_start_at_or_after(FILE *f, uint64_t pos, uint64_t fsz, uint64_t *out);
+template <class F> static int text_pieces(harc_amd_ctx *c, FILE *f, const char *name, uint64_t lo, uint64_t end, uint64_t fsz, bool bgzf,
+                                          double *t_wait, double *t_inflate, F &&fn);
+// bytes of the file per piece of the ingest: 1 GiB of FASTQ; 4 GiB of BGZF (compressed bytes), because the inflate kernel runs one lane per
+// member and a piece of 1 GiB holds ~27 000 of them, too few to fill the chip (NOTES.md, BGZF); HARC_AMD_INGEST_CHUNK in tests (pieces of a few records)
+static uint64_t ingest_piece_bytes(bool bgzf)
+{
+    uint64_t piece = (uint64_t)1 << (bgzf ? 32 : 30);
+    if (const char *e = getenv("HARC_AMD_INGEST_CHUNK")) { piece = strtoull(e, nullptr, 10); if (piece < 16) piece = 16; }
+    return piece;
+}
 static int write_device_range(harc_amd_ctx *c, const char *d, size_t n, FILE *fo)
 {
     std::vector<uint8_t> host;
@@ -482,7 +493,7 @@ static int write_device_range(harc_amd_ctx *c, const char *d, size_t n, FILE *fo
     }
     return HARC_AMD_OK;
 }
-static int emit_quality_and_ids_streamed(harc_amd_ctx *c, FILE *f, const char *name, uint64_t fsz, const IngestState &st, const std::string &od, const char *qname, const char *iname)
+static int emit_quality_and_ids_streamed(harc_amd_ctx *c, FILE *f, const char *name, uint64_t fsz, bool bgzf, const IngestState &st, const std::string &od, const char *qname, const char *iname)
 {
     FILE *fq = fopen((od + qname).c_str(), "wb"), *fi = fopen((od + iname).c_str(), "wb");
     struct Closer { FILE *a, *b; ~Closer() { if (a) fclose(a); if (b) fclose(b); } } closer{ fq, fi };
@@ -528,8 +539,6 @@ static int emit_quality_and_ids_streamed(harc_amd_ctx *c, FILE *f, const char *n
         if (budget < ((size_t)64 << 20)) budget = (size_t)64 << 20;
         if (const char *e = getenv("HARC_AMD_Q_BIN")) { const unsigned long long v = strtoull(e, nullptr, 10); if (v >= 1) budget = (size_t)v; }       // tests: bins of a few lines
     }
-    uint64_t piece = (uint64_t)1 << 30;
-    if (const char *e = getenv("HARC_AMD_INGEST_CHUNK")) { piece = strtoull(e, nullptr, 10); if (piece < 16) piece = 16; }
     uint32_t q0 = 0, i0 = 0; int passes = 0;
     while (q0 < nQ || i0 < nI) {
         PoolScope pass_scope(c);
@@ -547,23 +556,20 @@ static int emit_quality_and_ids_streamed(harc_amd_ctx *c, FILE *f, const char *n
         const size_t bytesQ = (size_t)(q1 - q0) * (size_t)(L + 1), bytesI = (size_t)(ob[1] - ob[0]);
         char *outQ = nullptr, *outI = nullptr;
         RC_TRY(dalloc(c, &outQ, bytesQ + 16)); RC_TRY(dalloc(c, &outI, bytesI + 16));
-        uint64_t lo = 0; uint32_t base = 0;
-        while (lo < fsz) {
-            uint64_t hi = fsz;
-            if (fsz - lo > piece) { RC_TRY(record_start_at_or_after(f, lo + piece, fsz, &hi)); if (hi <= lo) hi = fsz; }
-            char *d_txt = nullptr;
-            RC_TRY(load_file_range(c, f, name, lo, hi, &d_txt));
-            struct Free { harc_amd_ctx *c; char *p; ~Free() { harc_raw_free(c, p); } } fr{ c, d_txt };
+        uint32_t base = 0;
+        RC_TRY(text_pieces(c, f, name, 0, fsz, fsz, bgzf, nullptr, nullptr, [&](const char *d_txt, uint64_t n, bool, uint64_t) -> int {
+            if (n == 0) return HARC_AMD_OK;
             PoolScope piece_scope(c);
             const uint64_t *nls = nullptr; uint64_t tl = 0;
-            RC_TRY(build_line_index(c, d_txt, hi - lo, &nls, &tl));
+            RC_TRY(build_line_index(c, d_txt, n, &nls, &tl));
             const uint32_t pr = (uint32_t)(tl / 4), pi = pr + (tl % 4 ? 1u : 0u);
             if ((uint64_t)base + pi > (uint64_t)nid) { harc_set_error("-q: the FASTQ file changed between the passes"); return HARC_AMD_EIO; }
-            if (pi) hipLaunchKernelGGL(k_q_place, dim3((pi + 3) / 4), dim3(256), 0, c->stream, (const char *)d_txt, nls, pr, pi, base, L, (const uint32_t *)posQ, q0, q1, outQ,
+            if (pi) hipLaunchKernelGGL(k_q_place, dim3((pi + 3) / 4), dim3(256), 0, c->stream, d_txt, nls, pr, pi, base, L, (const uint32_t *)posQ, q0, q1, outQ,
                                        (const uint32_t *)posI, (const uint64_t *)offI, i0, i1, outI, d_err);
             HIP_TRY(hipStreamSynchronize(c->stream));
-            base += pr; lo = hi;
-        }
+            base += pr;
+            return HARC_AMD_OK;
+        }));
         unsigned int err = 0;
         HIP_TRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -579,13 +585,13 @@ static int emit_quality_and_ids_streamed(harc_amd_ctx *c, FILE *f, const char *n
 // Where the wall time of the last harc_amd_compress_fastq_files_ex of this process went (seconds; harc_amd_last_fastq_timing): [0] context + device pool,
 // [1] ingest = file -> HBM -> packed stores, reads / uploads / kernels overlapped, [2] of it the calling thread waiting for the reader threads (file-read bound),
 // [3] of it the device's line index / classify / pack kernels and their syncs, [4] reorder, [5] encode (the D2H of the streams inside), [6] stream files written,
-// [7] total
-static double g_fastq_timing[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+// [7] total, [8] of [1] the BGZF member scan and inflate (0 for a plain file)
+static double g_fastq_timing[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 static inline double mono_now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 extern "C" int harc_amd_last_fastq_timing(double *out, int32_t n)
 {
     if (!out || n < 1) return HARC_AMD_EINVAL;
-    for (int i = 0; i < n; i++) out[i] = i < 8 ? g_fastq_timing[i] : 0.0;
+    for (int i = 0; i < n; i++) out[i] = i < 9 ? g_fastq_timing[i] : 0.0;
     return HARC_AMD_OK;
 }
 // File -> HBM at the rate of the host's memory system instead of one core's (round 6; round 3's ./harc -c spent most of its 6 s on 100 M reads in a
@@ -813,58 +819,147 @@ static int record_start_at_or_after(FILE *f, uint64_t pos, uint64_t fsz, uint64_
         if (lo + n >= fsz) { *out = fsz; return HARC_AMD_OK; }   // no further record
     }
 }
-// The records of bytes [lo, end) of the file, a piece at a time: every piece goes to HBM, is indexed, classified and packed, then makes room
-// for the next -- the file never has to fit next to the dictionaries.  With fq / fi (-q -p) the quality and id lines of every piece
-// are written out in file order on the way.
-static int ingest_file_range(harc_amd_ctx *c, FILE *f, const char *name, uint64_t lo, uint64_t end, uint64_t fsz, IngestState &st, FILE *fq, FILE *fi)
+// The last record start in d_txt[0 .. n) by the rule of record_start_at_or_after (a line that begins with '@' whose second successor begins with '+'),
+// looked for from the end of the text through a window that grows until one is found: what lies before it is whole records (the text starts at a
+// record), the rest is carried into the next piece.  0 when no record start is seen but the first.
+static int last_record_start(harc_amd_ctx *c, const char *d_txt, uint64_t n, uint64_t *cut)
 {
-    uint64_t piece = (uint64_t)1 << 30;
-    if (const char *e = getenv("HARC_AMD_INGEST_CHUNK")) { piece = strtoull(e, nullptr, 10); if (piece < 16) piece = 16; }    // tests: pieces of a few records
+    *cut = 0;
+    std::vector<char> buf;
+    std::vector<size_t> ls;
+    for (uint64_t win = (uint64_t)1 << 16;; win <<= 2) {
+        const uint64_t w = std::min<uint64_t>(win, n), lo = n - w;
+        if (w == 0) return HARC_AMD_OK;
+        buf.resize((size_t)w);
+        HIP_TRY(hipMemcpyAsync(buf.data(), d_txt + lo, (size_t)w, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        ls.clear();                                               // line starts inside the window whose first byte is there
+        if (lo == 0) ls.push_back(0);
+        for (size_t i = 1; i < (size_t)w; i++) if (buf[i - 1] == '\n') ls.push_back(i);
+        for (size_t k = ls.size(); k-- > 0;)
+            if (k + 2 < ls.size() && buf[ls[k]] == '@' && buf[ls[k + 2]] == '+') { *cut = lo + ls[k]; return HARC_AMD_OK; }
+        if (lo == 0) return HARC_AMD_OK;
+    }
+}
+// The text of bytes [lo, end) of the file as pieces of whole 4-line records, in file order -- what ingest_file_range, the in-HBM -q load of a BGZF
+// file and emit_quality_and_ids_streamed consume: fn(d_txt, nbytes, last, at) with `at` the file offset the piece came from (a measure of progress).
+// Plain FASTQ: byte ranges that end where a record starts (a 64-KB look at the file per boundary), read through the FileFeeder -- the readers run
+// ahead over all pieces, two device buffers alternate.  BGZF (whole files only): compressed ranges [a_p, a_p+1 + 64 KiB) through the same feeder;
+// piece p owns the members that START in [a_p, a_p+1) (a member is at most 64 KiB, so they are whole), their text is inflated behind the incomplete
+// record carried over from piece p - 1 and cut after its last whole record, the rest is carried on.  HARC_AMD_INGEST_CHUNK: file bytes per piece
+// (compressed bytes for BGZF; tests: pieces of a few records).  t_wait / t_inflate (may be null): seconds waited for the readers / in the member
+// scan and inflate.
+template <class F> static int text_pieces(harc_amd_ctx *c, FILE *f, const char *name, uint64_t lo, uint64_t end, uint64_t fsz, bool bgzf,
+                                          double *t_wait, double *t_inflate, F &&fn)
+{
+    const uint64_t piece = ingest_piece_bytes(bgzf);
     const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
     double tl = mono_now();
     auto lap = [&](const char *what) { if (tlog) { const double t = mono_now(); fprintf(stderr, "[ingest] %s: %.3f s\n", what, t - tl); tl = t; } };
-    RC_TRY(ingest_begin(c, st));
-    lap("previous inputs dropped");
-    // the pieces first (a piece ends where a record starts: a 64-KB look at the file per boundary), so that the readers can run ahead over all of them
-    std::vector<std::pair<uint64_t, uint64_t>> pieces;
+    const uint64_t SLOP = 65536;                                  // BGZF: a member is at most BSIZE + 1 = 65536 bytes
+    // the pieces first, so that the readers can run ahead over all of them
+    std::vector<std::pair<uint64_t, uint64_t>> pieces;            // file ranges that are read
+    std::vector<uint64_t> owned;                                  // BGZF: end of the range whose members a piece owns
     uint64_t maxlen = 0;
-    for (uint64_t a = lo; a < end;) {
-        uint64_t hi = end;
-        if (end - a > piece) { RC_TRY(record_start_at_or_after(f, a + piece, fsz, &hi)); if (hi > end) hi = end; if (hi <= a) hi = end; }
-        pieces.emplace_back(a, hi); if (hi - a > maxlen) maxlen = hi - a;
-        a = hi;
+    if (bgzf) {
+        for (uint64_t a = lo; a < end; a += piece) {
+            const uint64_t oe = end - a > piece ? a + piece : end;
+            pieces.emplace_back(a, std::min<uint64_t>(end, oe + SLOP)); owned.push_back(oe);
+            maxlen = std::max<uint64_t>(maxlen, pieces.back().second - a);
+        }
+    } else {
+        for (uint64_t a = lo; a < end;) {
+            uint64_t hi = end;
+            if (end - a > piece) { RC_TRY(record_start_at_or_after(f, a + piece, fsz, &hi)); if (hi > end) hi = end; if (hi <= a) hi = end; }
+            pieces.emplace_back(a, hi); if (hi - a > maxlen) maxlen = hi - a;
+            a = hi;
+        }
     }
-    if (pieces.empty()) return ingest_finish(c, st);
+    if (pieces.empty()) return HARC_AMD_OK;
     lap("piece boundaries");
     // two device buffers: piece i + 1 is uploaded (behind piece i's kernels on the stream) while the host still waits for piece i's counts
-    struct Bufs { harc_amd_ctx *c; char *p[2] = { nullptr, nullptr }; ~Bufs() { for (char *x : p) if (x) harc_raw_free(c, x); } } db{ c };
+    struct Bufs { harc_amd_ctx *c; char *p[4] = { nullptr, nullptr, nullptr, nullptr }; ~Bufs() { for (char *x : p) if (x) harc_raw_free(c, x); } } db{ c };
     RC_TRY(harc_raw_alloc(c, (void **)&db.p[0], (size_t)maxlen + 16));
     if (pieces.size() > 1) RC_TRY(harc_raw_alloc(c, (void **)&db.p[1], (size_t)maxlen + 16));
+    size_t tcap[2] = { 0, 0 };                                    // BGZF: the text buffers db.p[2 + (p & 1)], grown as needed
     lap("two device buffers");
-    {
     FileFeeder feed(c, name);
     RC_TRY(feed.start(pieces));
     lap("feeder started (file mapped, ring pinned, readers running)");
-    const uint64_t start = lo;
+    uint64_t next = lo, carry = 0; const char *carry_at = nullptr;   // BGZF: where the next member starts; the text carried into the next piece
     for (size_t p = 0; p < pieces.size(); p++) {
         const uint64_t a = pieces[p].first, hi = pieces[p].second;
-        char *d_txt = db.p[p & 1];
+        char *d_in = db.p[p & 1];
         const double tu = mono_now();
-        RC_TRY(feed.upload_piece(p, d_txt, p + 1 < pieces.size() ? db.p[(p + 1) & 1] : nullptr));
-        const double ta = mono_now(); g_fastq_timing[2] += ta - tu;
+        RC_TRY(feed.upload_piece(p, d_in, p + 1 < pieces.size() ? db.p[(p + 1) & 1] : nullptr));
+        if (t_wait) *t_wait += mono_now() - tu;
+        if (!bgzf) { RC_TRY(fn((const char *)d_in, hi - a, hi == fsz, a)); continue; }
+        const double ti = mono_now();
+        BgzfPlan plan;
+        RC_TRY(harc_bgzf_plan(c, (const uint8_t *)d_in, hi - a, next - a, owned[p] - a, a, &plan));
+        const size_t need = (size_t)(carry + plan.text) + 16;
+        char *&tb = db.p[2 + (p & 1)];
+        if (tcap[p & 1] < need) {
+            if (tb) harc_raw_free(c, tb);
+            tb = nullptr; tcap[p & 1] = 0;
+            RC_TRY(harc_raw_alloc(c, (void **)&tb, need + need / 4));
+            tcap[p & 1] = need + need / 4;
+        }
+        if (carry) HIP_TRY(hipMemcpyAsync(tb, carry_at, (size_t)carry, hipMemcpyDeviceToDevice, c->stream));
+        RC_TRY(harc_bgzf_run(c, (const uint8_t *)d_in, plan, a, tb + carry));
+        if (t_inflate) *t_inflate += mono_now() - ti;
+        next = a + plan.next;
+        const uint64_t total = carry + plan.text;
+        if (p + 1 == pieces.size()) {                             // a last piece may hold no text at all (bgzip's EOF marker alone)
+            if (total) RC_TRY(fn((const char *)tb, total, true, a));
+            break;
+        }
+        uint64_t cut = 0;
+        RC_TRY(last_record_start(c, tb, total, &cut));
+        if (cut) RC_TRY(fn((const char *)tb, cut, false, a));
+        carry = total - cut; carry_at = tb + cut;
+    }
+    lap("pieces uploaded and processed");
+    return HARC_AMD_OK;
+}
+// The records of bytes [lo, end) of the file, a piece at a time: every piece goes to HBM, is indexed, classified and packed, then makes room
+// for the next -- the file never has to fit next to the dictionaries.  With fq / fi (-q -p) the quality and id lines of every piece
+// are written out in file order on the way.
+static int ingest_file_range(harc_amd_ctx *c, FILE *f, const char *name, uint64_t lo, uint64_t end, uint64_t fsz, bool bgzf, IngestState &st, FILE *fq, FILE *fi)
+{
+    RC_TRY(ingest_begin(c, st));
+    const uint64_t start = lo;
+    RC_TRY(text_pieces(c, f, name, lo, end, fsz, bgzf, &g_fastq_timing[2], &g_fastq_timing[8], [&](const char *d_txt, uint64_t n, bool last, uint64_t a) -> int {
+        const double ta = mono_now();
         // the first piece tells how many reads the whole range will hold, give or take: the stores are sized once
         uint64_t expC = 0, expN = 0;
         if (a > start) { const double scale = 1.03 * (double)(end - start) / (double)(a - start); expC = (uint64_t)(scale * (double)st.nC); expN = (uint64_t)(scale * (double)st.nN); }
-        RC_TRY(ingest_append(c, st, d_txt, hi - a, hi == fsz, expC, expN));
+        RC_TRY(ingest_append(c, st, d_txt, n, last, expC, expN));
         g_fastq_timing[3] += mono_now() - ta;
-        if (fq) RC_TRY(emit_q_fileorder(c, d_txt, hi - a, fq, fi));
+        if (fq) RC_TRY(emit_q_fileorder(c, d_txt, n, fq, fi));
+        return HARC_AMD_OK;
+    }));
+    return ingest_finish(c, st);
+}
+
+// What the first bytes of a file say: 0 = not gzip, 1 = BGZF (the first member carries a BC subfield), -1 = another gzip.  *ratio (may be null):
+// text bytes per compressed byte over the members that start in the first MB (the -q mode is chosen by the size of the text).
+static int gzip_kind(const char *path, double *ratio)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) return 0;
+    std::vector<uint8_t> b((size_t)1 << 20);
+    const size_t got = fread(b.data(), 1, b.size(), f);
+    fclose(f);
+    if (got < 2 || b[0] != 0x1f || b[1] != 0x8b) return 0;
+    uint32_t bs = 0, hdr = 0;
+    if (!im_bgzf_header(b.data(), got, &bs, &hdr)) return -1;
+    if (ratio) {
+        uint64_t pos = 0, txt = 0;
+        while (pos < got && im_bgzf_header(b.data() + pos, got - pos, &bs, &hdr) && pos + bs + 1 <= got) { txt += im_le32(b.data() + pos + bs + 1 - 4); pos += (uint64_t)bs + 1; }
+        *ratio = pos ? (double)txt / (double)pos : 1.0;
     }
-    lap("pieces uploaded, indexed, classified, packed");
-    }
-    lap("feeder gone (readers joined, file unmapped)");
-    const int rc = ingest_finish(c, st);
-    lap("ingest_finish");
-    return rc;
+    return 1;
 }
 
 // FASTQ file -> every stage-II file under <basedir>/output (+ read_order_N.bin, numreads.bin): harc:50-69 without input_clean.dna
@@ -873,6 +968,11 @@ extern "C" int harc_amd_compress_fastq_files_ex(const harc_amd_params *params, c
     if (!params || !fastq || !basedir) return HARC_AMD_EINVAL;
     for (double &x : g_fastq_timing) x = 0;
     const double t_begin = mono_now();
+    // gzip input: only BGZF is read on the GPU; the sniff needs no device, so that the refusal comes first
+    double ratio = 1.0;
+    const int gz = gzip_kind(fastq, &ratio);
+    if (gz < 0) { harc_set_error("%s is gzip but not BGZF: recompress it with bgzip or decompress it first", fastq); return HARC_AMD_EINVAL; }
+    const bool bgzf = gz > 0;
     harc_amd_ctx *c = nullptr;
     RC_TRY(harc_amd_create(params, &c));
     struct Guard { harc_amd_ctx *c; ~Guard() { harc_amd_destroy(c); } } guard{ c };
@@ -889,15 +989,38 @@ extern "C" int harc_amd_compress_fastq_files_ex(const harc_amd_params *params, c
     // -q without -p: the text stays in HBM until the orders are known when it fits next to everything else; a larger file is ingested in pieces
     // like any other and streamed again, once per bin of output, when the orders are there (emit_quality_and_ids_streamed)
     bool stream_q = false;
+    uint64_t tsz = fsz;                                           // bytes of FASTQ text (BGZF, -q in HBM: known once inflated)
     if (preserve_quality && !preserve_order) {
         size_t fr = 0, tot = 0;
-        stream_q = (hipMemGetInfo(&fr, &tot) == hipSuccess && (double)fsz > 0.45 * (double)fr);
+        // BGZF: the text size estimated from the first members, plus what the piece loop holds meanwhile (two compressed pieces, two text buffers)
+        const double text_est = bgzf ? ratio * (double)fsz + 2.0 * (1.0 + ratio) * (double)std::min<uint64_t>(fsz, ingest_piece_bytes(true)) : (double)fsz;
+        stream_q = (hipMemGetInfo(&fr, &tot) == hipSuccess && text_est > 0.45 * (double)fr);
         if (const char *e = getenv("HARC_AMD_Q_STREAM")) stream_q = atoi(e) != 0;       // tests: either way on a small file
     }
     if (preserve_quality && !preserve_order && !stream_q) {
-        RC_TRY(load_file_range(c, f, fastq, 0, fsz, &d_txt));
+        if (bgzf) {                                               // the text pieces appended into one buffer
+            size_t cap = 0; tsz = 0;
+            {   // sized once from the estimate; grown (with a copy) only where the estimate was short
+                cap = (size_t)(1.02 * ratio * (double)fsz) + ((size_t)1 << 20);
+                RC_TRY(harc_raw_alloc(c, (void **)&d_txt, cap));
+            }
+            RC_TRY(text_pieces(c, f, fastq, 0, fsz, fsz, true, &g_fastq_timing[2], &g_fastq_timing[8], [&](const char *p, uint64_t n, bool, uint64_t) -> int {
+                if (tsz + n + 16 > cap) {
+                    const size_t ncap = (size_t)(tsz + n + 16) + (size_t)(tsz + n) / 2;
+                    char *nb = nullptr; RC_TRY(harc_raw_alloc(c, (void **)&nb, ncap));
+                    if (tsz) HIP_TRY(hipMemcpyAsync(nb, d_txt, (size_t)tsz, hipMemcpyDeviceToDevice, c->stream));
+                    HIP_TRY(hipStreamSynchronize(c->stream));
+                    if (d_txt) harc_raw_free(c, d_txt);
+                    d_txt = nb; cap = ncap;
+                }
+                HIP_TRY(hipMemcpyAsync(d_txt + tsz, p, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+                HIP_TRY(hipStreamSynchronize(c->stream));
+                tsz += n;
+                return HARC_AMD_OK;
+            }));
+        } else RC_TRY(load_file_range(c, f, fastq, 0, fsz, &d_txt));
         RC_TRY(ingest_begin(c, st));
-        RC_TRY(ingest_append(c, st, d_txt, fsz, true, 0, 0));
+        RC_TRY(ingest_append(c, st, d_txt, tsz, true, 0, 0));
         RC_TRY(ingest_finish(c, st));
     } else {
         FILE *fq = nullptr, *fi = nullptr;
@@ -907,7 +1030,7 @@ extern "C" int harc_amd_compress_fastq_files_ex(const harc_amd_params *params, c
             if (!fq || !fi) { harc_set_error("cannot create %soutput.quality / output.id", od.c_str()); return HARC_AMD_EIO; }
         }
         st.want_idlen = stream_q;
-        RC_TRY(ingest_file_range(c, f, fastq, 0, fsz, fsz, st, fq, fi));
+        RC_TRY(ingest_file_range(c, f, fastq, 0, fsz, fsz, bgzf, st, fq, fi));
     }
     g_fastq_timing[1] = mono_now() - t_ingest;
     printf("Read length: %d\nTotal number of reads: %llu\nTotal number of reads without N: %llu\nPreprocessing Done!\n", params->readlen,
@@ -938,8 +1061,8 @@ extern "C" int harc_amd_compress_fastq_files_ex(const harc_amd_params *params, c
     if (preserve_quality && !preserve_order) {
         printf("Reordering quality values and ids\n");                                                      // harc:122
         lap("whole-job files");
-        if (stream_q) RC_TRY(emit_quality_and_ids_streamed(c, f, fastq, fsz, st, od, "output.quality", "output.id"));
-        else RC_TRY(emit_quality_and_ids(c, d_txt, fsz, false, od, "output.quality", "output.id"));
+        if (stream_q) RC_TRY(emit_quality_and_ids_streamed(c, f, fastq, fsz, bgzf, st, od, "output.quality", "output.id"));
+        else RC_TRY(emit_quality_and_ids(c, d_txt, tsz, false, od, "output.quality", "output.id"));
         lap("quality values and ids");
     }
     return HARC_AMD_OK;
@@ -994,6 +1117,7 @@ static int compress_fastq_rank(const harc_amd_params *params, const char *fastq,
 {
     if (!params || !fastq || !basedir || world < 1 || rank < 0 || rank >= world) { harc_set_error("compress_fastq_shard: bad arguments"); return HARC_AMD_EINVAL; }
     if (preserve_quality && !preserve_order) { harc_set_error("multi-GPU -q needs -p (quality values and ids stay in file order)"); return HARC_AMD_EINVAL; }
+    if (gzip_kind(fastq, nullptr) != 0) { harc_set_error("multi-GPU runs read a plain FASTQ: %s is gzip / BGZF, expand it first", fastq); return HARC_AMD_EINVAL; }
     harc_amd_ctx *c = nullptr;
     RC_TRY(harc_amd_create(params, &c));
     struct Guard { harc_amd_ctx *c; ~Guard() { harc_amd_destroy(c); } } guard{ c };
@@ -1014,7 +1138,7 @@ static int compress_fastq_rank(const harc_amd_params *params, const char *fastq,
             fq = fopen((sd + "quality" + r).c_str(), "wb"); fi = fopen((sd + "id" + r).c_str(), "wb");
             if (!fq || !fi) { harc_set_error("cannot create the quality / id parts under %s", sd.c_str()); return HARC_AMD_EIO; }
         }
-        RC_TRY(ingest_file_range(c, f, fastq, lo, hi, fsz, st, fq, fi));
+        RC_TRY(ingest_file_range(c, f, fastq, lo, hi, fsz, false, st, fq, fi));
     }
     const uint64_t nrec_full = st.nfull;
     const uint64_t n_clean_own = c->N_own;

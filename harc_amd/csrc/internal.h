@@ -229,3 +229,13 @@ static inline void out_slice(harc_amd_ctx *c, int id, int shard, const void *p, 
 int harc_host_alloc(harc_amd_ctx *c, void **p, size_t bytes);    // pinned, valid until the results are dropped
 void harc_host_reset(harc_amd_ctx *c);
 int harc_d2h(harc_amd_ctx *c, std::vector<uint8_t> &dst, const void *d_src, size_t bytes);
+
+// ---- BGZF (bgzf.hip): the member chain of a buffer of compressed bytes in device memory, then every member inflated on its own
+struct BgzfCand { uint64_t off; uint32_t bsize, hdr, isize, crc; };                   // a member header that parses at `off`
+struct BgzfMember { uint64_t cdata, text; uint32_t clen, isize, crc, hdr; };          // CDATA at cdata (clen bytes) -> text[text .. + isize)
+struct BgzfPlan { std::vector<BgzfMember> m; uint64_t text = 0, next = 0; };           // members, text bytes, where the member after them starts
+// the members of d_in[0 .. n) that start in [start, own_end), the first at `start`; each must end inside n.  base_off: file offset of d_in[0]
+// (error messages name compressed bytes of the file)
+int harc_bgzf_plan(harc_amd_ctx *c, const uint8_t *d_in, uint64_t n, uint64_t start, uint64_t own_end, uint64_t base_off, BgzfPlan *plan);
+// their text -> d_out[0 .. plan.text); HARC_AMD_EINVAL naming the first bad member (length, CRC-32, any malformed DEFLATE data)
+int harc_bgzf_run(harc_amd_ctx *c, const uint8_t *d_in, const BgzfPlan &plan, uint64_t base_off, char *d_out);

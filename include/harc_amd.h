@@ -162,6 +162,13 @@ int harc_amd_set_nreads_ascii_device(harc_amd_ctx *ctx, const char *d_ascii, uin
    record, checks the fixed read length, packs reads without N into the 2-bit store and reads with N into the 3-bit store; the
    original indices of the N reads become stream HARC_AMD_IN_ORDER_N.  Replaces harc_amd_set_reads_* + harc_amd_set_nreads_*. */
 int harc_amd_set_fastq_device(harc_amd_ctx *ctx, const char *d_fastq, uint64_t n_bytes, uint64_t *n_records_out);
+/* BGZF bytes (SAM/BAM spec 4.1: gzip members carrying a BC subfield) in device memory -> their text in device memory, inflated on the GPU.
+   d_out == NULL: *n_out = size of the text (sum of ISIZE), nothing decoded; else out_capacity must be at least that.  A chain of members that
+   leaves the buffer, a position where a member must start but none parses, ISIZE > 65536, a wrong length or CRC-32 or malformed DEFLATE
+   data: HARC_AMD_EINVAL naming the compressed byte offset of the member. */
+int harc_amd_bgzf_inflate_device(harc_amd_ctx *ctx, const uint8_t *d_bgzf, uint64_t n_bytes, char *d_out, uint64_t out_capacity, uint64_t *n_out);
+/* harc_amd_set_fastq_device for a BGZF-compressed FASTQ in device memory: the context holds the same inputs afterwards, byte for byte */
+int harc_amd_set_fastq_bgzf_device(harc_amd_ctx *ctx, const uint8_t *d_bgzf, uint64_t n_bytes, uint64_t *n_records_out);
 /* stage-II inputs when stage I ran elsewhere (the file family of reorder.cpp:722-830): host buffers.
    dna/dna_s are text with stride readlen+1 */
 int harc_amd_set_stage1_streams(harc_amd_ctx *ctx, const char *temp_dna, const uint8_t *flag, const uint8_t *pos,
@@ -243,7 +250,8 @@ int harc_amd_selftest_launch(harc_amd_ctx *ctx, uint64_t n, uint64_t *visited, u
 /* Where the wall time of this process's last harc_amd_compress_fastq_files_ex went, in seconds (the end-to-end leg of bench.py; preprocess.cpp:81-121 + harc:50-69):
  * out[0] context + device pool, [1] ingest (file -> HBM -> packed stores; reads, uploads and kernels overlapped), [2] of it the calling thread waiting for
  * the file reader threads, [3] of it the device's line index / classify / pack passes, [4] reorder, [5] encode (the D2H of the streams inside),
- * [6] stream files written, [7] total up to there (the -q files of a run without -p come after it).  n = how many of them the caller wants. */
+ * [6] stream files written, [7] total up to there (the -q files of a run without -p come after it), [8] of [1] the BGZF member scan and inflate
+ * (0 for a plain file).  n = how many of them the caller wants. */
 int harc_amd_last_fastq_timing(double *out, int32_t n);
 
 /* ---- file contract: drop-ins for the reference's stage programs.  basedir as argv[1] of those programs. */
@@ -259,7 +267,9 @@ int harc_amd_compress_fastq_files(const harc_amd_params *params, const char *fas
    post-encoding orders exactly as reorder_quality.out does (reorder_quality.cpp:47-219, quirks included: see oracle/harc_oracle.c
    harc_oracle_quality).  preserve_order itself changes nothing else here: pack_order stays a separate call (harc:112).
    The file may be larger than HBM in every mode: it is ingested a piece at a time; without preserve_order the quality values and ids are
-   then permuted by streaming the file again once per bin of output (reorder_quality.cpp:61-77 bins through host memory). */
+   then permuted by streaming the file again once per bin of output (reorder_quality.cpp:61-77 bins through host memory).
+   The file may be BGZF (what bgzip writes; told by its first bytes): its members are inflated on the GPU, piece by piece, and every output file is
+   the one the plain FASTQ with the same text gives.  Any other gzip is refused with HARC_AMD_EINVAL before a device is touched. */
 int harc_amd_compress_fastq_files_ex(const harc_amd_params *params, const char *fastq, const char *basedir, int32_t preserve_order, int32_t preserve_quality);
 /* == `preprocess.out <fastq> <basedir> <preserve_order> <preserve_quality> <readlen>` (src/preprocess.cpp:22-137, harc:50),
    the N split only; host code, feeds the boundary */
@@ -277,7 +287,8 @@ int harc_amd_decoder_preserve_files(const harc_amd_params *params, const char *b
    file), joins the communicator named by comm_spec -- "rccl:<file>" (rank 0 writes the ncclUniqueId there, the others wait for it) or
    "mailbox:<dir>" (test transport) --, exchanges, compresses its shard and writes read_*.txt.<rank*num_thr + e> into
    <basedir>/output plus its part of the whole-job files under <basedir>/output/.shard/.  preserve_quality needs preserve_order
-   (quality values and ids then stay in file order, preprocess.cpp:64-69). */
+   (quality values and ids then stay in file order, preprocess.cpp:64-69).  The file must be plain FASTQ: gzip / BGZF input is refused with
+   HARC_AMD_EINVAL before any device call (./harc -g expands it first); so for harc_amd_compress_fastq_replicated_files. */
 int harc_amd_compress_fastq_shard_files(const harc_amd_params *params, const char *fastq, const char *basedir, int32_t preserve_order,
                                         int32_t preserve_quality, int32_t world, int32_t rank, const char *comm_spec);
 /* After every rank has finished: the whole-job files of the archive (read_singleton.txt(+.tail), input_N.dna, read_order.bin,

@@ -57,6 +57,21 @@ __device__ __forceinline__ uint64_t key_scramble(uint64_t key)
     y = a * 0xC2B2AE3Du; b ^= y ^ (y >> 16);
     return ((uint64_t)b << 32) | a;
 }
+// the same in two parts: the low word of the scrambled key is final after two rounds (the bitmap in front of a dictionary asks for nothing else:
+// bloom_pos), the third round makes the high word (the bucket, and what the table compares) -- k_steps runs it for the probes that pass the bitmap only
+__device__ __forceinline__ uint32_t key_scramble_lo(uint64_t key, uint32_t *bmid)
+{
+    uint32_t a = (uint32_t)key, b = (uint32_t)(key >> 32), y;
+    y = a * 0x9E3779B1u; b ^= y ^ (y >> 15);
+    y = b * 0x85EBCA77u; a ^= y ^ (y >> 13);
+    *bmid = b;
+    return a;
+}
+__device__ __forceinline__ uint64_t key_scramble_hi(uint32_t a, uint32_t bmid)
+{
+    const uint32_t y = a * 0xC2B2AE3Du;
+    return ((uint64_t)(bmid ^ y ^ (y >> 16)) << 32) | a;
+}
 // first slot of the 64-byte bucket (4 slots of 16 bytes) a scrambled key belongs to; non-decreasing in h
 __device__ __forceinline__ uint64_t bucket_slot(uint64_t h, uint64_t cap)
 {

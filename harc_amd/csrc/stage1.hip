@@ -10,6 +10,7 @@
 // Integer / HBM-latency bound; no MFMA.  Wave = 64 everywhere.
 #include "devutil.h"
 #include <stdlib.h>
+#include <type_traits>
 
 // ------------------------------------------------------------------------------------------------ kernel argument block
 struct S1Args {
@@ -1562,17 +1563,22 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
     const uint64_t cap = s.cap[0];                               // both dictionaries have the same geometry (stage1_run_w)
     uint32_t dbg_bins = 0, dbg_iter = 0, dbg_miss = 0, dbg_surv = 0, dbg_batches = 0;   // coop scans / their 64-entry chunks / steps without a hit / (unused) / batches
     uint32_t np = 0, nc = 0, nuse = 0, ncu = 0;                   // ncu: candidates a strictly sequential scan (reorder.cpp:517-649) would have tested too
-    int nst = 0; bool needseed = false, defer = false;
+    // the walk's own flags are ints, not bools: a bool that lives across the step loop is kept as a 64-bit lane mask (two scalar registers, and the
+    // tests on it are mask arithmetic); as ints they are one register each -- 100 -> 66 reloads and stores of spilled scalars inside the loops of the
+    // dense 100-bp kernel
+    // (the dense kernels only: elsewhere the same change costs vector registers)
+    using flag_t = typename std::conditional<SEQ, int, bool>::type;
+    int nst = 0; flag_t needseed = false, defer = false;
     int lastp = (int)(h.pad0 & 0xFFFF);                          // 16 x running mean (weight 1/4) of the priority index of this chain's hits
     int spos = (int)((h.nsteps >> 16) & 0xFF); const int nsugg = (int)(h.nsteps >> 24);   // look-ahead seeds: next to try / held
     int bigprobes = 0;                                           // COOP: probes into large live bins made by this walk so far
     const int resume = (int)(h.flags >> 16);                     // the first step of this super-round was put off before: where it takes up again
-    bool stalled = false; int resume_next = 0;
+    flag_t stalled = false; int resume_next = 0;
     // steps that agreed with the consensus everywhere (rows_from_read): the rows are current, `pend` of them wait for cons_flush, ptot = their shifts
-    bool rows_ok = false; int pend = 0, ptot = 0;
+    flag_t rows_ok = false; int pend = 0, ptot = 0;
     // (compiled into the wave-uniform kernels only: there the run of agreeing steps is the rule -- dense launches over error-free or nearly error-free
     // reads -- and the code fits; in the other kernels the second path cost registers: the 150-bp dense kernel lost 3.7 % to it)
-    const bool lazy = (SEQ || (QUAD && !COOP)) && s.lazy != 0;
+    const flag_t lazy = (SEQ || (QUAD && !COOP)) && s.lazy != 0;
     // FASTP (the kernel of runs with few chains; k_succ): while the consensus IS a read -- `lastrid`, taken in orientation `lastdir`: after a fresh
     // seed and after every step with Hamming distance 0 -- the step reads its candidates from that read's successor list instead of asking the
     // tables.  Such a step does not even fetch the read it takes: the window rows are made from it only when something asks for them
@@ -1673,13 +1679,15 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
             if (bend <= base) bend = s.nprobe;
             const int p = base + lane; dbg_batches++;
             uint32_t mine = HARC_NONE; int j = 0, dir = 0, l = 0, myhd = 0;
+            uint32_t pix = 0;                                             // SEQ: the probe's descriptor word -- shift, direction and dictionary are taken from it again below (one register, not three, across the scans)
             uint32_t ncb = 0;                                             // candidates this lane tests in this batch
             bool big = false; uint32_t b_cnt = 0; uint64_t b_slot = 0;   // a bin too large for one lane: scanned by the whole wave below
             uint2 b_lt = make_uint2(0, 0);                               // COOP: its row of largetab, fetched by the lane that found it (all bins of the batch in ONE round trip)
             bool cand = false; uint32_t c_sst = 0, c_cw = 0, c_piy = 0; uint64_t c_slot = 0;     // SEQ (see "ONE AFTER THE OTHER" below): the small bin this lane's probe found
             uint32_t mrd[NW];                                             // !SEQ: only the lane that wins has loaded them, and only it reads them
-            if (p < bend && cap) {
+            if (p < bend && (SPEC || cap)) {                             // (SPEC: there is a bitmap, so there are reads and a table)
                 const uint2 pi = s_pinfo[p];
+                pix = pi.x;
                 j = (int)(pi.x >> 16); dir = (int)((pi.x >> 13) & 1);
                 l = (int)((pi.x >> 14) & 1);
                 uint64_t key;
@@ -1694,16 +1702,26 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                 // (many chains) two slots at a time -- the second pair is the same 64-B sector.  A full bucket ends the
                 // search unless its overflow flag says that keys went on to the next one.
                 // phase 1: every lane finishes its slot search (the dependent bucket fetches of all lanes overlap) ...
-                const uint64_t hk = key_scramble(key);                    // what the table stores and compares
-                uint64_t sl;
-                if constexpr (SPEC) sl = (uint64_t)__umulhi((uint32_t)(hk >> 32), (uint32_t)(cap >> 2)) << 2; else sl = bucket_slot(hk, cap);
+                // hk = key_scramble(key) is what the table stores and compares.  The bitmap asks for its low word only; the third round and the
+                // bucket are made behind the bitmap in the dense kernels, by the probes that pass it (the asm keeps them there: a batch without such a probe skips them)
+                uint32_t hmid, hlo = key_scramble_lo(key, &hmid);
+                uint64_t hk = 0, sl = 0;
+                if constexpr (!SEQ) {                                     // (the other kernels: in front of the bitmap, as the compiler had it)
+                    hk = key_scramble_hi(hlo, hmid);
+                    sl = bucket_slot(hk, cap);
+                }
                 int state = 0, qhit = 0;                                  // 1 = the key is not in the table, 2 = key found
                 uint32_t sst = 0, cw = 0;
-                if (s.bloom_lines) {                                      // most keys of a step are in neither: they stop at the bitmap
+                if (SPEC || s.bloom_lines) {                              // most keys of a step are in neither: they stop at the bitmap
                     uint32_t bw, bm;
-                    if constexpr (SPEC) bloom_pos(key, hk, s.bloom_lines, 17, 0xFFFFFFFFu, &bw, &bm);
-                    else bloom_pos(key, hk, s.bloom_lines, s.bloom_nwin[0], s.bloom_mmask, &bw, &bm);      // both dictionaries have keys of the same width when nwin > 0
+                    if constexpr (SPEC) bloom_pos(key, hlo, s.bloom_lines, 17, 0xFFFFFFFFu, &bw, &bm);
+                    else bloom_pos(key, hlo, s.bloom_lines, s.bloom_nwin[0], s.bloom_mmask, &bw, &bm);      // both dictionaries have keys of the same width when nwin > 0
                     if (((l ? s.bloom[1] : s.bloom[0])[bw] & bm) != bm) state = 1;
+                }
+                if (SEQ && state == 0) {
+                    asm volatile("" : "+v"(hlo));
+                    hk = key_scramble_hi(hlo, hmid);
+                    if constexpr (SPEC) sl = (uint64_t)__umulhi((uint32_t)(hk >> 32), (uint32_t)(cap >> 2)) << 2; else sl = bucket_slot(hk, cap);
                 }
                 if (state == 0) for (;;) {
                     constexpr int NQ = QUAD ? 4 : 2;
@@ -1714,13 +1732,32 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                             uint4 rawq[NQ];
 #pragma unroll
                             for (int q = 0; q < NQ; q++) rawq[q] = *reinterpret_cast<const uint4 *>(&tab[sl + hp * NQ + q]);
-                            if (hp == 0) w0 = rawq[0].w;
+                            if constexpr (SEQ) {
+                                // the dense kernels: all four words of both slots are pinned right behind the loads -- left alone, the compiler splits
+                                // the 16-byte loads and sinks the key words under the test of the count word, a second, dependent load of a line
+                                // already asked for -- and the slots are classified by predicates and selects, no branch between them (np counts
+                                // the slots looked at as before).  The other kernels keep the ladder: pinned, the slots cost them registers they
+                                // do not have (the whole-bucket form would hold 16)
 #pragma unroll
-                            for (int q = 0; q < NQ; q++) {
-                                if (state == 0) {
-                                    np++;
-                                    if (rawq[q].w == 0) state = 1;
-                                    else if (rawq[q].x == (uint32_t)hk && rawq[q].y == (uint32_t)(hk >> 32)) { state = 2; qhit = hp * NQ + q; sst = rawq[q].z; cw = rawq[q].w; }
+                                for (int q = 0; q < NQ; q++) asm volatile("" : "+v"(rawq[q].x), "+v"(rawq[q].y), "+v"(rawq[q].z), "+v"(rawq[q].w));
+                                if (hp == 0) w0 = rawq[0].w;
+#pragma unroll
+                                for (int q = 0; q < NQ; q++) {
+                                    const bool live = state == 0;
+                                    const bool em = rawq[q].w == 0, mt = (rawq[q].x == (uint32_t)hk) & (rawq[q].y == (uint32_t)(hk >> 32)) & !em;
+                                    np += live ? 1u : 0u;
+                                    qhit = (live & mt) ? hp * NQ + q : qhit; sst = (live & mt) ? rawq[q].z : sst; cw = (live & mt) ? rawq[q].w : cw;
+                                    state = live ? (em ? 1 : (mt ? 2 : 0)) : state;
+                                }
+                            } else {
+                                if (hp == 0) w0 = rawq[0].w;
+#pragma unroll
+                                for (int q = 0; q < NQ; q++) {
+                                    if (state == 0) {
+                                        np++;
+                                        if (rawq[q].w == 0) state = 1;
+                                        else if (rawq[q].x == (uint32_t)hk && rawq[q].y == (uint32_t)(hk >> 32)) { state = 2; qhit = hp * NQ + q; sst = rawq[q].z; cw = rawq[q].w; }
+                                    }
                                 }
                             }
                         }
@@ -1800,7 +1837,8 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                     mc &= mc - 1ULL;
                     const uint32_t o_sst = (uint32_t)__builtin_amdgcn_readlane((int)c_sst, w), o_cw = (uint32_t)__builtin_amdgcn_readlane((int)c_cw, w);
                     const uint32_t o_piy = (uint32_t)__builtin_amdgcn_readlane((int)c_piy, w);
-                    const int o_l = __builtin_amdgcn_readlane(l, w);
+                    const uint32_t o_pix = (uint32_t)__builtin_amdgcn_readlane((int)pix, w);
+                    const int o_l = (int)((o_pix >> 14) & 1);
                     const uint32_t cntb = o_cw & SLOT_CNT_MASK;
                     const bool emb = (o_cw & SLOT_EMB) != 0;                  // single-read bin: `start` IS the read id
                     const uint32_t *const ids = o_l ? s.ids[1] : s.ids[0];
@@ -1808,14 +1846,20 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                     const uint32_t *const mrow = s_mask + (o_piy >> 16);
                     const uint64_t o_slot = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)c_slot, w) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(c_slot >> 32), w) << 32);
                     uint32_t lead = 0, hit = HARC_NONE, rd = 0; bool alltop = true; int seen = 0, hit_hd = -1;
+                    // a bin of several reads (at most HARC_LARGEBIN = 16, above that it is SLOT_BIG): lane i fetches the id of entry i, ONE trip for
+                    // the whole bin instead of one in front of every candidate
+                    uint32_t idv = 0;
+                    if (!emb && (uint32_t)lane < cntb) idv = ids[o_sst + lane];
                     for (uint32_t i = cntb; i > 0 && seen < s.maxsearch; i--) {
-                        const uint32_t rid = emb ? o_sst : (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[o_sst + i - 1]);
+                        const uint32_t rid = emb ? o_sst : (uint32_t)__builtin_amdgcn_readlane((int)idv, (int)(i - 1));
                         // taken by this chain earlier in this super-round? (not in the frozen bitmap: the read the consensus came from sits in the first bins of
                         // every step).  Such a read is not a candidate at all; asked of the wave's registers BEFORE anything is fetched for it
                         if (!OWNT && __ballot(ownreg == rid && lane < t)) { alltop = false; continue; }
-                        // claim bit and read words are fetched together (one dependent hop instead of two)
-                        const uint32_t cwd = (uint32_t)__builtin_amdgcn_readfirstlane((int)reinterpret_cast<const uint32_t *>(s.claimed)[rid >> 5]);
+                        // claim word and read words are asked for together, one wait for both: the claim word stays in a vector register until
+                        // the read's load is out (a readfirstlane of it in front of that load puts a full wait between the two)
+                        const uint32_t cwv = reinterpret_cast<const uint32_t *>(s.claimed)[rid >> 5];
                         rd = lane < NW ? reinterpret_cast<const uint32_t *>(s.reads)[(size_t)rid * NW + lane] : 0u;
+                        const uint32_t cwd = (uint32_t)__builtin_amdgcn_readfirstlane((int)cwv);
                         if ((cwd >> (rid & 31u)) & 1u) { if (alltop) lead++; continue; }
                         alltop = false;
                         if (OWNT && __ballot(ownreg == rid && lane < t)) continue;     // (with the LDS table the lanes have weeded most of these out already)
@@ -1836,7 +1880,7 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                         if (lead == cntb) atomicOr(cp, SLOT_DEAD); else if (!emb) atomicMin(cp, (cntb - lead) | (o_cw & SLOT_OVF));
                     }
                     if (hit != HARC_NONE) {
-                        winlane = w; found = hit; fj = __builtin_amdgcn_readlane(j, w); fdir = __builtin_amdgcn_readlane(dir, w); fhd = hit_hd;
+                        winlane = w; found = hit; fj = (int)(o_pix >> 16); fdir = (int)((o_pix >> 13) & 1); fhd = hit_hd;
                         if (lane < NW) rdl[lane] = rd;                         // the accepted read, for updaterefcount
                         break;
                     }

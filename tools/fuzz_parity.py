@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Parity fuzz on the GPU box: random small inputs rich in what the schedule is sensitive to (exact repeats, diverged repeat families,
 poly-A / (CA)n runs, duplicates, N reads, short and long reads), random (K, S, E); libharc_amd.so through its file contract against the
-CPU oracle, every stage-I and stage-II file byte for byte, then the decoder round trip.   [FUZZ_K=k] [FUZZ_S=s] python tools/fuzz_parity.py [iterations] [seed]"""
+CPU oracle, every stage-I and stage-II file byte for byte, then the decoder round trip.  Each iteration also draws the FORM of stage I's chain kernel:
+the library's choice (whole-bucket fetches at these chain counts) or one of the dense forms every run of more than 16 384 chains takes, forced through the
+environment (tests/test_gpu_dense_widths.py FORMS), and a read length from a list that covers every packed-read width W = ceil(2L/64) = 1 ... 8.
+[FUZZ_K=k] [FUZZ_S=s] python tools/fuzz_parity.py [iterations] [seed]"""
 import os
 import sys
 import tempfile
@@ -17,6 +20,35 @@ COMP = np.zeros(256, dtype=np.uint8)
 for a, b in zip(b"ACGTN", b"TGCAN"):
     COMP[a] = b
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+LENGTHS = [32, 40, 63, 64, 65, 96, 99, 100, 100, 101, 128, 129, 150, 150, 160, 161, 192, 193, 224, 225, 250, 255]      # W = 1 ... 8, both sides of the word boundaries
+_Q0 = {"HARC_AMD_QUAD": "0"}
+FORMS = {                                                          # as in tests/test_gpu_dense_widths.py
+    "library": {},
+    "lanes": dict(_Q0, HARC_AMD_SEQ="0"),
+    "seq": dict(_Q0, HARC_AMD_SEQ="1"),
+    "seq_spec": dict(_Q0, HARC_AMD_SEQ="1", HARC_AMD_S1BLOOM_MZMB="0"),
+    "seq_nospec": dict(_Q0, HARC_AMD_SEQ="1", HARC_AMD_S1BLOOM_MZMB="0", HARC_AMD_SPEC="0"),
+    "seq_eager": dict(_Q0, HARC_AMD_SEQ="1", HARC_AMD_LAZY="0"),
+}
+FORM_VARS = sorted({v for env in FORMS.values() for v in env})
+
+
+class forced:
+    """the environment of a form around the GPU calls: set on entry, the caller's own values back on exit"""
+    def __init__(self, env):
+        self.env = env
+
+    def __enter__(self):
+        self.saved = {v: os.environ.get(v) for v in FORM_VARS}
+        for v in FORM_VARS:
+            os.environ.pop(v, None)
+        os.environ.update(self.env)
+
+    def __exit__(self, *exc):
+        for v, old in self.saved.items():
+            os.environ.pop(v, None)
+            if old is not None:
+                os.environ[v] = old
 
 
 def make_reads(rs, L):
@@ -78,7 +110,8 @@ def main():
     bad = 0
     for it in range(iters):
         rs = np.random.RandomState(seed0 * 1000 + it)
-        L = int(rs.choice([40, 63, 100, 100, 100, 101, 150]))
+        L = int(rs.choice(LENGTHS))
+        form = str(rs.choice(list(FORMS)))
         txt = make_reads(rs, L)
         nreads = len(txt) // (L + 1)
         K = int(rs.choice([1, 2, 7, 33, 0, nreads // 64 + 1]))
@@ -100,18 +133,19 @@ def main():
             assert oracle.harc_oracle_encoder(bo.encode(), L, E, None, None) == 0
             s2 = ol.read_dir(bo)
             bg = ol.stage_dir(gd, {k: inputs[k] for k in ["input_clean.dna", "numreads.bin", "input_N.dna"]})
-            harc_amd.reorder(bg, L, num_chains=K, num_steps=S)
-            g1 = ol.read_dir(bg)
-            diff = [f for f in ol.STAGE1_FILES if g1.get(f) != s1[f]]
-            if not diff:
-                harc_amd.encoder(bg, L, num_thr=E)
-                g2 = ol.read_dir(bg)
-                diff = [f for f in ol.stage2_files(E) if g2.get(f) != s2[f]]
+            with forced(FORMS[form]):
+                harc_amd.reorder(bg, L, num_chains=K, num_steps=S)
+                g1 = ol.read_dir(bg)
+                diff = [f for f in ol.STAGE1_FILES if g1.get(f) != s1[f]]
                 if not diff:
-                    harc_amd.decoder(bg, E)
-                    if sorted(ol.read_dir(bg)["output.dna"].split()) != sorted(txt.split()):
-                        diff = ["round trip"]
-            print(f"iter {it}: L={L} reads={nreads} K={K} S={S} E={E} -> {'OK' if not diff else 'DIFF ' + ','.join(diff)}", flush=True)
+                    harc_amd.encoder(bg, L, num_thr=E)
+                    g2 = ol.read_dir(bg)
+                    diff = [f for f in ol.stage2_files(E) if g2.get(f) != s2[f]]
+                    if not diff:
+                        harc_amd.decoder(bg, E)
+                        if sorted(ol.read_dir(bg)["output.dna"].split()) != sorted(txt.split()):
+                            diff = ["round trip"]
+            print(f"iter {it}: L={L} W={(2 * L + 63) // 64} form={form} reads={nreads} K={K} S={S} E={E} -> {'OK' if not diff else 'DIFF ' + ','.join(diff)}", flush=True)
             bad += bool(diff)
     print(f"{iters - bad} / {iters} identical to the oracle")
     return 1 if bad else 0

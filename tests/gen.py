@@ -162,6 +162,32 @@ def reads_text_hugebin_stage1(seed, n_core=9000, n_norm=6000, L=100, genome_len=
     return lines_of(np.frombuffer(b"ACGT", dtype=np.uint8)[allr])
 
 
+def reads_text_hugebin_families(seed, L, n_core=10400, n_norm=6000, genome_len=60000, fam_size=4):
+    """stage-I bins above maxsearch and above 4096 at ANY read length, with hits deep inside them: n_core // fam_size random templates of L bases, each
+    repeated fam_size times with one substitution at a random column (mates pass the Hamming threshold of 4), then columns [L/2 - w - 3, L/2 + 5) of all of
+    them -- the first dictionary's whole window, w as harc:57-58 -- overwritten with one shared string.  Mixed with n_norm reads of an i.i.d. genome, permuted,
+    odd reads reverse-complemented: the core reads that stay forward share their first-dictionary k-mer, the reversed ones their second-dictionary k-mer --
+    one bin of about n_core / 2 reads in each dictionary, whose scans find mates inside the maxsearch window and miss the ones beyond it"""
+    rs = np.random.RandomState(seed)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    nfam = n_core // fam_size
+    core = np.repeat(rs.randint(0, 4, (nfam, L)), fam_size, axis=0)
+    m = core.shape[0]
+    col = rs.randint(0, L, size=m)
+    core[np.arange(m), col] = (core[np.arange(m), col] + rs.randint(1, 4, size=m)) % 4
+    w = 32 if L >= 100 else 32 * L // 100                              # harc:57-58
+    lo, hi = max(0, L // 2 - w - 3), L // 2 + 5
+    core[:, lo:hi] = rs.randint(0, 4, hi - lo)
+    g = rs.randint(0, 4, genome_len)
+    st = rs.randint(0, genome_len - L, n_norm)
+    norm = g[st[:, None] + np.arange(L)[None, :]]
+    allr = np.concatenate([core, norm])
+    r = acgt[allr[rs.permutation(allr.shape[0])]]
+    odd = np.arange(r.shape[0]) % 2 == 1
+    r[odd] = _COMP[r[odd][:, ::-1]]
+    return lines_of(r)
+
+
 def auto_chains(n_clean, reads_per_chain=2048, clean=None):
     """auto_chains() of harc_amd/csrc/stage1.hip: K when harc_amd_params.num_chains = 0.  clean: the clean reads ([n, L] uint8 array or
     the lines of input_clean.dna) for the low-coverage rule of stage1_run_w -- more than 98 % distinct first-dictionary k-mers: up to

@@ -435,10 +435,10 @@ def test_stage2_big_bins_partial_claims_exact(K, S, E, seed, fail, sched, oracle
     assert 200 < nleft < 3000 - 200                              # some were taken, some never are
 
 
-@pytest.mark.parametrize("L,sched", [(150, ""), (150, "rank0=2"), (250, ""), (250, "wave"), (106, "rank0=1"), (107, "")])
+@pytest.mark.parametrize("L,sched", [(150, ""), (150, "rank0=2"), (250, ""), (250, "wave"), (106, "rank0=1"), (107, ""), (170, ""), (171, ""), (171, "wave"), (255, "rank0=2")])
 def test_stage2_big_bins_other_read_lengths(L, sched, oracle, tmp_path, monkeypatch):
     """the same partly matching bins above maxsearch at other read lengths: k_realign_block is compiled for windows of up to 5 / 8 / 12 words of the
-    3-bit code (reads of up to 106 / 170 / 255 bases)"""
+    3-bit code (reads of up to 106 / 170 / 255 bases) -- both sides of either boundary and the longest read"""
     import harc_amd
     _set_sched(monkeypatch, sched)
     txt = gen.reads_text_bigbin_stage2_mixed(11 + L, L=L, genome_len=8000, fail_frac=0.5, nsub=max(16, L // 3))

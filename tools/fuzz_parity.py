@@ -4,6 +4,8 @@ poly-A / (CA)n runs, duplicates, N reads, short and long reads), random (K, S, E
 CPU oracle, every stage-I and stage-II file byte for byte, then the decoder round trip.  Each iteration also draws the FORM of stage I's chain kernel:
 the library's choice (whole-bucket fetches at these chain counts) or one of the dense forms every run of more than 16 384 chains takes, forced through the
 environment (tests/test_gpu_dense_widths.py FORMS), and a read length from a list that covers every packed-read width W = ceil(2L/64) = 1 ... 8.
+After (K, S, E) it draws the waves per workgroup of the cooperative kernel (HARC_AMD_COOP_WAVES unset, 1, 2 or 4) and whether the few-chains kernel steps by
+successor list (HARC_AMD_SUCC unset or 1), as tests/test_gpu_large_bin_widths.py forces them; input, form and schedule of an iteration are what they were.
 [FUZZ_K=k] [FUZZ_S=s] python tools/fuzz_parity.py [iterations] [seed]"""
 import os
 import sys
@@ -30,7 +32,9 @@ FORMS = {                                                          # as in tests
     "seq_nospec": dict(_Q0, HARC_AMD_SEQ="1", HARC_AMD_S1BLOOM_MZMB="0", HARC_AMD_SPEC="0"),
     "seq_eager": dict(_Q0, HARC_AMD_SEQ="1", HARC_AMD_LAZY="0"),
 }
-FORM_VARS = sorted({v for env in FORMS.values() for v in env})
+COOP_WAVES = [None, "1", "2", "4"]                                 # None: the library's own rule
+SUCC = [None, "1"]                                                 # None: lists in exact mode (one chain) only
+FORM_VARS = sorted({v for env in FORMS.values() for v in env} | {"HARC_AMD_COOP_WAVES", "HARC_AMD_SUCC"})
 
 
 class forced:
@@ -117,6 +121,8 @@ def main():
         K = int(rs.choice([1, 2, 7, 33, 0, nreads // 64 + 1]))
         S = int(rs.choice([1, 4, 16, 16, 32, 64]))
         E = int(rs.choice([1, 2, 5]))
+        waves, succ = COOP_WAVES[rs.randint(0, len(COOP_WAVES))], SUCC[rs.randint(0, len(SUCC))]
+        env = dict(FORMS[form], **{k: v for k, v in (("HARC_AMD_COOP_WAVES", waves), ("HARC_AMD_SUCC", succ)) if v is not None})
         if os.environ.get("FUZZ_K"): K = int(os.environ["FUZZ_K"])          # e.g. FUZZ_K=1 FUZZ_S=64: exact mode only
         if os.environ.get("FUZZ_S"): S = int(os.environ["FUZZ_S"])
         with tempfile.TemporaryDirectory() as d:
@@ -133,7 +139,7 @@ def main():
             assert oracle.harc_oracle_encoder(bo.encode(), L, E, None, None) == 0
             s2 = ol.read_dir(bo)
             bg = ol.stage_dir(gd, {k: inputs[k] for k in ["input_clean.dna", "numreads.bin", "input_N.dna"]})
-            with forced(FORMS[form]):
+            with forced(env):
                 harc_amd.reorder(bg, L, num_chains=K, num_steps=S)
                 g1 = ol.read_dir(bg)
                 diff = [f for f in ol.STAGE1_FILES if g1.get(f) != s1[f]]
@@ -145,7 +151,7 @@ def main():
                         harc_amd.decoder(bg, E)
                         if sorted(ol.read_dir(bg)["output.dna"].split()) != sorted(txt.split()):
                             diff = ["round trip"]
-            print(f"iter {it}: L={L} W={(2 * L + 63) // 64} form={form} reads={nreads} K={K} S={S} E={E} -> {'OK' if not diff else 'DIFF ' + ','.join(diff)}", flush=True)
+            print(f"iter {it}: L={L} W={(2 * L + 63) // 64} form={form} reads={nreads} K={K} S={S} E={E} COOP_WAVES={waves or '-'} SUCC={succ or '-'} -> {'OK' if not diff else 'DIFF ' + ','.join(diff)}", flush=True)
             bad += bool(diff)
     print(f"{iters - bad} / {iters} identical to the oracle")
     return 1 if bad else 0

@@ -131,6 +131,12 @@ CASES = {
     # mirror, the COOP kernel and the scan budget of the GPU build all sit on this path)
     "L100_repfam_5k": dict(custom="repfam", seed=41, n=5000, L=100, genome_len=40000, ncopy=40, div=0.10, npolya=8, nstr=4, err=0.004),
     "L101_repfam_4k": dict(custom="repfam", seed=42, n=4000, L=101, genome_len=30000, ncopy=30, div=0.13, npolya=6, nstr=4, err=0.006),
+    # the upper side of four word boundaries of the 3-bit store (W3 = ceil(3L/64) = 2, 3, 5, 11), half of the errors N: stage II's windows of 9 + 10
+    # bases (L = 22) and 18 + 18 (L = 43), the `L <= 50` formulas of encoder.cpp:132-145, and the minimizer proposer at 86 and 214
+    "L22_err_2k": dict(seed=51, n=2000, L=22, genome_len=3000, err=0.02, n_frac=0.5),
+    "L43_err_2k": dict(seed=52, n=2000, L=43, genome_len=5000, err=0.02, n_frac=0.5),
+    "L86_err_2k": dict(seed=53, n=2000, L=86, genome_len=9000, err=0.02, n_frac=0.5),
+    "L214_err_1k": dict(seed=54, n=1000, L=214, genome_len=10000, err=0.02, n_frac=0.5),
 }
 
 

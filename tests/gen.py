@@ -237,3 +237,50 @@ def auto_steps(clean, K):
         large += int(cnt[cnt > 16].sum())
     lowcov = nb1 > 0.98 * n
     return 32 if (K > 16384 or (K >= 2048 and not lowcov)) and large * 50 <= n else 16
+
+
+def edge_columns_3bit(L):
+    """the columns of a read of L bases at which the 3-bit store (three bits a base, 64-bit words) has an edge: the first and the last base, bases 31 and
+    32 (the word boundary of the 2-bit copies), every base whose field straddles two words (3b mod 64 > 61) and the first and last whole field of a word"""
+    cols = {0, L - 1} | {b for b in (31, 32) if b < L}
+    cols |= {b for b in range(L) if (3 * b) % 64 > 61}
+    cols |= {b for b in range(L) if (3 * b) % 64 == 0 or (3 * b + 3) % 64 == 0}
+    return sorted(cols)
+
+
+def reads_text_edge_N(seed, n, L, genome_len, n_share=0.3, err=0.01):
+    """reads of an i.i.d. genome with substitutions only (reads_array with n_frac = 0), of which a random n_share then get one to three N each, all of them
+    at columns of edge_columns_3bit(L): every N of the input sits where a kernel that puts a 3-bit field together by hand can drop half of it"""
+    r = reads_array(seed, n, L, genome_len, err=err, n_frac=0.0)
+    rs = np.random.RandomState(seed + 1)
+    cols = np.array(edge_columns_3bit(L))
+    for i in np.nonzero(rs.random_sample(n) < n_share)[0]:
+        k = min(int(rs.randint(1, 4)), cols.size)
+        r[i, rs.choice(cols, size=k, replace=False)] = ord("N")
+    return lines_of(r)
+
+
+def reads_text_bigbin_stage2_at(seed, L, n_clean=4000, n_dupN=3000, genome_len=8000, copies=3, fail_frac=0.5):
+    """reads_text_bigbin_stage2_mixed for any read length: the N reads share their first P bases -- through the end of stage II's second window
+    (encoder.cpp:132-145: 42 bases above 50 bp, 41 * L / 50 + 1 below) -- and differ in the free columns [P, L) only: the one N of every read and the
+    nsub = min(L - P - 1, max(16, L / 3)) substitutions of the failing share go there"""
+    rs = np.random.RandomState(seed)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    P = 42 if L > 50 else 41 * L // 50 + 1
+    nsub = min(L - P - 1, max(16, L // 3))
+    genome = acgt[rs.randint(0, 4, size=genome_len)]
+    win = genome[200:200 + L].copy()
+    for k in range(1, copies):
+        at = 200 + k * (genome_len - 400) // copies
+        genome[at:at + L] = win
+    starts = rs.randint(0, genome_len - L, size=n_clean)
+    clean = genome[starts[:, None] + np.arange(L)[None, :]].copy()
+    dup = np.tile(win, (n_dupN, 1)).copy()
+    bad = rs.rand(n_dupN) < fail_frac
+    for i in np.nonzero(bad)[0]:
+        cols = rs.choice(np.arange(P, L), size=nsub, replace=False)
+        dup[i, cols] = acgt[(np.searchsorted(acgt, dup[i, cols]) + 1 + rs.randint(0, 3, size=nsub)) % 4]
+    dup[np.arange(n_dupN), rs.randint(P, L, size=n_dupN)] = ord("N")
+    allr = np.concatenate([clean, dup])
+    rs.shuffle(allr)
+    return lines_of(allr)

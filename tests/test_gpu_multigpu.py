@@ -113,7 +113,9 @@ def _run_ranks(world, slices, L, E, K, S, mbox):
     return res
 
 
-@pytest.mark.parametrize("world,n,L,err,E,K,S", [(2, 30000, 100, 0.01, 2, 9, 16), (3, 24000, 100, 0.02, 1, 0, 16), (2, 9000, 150, 0.01, 1, 4, 8)])
+@pytest.mark.parametrize("world,n,L,err,E,K,S", [(2, 30000, 100, 0.01, 2, 9, 16), (3, 24000, 100, 0.02, 1, 0, 16), (2, 9000, 150, 0.01, 1, 4, 8),
+                                                 # k_bucket3 and the exchange of reads with N at 3, 5, 11 and 12 words of the 3-bit store, the upper side of a word boundary each
+                                                 (2, 9000, 43, 0.02, 1, 4, 8), (2, 9000, 86, 0.02, 1, 4, 8), (2, 9000, 214, 0.02, 1, 4, 8), (2, 9000, 235, 0.02, 1, 4, 8)])
 def test_two_ranks_one_gpu_match_the_cpu_model(world, n, L, err, E, K, S, oracle, tmp_path):
     os.environ["HARC_AMD_MAILBOX_TIMEOUT"] = "120"
     arr = gen.reads_array(77 + world, n, L, 8 * n, err=err)

@@ -485,7 +485,15 @@ def _fastq(reads, L):
     return b"".join(b"@T.%d\n%s\n+\n%s\n" % (i, r, b"H" * L) for i, r in enumerate(reads))
 
 
-@pytest.mark.parametrize("case,K,S,E", [(c, 1 + (i % 3) * 7, 16 if i % 2 else 4, 1 + i % 4) for i, c in enumerate(CASES)])
+# the schedule of a case goes by its position in this list -- the sixteen fixtures as ol.golden_cases() listed them before the fixtures at the word
+# boundaries of the 3-bit store came, then those: a new fixture goes to the end and moves nobody's (K, S, E)
+_PRESERVE_ORDER_CASES = ["L100_allN_20", "L100_bigbin2_5k", "L100_clean_5k", "L100_err_5k", "L100_gen_noRC_e_3k", "L100_lowcov_4k", "L100_one", "L100_repeat_dup_4k",
+                         "L100_repfam_5k", "L100_three", "L101_err_3k", "L101_repfam_4k", "L150_err_3k", "L255_err_1k", "L40_err_3k", "L63_err_3k",
+                         "L22_err_2k", "L43_err_2k", "L86_err_2k", "L214_err_1k"]
+assert sorted(_PRESERVE_ORDER_CASES) == CASES
+
+
+@pytest.mark.parametrize("case,K,S,E", [(c, 1 + (i % 3) * 7, 16 if i % 2 else 4, 1 + i % 4) for i, c in enumerate(_PRESERVE_ORDER_CASES)])
 def test_preserve_order_roundtrip_is_the_input_file(case, K, S, E, tmp_path):
     """-p: compress (FASTQ ingest on the GPU, stage I, stage II, pack_order) then unpack_order + decoder_preserve + merge_N in
     harc_amd_decoder_preserve_files gives back the sequence lines of the FASTQ in their original order, N reads included
@@ -896,7 +904,9 @@ def test_partition_kernel_is_a_stable_sort_by_bucket():
     h.close()
 
 
-_FUZZ_L = [20, 31, 32, 33, 47, 50, 51, 64, 65, 95, 96, 97, 127, 128, 129, 159, 160, 161, 191, 192, 193, 223, 224, 225, 254]
+_FUZZ_L = [20, 31, 32, 33, 47, 50, 51, 64, 65, 95, 96, 97, 127, 128, 129, 159, 160, 161, 191, 192, 193, 223, 224, 225, 254,
+           21, 22, 42, 43, 85, 86, 106, 107, 149, 150, 170, 171, 213, 214, 234, 235]        # the boundaries of the 3-bit store that are none of the 2-bit store
+assert all(L in _FUZZ_L and L + 1 in _FUZZ_L for b in (2, 3) for L in range(1, 255) if (b * L + 63) // 64 != (b * L + b + 63) // 64)
 
 
 @pytest.mark.parametrize("L", _FUZZ_L)

@@ -6,6 +6,8 @@ the library's choice (whole-bucket fetches at these chain counts) or one of the 
 environment (tests/test_gpu_dense_widths.py FORMS), and a read length from a list that covers every packed-read width W = ceil(2L/64) = 1 ... 8.
 After (K, S, E) it draws the waves per workgroup of the cooperative kernel (HARC_AMD_COOP_WAVES unset, 1, 2 or 4) and whether the few-chains kernel steps by
 successor list (HARC_AMD_SUCC unset or 1), as tests/test_gpu_large_bin_widths.py forces them; input, form and schedule of an iteration are what they were.
+A stream of random numbers of its own then moves every third iteration or so to a read length at a word boundary of the 3-bit store (W3 = ceil(3L/64),
+tests/test_gpu_stage2_widths.py LENGTHS): the other iterations keep their inputs, and a moved one keeps every other draw.
 [FUZZ_K=k] [FUZZ_S=s] python tools/fuzz_parity.py [iterations] [seed]"""
 import os
 import sys
@@ -23,6 +25,7 @@ for a, b in zip(b"ACGTN", b"TGCAN"):
     COMP[a] = b
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 LENGTHS = [32, 40, 63, 64, 65, 96, 99, 100, 100, 101, 128, 129, 150, 150, 160, 161, 192, 193, 224, 225, 250, 255]      # W = 1 ... 8, both sides of the word boundaries
+LENGTHS_W3 = [21, 22, 42, 43, 64, 65, 85, 86, 106, 107, 128, 129, 149, 150, 170, 171, 192, 193, 213, 214, 234, 235, 255]     # both sides of the word boundaries of the 3-bit store
 _Q0 = {"HARC_AMD_QUAD": "0"}
 FORMS = {                                                          # as in tests/test_gpu_dense_widths.py
     "library": {},
@@ -115,6 +118,9 @@ def main():
     for it in range(iters):
         rs = np.random.RandomState(seed0 * 1000 + it)
         L = int(rs.choice(LENGTHS))
+        rs3 = np.random.RandomState(seed0 * 1000 + it + (3 << 24))   # the later draws' own stream: rs gives what it always gave
+        if rs3.randint(0, 3) == 0:
+            L = int(rs3.choice(LENGTHS_W3))
         form = str(rs.choice(list(FORMS)))
         txt = make_reads(rs, L)
         nreads = len(txt) // (L + 1)
@@ -151,7 +157,7 @@ def main():
                         harc_amd.decoder(bg, E)
                         if sorted(ol.read_dir(bg)["output.dna"].split()) != sorted(txt.split()):
                             diff = ["round trip"]
-            print(f"iter {it}: L={L} W={(2 * L + 63) // 64} form={form} reads={nreads} K={K} S={S} E={E} COOP_WAVES={waves or '-'} SUCC={succ or '-'} -> {'OK' if not diff else 'DIFF ' + ','.join(diff)}", flush=True)
+            print(f"iter {it}: L={L} W={(2 * L + 63) // 64} W3={(3 * L + 63) // 64} form={form} reads={nreads} K={K} S={S} E={E} COOP_WAVES={waves or '-'} SUCC={succ or '-'} -> {'OK' if not diff else 'DIFF ' + ','.join(diff)}", flush=True)
             bad += bool(diff)
     print(f"{iters - bad} / {iters} identical to the oracle")
     return 1 if bad else 0

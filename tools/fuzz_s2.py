@@ -2,7 +2,9 @@
 """Fuzz of stage II's window passes on the GPU box: random inputs with bins above maxsearch whose reads only partly pass the Hamming test and are probed
 from several places of the consensus (tests/gen.py reads_text_bigbin_stage2_mixed, random depth / copies / failing share / read length), every form the
 passes can take (an event per lane, a wave per event, that in two kernels; narrow rank ranges, flat passes, no chaser; with and without the two rules
-about who looks again) against the CPU oracle, every stage-II file byte for byte.      python tools/fuzz_s2.py [iterations] [seed]"""
+about who looks again) against the CPU oracle, every stage-II file byte for byte.  A stream of random numbers of its own moves every other iteration to
+one of the read lengths at the word boundaries of the 3-bit store (tests/test_gpu_stage2_widths.py LENGTHS), through gen.reads_text_bigbin_stage2_at where
+the length is none of the four above; the other iterations keep their inputs, and all keep their forms.      python tools/fuzz_s2.py [iterations] [seed]"""
 import os
 import sys
 import tempfile
@@ -17,6 +19,7 @@ from tests import gen, oracle_lib as ol                            # noqa: E402
 FORMS = [{"HARC_AMD_S2_BLOCK": "1"}, {"HARC_AMD_S2_BLOCK": "0"}, {"HARC_AMD_S2_TWOKERNELS": "1"}, {}]
 SCHED = [{}, {"HARC_AMD_S2_RANK0": "1"}, {"HARC_AMD_S2_RANK0": "3"}, {"HARC_AMD_S2_FLATPASSES": "1"}, {"HARC_AMD_S2_NOCHASE": "1"}, {"HARC_AMD_S2_RANK0": "2", "HARC_AMD_S2_NOCHASE": "1"}]
 RULES = [{}, {}, {"HARC_AMD_S2_RANGE": "0"}, {"HARC_AMD_S2_EBOT": "0"}, {"HARC_AMD_S2_RANGE": "0", "HARC_AMD_S2_EBOT": "0"}, {"HARC_AMD_S2_COMPACT": "0"}, {"HARC_AMD_S2_COMPACT": "0", "HARC_AMD_S2_EBOT": "0"}]
+LENGTHS_W3 = [21, 22, 42, 43, 64, 65, 85, 86, 106, 107, 128, 129, 149, 150, 170, 171, 192, 193, 213, 214, 234, 235, 255]
 KEYS = sorted({k for group in (FORMS, SCHED, RULES) for e in group for k in e})
 
 
@@ -31,9 +34,16 @@ def main():
         ndup = int(rs.choice([1300, 2200, 3000, 4300, 6100]))
         copies = int(rs.choice([1, 2, 3, 5]))
         fail = float(rs.choice([0.0, 0.3, 0.5, 0.8]))
-        nsub = max(4, min(L - 52, int(rs.choice([20, 32, 40]))))
-        txt = gen.reads_text_bigbin_stage2_mixed(int(rs.randint(1, 1 << 30)), n_clean=int(rs.choice([2000, 4000])), n_dupN=ndup, L=L, genome_len=int(rs.choice([5000, 9000])),
-                                                 copies=copies, fail_frac=fail, nsub=nsub)
+        nsub = int(rs.choice([20, 32, 40]))
+        seed, n_clean, glen = int(rs.randint(1, 1 << 30)), int(rs.choice([2000, 4000])), int(rs.choice([5000, 9000]))
+        rs3 = np.random.RandomState(seed0 * 1000 + it + (3 << 24))   # the later draws' own stream: rs gives what it always gave
+        if rs3.randint(0, 2) == 0:
+            L = int(rs3.choice(LENGTHS_W3))
+        if L in (100, 101, 150, 63):
+            nsub = max(4, min(L - 52, nsub))
+            txt = gen.reads_text_bigbin_stage2_mixed(seed, n_clean=n_clean, n_dupN=ndup, L=L, genome_len=glen, copies=copies, fail_frac=fail, nsub=nsub)
+        else:
+            txt = gen.reads_text_bigbin_stage2_at(seed, L, n_clean=n_clean, n_dupN=ndup, genome_len=glen, copies=copies, fail_frac=fail)
         K = int(rs.choice([1, 2, 4, 8])); S = 16; E = int(rs.choice([1, 2, 3]))
         with tempfile.TemporaryDirectory() as d:
             od = os.path.join(d, "o"); os.makedirs(od)

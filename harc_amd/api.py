@@ -88,6 +88,9 @@ def lib():
     l.harc_amd_set_fastq_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     l.harc_amd_bgzf_inflate_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     l.harc_amd_set_fastq_bgzf_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_fastq_assemble_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64,
+                                                 C.POINTER(C.c_uint64)]
+    l.harc_amd_fastq_assemble_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]
     l.harc_amd_decode_signature.argtypes = [ctx, C.POINTER(C.c_uint64)]
     l.harc_amd_input_signature.argtypes = [ctx, C.POINTER(C.c_uint64)]
     l.harc_amd_reads_signature_device.argtypes = [ctx, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
@@ -207,6 +210,13 @@ def decoder(basedir, num_thr_e, device=0, preserve_order=False, memory_gb=0):
     _check(f(C.byref(p), os.fsencode(basedir), num_thr_e))
 
 
+def fastq_assemble(dna, ids, quality, out, device=0):
+    """line i of the files `dna` (fixed-length reads), `ids` and `quality` -> record i of the FASTQ file `out` (id, read, a bare '+', quality), assembled on
+    the GPU; the read length is that of the first read (include/harc_amd.h: harc_amd_fastq_assemble_files)"""
+    p = default_params(100, device=device)
+    _check(lib().harc_amd_fastq_assemble_files(C.byref(p), os.fsencode(dna), os.fsencode(ids), os.fsencode(quality), os.fsencode(out)))
+
+
 def pack_order(basedir, readlen=100, **kw):
     """== `pack_order.out <basedir>` (src/pack_order.cpp:11-77)"""
     p = default_params(readlen, **kw)
@@ -254,6 +264,15 @@ class HarcAmd:
         n = C.c_uint64(0)
         _check(lib().harc_amd_bgzf_inflate_device(self._ctx, C.c_void_p(dptr), nbytes, C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
         return n.value
+
+    def fastq_assemble_device(self, d_ids, id_bytes, d_dna, d_quality, n, readlen, out_ptr=None, out_capacity=0):
+        """n ids (id_bytes of text, a line each), reads and quality values (n lines of readlen + 1 bytes each) in device memory -> the n FASTQ records at
+        out_ptr (device memory); without out_ptr the inputs are only validated. -> bytes of the records"""
+        n_out = C.c_uint64(0)
+        _check(lib().harc_amd_fastq_assemble_device(self._ctx, C.c_void_p(d_ids) if d_ids else None, id_bytes, C.c_void_p(d_dna) if d_dna else None,
+                                                    C.c_void_p(d_quality) if d_quality else None, n, readlen, C.c_void_p(out_ptr) if out_ptr else None,
+                                                    out_capacity, C.byref(n_out)))
+        return n_out.value
 
     def set_fastq_bgzf_device(self, dptr, nbytes):
         """set_fastq_device for a BGZF-compressed FASTQ in device memory (inflated on the GPU) -> complete records"""

@@ -1,0 +1,369 @@
+// fastq_out.hip -- the way back to FASTQ (./harc -d -q): the three files a -c -q run took the FASTQ apart into -- one id per line, one read per line, one
+// quality string per line -- become 4-line records again, on the GPU.  Record i of the output is
+//     id_i \n read_i \n + \n quality_i \n
+// The third line is a bare '+': preprocess drops whatever followed it in the input, so nothing else can be restored.
+//
+// A streaming kernel: B bytes in, B bytes out, its floor is a device-to-device copy.  It is OUTPUT-centric.  A workgroup owns one 16-byte-aligned tile of
+// FQ_TILE output bytes; it finds the first record that reaches into the tile by binary search on out_off[i] = id_start[i] + i * (2 * readlen + 4) (the line
+// index of the id text is the only index there is: reads and quality values have a fixed stride), its waves take the records of the tile round robin and
+// build an image of the tile in LDS, and the image leaves with one aligned 16-byte store per lane.  A lane of the wave that copies a record owns one aligned
+// DWORD of the image: it fetches the (up to two) aligned source dwords that hold its four bytes from whichever of id / read / quality they come from, shifts them
+// into place (v_alignbyte) and writes the dword; only a dword that a record shares with its neighbour (another wave's) is written byte by byte.  A record
+// longer than a tile (an id of 40 000 bytes) is simply clipped to the tile by every workgroup it reaches into.  The first and the last 16 bytes of the whole
+// output, where the caller's buffer is not aligned or does not end on a 16-byte boundary, are stored byte by byte by the lanes that hold them.
+// The same lanes check the fixed-width inputs on the way -- a newline at every (readlen + 1)-stride position and nowhere else -- into an error counter.
+#include "devutil.h"
+#include "fileio.h"
+
+#define FQ_TILE 16384
+#define FQ_WAVES 4
+
+// The part of the image dword at tile byte p that comes from a source segment: the segment's bytes go to tile bytes [d0, d0 + len), src is its first byte.
+// Returns the bytes in place (others zero), *mask has 0xFF for each.  An aligned source dword is fetched only when one of the bytes asked for lies in it.
+__device__ __forceinline__ uint32_t fq_seg(const char *src, int64_t d0, int64_t len, int64_t p, uint32_t *mask)
+{
+    const int64_t a = d0 - p, b = d0 + len - p;                   // the segment in the dword's own coordinates
+    const int k0 = a > 0 ? (a < 4 ? (int)a : 4) : 0, k1 = b < 4 ? (b > 0 ? (int)b : 0) : 4;
+    if (k0 >= k1) { *mask = 0; return 0; }
+    const uintptr_t u = (uintptr_t)src + (uintptr_t)(p - d0);    // where byte 0 of the dword comes from (in front of src when k0 > 0: not fetched)
+    const int sh = (int)(u & 3);
+    const uint32_t *w = (const uint32_t *)(u - (uintptr_t)sh);
+    uint32_t lo = 0, hi = 0;                                      // w[0] holds bytes [-sh, 4 - sh) of the dword, w[1] bytes [4 - sh, 8 - sh)
+    if (k0 < 4 - sh) lo = w[0];
+    if (k1 > 4 - sh) hi = w[1];
+    const uint32_t v = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)sh);
+    const uint32_t m = (k1 == 4 ? 0xFFFFFFFFu : ((1u << (8 * k1)) - 1u)) & ~((1u << (8 * k0)) - 1u);
+    *mask = m;
+    return v & m;
+}
+// bytes of a fixed-width line (L characters and a newline, at tile bytes [d0, d0 + L + 1)) in the dword at p that break the stride: a newline that is not the
+// line's last byte, or a last byte that is no newline
+__device__ __forceinline__ uint32_t fq_stride_errors(uint32_t v, uint32_t m, int64_t d0, int L, int64_t p)
+{
+    const int64_t knl = d0 + L - p;                               // where the newline belongs, in the dword's coordinates
+    uint32_t bad = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const bool mine = (m >> (8 * k)) & 1u, isnl = ((v >> (8 * k)) & 0xFFu) == (uint32_t)'\n';
+        bad += (mine && isnl != (knl == (int64_t)k)) ? 1u : 0u;
+    }
+    return bad;
+}
+__device__ __forceinline__ void fq_const(char ch, int64_t at, int64_t p, uint32_t *v, uint32_t *m)
+{
+    const int64_t k = at - p;
+    if (k >= 0 && k < 4) { *v |= (uint32_t)(uint8_t)ch << (8 * (int)k); *m |= 0xFFu << (8 * (int)k); }
+}
+
+// Tile t holds the output bytes whose ADDRESS, counted from the 16-byte boundary at or below out, lies in [t * FQ_TILE, (t + 1) * FQ_TILE): `mis` = out & 15.
+// nls: the line index of the id text (build_line_index; nls[-1] = -1).  err[0] / err[1]: stride errors of the reads / the quality values.
+__global__ __launch_bounds__(64 * FQ_WAVES) void k_fq_tiles(const char *ids, const uint64_t *nls, const char *dna, const char *qual, uint32_t n, int L,
+                                                            char *out, uint64_t total, uint32_t mis, uint64_t ntiles, unsigned int *err)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t tile[FQ_TILE / 4];
+    __shared__ uint32_t s_first;
+    const uint64_t t = harc_bid();
+    if (t >= ntiles) return;
+    const uint64_t K = 2ull * (uint64_t)L + 4, LL = (uint64_t)L + 1;
+    const int64_t v0 = (int64_t)(t * FQ_TILE);                    // first byte of the tile, counted from the aligned boundary
+    if (threadIdx.x == 0) {
+        // the last record that starts at or in front of the tile's first output byte
+        const uint64_t o0 = v0 > (int64_t)mis ? (uint64_t)v0 - mis : 0;
+        uint64_t lo = 0, hi = (uint64_t)n - 1;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi + 1) >> 1;
+            if (nls[(int64_t)mid - 1] + 1 + mid * K <= o0) lo = mid; else hi = mid - 1;
+        }
+        s_first = (uint32_t)lo;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint32_t errR = 0, errQ = 0;
+    uint8_t *tile8 = (uint8_t *)tile;
+    for (uint64_t i = (uint64_t)s_first + wave; i < (uint64_t)n; i += FQ_WAVES) {
+        const uint64_t ids0 = nls[(int64_t)i - 1] + 1, idlen = nls[i] - ids0;
+        const int64_t b = (int64_t)(ids0 + i * K) + (int64_t)mis - v0;       // the record in the tile's coordinates: [b, e)
+        if (b >= FQ_TILE) break;
+        const int64_t e = b + (int64_t)(idlen + 1 + K);              // id and its newline, then the 2 * readlen + 4 bytes every record has
+        const int64_t clo = b > 0 ? b : 0, chi = e < FQ_TILE ? e : FQ_TILE;
+        const int64_t d_read = b + (int64_t)idlen + 1, d_plus = d_read + (int64_t)LL, d_qual = d_plus + 2;
+        const char *s_id = ids + ids0, *s_read = dna + i * LL, *s_qual = qual + i * LL;
+        for (int64_t j = (clo >> 2) + lane; j < ((chi + 3) >> 2); j += 64) {
+            const int64_t p = 4 * j;
+            uint32_t m0, m1, m2;
+            uint32_t v = fq_seg(s_id, b, (int64_t)idlen, p, &m0);
+            const uint32_t vr = fq_seg(s_read, d_read, (int64_t)LL, p, &m1);      // the line's own newline comes with it
+            const uint32_t vq = fq_seg(s_qual, d_qual, (int64_t)LL, p, &m2);
+            if (m1) errR += fq_stride_errors(vr, m1, d_read, L, p);
+            if (m2) errQ += fq_stride_errors(vq, m2, d_qual, L, p);
+            v |= vr | vq;
+            uint32_t m = m0 | m1 | m2;
+            fq_const('\n', d_read - 1, p, &v, &m);
+            fq_const('+', d_plus, p, &v, &m);
+            fq_const('\n', d_plus + 1, p, &v, &m);
+            if (m == 0xFFFFFFFFu) tile[j] = v;                    // p >= 0 and p + 4 <= FQ_TILE: all four bytes are this record's and inside the tile
+            else {
+#pragma unroll
+                for (int k = 0; k < 4; k++) if ((m >> (8 * k)) & 1u) tile8[p + k] = (uint8_t)(v >> (8 * k));      // (m never covers a byte outside [clo, chi))
+            }
+        }
+    }
+    if (errR) atomicAdd(&err[0], errR);
+    if (errQ) atomicAdd(&err[1], errQ);
+    __syncthreads();
+    char *gbase = out - mis;
+    const int64_t vlo = (int64_t)mis, vhi = (int64_t)mis + (int64_t)total;       // the output's bytes, counted from the aligned boundary
+    for (int ch = threadIdx.x; ch < FQ_TILE / 16; ch += 64 * FQ_WAVES) {
+        const int64_t g = v0 + 16 * (int64_t)ch;
+        if (g >= vlo && g + 16 <= vhi) *(uint4 *)(gbase + g) = ((const uint4 *)tile)[ch];
+        else if (g + 16 > vlo && g < vhi) {                       // the ragged head or tail of the whole output
+            for (int k = 0; k < 16; k++) if (g + k >= vlo && g + k < vhi) gbase[g + k] = (char)tile8[16 * ch + k];
+        }
+    }
+}
+// the stride check alone (d_out == NULL): 16 bytes per thread of n lines of L characters and a newline
+__global__ void k_fq_stride_check(const char *txt, uint64_t nbytes, int L, unsigned int *err)
+{
+    const uint64_t at = harc_gid() * 16;
+    if (at >= nbytes) return;
+    const uint64_t LL = (uint64_t)L + 1;
+    uint32_t q = (uint32_t)(at % LL), bad = 0;
+    for (int k = 0; k < 16 && at + k < nbytes; k++) {
+        bad += ((txt[at + k] == '\n') != (q == (uint32_t)L)) ? 1u : 0u;
+        if (++q == (uint32_t)LL) q = 0;
+    }
+    if (bad) atomicAdd(err, bad);
+}
+
+// the line index of an id text and whether its last line lacks the newline.  Pool memory: the caller brackets it
+static int fq_index(harc_amd_ctx *c, const char *d_ids, uint64_t id_bytes, const uint64_t **nls, uint64_t *lines, bool *open_tail)
+{
+    *lines = 0; *open_tail = false;
+    if (id_bytes == 0) {                                          // no text, no line; the kernel still reads nls[-1]
+        uint64_t *z = nullptr; RC_TRY(dalloc(c, &z, 2));
+        HIP_TRY(hipMemsetAsync(z, 0xFF, 16, c->stream));
+        *nls = z + 1;
+        return HARC_AMD_OK;
+    }
+    RC_TRY(build_line_index(c, d_ids, id_bytes, nls, lines));
+    char lastch = 0;
+    HIP_TRY(hipMemcpyAsync(&lastch, d_ids + id_bytes - 1, 1, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *open_tail = lastch != '\n';
+    return HARC_AMD_OK;
+}
+// n records -> d_out[0 .. total), enqueued on the context's stream; d_err[0..1] count the stride errors
+static int fq_run(harc_amd_ctx *c, const char *d_ids, const uint64_t *nls, const char *d_dna, const char *d_quality, uint32_t n, int L, char *d_out, uint64_t total,
+                  unsigned int *d_err)
+{
+    if (n == 0 || total == 0) return HARC_AMD_OK;
+    const uint32_t mis = (uint32_t)((uintptr_t)d_out & 15);
+    const uint64_t ntiles = (mis + total + FQ_TILE - 1) / FQ_TILE;
+    hipLaunchKernelGGL(k_fq_tiles, harc_fold256(ntiles), dim3(64 * FQ_WAVES), 0, c->stream, d_ids, nls, d_dna, d_quality, n, L, d_out, total, mis, ntiles, d_err);
+    HIP_TRY(hipGetLastError());
+    return HARC_AMD_OK;
+}
+static int fq_check_errors(harc_amd_ctx *c, const unsigned int *d_err, int L)
+{
+    unsigned int err[2] = { 0, 0 };
+    HIP_TRY(hipMemcpyAsync(err, d_err, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (err[0] || err[1]) {
+        harc_set_error("fastq_assemble: the fixed-width inputs are not lines of %d characters: %u bytes of the reads and %u bytes of the quality values are a newline off the %d-byte stride or no newline on it",
+                       L, err[0], err[1], L + 1);
+        return HARC_AMD_EINVAL;
+    }
+    return HARC_AMD_OK;
+}
+
+extern "C" int harc_amd_fastq_assemble_device(harc_amd_ctx *c, const char *d_ids, uint64_t id_bytes, const char *d_dna, const char *d_quality, uint32_t n_records,
+                                              int32_t readlen, char *d_out, uint64_t out_capacity, uint64_t *n_out)
+{
+    if (!c || !n_out || readlen < 1 || readlen > 255 || (id_bytes && !d_ids) || (n_records && (!d_dna || !d_quality))) { harc_set_error("fastq_assemble_device: bad arguments"); return HARC_AMD_EINVAL; }
+    HIP_TRY(hipSetDevice(c->P.device));
+    PoolScope scope(c);
+    const uint64_t *nls = nullptr; uint64_t lines = 0; bool open_tail = false;
+    RC_TRY(fq_index(c, d_ids, id_bytes, &nls, &lines, &open_tail));
+    if (lines != (uint64_t)n_records) { harc_set_error("fastq_assemble_device: the id text holds %llu lines, %u records were announced", (unsigned long long)lines, n_records); return HARC_AMD_EINVAL; }
+    const uint64_t total = id_bytes + (open_tail ? 1 : 0) + (uint64_t)n_records * (2ull * (uint64_t)readlen + 4);
+    *n_out = total;
+    unsigned int *d_err = nullptr; RC_TRY(dalloc(c, &d_err, 4));
+    HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
+    if (!d_out) {
+        const uint64_t nb = (uint64_t)n_records * ((uint64_t)readlen + 1);
+        if (nb) {
+            hipLaunchKernelGGL(k_fq_stride_check, harc_grid256((nb + 15) / 16), dim3(256), 0, c->stream, d_dna, nb, (int)readlen, d_err);
+            hipLaunchKernelGGL(k_fq_stride_check, harc_grid256((nb + 15) / 16), dim3(256), 0, c->stream, d_quality, nb, (int)readlen, d_err + 1);
+            HIP_TRY(hipGetLastError());
+        }
+        return fq_check_errors(c, d_err, readlen);
+    }
+    if (out_capacity < total) { harc_set_error("fastq_assemble_device: the records take %llu bytes, the buffer holds %llu", (unsigned long long)total, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
+    if (!getenv("HARC_AMD_TRACE")) {
+        RC_TRY(fq_run(c, d_ids, nls, d_dna, d_quality, n_records, readlen, d_out, total, d_err));
+        return fq_check_errors(c, d_err, readlen);
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;                        // the tile kernel alone, for tools/fastq_out_rate.py
+    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evguard{ e0, e1 };
+    HIP_TRY(hipEventRecord(e0, c->stream));
+    RC_TRY(fq_run(c, d_ids, nls, d_dna, d_quality, n_records, readlen, d_out, total, d_err));
+    HIP_TRY(hipEventRecord(e1, c->stream));
+    const int rc = fq_check_errors(c, d_err, readlen);
+    float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
+    fprintf(stderr, "[fastq_out] device call: %llu bytes, tile kernel %.3f ms (%.1f GB/s of output)\n", (unsigned long long)total, ms, ms > 0 ? 1e-6 * (double)total / ms : 0.0);
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------ the files
+namespace {
+struct DevBuf { char *p = nullptr; size_t cap = 0; };
+struct DevBufs {
+    harc_amd_ctx *c; DevBuf id[2], dna, qual, out;
+    ~DevBufs() { for (DevBuf *b : { &id[0], &id[1], &dna, &qual, &out }) if (b->p) harc_raw_free(c, b->p); }
+};
+// at least `need` bytes, the first `keep` of them kept
+int buf_reserve(harc_amd_ctx *c, DevBuf *b, size_t need, size_t keep)
+{
+    if (b->p && b->cap >= need) return HARC_AMD_OK;
+    char *np = nullptr; const size_t cap = need + (keep ? need / 4 : 0);
+    RC_TRY(harc_raw_alloc(c, (void **)&np, cap + 16));
+    if (keep) HIP_TRY(hipMemcpyAsync(np, b->p, keep, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                     // whatever still reads the old buffer has finished
+    if (b->p) harc_raw_free(c, b->p);
+    b->p = np; b->cap = cap;
+    return HARC_AMD_OK;
+}
+bool file_size(const char *path, uint64_t *n) { struct stat st; if (stat(path, &st) != 0 || !S_ISREG(st.st_mode)) return false; *n = (uint64_t)st.st_size; return true; }
+}
+
+extern "C" int harc_amd_fastq_assemble_files(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out_path)
+{
+    if (!params || !dna_path || !id_path || !quality_path || !out_path) { harc_set_error("fastq_assemble_files: bad arguments"); return HARC_AMD_EINVAL; }
+    uint64_t dsz = 0, isz = 0, qsz = 0;
+    if (!file_size(dna_path, &dsz)) { harc_set_error("cannot open %s", dna_path); return HARC_AMD_EIO; }
+    if (!file_size(id_path, &isz)) { harc_set_error("cannot open %s", id_path); return HARC_AMD_EIO; }
+    if (!file_size(quality_path, &qsz)) { harc_set_error("cannot open %s", quality_path); return HARC_AMD_EIO; }
+    // the read length is the length of the first read; everything else about the sizes follows from it, before a device is touched
+    int L = 1; bool id_open_tail = false;
+    {
+        char head[257]; size_t got = 0;
+        FILE *f = fopen(dna_path, "rb");
+        if (!f) { harc_set_error("cannot open %s", dna_path); return HARC_AMD_EIO; }
+        got = fread(head, 1, sizeof head, f);
+        fclose(f);
+        size_t nl = 0;
+        while (nl < got && head[nl] != '\n') nl++;
+        if (dsz) {
+            if (nl == got && got == sizeof head) { harc_set_error("fastq_assemble_files: the first line of %s is longer than 255 characters", dna_path); return HARC_AMD_EINVAL; }
+            if (nl == 0) { harc_set_error("fastq_assemble_files: the first line of %s is empty", dna_path); return HARC_AMD_EINVAL; }
+            if (nl > 255) { harc_set_error("fastq_assemble_files: the first line of %s is longer than 255 characters", dna_path); return HARC_AMD_EINVAL; }
+            L = (int)nl;
+        }
+        if (isz) {
+            FILE *g = fopen(id_path, "rb"); char last = '\n';
+            if (!g || fseeko(g, (off_t)isz - 1, SEEK_SET) != 0 || fread(&last, 1, 1, g) != 1) { if (g) fclose(g); harc_set_error("cannot read %s", id_path); return HARC_AMD_EIO; }
+            fclose(g);
+            id_open_tail = last != '\n';
+        }
+    }
+    const uint64_t LL = (uint64_t)L + 1, K = 2ull * (uint64_t)L + 4;
+    if (dsz % LL) { harc_set_error("fastq_assemble_files: %s holds %llu bytes, no multiple of the %llu bytes of a read of %d characters and its newline", dna_path, (unsigned long long)dsz, (unsigned long long)LL, L); return HARC_AMD_EINVAL; }
+    if (qsz != dsz) { harc_set_error("fastq_assemble_files: %s holds %llu bytes and %s %llu: not a quality line per read", quality_path, (unsigned long long)qsz, dna_path, (unsigned long long)dsz); return HARC_AMD_EINVAL; }
+    const uint64_t n = dsz / LL;
+    if (n > 4294967290ull) { harc_set_error("Too many reads. HARC supports at most 4294967290 reads"); return HARC_AMD_EINVAL; }
+    const uint64_t out_size = isz + (id_open_tail ? 1 : 0) + n * K;    // known before a byte is read: the output is sized and mapped up front
+    harc_amd_params P = *params;
+    if (harc_amd_default_params(L, &P) != HARC_AMD_OK) return HARC_AMD_EINVAL;
+    P.device = params->device;
+    harc_amd_ctx *c = nullptr;
+    RC_TRY(harc_amd_create(&P, &c));
+    struct Guard { harc_amd_ctx *c; ~Guard() { harc_amd_destroy(c); } } guard{ c };
+    // Three feeders (ids, reads, quality values) and the drain are alive at the same time and the context has ONE pinned ring: it is split into four quarters of four
+    // slices each -- quarter 0: the id feeder, 1: the read feeder, 2: the quality feeder, 3: the drain -- and reserved whole before any of them starts.  With the default
+    // slice of 64 MB that is the 1 GiB the ring always had.  HARC_AMD_FEED_SLICE sets the slice, HARC_AMD_FEED_THREADS the host threads of all four together.
+    RingGeom gq[4];
+    {
+        RingGeom base; harc_ring_geom_env(&base);
+        for (int k = 0; k < 4; k++) { gq[k].slice = base.slice; gq[k].nslices = 4; gq[k].nthr = base.nthr / 4 > 0 ? base.nthr / 4 : 1; gq[k].ring_off = (size_t)k * 4 * base.slice; }
+        RC_TRY(harc_ring_reserve(c, 16 * base.slice, "FASTQ output"));
+    }
+    struct OutGuard { std::string path; bool ok = false; ~OutGuard() { if (!ok) (void)remove(path.c_str()); } } outguard{ out_path };   // declared in front of the drain: it goes after the drain has closed the file
+    DevBufs B{ c };
+    const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
+    double t_kernel = 0, t_read = 0, t_write = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    HIP_TRY(hipEventCreate(&ev0)); HIP_TRY(hipEventCreate(&ev1));
+    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evguard{ ev0, ev1 };
+    PoolScope scope(c);
+    unsigned int *d_err = nullptr; RC_TRY(dalloc(c, &d_err, 4));
+    HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
+    FileDrain drain(c);
+    RC_TRY(drain.start(out_path, (size_t)out_size, &gq[3]));
+    // the job is driven by the id file: a piece is a byte range of it; what follows the piece's last newline is carried into the next piece
+    uint64_t piece = (uint64_t)256 << 20;
+    if (const char *e = getenv("HARC_AMD_FQOUT_PIECE")) { const unsigned long long v = strtoull(e, nullptr, 10); if (v >= 1) piece = v; }
+    std::vector<std::pair<uint64_t, uint64_t>> pieces;
+    for (uint64_t a = 0; a < isz; a += piece) pieces.emplace_back(a, isz - a < piece ? isz : a + piece);
+    FileFeeder idf(c, id_path);
+    if (!pieces.empty()) RC_TRY(idf.start(pieces, gq[0]));
+    uint64_t carry = 0, r0 = 0, lines_seen = 0, out_at = 0; int cur = 0, npieces = 0; bool over = false;
+    for (size_t p = 0; p < pieces.size(); p++) {
+        const uint64_t len = pieces[p].second - pieces[p].first; const bool lastp = p + 1 == pieces.size();
+        RC_TRY(buf_reserve(c, &B.id[cur], (size_t)(carry + len), (size_t)carry));          // the carried bytes sit at its front
+        { const double t0 = mono_now(); RC_TRY(idf.upload_piece(p, B.id[cur].p + carry, nullptr)); t_read += mono_now() - t0; }
+        const uint64_t total = carry + len;
+        const char *d_ids = B.id[cur].p;
+        PoolScope piece_scope(c);
+        const uint64_t *nls = nullptr; uint64_t lines = 0; bool open_tail = false;
+        RC_TRY(fq_index(c, d_ids, total, &nls, &lines, &open_tail));
+        const uint64_t m = lines - ((open_tail && !lastp) ? 1 : 0);                        // whole lines; a last line of the FILE without its newline is one
+        if (m == 0 && !lastp) { carry = total; continue; }                                   // not one whole line yet: the piece grows by the next one
+        uint64_t cut = total;
+        if (open_tail && !lastp) {
+            HIP_TRY(hipMemcpyAsync(&cut, nls + (m - 1), 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            cut += 1;
+        }
+        lines_seen += m;
+        if (r0 + m > n) over = true;                                                         // more ids than reads: the lines are still counted, for the message
+        if (!over && m) {
+            const uint64_t nb = m * LL, out_bytes = cut + ((lastp && open_tail) ? 1 : 0) + m * K;
+            RC_TRY(buf_reserve(c, &B.dna, (size_t)nb, 0)); RC_TRY(buf_reserve(c, &B.qual, (size_t)nb, 0)); RC_TRY(buf_reserve(c, &B.out, (size_t)out_bytes, 0));
+            {   // lines [r0, r0 + m) of the two fixed-width files, by offset
+                FileFeeder fd(c, dna_path), fq(c, quality_path);
+                RC_TRY(fd.start({ { r0 * LL, (r0 + m) * LL } }, gq[1])); RC_TRY(fq.start({ { r0 * LL, (r0 + m) * LL } }, gq[2]));
+                const double t0 = mono_now();
+                RC_TRY(fd.upload_piece(0, B.dna.p, nullptr)); RC_TRY(fq.upload_piece(0, B.qual.p, nullptr));
+                t_read += mono_now() - t0;
+                HIP_TRY(hipEventRecord(ev0, c->stream));
+                RC_TRY(fq_run(c, d_ids, nls, B.dna.p, B.qual.p, (uint32_t)m, L, B.out.p, out_bytes, d_err));
+                HIP_TRY(hipEventRecord(ev1, c->stream));
+                { const double t0w = mono_now(); RC_TRY(drain.put(B.out.p, (size_t)out_bytes, out_at)); t_write += mono_now() - t0w; }
+                out_at += out_bytes; npieces++;
+                HIP_TRY(hipEventSynchronize(ev1));
+                float ms = 0; (void)hipEventElapsedTime(&ms, ev0, ev1); t_kernel += 1e-3 * (double)ms;
+            }                                                                                // (the feeders wait for the stream when they go)
+        }
+        if (!over) r0 += m;
+        const uint64_t rest = total - cut;
+        if (rest) {
+            RC_TRY(buf_reserve(c, &B.id[cur ^ 1], (size_t)rest, 0));
+            HIP_TRY(hipMemcpyAsync(B.id[cur ^ 1].p, d_ids + cut, (size_t)rest, hipMemcpyDeviceToDevice, c->stream));
+            cur ^= 1;
+        }
+        carry = rest;
+    }
+    if (over || r0 != n) {
+        harc_set_error("fastq_assemble_files: %s holds %llu lines, %s %llu reads", id_path, (unsigned long long)lines_seen, dna_path, (unsigned long long)n);
+        return HARC_AMD_EINVAL;
+    }
+    if (out_at != out_size) { harc_set_error("fastq_assemble_files: %llu bytes assembled, the file sizes announce %llu", (unsigned long long)out_at, (unsigned long long)out_size); return HARC_AMD_EINTERNAL; }
+    RC_TRY(fq_check_errors(c, d_err, L));
+    { const double t0 = mono_now(); RC_TRY(drain.finish()); t_write += mono_now() - t0; }
+    if (tlog) fprintf(stderr, "[fastq_out] %llu bytes in %d pieces: %.3f s in the kernel, %.3f s waiting for the readers, %.3f s waiting for the writers\n",
+                      (unsigned long long)out_size, npieces, t_kernel, t_read, t_write);
+    outguard.ok = true;
+    return HARC_AMD_OK;
+}

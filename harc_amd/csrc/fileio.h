@@ -1,0 +1,296 @@
+// fileio.h -- the two file <-> HBM movers of the library, shared by ingest.hip (FASTQ in), verify.hip (decoded reads out) and fastq_out.hip (both at once):
+// FileFeeder reads a file into device memory, FileDrain writes device memory into a file, each through pinned slices of the context's ring (c->feed_ring)
+// worked by a few host threads.
+#pragma once
+#include "internal.h"
+#include <string>
+#include <stdlib.h>
+#include <time.h>
+#include <errno.h>
+#include <sys/stat.h>
+#include <unistd.h>
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <atomic>
+#include <condition_variable>
+#include <deque>
+#include <mutex>
+#include <thread>
+
+// Which part of the context's ONE pinned ring a feeder or a drain works with, and how: `nslices` slices of `slice` bytes from byte `ring_off` of the ring on,
+// `nthr` host threads.  The default is what every caller used before the geometry became an argument: the whole ring, 16 slices of 64 MB, 16 threads.
+// Two movers alive at the same time must be given disjoint parts (fastq_out.hip splits the ring four ways), and the ring must have been reserved for all of
+// them first (harc_ring_reserve): a mover that finds the ring too small replaces it, which is right only when it is alone.
+struct RingGeom { size_t slice = (size_t)64 << 20; int nslices = 16; int nthr = 16; size_t ring_off = 0; };
+static inline int harc_ring_reserve(harc_amd_ctx *c, size_t bytes, const char *what)
+{
+    if (c->feed_ring_bytes >= bytes) return HARC_AMD_OK;
+    if (c->feed_ring) { (void)hipHostFree(c->feed_ring); c->feed_ring = nullptr; c->feed_ring_bytes = 0; }
+    if (hipHostMalloc((void **)&c->feed_ring, bytes) != hipSuccess) { harc_set_error("hipHostMalloc of the %s ring (%zu bytes) failed", what, bytes); return HARC_AMD_ENOMEM; }
+    c->feed_ring_bytes = bytes;
+    return HARC_AMD_OK;
+}
+// HARC_AMD_FEED_SLICE / HARC_AMD_FEED_THREADS over a geometry (tests: slices of a few reads)
+static inline void harc_ring_geom_env(RingGeom *g)
+{
+    if (const char *e = getenv("HARC_AMD_FEED_THREADS")) { const int x = atoi(e); if (x >= 1 && x <= 64) g->nthr = x; }
+    if (const char *e = getenv("HARC_AMD_FEED_SLICE")) { const long long x = atoll(e); if (x >= 16 && x <= ((long long)1 << 30)) g->slice = (size_t)x; }
+}
+
+static inline double mono_now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
+
+// File -> HBM at the rate of the host's memory system instead of one core's (round 6; round 3's ./harc -c spent most of its 6 s on 100 M reads in a
+// single-threaded fread into one pinned buffer): reader threads pread() slices of the file into a ring of pinned slices kept by the context, the calling
+// thread uploads every filled slice (hipMemcpyAsync on the context's stream) and hands the slice back when its copy has finished.  The slices of ALL the
+// pieces of a range are read ahead in file order as far as the ring goes: while the device indexes and packs piece i the readers already hold the first
+// slices of piece i + 1.  A slice is taken from the ring BEFORE its chunk number, under one lock: the chunks that hold slices are always the lowest
+// unfinished ones, so a piece being waited for can never starve behind read-ahead that cannot be uploaded yet.
+struct FileFeeder {
+    struct Chunk { uint64_t off; uint32_t len; uint32_t piece; uint64_t at; };     // file offset, bytes, piece, byte offset inside the piece
+    harc_amd_ctx *c; int fd = -1; const char *name;
+    bool use_mmap = true;                                         // the readers copy out of a mapping of their slice instead of calling pread (HARC_AMD_FEED_MMAP=0: pread)
+    std::vector<Chunk> chunks; std::vector<size_t> piece_left;                     // chunks of each piece not uploaded yet
+    size_t SL = 0; int NS = 0; char *ring = nullptr;              // this feeder's part of c->feed_ring
+    std::vector<hipEvent_t> ev;
+    std::mutex mu; std::condition_variable cv_free, cv_filled;
+    std::deque<int> free_slices; std::deque<std::pair<int, size_t>> filled, held;  // (slice, chunk)
+    std::deque<int> inflight;                                                      // slices whose upload is on the stream, oldest first
+    size_t next_chunk = 0; bool stop = false; int err = 0;
+    double t_ring = 0, t_pread = 0, t_wait_free = 0, t_wait_filled = 0, t_wait_copy = 0, t_enqueue = 0;      // HARC_AMD_TRACE: summed over the readers / of the calling thread
+    std::vector<std::thread> th;
+    FileFeeder(harc_amd_ctx *c_, const char *name_) : c(c_), name(name_) {}
+    ~FileFeeder()
+    {
+        { std::lock_guard<std::mutex> lk(mu); stop = true; }
+        cv_free.notify_all();
+        for (auto &t : th) t.join();
+        (void)hipStreamSynchronize(c->stream);                    // before the ring is used again
+        if (getenv("HARC_AMD_TRACE")) fprintf(stderr, "[file feeder] %zu slices of %zu MB through %d pinned slices by %zu readers (pinned ring allocated in %.3f s): readers in pread %.2f s, waiting for a free slice %.2f s (summed); uploader enqueueing %.2f s, waiting for a filled slice %.2f s, for a copy %.2f s\n",
+                                              chunks.size(), SL >> 20, NS, th.size(), t_ring, t_pread, t_wait_free, t_enqueue, t_wait_filled, t_wait_copy);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (fd >= 0) close(fd);
+    }
+    // pieces: [lo, hi) byte ranges of the file, in file order
+    int start(const std::vector<std::pair<uint64_t, uint64_t>> &pieces, const RingGeom &geom = RingGeom())
+    {
+        fd = open(name, O_RDONLY);
+        if (fd < 0) { harc_set_error("cannot open %s", name); return HARC_AMD_EIO; }
+        // 16 slices of 64 MB, 16 readers (tools/micro/feed_rate.cpp, profiles/r06/feed_rate.txt: a file that has been read before reaches HBM at 54 GB/s this way, the
+        // PCIe rate is 57; 16-MB slices 42; the FIRST read of a freshly written tmpfs file runs at 24 GB/s whatever is done here -- the kernel's own first touch)
+        SL = geom.slice; NS = geom.nslices;
+        int nthr = geom.nthr;
+        // a read() of page-cache pages that nobody has read yet marks every one of them accessed (LRU lists, under a lock the readers share): the first read of
+        // a freshly written 21.7-GB file ran at 14-24 GB/s with 16 readers, the second at 54.  Copies out of a shared mapping do not go that way -- but ONE
+        // mapping of the whole file took 0.8 s to take down again (the same marking, at unmap, by one thread): every reader maps its own slice, tells the kernel
+        // that it reads it once from front to back (no recency kept for such a mapping), copies and unmaps.  HARC_AMD_FEED_MMAP=0: pread -- the way to read a file
+        // that somebody may TRUNCATE meanwhile: a copy out of a mapping beyond the new end of the file is a SIGBUS, not a short read.
+        use_mmap = !(getenv("HARC_AMD_FEED_MMAP") && atoi(getenv("HARC_AMD_FEED_MMAP")) == 0);
+        const double t_ring0 = mono_now();
+        RC_TRY(harc_ring_reserve(c, geom.ring_off + SL * (size_t)NS, "ingest"));
+        ring = c->feed_ring + geom.ring_off;
+        t_ring = mono_now() - t_ring0;
+        ev.assign(NS, nullptr);
+        for (int k = 0; k < NS; k++) { if (hipEventCreate(&ev[k]) != hipSuccess) { harc_set_error("hipEventCreate failed"); return HARC_AMD_ENODEVICE; } free_slices.push_back(k); }
+        piece_left.assign(pieces.size(), 0);
+        for (size_t p = 0; p < pieces.size(); p++)
+            for (uint64_t a = pieces[p].first; a < pieces[p].second; a += SL) {
+                const uint64_t b = pieces[p].second - a < SL ? pieces[p].second : a + SL;
+                chunks.push_back(Chunk{ a, (uint32_t)(b - a), (uint32_t)p, a - pieces[p].first });
+                piece_left[p]++;
+            }
+        if ((size_t)nthr > chunks.size()) nthr = (int)chunks.size();
+        for (int t = 0; t < nthr; t++) th.emplace_back([this] { reader(); });
+        return HARC_AMD_OK;
+    }
+    void reader()
+    {
+        for (;;) {
+            int sl; size_t k;
+            const double tw0 = mono_now();
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv_free.wait(lk, [&] { return stop || next_chunk >= chunks.size() || !free_slices.empty(); });
+                if (stop || next_chunk >= chunks.size()) return;
+                sl = free_slices.front(); free_slices.pop_front(); k = next_chunk++;
+            }
+            const Chunk &ch = chunks[k];
+            const double tr0 = mono_now();
+            char *dst = ring + (size_t)sl * SL; size_t got = 0; int e = 0;
+            if (use_mmap) {
+                const uint64_t a0 = ch.off & ~(uint64_t)4095; const size_t mlen = (size_t)(ch.off + ch.len - a0);
+                void *m = mmap(nullptr, mlen, PROT_READ, MAP_SHARED, fd, (off_t)a0);
+                if (m != MAP_FAILED) {
+                    (void)madvise(m, mlen, MADV_SEQUENTIAL);
+                    memcpy(dst, (const char *)m + (ch.off - a0), ch.len); got = ch.len;
+                    munmap(m, mlen);
+                }
+            }
+            while (got < ch.len) {
+                const ssize_t r = pread(fd, dst + got, ch.len - got, (off_t)(ch.off + got));
+                if (r <= 0) { e = 1; break; }
+                got += (size_t)r;
+            }
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                if (e) { err = 1; stop = true; }
+                filled.emplace_back(sl, k);
+                t_wait_free += tr0 - tw0; t_pread += mono_now() - tr0;
+            }
+            cv_filled.notify_one();
+            if (e) { cv_free.notify_all(); return; }
+        }
+    }
+    void give_back(int sl) { { std::lock_guard<std::mutex> lk(mu); free_slices.push_back(sl); } cv_free.notify_one(); }
+    // every chunk of piece p on the stream towards d_txt; chunks of piece p + 1 that are ready meanwhile go to d_next (may be null: they wait)
+    int upload_piece(size_t p, char *d_txt, char *d_next)
+    {
+        auto put = [&](int sl, size_t k) -> int {
+            const Chunk &ch = chunks[k];
+            char *base = ch.piece == p ? d_txt : d_next;
+            const double te0 = mono_now();
+            if (hipMemcpyAsync(base + ch.at, ring + (size_t)sl * SL, ch.len, hipMemcpyHostToDevice, c->stream) != hipSuccess) { harc_set_error("upload of %s failed", name); return HARC_AMD_ENODEVICE; }
+            (void)hipEventRecord(ev[sl], c->stream);
+            inflight.push_back(sl); piece_left[ch.piece]--;
+            t_enqueue += mono_now() - te0;
+            return HARC_AMD_OK;
+        };
+        // what was read ahead for this piece while the last one was uploaded
+        for (size_t i = 0; i < held.size();) {
+            const Chunk &ch = chunks[held[i].second];
+            if (ch.piece == p || (ch.piece == p + 1 && d_next)) { RC_TRY(put(held[i].first, held[i].second)); held.erase(held.begin() + (long)i); } else i++;
+        }
+        while (piece_left[p] > 0) {
+            while (!inflight.empty() && hipEventQuery(ev[inflight.front()]) == hipSuccess) { give_back(inflight.front()); inflight.pop_front(); }
+            std::pair<int, size_t> it(-1, 0);
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                if (filled.empty() && !err) {
+                    if (!inflight.empty()) { lk.unlock(); const double t0 = mono_now(); (void)hipEventSynchronize(ev[inflight.front()]); t_wait_copy += mono_now() - t0; give_back(inflight.front()); inflight.pop_front(); continue; }
+                    const double t0 = mono_now();
+                    cv_filled.wait(lk, [&] { return !filled.empty() || err; });
+                    t_wait_filled += mono_now() - t0;
+                }
+                if (err) { harc_set_error("short read on %s", name); return HARC_AMD_EIO; }
+                it = filled.front(); filled.pop_front();
+            }
+            const Chunk &ch = chunks[it.second];
+            if (ch.piece == p || (ch.piece == p + 1 && d_next)) RC_TRY(put(it.first, it.second));
+            else held.push_back(it);
+        }
+        return HARC_AMD_OK;
+    }
+};
+
+// HBM -> file at the rate of the host's memory system (round 6: decoder.out's replacement spent 4.4 of its 4.7 s on 100 M reads in D2H copies into pageable
+// vectors and one thread's fwrite): the output file is sized and mapped first (its length is known from the stream files' sizes), the calling thread sends
+// pieces of device memory through a ring of pinned slices (hipMemcpyAsync on the context's stream), writer threads copy every slice that has arrived into the
+// mapping.  write() calls to ONE tmpfs file serialise on its inode (tools/micro/feed_rate.cpp: 6 GB/s with 1 or 16 threads); page faults of a shared mapping do not.
+struct FileDrain {
+    struct Job { int sl; size_t len; uint64_t off; };
+    harc_amd_ctx *c; int fd = -1; char *map = nullptr; size_t fsize = 0;
+    size_t SL = 0; int NS = 0; char *ring = nullptr;              // this drain's part of c->feed_ring
+    std::vector<hipEvent_t> ev;
+    std::mutex mu; std::condition_variable cv_free, cv_job, cv_idle;
+    std::deque<int> free_slices; std::deque<Job> jobs; int busy = 0; bool stop = false;
+    std::vector<std::thread> th;
+    // the file's blocks are ALLOCATED ahead of the writers by a thread of its own (posix_fallocate, 64 MB at a time): a store into a mapping of a sparse file on a full
+    // file system is a SIGBUS, not an error code -- this way "no space left" is an error of the call, as it was with fwrite
+    std::thread alloc_th; std::condition_variable cv_alloc; uint64_t alloc_upto = 0; int alloc_err = 0;
+    std::string fname;
+    explicit FileDrain(harc_amd_ctx *c_) : c(c_) {}
+    ~FileDrain() { (void)finish(); }
+    // geom == nullptr: the whole ring in the default geometry, with HARC_AMD_FEED_SLICE / HARC_AMD_FEED_THREADS read here
+    int start(const std::string &path, size_t bytes, const RingGeom *geom = nullptr)
+    {
+        fd = open(path.c_str(), O_CREAT | O_RDWR | O_TRUNC, 0644);
+        if (fd < 0) { harc_set_error("cannot create %s", path.c_str()); return HARC_AMD_EIO; }
+        fsize = bytes; fname = path;
+        if (bytes) {
+            if (ftruncate(fd, (off_t)bytes) != 0) { harc_set_error("cannot size %s to %zu bytes", path.c_str(), bytes); return HARC_AMD_EIO; }
+            map = (char *)mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
+            if (map == MAP_FAILED) { map = nullptr; harc_set_error("cannot map %s", path.c_str()); return HARC_AMD_EIO; }
+        }
+        RingGeom g;
+        if (geom) g = *geom; else harc_ring_geom_env(&g);
+        SL = g.slice; NS = g.nslices;
+        const int nthr = g.nthr;
+        RC_TRY(harc_ring_reserve(c, g.ring_off + SL * (size_t)NS, "output"));
+        ring = c->feed_ring + g.ring_off;
+        ev.assign(NS, nullptr);
+        for (int k = 0; k < NS; k++) { if (hipEventCreate(&ev[k]) != hipSuccess) { harc_set_error("hipEventCreate failed"); return HARC_AMD_ENODEVICE; } free_slices.push_back(k); }
+        alloc_th = std::thread([this] {
+            const uint64_t STEP = (uint64_t)64 << 20;
+            for (uint64_t a = 0; a < (uint64_t)fsize; a += STEP) {
+                const uint64_t len = (uint64_t)fsize - a < STEP ? (uint64_t)fsize - a : STEP;
+                const int e = posix_fallocate(fd, (off_t)a, (off_t)len);
+                std::lock_guard<std::mutex> lk(mu);
+                if (e == EOPNOTSUPP || e == EINVAL) { alloc_upto = (uint64_t)fsize; break; }      // a file system without preallocation: as before this round
+                if (e) { alloc_err = e; break; }
+                alloc_upto = a + len;
+                cv_alloc.notify_all();
+                if (stop) break;
+            }
+            cv_alloc.notify_all();
+        });
+        const int dev = c->P.device;
+        for (int t = 0; t < nthr; t++) th.emplace_back([this, dev] {
+            (void)hipSetDevice(dev);
+            for (;;) {
+                Job j;
+                {
+                    std::unique_lock<std::mutex> lk(mu);
+                    cv_job.wait(lk, [&] { return stop || !jobs.empty(); });
+                    if (jobs.empty()) return;
+                    j = jobs.front(); jobs.pop_front(); busy++;
+                }
+                (void)hipEventSynchronize(ev[j.sl]);              // the slice has arrived
+                bool space;
+                { std::unique_lock<std::mutex> lk(mu); cv_alloc.wait(lk, [&] { return alloc_err != 0 || alloc_upto >= j.off + j.len; }); space = alloc_err == 0; }
+                if (space) memcpy(map + j.off, ring + (size_t)j.sl * SL, j.len);
+                { std::lock_guard<std::mutex> lk(mu); busy--; free_slices.push_back(j.sl); }
+                cv_free.notify_one(); cv_idle.notify_all();
+            }
+        });
+        return HARC_AMD_OK;
+    }
+    // n bytes of device memory -> bytes [off, off + n) of the file.  The copies are on the context's stream: what is enqueued behind them may reuse d_src
+    int put(const void *d_src, size_t n, uint64_t off)
+    {
+        if (off + n > fsize) { harc_set_error("output file: %zu bytes at %llu do not fit its %zu bytes", n, (unsigned long long)off, fsize); return HARC_AMD_EINTERNAL; }
+        for (size_t a = 0; a < n; a += SL) {
+            const size_t len = n - a < SL ? n - a : SL;
+            int sl;
+            { std::unique_lock<std::mutex> lk(mu); cv_free.wait(lk, [&] { return !free_slices.empty(); }); sl = free_slices.front(); free_slices.pop_front(); }
+            if (hipMemcpyAsync(ring + (size_t)sl * SL, (const char *)d_src + a, len, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipEventRecord(ev[sl], c->stream) != hipSuccess) {
+                harc_set_error("device -> host copy of the output failed"); return HARC_AMD_ENODEVICE; }
+            { std::lock_guard<std::mutex> lk(mu); jobs.push_back(Job{ sl, len, off + a }); }
+            cv_job.notify_one();
+        }
+        return HARC_AMD_OK;
+    }
+    int put_host(const void *h, size_t n, uint64_t off)
+    {
+        if (off + n > fsize) { harc_set_error("output file: %zu bytes at %llu do not fit its %zu bytes", n, (unsigned long long)off, fsize); return HARC_AMD_EINTERNAL; }
+        if (n) {
+            { std::unique_lock<std::mutex> lk(mu); cv_alloc.wait(lk, [&] { return alloc_err != 0 || alloc_upto >= off + n; }); if (alloc_err) return HARC_AMD_OK; }      // (finish() reports it)
+            memcpy(map + off, h, n);
+        }
+        return HARC_AMD_OK;
+    }
+    int finish()
+    {
+        if (!th.empty()) {
+            { std::unique_lock<std::mutex> lk(mu); cv_idle.wait(lk, [&] { return jobs.empty() && busy == 0; }); stop = true; }
+            cv_job.notify_all();
+            for (auto &t : th) t.join();
+            th.clear();
+        }
+        if (alloc_th.joinable()) alloc_th.join();
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        ev.clear();
+        if (map) { munmap(map, fsize); map = nullptr; }
+        if (fd >= 0) { close(fd); fd = -1; }
+        if (alloc_err) { harc_set_error("cannot allocate %zu bytes for %s: %s", fsize, fname.c_str(), strerror(alloc_err)); const int e = alloc_err; alloc_err = 0; (void)e; return HARC_AMD_EIO; }
+        return HARC_AMD_OK;
+    }
+};

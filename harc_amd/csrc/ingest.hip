@@ -5,6 +5,7 @@
 // per record classifies, two compactions pack the reads straight into the 2-bit / 3-bit stores of the context.
 #include "devutil.h"
 #include "inflate_member.h"
+#include "fileio.h"
 #include <string>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -93,7 +94,7 @@ __global__ void k_ingest_pack3(const char *txt, const uint64_t *nl, const uint32
 
 // nls[k] = byte position of the newline that ends line k (a last line without one ends at nbytes); nls[-1] = (u64)-1 so that line k
 // starts at nls[k-1]+1 for every k.  Pool memory: the caller brackets it with harc_pool_mark / release.
-static int build_line_index(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const uint64_t **nls_out, uint64_t *total_lines_out)
+int build_line_index(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const uint64_t **nls_out, uint64_t *total_lines_out)
 {
     const uint64_t ntiles = (nbytes + NL_TILE - 1) / NL_TILE;
     uint32_t *tilecnt = nullptr; uint64_t *tilebase = nullptr;
@@ -587,157 +588,12 @@ static int emit_quality_and_ids_streamed(harc_amd_ctx *c, FILE *f, const char *n
 // [3] of it the device's line index / classify / pack kernels and their syncs, [4] reorder, [5] encode (the D2H of the streams inside), [6] stream files written,
 // [7] total, [8] of [1] the BGZF member scan and inflate (0 for a plain file)
 static double g_fastq_timing[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-static inline double mono_now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 extern "C" int harc_amd_last_fastq_timing(double *out, int32_t n)
 {
     if (!out || n < 1) return HARC_AMD_EINVAL;
     for (int i = 0; i < n; i++) out[i] = i < 9 ? g_fastq_timing[i] : 0.0;
     return HARC_AMD_OK;
 }
-// File -> HBM at the rate of the host's memory system instead of one core's (round 6; round 3's ./harc -c spent most of its 6 s on 100 M reads in a
-// single-threaded fread into one pinned buffer): reader threads pread() slices of the file into a ring of pinned slices kept by the context, the calling
-// thread uploads every filled slice (hipMemcpyAsync on the context's stream) and hands the slice back when its copy has finished.  The slices of ALL the
-// pieces of a range are read ahead in file order as far as the ring goes: while the device indexes and packs piece i the readers already hold the first
-// slices of piece i + 1.  A slice is taken from the ring BEFORE its chunk number, under one lock: the chunks that hold slices are always the lowest
-// unfinished ones, so a piece being waited for can never starve behind read-ahead that cannot be uploaded yet.
-struct FileFeeder {
-    struct Chunk { uint64_t off; uint32_t len; uint32_t piece; uint64_t at; };     // file offset, bytes, piece, byte offset inside the piece
-    harc_amd_ctx *c; int fd = -1; const char *name;
-    bool use_mmap = true;                                         // the readers copy out of a mapping of their slice instead of calling pread (HARC_AMD_FEED_MMAP=0: pread)
-    std::vector<Chunk> chunks; std::vector<size_t> piece_left;                     // chunks of each piece not uploaded yet
-    size_t SL = 0; int NS = 0;
-    std::vector<hipEvent_t> ev;
-    std::mutex mu; std::condition_variable cv_free, cv_filled;
-    std::deque<int> free_slices; std::deque<std::pair<int, size_t>> filled, held;  // (slice, chunk)
-    std::deque<int> inflight;                                                      // slices whose upload is on the stream, oldest first
-    size_t next_chunk = 0; bool stop = false; int err = 0;
-    double t_ring = 0, t_pread = 0, t_wait_free = 0, t_wait_filled = 0, t_wait_copy = 0, t_enqueue = 0;      // HARC_AMD_TRACE: summed over the readers / of the calling thread
-    std::vector<std::thread> th;
-    FileFeeder(harc_amd_ctx *c_, const char *name_) : c(c_), name(name_) {}
-    ~FileFeeder()
-    {
-        { std::lock_guard<std::mutex> lk(mu); stop = true; }
-        cv_free.notify_all();
-        for (auto &t : th) t.join();
-        (void)hipStreamSynchronize(c->stream);                    // before the ring is used again
-        if (getenv("HARC_AMD_TRACE")) fprintf(stderr, "[file feeder] %zu slices of %zu MB through %d pinned slices by %zu readers (pinned ring allocated in %.3f s): readers in pread %.2f s, waiting for a free slice %.2f s (summed); uploader enqueueing %.2f s, waiting for a filled slice %.2f s, for a copy %.2f s\n",
-                                              chunks.size(), SL >> 20, NS, th.size(), t_ring, t_pread, t_wait_free, t_enqueue, t_wait_filled, t_wait_copy);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (fd >= 0) close(fd);
-    }
-    // pieces: [lo, hi) byte ranges of the file, in file order
-    int start(const std::vector<std::pair<uint64_t, uint64_t>> &pieces)
-    {
-        fd = open(name, O_RDONLY);
-        if (fd < 0) { harc_set_error("cannot open %s", name); return HARC_AMD_EIO; }
-        // 16 slices of 64 MB, 16 readers (tools/micro/feed_rate.cpp, profiles/r06/feed_rate.txt: a file that has been read before reaches HBM at 54 GB/s this way, the
-        // PCIe rate is 57; 16-MB slices 42; the FIRST read of a freshly written tmpfs file runs at 24 GB/s whatever is done here -- the kernel's own first touch)
-        SL = (size_t)64 << 20; NS = 16;
-        int nthr = 16;
-        // a read() of page-cache pages that nobody has read yet marks every one of them accessed (LRU lists, under a lock the readers share): the first read of
-        // a freshly written 21.7-GB file ran at 14-24 GB/s with 16 readers, the second at 54.  Copies out of a shared mapping do not go that way -- but ONE
-        // mapping of the whole file took 0.8 s to take down again (the same marking, at unmap, by one thread): every reader maps its own slice, tells the kernel
-        // that it reads it once from front to back (no recency kept for such a mapping), copies and unmaps.  HARC_AMD_FEED_MMAP=0: pread -- the way to read a file
-        // that somebody may TRUNCATE meanwhile: a copy out of a mapping beyond the new end of the file is a SIGBUS, not a short read.
-        use_mmap = !(getenv("HARC_AMD_FEED_MMAP") && atoi(getenv("HARC_AMD_FEED_MMAP")) == 0);
-        const double t_ring0 = mono_now();
-        if (c->feed_ring_bytes < SL * (size_t)NS) {
-            if (c->feed_ring) { (void)hipHostFree(c->feed_ring); c->feed_ring = nullptr; c->feed_ring_bytes = 0; }
-            if (hipHostMalloc((void **)&c->feed_ring, SL * (size_t)NS) != hipSuccess) { harc_set_error("hipHostMalloc of the ingest ring (%zu bytes) failed", SL * (size_t)NS); return HARC_AMD_ENOMEM; }
-            c->feed_ring_bytes = SL * (size_t)NS;
-        }
-        t_ring = mono_now() - t_ring0;
-        ev.assign(NS, nullptr);
-        for (int k = 0; k < NS; k++) { if (hipEventCreate(&ev[k]) != hipSuccess) { harc_set_error("hipEventCreate failed"); return HARC_AMD_ENODEVICE; } free_slices.push_back(k); }
-        piece_left.assign(pieces.size(), 0);
-        for (size_t p = 0; p < pieces.size(); p++)
-            for (uint64_t a = pieces[p].first; a < pieces[p].second; a += SL) {
-                const uint64_t b = pieces[p].second - a < SL ? pieces[p].second : a + SL;
-                chunks.push_back(Chunk{ a, (uint32_t)(b - a), (uint32_t)p, a - pieces[p].first });
-                piece_left[p]++;
-            }
-        if ((size_t)nthr > chunks.size()) nthr = (int)chunks.size();
-        for (int t = 0; t < nthr; t++) th.emplace_back([this] { reader(); });
-        return HARC_AMD_OK;
-    }
-    void reader()
-    {
-        for (;;) {
-            int sl; size_t k;
-            const double tw0 = mono_now();
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv_free.wait(lk, [&] { return stop || next_chunk >= chunks.size() || !free_slices.empty(); });
-                if (stop || next_chunk >= chunks.size()) return;
-                sl = free_slices.front(); free_slices.pop_front(); k = next_chunk++;
-            }
-            const Chunk &ch = chunks[k];
-            const double tr0 = mono_now();
-            char *dst = c->feed_ring + (size_t)sl * SL; size_t got = 0; int e = 0;
-            if (use_mmap) {
-                const uint64_t a0 = ch.off & ~(uint64_t)4095; const size_t mlen = (size_t)(ch.off + ch.len - a0);
-                void *m = mmap(nullptr, mlen, PROT_READ, MAP_SHARED, fd, (off_t)a0);
-                if (m != MAP_FAILED) {
-                    (void)madvise(m, mlen, MADV_SEQUENTIAL);
-                    memcpy(dst, (const char *)m + (ch.off - a0), ch.len); got = ch.len;
-                    munmap(m, mlen);
-                }
-            }
-            while (got < ch.len) {
-                const ssize_t r = pread(fd, dst + got, ch.len - got, (off_t)(ch.off + got));
-                if (r <= 0) { e = 1; break; }
-                got += (size_t)r;
-            }
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                if (e) { err = 1; stop = true; }
-                filled.emplace_back(sl, k);
-                t_wait_free += tr0 - tw0; t_pread += mono_now() - tr0;
-            }
-            cv_filled.notify_one();
-            if (e) { cv_free.notify_all(); return; }
-        }
-    }
-    void give_back(int sl) { { std::lock_guard<std::mutex> lk(mu); free_slices.push_back(sl); } cv_free.notify_one(); }
-    // every chunk of piece p on the stream towards d_txt; chunks of piece p + 1 that are ready meanwhile go to d_next (may be null: they wait)
-    int upload_piece(size_t p, char *d_txt, char *d_next)
-    {
-        auto put = [&](int sl, size_t k) -> int {
-            const Chunk &ch = chunks[k];
-            char *base = ch.piece == p ? d_txt : d_next;
-            const double te0 = mono_now();
-            if (hipMemcpyAsync(base + ch.at, c->feed_ring + (size_t)sl * SL, ch.len, hipMemcpyHostToDevice, c->stream) != hipSuccess) { harc_set_error("upload of %s failed", name); return HARC_AMD_ENODEVICE; }
-            (void)hipEventRecord(ev[sl], c->stream);
-            inflight.push_back(sl); piece_left[ch.piece]--;
-            t_enqueue += mono_now() - te0;
-            return HARC_AMD_OK;
-        };
-        // what was read ahead for this piece while the last one was uploaded
-        for (size_t i = 0; i < held.size();) {
-            const Chunk &ch = chunks[held[i].second];
-            if (ch.piece == p || (ch.piece == p + 1 && d_next)) { RC_TRY(put(held[i].first, held[i].second)); held.erase(held.begin() + (long)i); } else i++;
-        }
-        while (piece_left[p] > 0) {
-            while (!inflight.empty() && hipEventQuery(ev[inflight.front()]) == hipSuccess) { give_back(inflight.front()); inflight.pop_front(); }
-            std::pair<int, size_t> it(-1, 0);
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                if (filled.empty() && !err) {
-                    if (!inflight.empty()) { lk.unlock(); const double t0 = mono_now(); (void)hipEventSynchronize(ev[inflight.front()]); t_wait_copy += mono_now() - t0; give_back(inflight.front()); inflight.pop_front(); continue; }
-                    const double t0 = mono_now();
-                    cv_filled.wait(lk, [&] { return !filled.empty() || err; });
-                    t_wait_filled += mono_now() - t0;
-                }
-                if (err) { harc_set_error("short read on %s", name); return HARC_AMD_EIO; }
-                it = filled.front(); filled.pop_front();
-            }
-            const Chunk &ch = chunks[it.second];
-            if (ch.piece == p || (ch.piece == p + 1 && d_next)) RC_TRY(put(it.first, it.second));
-            else held.push_back(it);
-        }
-        return HARC_AMD_OK;
-    }
-};
 // bytes [lo, hi) of the file -> device memory; *d_txt is a raw allocation of the context
 static int load_file_range(harc_amd_ctx *c, FILE *f, const char *name, uint64_t lo, uint64_t hi, char **d_txt)
 {

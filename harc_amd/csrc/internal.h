@@ -230,6 +230,10 @@ int harc_host_alloc(harc_amd_ctx *c, void **p, size_t bytes);    // pinned, vali
 void harc_host_reset(harc_amd_ctx *c);
 int harc_d2h(harc_amd_ctx *c, std::vector<uint8_t> &dst, const void *d_src, size_t bytes);
 
+// ---- line index of a text in device memory (ingest.hip): nls[k] = byte position of the newline that ends line k (a last line without one ends at
+// nbytes and counts as a line); nls[-1] = (u64)-1, so that line k starts at nls[k-1] + 1 for every k.  nbytes > 0.  Pool memory: the caller brackets it
+int build_line_index(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const uint64_t **nls_out, uint64_t *total_lines_out);
+
 // ---- BGZF (bgzf.hip): the member chain of a buffer of compressed bytes in device memory, then every member inflated on its own
 struct BgzfCand { uint64_t off; uint32_t bsize, hdr, isize, crc; };                   // a member header that parses at `off`
 struct BgzfMember { uint64_t cdata, text; uint32_t clen, isize, crc, hdr; };          // CDATA at cdata (clen bytes) -> text[text .. + isize)

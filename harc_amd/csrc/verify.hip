@@ -6,6 +6,7 @@
 // (:109-129).  Instead of writing 100 B per read back to the host, every decoded read is hashed and the hashes are summed and
 // xored: an order-independent signature of the decoded multiset that is compared with the same signature of the input reads.
 #include "devutil.h"
+#include "fileio.h"
 #include <string>
 #include <stdlib.h>
 #include <fcntl.h>
@@ -255,121 +256,6 @@ static bool slurp_file(const std::string &path, std::vector<uint8_t> &out)
     return ok;
 }
 
-// HBM -> file at the rate of the host's memory system (round 6: decoder.out's replacement spent 4.4 of its 4.7 s on 100 M reads in D2H copies into pageable
-// vectors and one thread's fwrite): the output file is sized and mapped first (its length is known from the stream files' sizes), the calling thread sends
-// pieces of device memory through a ring of pinned slices (hipMemcpyAsync on the context's stream), writer threads copy every slice that has arrived into the
-// mapping.  write() calls to ONE tmpfs file serialise on its inode (tools/micro/feed_rate.cpp: 6 GB/s with 1 or 16 threads); page faults of a shared mapping do not.
-struct FileDrain {
-    struct Job { int sl; size_t len; uint64_t off; };
-    harc_amd_ctx *c; int fd = -1; char *map = nullptr; size_t fsize = 0;
-    size_t SL = 0; int NS = 0;
-    std::vector<hipEvent_t> ev;
-    std::mutex mu; std::condition_variable cv_free, cv_job, cv_idle;
-    std::deque<int> free_slices; std::deque<Job> jobs; int busy = 0; bool stop = false;
-    std::vector<std::thread> th;
-    // the file's blocks are ALLOCATED ahead of the writers by a thread of its own (posix_fallocate, 64 MB at a time): a store into a mapping of a sparse file on a full
-    // file system is a SIGBUS, not an error code -- this way "no space left" is an error of the call, as it was with fwrite
-    std::thread alloc_th; std::condition_variable cv_alloc; uint64_t alloc_upto = 0; int alloc_err = 0;
-    std::string fname;
-    explicit FileDrain(harc_amd_ctx *c_) : c(c_) {}
-    ~FileDrain() { (void)finish(); }
-    int start(const std::string &path, size_t bytes)
-    {
-        fd = open(path.c_str(), O_CREAT | O_RDWR | O_TRUNC, 0644);
-        if (fd < 0) { harc_set_error("cannot create %s", path.c_str()); return HARC_AMD_EIO; }
-        fsize = bytes; fname = path;
-        if (bytes) {
-            if (ftruncate(fd, (off_t)bytes) != 0) { harc_set_error("cannot size %s to %zu bytes", path.c_str(), bytes); return HARC_AMD_EIO; }
-            map = (char *)mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-            if (map == MAP_FAILED) { map = nullptr; harc_set_error("cannot map %s", path.c_str()); return HARC_AMD_EIO; }
-        }
-        SL = (size_t)64 << 20; NS = 16;
-        int nthr = 16;
-        if (const char *e = getenv("HARC_AMD_FEED_THREADS")) { const int x = atoi(e); if (x >= 1 && x <= 64) nthr = x; }
-        if (const char *e = getenv("HARC_AMD_FEED_SLICE")) { const long long x = atoll(e); if (x >= 16 && x <= ((long long)1 << 30)) SL = (size_t)x; }      // tests: slices of a few reads
-        if (c->feed_ring_bytes < SL * (size_t)NS) {
-            if (c->feed_ring) { (void)hipHostFree(c->feed_ring); c->feed_ring = nullptr; c->feed_ring_bytes = 0; }
-            if (hipHostMalloc((void **)&c->feed_ring, SL * (size_t)NS) != hipSuccess) { harc_set_error("hipHostMalloc of the output ring (%zu bytes) failed", SL * (size_t)NS); return HARC_AMD_ENOMEM; }
-            c->feed_ring_bytes = SL * (size_t)NS;
-        }
-        ev.assign(NS, nullptr);
-        for (int k = 0; k < NS; k++) { if (hipEventCreate(&ev[k]) != hipSuccess) { harc_set_error("hipEventCreate failed"); return HARC_AMD_ENODEVICE; } free_slices.push_back(k); }
-        alloc_th = std::thread([this] {
-            const uint64_t STEP = (uint64_t)64 << 20;
-            for (uint64_t a = 0; a < (uint64_t)fsize; a += STEP) {
-                const uint64_t len = (uint64_t)fsize - a < STEP ? (uint64_t)fsize - a : STEP;
-                const int e = posix_fallocate(fd, (off_t)a, (off_t)len);
-                std::lock_guard<std::mutex> lk(mu);
-                if (e == EOPNOTSUPP || e == EINVAL) { alloc_upto = (uint64_t)fsize; break; }      // a file system without preallocation: as before this round
-                if (e) { alloc_err = e; break; }
-                alloc_upto = a + len;
-                cv_alloc.notify_all();
-                if (stop) break;
-            }
-            cv_alloc.notify_all();
-        });
-        const int dev = c->P.device;
-        for (int t = 0; t < nthr; t++) th.emplace_back([this, dev] {
-            (void)hipSetDevice(dev);
-            for (;;) {
-                Job j;
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv_job.wait(lk, [&] { return stop || !jobs.empty(); });
-                    if (jobs.empty()) return;
-                    j = jobs.front(); jobs.pop_front(); busy++;
-                }
-                (void)hipEventSynchronize(ev[j.sl]);              // the slice has arrived
-                bool space;
-                { std::unique_lock<std::mutex> lk(mu); cv_alloc.wait(lk, [&] { return alloc_err != 0 || alloc_upto >= j.off + j.len; }); space = alloc_err == 0; }
-                if (space) memcpy(map + j.off, c->feed_ring + (size_t)j.sl * SL, j.len);
-                { std::lock_guard<std::mutex> lk(mu); busy--; free_slices.push_back(j.sl); }
-                cv_free.notify_one(); cv_idle.notify_all();
-            }
-        });
-        return HARC_AMD_OK;
-    }
-    // n bytes of device memory -> bytes [off, off + n) of the file.  The copies are on the context's stream: what is enqueued behind them may reuse d_src
-    int put(const void *d_src, size_t n, uint64_t off)
-    {
-        if (off + n > fsize) { harc_set_error("output file: %zu bytes at %llu do not fit its %zu bytes", n, (unsigned long long)off, fsize); return HARC_AMD_EINTERNAL; }
-        for (size_t a = 0; a < n; a += SL) {
-            const size_t len = n - a < SL ? n - a : SL;
-            int sl;
-            { std::unique_lock<std::mutex> lk(mu); cv_free.wait(lk, [&] { return !free_slices.empty(); }); sl = free_slices.front(); free_slices.pop_front(); }
-            if (hipMemcpyAsync(c->feed_ring + (size_t)sl * SL, (const char *)d_src + a, len, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipEventRecord(ev[sl], c->stream) != hipSuccess) {
-                harc_set_error("device -> host copy of the output failed"); return HARC_AMD_ENODEVICE; }
-            { std::lock_guard<std::mutex> lk(mu); jobs.push_back(Job{ sl, len, off + a }); }
-            cv_job.notify_one();
-        }
-        return HARC_AMD_OK;
-    }
-    int put_host(const void *h, size_t n, uint64_t off)
-    {
-        if (off + n > fsize) { harc_set_error("output file: %zu bytes at %llu do not fit its %zu bytes", n, (unsigned long long)off, fsize); return HARC_AMD_EINTERNAL; }
-        if (n) {
-            { std::unique_lock<std::mutex> lk(mu); cv_alloc.wait(lk, [&] { return alloc_err != 0 || alloc_upto >= off + n; }); if (alloc_err) return HARC_AMD_OK; }      // (finish() reports it)
-            memcpy(map + off, h, n);
-        }
-        return HARC_AMD_OK;
-    }
-    int finish()
-    {
-        if (!th.empty()) {
-            { std::unique_lock<std::mutex> lk(mu); cv_idle.wait(lk, [&] { return jobs.empty() && busy == 0; }); stop = true; }
-            cv_job.notify_all();
-            for (auto &t : th) t.join();
-            th.clear();
-        }
-        if (alloc_th.joinable()) alloc_th.join();
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        ev.clear();
-        if (map) { munmap(map, fsize); map = nullptr; }
-        if (fd >= 0) { close(fd); fd = -1; }
-        if (alloc_err) { harc_set_error("cannot allocate %zu bytes for %s: %s", fsize, fname.c_str(), strerror(alloc_err)); const int e = alloc_err; alloc_err = 0; (void)e; return HARC_AMD_EIO; }
-        return HARC_AMD_OK;
-    }
-};
 static size_t file_size_or_zero(const std::string &path) { struct stat st; return stat(path.c_str(), &st) == 0 ? (size_t)st.st_size : 0; }
 
 // decoder.out <basedir> <num_thr> <num_thr_e>  (src/decoder.cpp:44-172, harc:188): writes output/output.dna

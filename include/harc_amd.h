@@ -167,6 +167,16 @@ int harc_amd_set_fastq_device(harc_amd_ctx *ctx, const char *d_fastq, uint64_t n
    leaves the buffer, a position where a member must start but none parses, ISIZE > 65536, a wrong length or CRC-32 or malformed DEFLATE
    data: HARC_AMD_EINVAL naming the compressed byte offset of the member. */
 int harc_amd_bgzf_inflate_device(harc_amd_ctx *ctx, const uint8_t *d_bgzf, uint64_t n_bytes, char *d_out, uint64_t out_capacity, uint64_t *n_out);
+/* The way back to FASTQ: n_records ids (d_ids: id_bytes of text, one id per line, any length, 0 included; a last line without its newline counts as a
+   line), reads and quality values (d_dna, d_quality: n_records lines at a stride of readlen + 1, readlen 1..255 whatever the context's own read length
+   is), all in device memory -> the records  id_i \n read_i \n + \n quality_i \n  at d_out.  The third line is a bare '+': preprocess.cpp drops the rest
+   of it, so that is the only faithful choice.  *n_out = id_bytes (+ 1 if the last id lacks its newline) + n_records * (2 * readlen + 4).
+   d_out == NULL: the inputs are validated and the size returned, nothing written; else out_capacity must be at least that.
+   HARC_AMD_EINVAL, with the counts in harc_amd_last_error(): the id text does not hold exactly n_records lines; a byte at a (readlen + 1)-stride position
+   of the reads or the quality values is no newline, or a newline sits anywhere else in them (counted on the device; what was written to d_out by
+   then is unspecified); out_capacity is too small. */
+int harc_amd_fastq_assemble_device(harc_amd_ctx *ctx, const char *d_ids, uint64_t id_bytes, const char *d_dna, const char *d_quality, uint32_t n_records,
+                                   int32_t readlen, char *d_out, uint64_t out_capacity, uint64_t *n_out);
 /* harc_amd_set_fastq_device for a BGZF-compressed FASTQ in device memory: the context holds the same inputs afterwards, byte for byte */
 int harc_amd_set_fastq_bgzf_device(harc_amd_ctx *ctx, const uint8_t *d_bgzf, uint64_t n_bytes, uint64_t *n_records_out);
 /* stage-II inputs when stage I ran elsewhere (the file family of reorder.cpp:722-830): host buffers.
@@ -271,6 +281,15 @@ int harc_amd_compress_fastq_files(const harc_amd_params *params, const char *fas
    The file may be BGZF (what bgzip writes; told by its first bytes): its members are inflated on the GPU, piece by piece, and every output file is
    the one the plain FASTQ with the same text gives.  Any other gzip is refused with HARC_AMD_EINVAL before a device is touched. */
 int harc_amd_compress_fastq_files_ex(const harc_amd_params *params, const char *fastq, const char *basedir, int32_t preserve_order, int32_t preserve_quality);
+/* The files of a -q run back into one FASTQ file: line i of dna_path (what the decoders write: fixed-length reads, one per line), of id_path and of
+   quality_path become record i of out_path,  id \n read \n + \n quality \n  (harc_amd_fastq_assemble_device).  The read length is the length of the first
+   line of dna_path (more than 255: HARC_AMD_EINVAL); only `device` is taken from params.  The output is size(id) + n * (2 * readlen + 4) bytes with
+   n = size(dna) / (readlen + 1), known before a byte is read.  HARC_AMD_EINVAL before any GPU work: size(dna) is no multiple of readlen + 1, or
+   size(quality) != size(dna).  The job runs in pieces of the id file (256 MiB of id text; HARC_AMD_FQOUT_PIECE=bytes in tests; a piece grows until it holds
+   a whole line), so the files may be larger than device memory.  An id file whose line count differs from n: HARC_AMD_EINVAL naming both counts (the .id
+   file the reference writes WITHOUT -p for an input with N reads can be a line short, and pairs ids wrongly on such inputs anyway: see README).  On any
+   failure out_path is removed.  HARC_AMD_TRACE=1: one "[fastq_out]" line on stderr (bytes, pieces, seconds in the kernel / waiting for readers / writers). */
+int harc_amd_fastq_assemble_files(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out_path);
 /* == `preprocess.out <fastq> <basedir> <preserve_order> <preserve_quality> <readlen>` (src/preprocess.cpp:22-137, harc:50),
    the N split only; host code, feeds the boundary */
 int harc_amd_preprocess_files(const char *fastq, const char *basedir, int32_t readlen);

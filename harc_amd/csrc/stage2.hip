@@ -3,7 +3,7 @@
 // Reference: src/encoder.cpp.  The per-thread sequential contig loop (:219-441) becomes a fully data-parallel pipeline over
 // ONE global column coordinate: every reordered read i gets gstart[i] = the column of its first base in the concatenation
 // of all contig consensi (a prefix sum of the shift bytes, a contig head advancing by readlen).  Then
-//   buildcontig  :619-652  -> k_consensus   (one thread per column, majority over the reads covering it, ties A<C<G<T)
+//   buildcontig  :619-652  -> k_consensus   (one thread per 16 columns, bit-sliced majority over the reads covering them, ties A<C<G<T)
 //   realignment  :231-418  -> k_realign_propose (one thread per window start, 4 dictionary probes, 3-bit XOR+popcount) +
 //                             atomicMin of the (column, direction, dictionary) tuple per candidate read: the sequential
 //                             first-come claim of the reference at num_thr=1 is exactly the minimum tuple
@@ -165,14 +165,39 @@ __global__ void k_contig_info(S2Args s, unsigned long long *cinfo)
 }
 
 // buildcontig (encoder.cpp:619-652): column x <- first strict maximum over A,C,G,T of the reads covering it.
-// A workgroup owns a tile of 2048 columns, a thread a strip of 8.  The reads are sorted by their first column, so the ones that touch
+// A workgroup of 128 threads owns a tile of 2048 columns, a thread a strip of 16.  The reads are sorted by their first column, so the ones that touch
 // the tile are one contiguous range: they go through LDS in pieces of CCHUNK (one coalesced pass over the reads instead of every strip
-// fetching its ~13 reads through L2: 10x the bytes), and a strip finds its own reads in a piece by binary search over their
-// tile-relative starts.  Byte written: base | 4 when a realignment window may start at x (fits in its contig, encoder.cpp:252, and the
-// contig is not the last of its shard).
-#define CSTRIP 8
-#define CTILE (256 * CSTRIP)
-#define CCHUNK 512
+// fetching its reads through L2), and a strip finds its own reads in a piece by binary search over their tile-relative starts.
+// Byte written: base | 4 when a realignment window may start at x (fits in its contig, encoder.cpp:252, and the contig is not the last
+// of its shard).
+//
+// The counting is bit-sliced (round 8): a read's 16 bases at the strip are ONE 32-bit window of its 2-bit words, never taken apart.
+// Its low-bit and high-bit planes give the four one-hot masks "column c holds code 0 / 1 / 2 / 3" on the even bits; two codes share a
+// register (A even | G odd, C even | T odd), so a counter plane of the whole strip is two registers and plane j holds bit j of all 64
+// counts.  A read is added by a ripple of AND/XOR through CL0 = 4 low planes (7 instructions a register, no carry out: at most 15 reads
+// go in before they are emptied); every 15 reads of the wave the low planes are added into the main planes -- a full adder on the first
+// four, then a carry ripple that stops at the first plane where no lane of the wave carries (plane 5 or 6 at 10x coverage, 9 or 10 at
+// 200x; the bound on the planes ever touched, `depth`, is wave-uniform).  Every tile is counted with CSHALLOW = 12 main planes (4095
+// reads on a column; 71 vector registers, 7 waves a SIMD); where a carry leaves plane 11 the tile is flagged and counted again with
+// CPLANES = 32 planes, which hold any count up to M < 2^32 (122 registers: the price of the rare tile, not of every tile).
+// The first strict maximum in row order A C G T is a tournament on the planes from the top one down: (A vs C) and (G vs T) are ONE
+// bitwise comparison of the two registers, the winners' planes a bit-select, their comparison a second pass.
+// The kernel waits more than it issues (staging loads, then LDS trips that depend on each other): the pieces are 256 reads so that LDS
+// does not cap the waves, the LDS trips of the next read are under way while this one is added, and the window flag of a strip costs
+// two trips to memory, not three a column.
+#define CSTRIP 16
+#define CTHREADS 128
+#define CTILE (CTHREADS * CSTRIP)                              // = RTILE: the proposal kernels run on the same tiles (ntiles, S2Args::tile_base)
+#ifndef CCHUNK
+#define CCHUNK 256
+#endif
+#ifndef CL0
+#define CL0 4
+#endif
+#define CPLANES 32
+#ifndef CSHALLOW
+#define CSHALLOW 12
+#endif
 // first and last read that touch tile t (a binary search per tile here, not two dependent ones at the top of every workgroup)
 __global__ void k_consensus_tiles(S2Args s, uint32_t ntiles, uint32_t *tlo, uint32_t *thi)
 {
@@ -182,99 +207,175 @@ __global__ void k_consensus_tiles(S2Args s, uint32_t ntiles, uint32_t *tlo, uint
     thi[t] = (uint32_t)ub_le(s.gstart, (long long)s.M, X1 - 1);             // last read starting inside or before the tile (every column is covered: >= 0)
     tlo[t] = X0 >= (uint64_t)s.L ? (uint32_t)(ub_le(s.gstart, (long long)s.M, X0 - (uint64_t)s.L) + 1) : 0u;   // first read that reaches column X0
 }
-__global__ __launch_bounds__(256) void k_consensus(S2Args s, const uint32_t *cid, const unsigned long long *cinfo, int want_windows, const uint32_t *tlo, const uint32_t *thi)
+// NPL = CSHALLOW: the kernel every tile goes through, its counts good for 2^CSHALLOW - 1 reads on a column; a tile where a carry leaves the top plane
+// says so in tovf[tile] and is counted again by NPL = CPLANES, launched behind it, whose other workgroups leave at once.
+template <int NPL> __global__ __launch_bounds__(CTHREADS, NPL == CPLANES ? 4 : 6) void k_consensus(S2Args s, const uint32_t *cid, const unsigned long long *cinfo, int want_windows, const uint32_t *tlo, const uint32_t *thi, uint32_t *tovf)
 {
+    if (NPL == CPLANES && !tovf[blockIdx.x]) return;
     extern __shared__ uint64_t cl_words[];                        // [CCHUNK][W] read words, then CCHUNK tile-relative starts
     int *const cl_g = reinterpret_cast<int *>(cl_words + (size_t)CCHUNK * s.W);
+    const uint32_t *const cl_w32 = reinterpret_cast<const uint32_t *>(cl_words);   // the same words, 16 bases each
     const uint64_t X0 = (uint64_t)(blockIdx.x + s.tile_base) * CTILE;
     const int L = s.L, W = s.W;
     const long long ilo = tlo[blockIdx.x], ihi = thi[blockIdx.x];
     const int x0r = (int)threadIdx.x * CSTRIP;                   // tile-relative first column of the strip
     const uint64_t x0 = X0 + (uint64_t)x0r;
     const bool mine = x0 < s.total;
-    const int xlr = (x0 + CSTRIP - 1 < s.total ? x0r + CSTRIP - 1 : (int)(s.total - 1 - X0));   // last column of the strip
-    // Column counts: four 32-bit counters per column (rows A C G T, reorder.cpp order of ties) fed from four 8-BIT counters packed into one
-    // register per column (in packed-code order A G C T: the 2-bit code is the byte index, no recoding per base), which are emptied into the
-    // wide ones before any of them can reach 256.  A read adds to all columns of the strip from ONE 16-bit window of its words (round 2:
-    // per base a word select, a shift, a recode and four compare-adds: 22.6 G vector instructions per launch at configs[2], 34 ms).
-    uint32_t cnt[CSTRIP][4], pk[CSTRIP];
+    const int ncol = !mine ? 0 : x0 + CSTRIP <= s.total ? CSTRIP : (int)(s.total - x0);   // columns of the strip inside the consensus
+    const int xlr = x0r + ncol - 1;                               // last column of the strip
+    const uint32_t EVEN = 0x55555555u;
+    // lo[h][j], pl[h][j]: plane j of the counts of codes 2h (even bits) and 2h + 1 (odd bits), packed code order A0 G1 C2 T3
+    uint32_t lo[2][CL0], pl[2][NPL];
 #pragma unroll
-    for (int c = 0; c < CSTRIP; c++) { cnt[c][0] = cnt[c][1] = cnt[c][2] = cnt[c][3] = 0; pk[c] = 0; }
-    int since = 0;                                                // reads added to pk since it was last emptied
+    for (int j = 0; j < CL0; j++) lo[0][j] = lo[1][j] = 0;
+#pragma unroll
+    for (int j = 0; j < NPL; j++) pl[0][j] = pl[1][j] = 0;
+    bool ovf = false;                                             // a carry left plane NPL - 1
+    int pend = 0, depth = CL0;                                    // wave-uniform: reads since the low planes were emptied; main planes ever written
     auto flush = [&]() {
+        uint32_t ca = 0, cb = 0;
 #pragma unroll
-        for (int c = 0; c < CSTRIP; c++) {
-            cnt[c][0] += pk[c] & 0xFFu; cnt[c][2] += (pk[c] >> 8) & 0xFFu; cnt[c][1] += (pk[c] >> 16) & 0xFFu; cnt[c][3] += pk[c] >> 24;   // code A0 G1 C2 T3 -> row A0 C1 G2 T3
-            pk[c] = 0;
+        for (int j = 0; j < CL0; j++) {
+            const uint32_t xa = pl[0][j] ^ lo[0][j], xb = pl[1][j] ^ lo[1][j];
+            const uint32_t na = (pl[0][j] & lo[0][j]) | (xa & ca), nb = (pl[1][j] & lo[1][j]) | (xb & cb);
+            pl[0][j] = xa ^ ca; pl[1][j] = xb ^ cb; ca = na; cb = nb;
+            lo[0][j] = lo[1][j] = 0;
         }
-        since = 0;
+#pragma unroll
+        for (int j = CL0; j < CSHALLOW; j++) {
+#ifndef HARC_CONS_FIXED_DEPTH
+            if (__builtin_amdgcn_ballot_w64((ca | cb) != 0) == 0) break;
+#endif
+            const uint32_t ta = pl[0][j] & ca, tb = pl[1][j] & cb;
+            pl[0][j] ^= ca; pl[1][j] ^= cb; ca = ta; cb = tb;
+            if (depth < j + 1) depth = j + 1;
+        }
+        if (NPL > CSHALLOW) {
+#ifndef HARC_CONS_FIXED_DEPTH
+            if (__builtin_amdgcn_ballot_w64((ca | cb) != 0) != 0)  // a count past 2^CSHALLOW - 1: the rest of the planes in one piece
+#endif
+            {
+#pragma unroll
+                for (int j = CSHALLOW; j < NPL; j++) {
+                    const uint32_t ta = pl[0][j] & ca, tb = pl[1][j] & cb;
+                    pl[0][j] ^= ca; pl[1][j] ^= cb; ca = ta; cb = tb;
+                }
+                depth = NPL;
+            }
+        } else ovf |= (ca | cb) != 0;
+        pend = 0;
     };
     long long ilast = ilo - 1;                                    // last read starting at or before x0
+    int nstart = 0;                                               // reads that start behind it inside the strip
     for (long long base = ilo; base <= ihi; base += CCHUNK) {
         const int nch = (int)(ihi + 1 - base < CCHUNK ? ihi + 1 - base : CCHUNK);
         __syncthreads();
-        for (int k = threadIdx.x; k < nch * W; k += 256) cl_words[k] = s.oreads[(size_t)base * W + k];
-        for (int k = threadIdx.x; k < nch; k += 256) cl_g[k] = (int)((long long)s.gstart[base + k] - (long long)X0);
+        for (int k = threadIdx.x; k < nch * W; k += CTHREADS) cl_words[k] = s.oreads[(size_t)base * W + k];
+        for (int k = threadIdx.x; k < nch; k += CTHREADS) cl_g[k] = (int)((long long)s.gstart[base + k] - (long long)X0);
         __syncthreads();
-        if (!mine) continue;
-        // reads of the piece that cover a column of the strip: start in (x0r - L, xlr]
-        int lo = -1, hi = nch;                                    // cl_g[lo] <= x0r - L < cl_g[hi]
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (cl_g[mid] <= x0r - L) lo = mid; else hi = mid; }
-        const int first = hi;
-        lo = first - 1; hi = nch;                                 // cl_g[lo] <= xlr < cl_g[hi]
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (cl_g[mid] <= xlr) lo = mid; else hi = mid; }
-        const int last = lo;
-        for (int k = first; k <= last; k++) {
-            const int g = cl_g[k];
-            if (g <= x0r) ilast = base + k;
-            const uint64_t *r = cl_words + (size_t)k * W;
-            const int o0 = x0r - g;                               // offset of column x0 inside the read (may be negative)
-            // the 2 CSTRIP bits of the read at the strip's columns: bases o0 .. o0 + CSTRIP - 1 (those before the read's start come out of the shift as zeros and are masked)
-            const int j0 = o0 < 0 ? 0 : o0;
-            const int w0 = j0 >> 5, sh = 2 * (j0 & 31);
-            const uint64_t wa = r[w0], wb = (w0 + 1 < W) ? r[w0 + 1] : 0;
-            uint32_t bits = (uint32_t)(sh ? ((wa >> sh) | (wb << (64 - sh))) : wa) & 0xFFFFu;
-            if (o0 < 0) bits <<= 2 * (-o0);                       // column c holds base o0 + c: the read starts inside the strip
-            // columns of the strip the read covers: c >= -o0, o0 + c < L, x0r + c <= xlr
-            const int c_lo = o0 < 0 ? -o0 : 0, c_hi = (L - o0 < xlr - x0r + 1 ? L - o0 : xlr - x0r + 1);      // [c_lo, c_hi)
-            uint32_t vm = c_hi >= CSTRIP ? 0xFFu : ((1u << (c_hi > 0 ? c_hi : 0)) - 1u);
-            vm &= ~((1u << c_lo) - 1u);
+        // reads of the piece that cover a column of the strip: start in (x0r - L, xlr].  The first one by binary search; the run ends at the first
+        // start past xlr, which the loop meets by itself (a strip past the end of the consensus: none)
+        int k = nch;
+        if (mine) {
+            int a = -1, b = nch;                                  // cl_g[a] <= x0r - L < cl_g[b]
+            while (b - a > 1) { const int mid = (a + b) >> 1; if (cl_g[mid] <= x0r - L) a = mid; else b = mid; }
+            k = b;
+        }
+        // two LDS trips a read, the second behind the first (its start, then the window at the offset the start gives): both are asked for one
+        // read ahead, so that the adds of read k run while the window of read k + 1 and the start of read k + 2 are on their way
+        auto start_of = [&](int kk) { return kk < nch ? cl_g[kk] : 0x7FFFFFFF; };      // past the piece: ends the run
+        auto window_of = [&](int kk, int g, uint32_t &w0, uint32_t &w1) {
+            // the read's bases o0 .. o0 + 15 lie in two 32-bit halves of its words.  The upper half may lie past the read's last word (the next
+            // read's, or the first start behind the words: inside the allocation) -- those bases are >= L and masked.
+            const int o0 = x0r - g, j0 = o0 < 0 ? 0 : o0;
+            const uint32_t *r = cl_w32 + (size_t)(kk < nch ? kk : nch - 1) * (2 * W) + (j0 >> 4);
+            w0 = r[0]; w1 = r[1];
+        };
+        int g = start_of(k), gn = start_of(k + 1);
+        uint32_t w0, w1;
+        window_of(k, g, w0, w1);
+        for (;; k++) {                                            // the wave goes on while one of its strips has a read left: pend is uniform
+            const bool act = g <= xlr;
+            if (__builtin_amdgcn_ballot_w64(act) == 0) break;
+            uint32_t w0n, w1n;
+            window_of(k + 1, gn, w0n, w1n);
+            const int gnn = start_of(k + 2);
+            if (act) {
+                if (g <= x0r) ilast = base + k; else nstart++;
+                const int o0 = x0r - g;                           // offset of column x0 inside the read (negative: the read starts inside the strip)
+                uint32_t bits = __builtin_amdgcn_alignbit(w1, w0, (uint32_t)(2 * ((o0 < 0 ? 0 : o0) & 15)));   // one 32-bit window: a funnel shift
+                if (o0 < 0) bits <<= 2 * (-o0);                   // column c holds base o0 + c
+                // columns of the strip the read covers: c >= -o0, o0 + c < L, c < ncol -- [c_lo, c_hi), never empty
+                const int c_lo = o0 < 0 ? -o0 : 0, c_hi = L - o0 < ncol ? L - o0 : ncol;
+                uint32_t vm = c_hi >= CSTRIP ? 0xFFFFFFFFu : ((1u << (2 * (c_hi > 0 ? c_hi : 0))) - 1u);
+                vm &= ~((1u << (2 * c_lo)) - 1u) & EVEN;
+                const uint32_t b0 = bits & vm, b1 = (bits >> 1) & vm;
+                uint32_t ma = (vm & ~(b0 | b1)) | ((b0 & ~b1) << 1);      // one-hot: code 0 on the even bits, code 1 on the odd ones
+                uint32_t mb = (b1 & ~b0) | ((b0 & b1) << 1);              //          code 2,                  code 3
 #pragma unroll
-            for (int c = 0; c < CSTRIP; c++) pk[c] += ((vm >> c) & 1u) << (8u * ((bits >> (2 * c)) & 3u));
-            if (++since == 255) flush();
+                for (int j = 0; j < CL0; j++) {
+                    const uint32_t ta = lo[0][j] & ma, tb = lo[1][j] & mb;
+                    lo[0][j] ^= ma; lo[1][j] ^= mb; ma = ta; mb = tb;
+                }
+            }
+            g = gn; gn = gnn; w0 = w0n; w1 = w1n;
+            if (++pend == (1 << CL0) - 1) flush();
         }
     }
     flush();
+    if (NPL < CPLANES && ovf) tovf[blockIdx.x] = 1;
     if (!mine) return;
-    uint32_t kprev = HARC_NONE; unsigned long long cend = 0; bool lastc = true;
-    long long i = ilast;
-    uint8_t outb[CSTRIP];
+    // first strict maximum over the rows A C G T = the earliest row that holds the largest count.  lt: C > A (even bits), T > G (odd bits);
+    // w = the planes of the two winners; lt2 (even bits): the winner of (G, T) > the winner of (A, C).  A tie keeps the earlier row every time.
+    depth = __builtin_amdgcn_readfirstlane(depth);
+    uint32_t lt = 0, dec = 0, lt2 = 0, dec2 = 0;
+#pragma unroll
+    for (int j = NPL - 1; j >= 0; j--)
+        if (j < depth) { const uint32_t d = pl[0][j] ^ pl[1][j]; lt |= d & ~dec & pl[1][j]; dec |= d; }
+#pragma unroll
+    for (int j = NPL - 1; j >= 0; j--)
+        if (j < depth) {
+            const uint32_t w = (pl[0][j] & ~lt) | (pl[1][j] & lt), d = (w ^ (w >> 1)) & EVEN;
+            lt2 |= d & ~dec2 & (w >> 1); dec2 |= d;
+        }
+    const uint32_t indw = (lt2 & (lt >> 1)) | (~lt2 & lt & EVEN) | (lt2 << 1);     // two bits a column: row A0 C1 G2 T3
+    // may a realignment window start at x: the contig of the last read that starts at or before x says.  The reads that start inside the strip
+    // are ilast + 1 .. ilast + nstart: where the last of them lies in the contig of read ilast (nearly everywhere) the whole strip has one
+    // answer behind two trips to memory; else the reads are walked column by column.
+    uint32_t outw[CSTRIP / 4];
+    uint32_t vmask = 0;                                           // bit c: a window may start at column c
+    if (want_windows) {
+        const long long ie = ilast + nstart;
+        const uint32_t ka = cid[ilast] + (uint32_t)s.head[ilast] - 1u, ke = cid[ie] + (uint32_t)s.head[ie] - 1u;    // cid = exclusive scan of the head flags: a head's own contig index
+        unsigned long long ci = cinfo[ka];
+        if (ka == ke) {
+            const unsigned long long cend = ci & ~(1ULL << 63);
+            if (!(ci >> 63) && x0 + (uint64_t)L <= cend) { const unsigned long long nv = cend - (x0 + (uint64_t)L) + 1; vmask = nv >= CSTRIP ? 0xFFFFu : (1u << (int)nv) - 1u; }
+        } else {
+            uint32_t kprev = ka; long long i = ilast;
+            uint64_t gnext = i + 1 < (long long)s.M ? s.gstart[i + 1] : ~0ull;
+            bool moved = false;
+            for (int c = 0; c < ncol; c++) {
+                const uint64_t x = x0 + c;
+                while (gnext <= x) { i++; gnext = i + 1 < (long long)s.M ? s.gstart[i + 1] : ~0ull; moved = true; }
+                if (moved) {
+                    const uint32_t k = cid[i] + (uint32_t)s.head[i] - 1u;
+                    if (k != kprev) { ci = cinfo[k]; kprev = k; }
+                    moved = false;
+                }
+                if (!(ci >> 63) && x + (uint64_t)L <= (ci & ~(1ULL << 63))) vmask |= 1u << c;
+            }
+        }
+    }
 #pragma unroll
     for (int c = 0; c < CSTRIP; c++) {
-        const uint64_t x = x0 + c;
-        outb[c] = 0;
-        if (x >= s.total) continue;
-        uint32_t mx = 0; int ind = 0;
-        if (cnt[c][0] > mx) { mx = cnt[c][0]; ind = 0; }
-        if (cnt[c][1] > mx) { mx = cnt[c][1]; ind = 1; }
-        if (cnt[c][2] > mx) { mx = cnt[c][2]; ind = 2; }
-        if (cnt[c][3] > mx) { mx = cnt[c][3]; ind = 3; }
-        int valid = 0;
-        if (want_windows) {
-            while (i + 1 < (long long)s.M && s.gstart[i + 1] <= x) i++;
-            const uint32_t k = cid[i] + (uint32_t)s.head[i] - 1u;    // cid = exclusive scan of the head flags: a head's own contig index
-            if (k != kprev) { const unsigned long long ci = cinfo[k]; kprev = k; cend = ci & ~(1ULL << 63); lastc = (ci >> 63) != 0; }
-            valid = (!lastc && x + (uint64_t)L <= cend) ? 1 : 0;
-        }
-        outb[c] = (uint8_t)(ind | (valid << 2));
+        if ((c & 3) == 0) outw[c >> 2] = 0;
+        outw[c >> 2] |= (((indw >> (2 * c)) & 3u) | (((vmask >> c) & 1u) << 2)) << (8 * (c & 3));
     }
-    if (x0 + CSTRIP <= s.total) {
-        uint2 w;
-        w.x = (uint32_t)outb[0] | ((uint32_t)outb[1] << 8) | ((uint32_t)outb[2] << 16) | ((uint32_t)outb[3] << 24);
-        w.y = (uint32_t)outb[4] | ((uint32_t)outb[5] << 8) | ((uint32_t)outb[6] << 16) | ((uint32_t)outb[7] << 24);
-        *reinterpret_cast<uint2 *>(s.cons + x0) = w;
+    if (ncol == CSTRIP) {
+        *reinterpret_cast<uint4 *>(s.cons + x0) = make_uint4(outw[0], outw[1], outw[2], outw[3]);
     } else {
-        for (int c = 0; c < CSTRIP && x0 + c < s.total; c++) s.cons[x0 + c] = outb[c];
+        for (int c = 0; c < ncol; c++) s.cons[x0 + c] = (uint8_t)(outw[c >> 2] >> (8 * (c & 3)));
     }
 }
 
@@ -422,6 +523,7 @@ template <int W> __device__ __forceinline__ void cons_words(const uint64_t *cons
 // read has a base, and 1 + popcount(window code) where it has an N (N = 001 against A 000, G 010, C 100, T 110).
 #define RSTRIP 8
 #define RTILE (256 * RSTRIP)
+static_assert(RTILE == CTILE, "the proposal kernels are launched on the consensus kernel's tiles");
 // one probe that passed the bitmap: window start x, direction, dictionary, key
 template <int W> __device__ __forceinline__ void realign_probe(const S2Args &s, uint64_t x, int dir, int l, uint64_t key)
 {
@@ -1725,8 +1827,12 @@ int stage2_run(harc_amd_ctx *c)
         const uint32_t ntiles = (uint32_t)((col1 + CTILE - 1) / CTILE) - a.tile_base;      // the tiles that hold a column of [col0, col1)
         uint32_t *tlo = nullptr, *thi = nullptr; RC_TRY(dalloc(c, &tlo, (size_t)ntiles + 1)); RC_TRY(dalloc(c, &thi, (size_t)ntiles + 1));
         hipLaunchKernelGGL(k_consensus_tiles, G256(ntiles), a, ntiles, tlo, thi);
-        hipLaunchKernelGGL(k_consensus, dim3(ntiles), dim3(256), (size_t)CCHUNK * (W * 8 + 4), c->stream, a, (const uint32_t *)u1, (const unsigned long long *)cinfo, T ? 1 : 0,
-                           (const uint32_t *)tlo, (const uint32_t *)thi);
+        uint32_t *tovf = nullptr; RC_TRY(dalloc(c, &tovf, (size_t)ntiles + 1));
+        HIP_TRY(hipMemsetAsync(tovf, 0, (size_t)ntiles * 4, c->stream));
+        hipLaunchKernelGGL(k_consensus<CSHALLOW>, dim3(ntiles), dim3(CTHREADS), (size_t)CCHUNK * (W * 8 + 4), c->stream, a, (const uint32_t *)u1, (const unsigned long long *)cinfo, T ? 1 : 0,
+                           (const uint32_t *)tlo, (const uint32_t *)thi, tovf);
+        hipLaunchKernelGGL(k_consensus<CPLANES>, dim3(ntiles), dim3(CTHREADS), (size_t)CCHUNK * (W * 8 + 4), c->stream, a, (const uint32_t *)u1, (const unsigned long long *)cinfo, T ? 1 : 0,
+                           (const uint32_t *)tlo, (const uint32_t *)thi, tovf);
         { const uint64_t w0 = col0 / 32, w1 = (col1 + 31) / 32; hipLaunchKernelGGL(k_pack_cons2, G256(w1 - w0), (const uint8_t *)a.cons, total, w0, w1 - w0, cons2); }
         {   // read_seq (packbits, encoder.cpp:527-548) is final here -- the realignment below does not touch the consensus -- and the shard
             // boundaries on the column axis follow from gstart alone: it is packed now and goes to the host on the copy stream while the

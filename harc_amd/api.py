@@ -91,6 +91,11 @@ def lib():
     l.harc_amd_fastq_assemble_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64,
                                                  C.POINTER(C.c_uint64)]
     l.harc_amd_fastq_assemble_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]
+    l.harc_amd_fastq_assemble_files_ex.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32]
+    l.harc_amd_bgzf_bound.argtypes = [C.c_uint64]
+    l.harc_amd_bgzf_bound.restype = C.c_uint64
+    l.harc_amd_bgzf_deflate_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_bgzf_deflate_host.argtypes = [C.c_char_p, C.c_uint64, C.c_int32, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
     l.harc_amd_decode_signature.argtypes = [ctx, C.POINTER(C.c_uint64)]
     l.harc_amd_input_signature.argtypes = [ctx, C.POINTER(C.c_uint64)]
     l.harc_amd_reads_signature_device.argtypes = [ctx, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
@@ -210,11 +215,29 @@ def decoder(basedir, num_thr_e, device=0, preserve_order=False, memory_gb=0):
     _check(f(C.byref(p), os.fsencode(basedir), num_thr_e))
 
 
-def fastq_assemble(dna, ids, quality, out, device=0):
+def fastq_assemble(dna, ids, quality, out, device=0, bgzf=False):
     """line i of the files `dna` (fixed-length reads), `ids` and `quality` -> record i of the FASTQ file `out` (id, read, a bare '+', quality), assembled on
-    the GPU; the read length is that of the first read (include/harc_amd.h: harc_amd_fastq_assemble_files)"""
+    the GPU; the read length is that of the first read (include/harc_amd.h: harc_amd_fastq_assemble_files).  bgzf: `out` is that text as BGZF (a .fastq.gz),
+    deflated on the GPU as well (harc_amd_fastq_assemble_files_ex)"""
     p = default_params(100, device=device)
-    _check(lib().harc_amd_fastq_assemble_files(C.byref(p), os.fsencode(dna), os.fsencode(ids), os.fsencode(quality), os.fsencode(out)))
+    if bgzf:
+        _check(lib().harc_amd_fastq_assemble_files_ex(C.byref(p), os.fsencode(dna), os.fsencode(ids), os.fsencode(quality), os.fsencode(out), 1))
+    else:
+        _check(lib().harc_amd_fastq_assemble_files(C.byref(p), os.fsencode(dna), os.fsencode(ids), os.fsencode(quality), os.fsencode(out)))
+
+
+def bgzf_bound(n):
+    """bytes of BGZF that n bytes of text take at most (every member stored, and the end-of-file marker); host only"""
+    return int(lib().harc_amd_bgzf_bound(n))
+
+
+def bgzf_deflate_host(text, eof=True):
+    """the encoder of HarcAmd.bgzf_deflate_device run in a row on the host: the bytes the kernels must write (tests; no device)"""
+    cap = bgzf_bound(len(text))
+    out = C.create_string_buffer(cap)
+    n = C.c_uint64(0)
+    _check(lib().harc_amd_bgzf_deflate_host(text, len(text), 1 if eof else 0, out, cap, C.byref(n)))
+    return out.raw[:n.value]
 
 
 def pack_order(basedir, readlen=100, **kw):
@@ -263,6 +286,14 @@ class HarcAmd:
         """BGZF bytes in device memory -> their text at out_ptr (device memory); without out_ptr only the text size. -> text bytes"""
         n = C.c_uint64(0)
         _check(lib().harc_amd_bgzf_inflate_device(self._ctx, C.c_void_p(dptr), nbytes, C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
+        return n.value
+
+    def bgzf_deflate_device(self, d_text, nbytes, out_ptr=None, out_capacity=0, eof=True):
+        """text in device memory -> BGZF at out_ptr (device memory), members of 65 280 bytes of text deflated on the GPU, the end-of-file marker behind them
+        when eof; without out_ptr only the size. -> bytes of BGZF.  bgzf_bound(nbytes) is always enough capacity"""
+        n = C.c_uint64(0)
+        _check(lib().harc_amd_bgzf_deflate_device(self._ctx, C.c_void_p(d_text) if d_text else None, nbytes, 1 if eof else 0,
+                                                  C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
         return n.value
 
     def fastq_assemble_device(self, d_ids, id_bytes, d_dna, d_quality, n, readlen, out_ptr=None, out_capacity=0):

@@ -14,6 +14,7 @@
 // The same lanes check the fixed-width inputs on the way -- a newline at every (readlen + 1)-stride position and nowhere else -- into an error counter.
 #include "devutil.h"
 #include "fileio.h"
+#include "deflate_member.h"
 
 #define FQ_TILE 16384
 #define FQ_WAVES 4
@@ -220,8 +221,8 @@ extern "C" int harc_amd_fastq_assemble_device(harc_amd_ctx *c, const char *d_ids
 namespace {
 struct DevBuf { char *p = nullptr; size_t cap = 0; };
 struct DevBufs {
-    harc_amd_ctx *c; DevBuf id[2], dna, qual, out;
-    ~DevBufs() { for (DevBuf *b : { &id[0], &id[1], &dna, &qual, &out }) if (b->p) harc_raw_free(c, b->p); }
+    harc_amd_ctx *c; DevBuf id[2], dna, qual, out, gz;
+    ~DevBufs() { for (DevBuf *b : { &id[0], &id[1], &dna, &qual, &out, &gz }) if (b->p) harc_raw_free(c, b->p); }
 };
 // at least `need` bytes, the first `keep` of them kept
 int buf_reserve(harc_amd_ctx *c, DevBuf *b, size_t need, size_t keep)
@@ -239,6 +240,14 @@ bool file_size(const char *path, uint64_t *n) { struct stat st; if (stat(path, &
 }
 
 extern "C" int harc_amd_fastq_assemble_files(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out_path)
+{
+    return harc_amd_fastq_assemble_files_ex(params, dna_path, id_path, quality_path, out_path, 0);
+}
+
+// bgzf: every assembled piece is deflated where it sits (bgzf_out.hip).  Members are cut at multiples of DM_TEXT of the whole text: what a piece leaves behind its
+// last full member stays at the front of the text buffer and the next piece is assembled behind it, so the file does not depend on how the job was cut into pieces
+extern "C" int harc_amd_fastq_assemble_files_ex(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out_path,
+                                                int32_t bgzf)
 {
     if (!params || !dna_path || !id_path || !quality_path || !out_path) { harc_set_error("fastq_assemble_files: bad arguments"); return HARC_AMD_EINVAL; }
     uint64_t dsz = 0, isz = 0, qsz = 0;
@@ -300,7 +309,8 @@ extern "C" int harc_amd_fastq_assemble_files(const harc_amd_params *params, cons
     unsigned int *d_err = nullptr; RC_TRY(dalloc(c, &d_err, 4));
     HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
     FileDrain drain(c);
-    RC_TRY(drain.start(out_path, (size_t)out_size, &gq[3]));
+    RC_TRY(drain.start(out_path, bgzf ? (size_t)dm_bound(out_size) : (size_t)out_size, &gq[3], bgzf != 0));
+    BgzfOutStats gst; uint64_t gz_at = 0, tcarry = 0;                  // bgzf: bytes of the file so far; text in front of B.out that no member holds yet
     // the job is driven by the id file: a piece is a byte range of it; what follows the piece's last newline is carried into the next piece
     uint64_t piece = (uint64_t)256 << 20;
     if (const char *e = getenv("HARC_AMD_FQOUT_PIECE")) { const unsigned long long v = strtoull(e, nullptr, 10); if (v >= 1) piece = v; }
@@ -330,7 +340,7 @@ extern "C" int harc_amd_fastq_assemble_files(const harc_amd_params *params, cons
         if (r0 + m > n) over = true;                                                         // more ids than reads: the lines are still counted, for the message
         if (!over && m) {
             const uint64_t nb = m * LL, out_bytes = cut + ((lastp && open_tail) ? 1 : 0) + m * K;
-            RC_TRY(buf_reserve(c, &B.dna, (size_t)nb, 0)); RC_TRY(buf_reserve(c, &B.qual, (size_t)nb, 0)); RC_TRY(buf_reserve(c, &B.out, (size_t)out_bytes, 0));
+            RC_TRY(buf_reserve(c, &B.dna, (size_t)nb, 0)); RC_TRY(buf_reserve(c, &B.qual, (size_t)nb, 0)); RC_TRY(buf_reserve(c, &B.out, (size_t)(tcarry + out_bytes), (size_t)tcarry));
             {   // lines [r0, r0 + m) of the two fixed-width files, by offset
                 FileFeeder fd(c, dna_path), fq(c, quality_path);
                 RC_TRY(fd.start({ { r0 * LL, (r0 + m) * LL } }, gq[1])); RC_TRY(fq.start({ { r0 * LL, (r0 + m) * LL } }, gq[2]));
@@ -338,9 +348,21 @@ extern "C" int harc_amd_fastq_assemble_files(const harc_amd_params *params, cons
                 RC_TRY(fd.upload_piece(0, B.dna.p, nullptr)); RC_TRY(fq.upload_piece(0, B.qual.p, nullptr));
                 t_read += mono_now() - t0;
                 HIP_TRY(hipEventRecord(ev0, c->stream));
-                RC_TRY(fq_run(c, d_ids, nls, B.dna.p, B.qual.p, (uint32_t)m, L, B.out.p, out_bytes, d_err));
+                RC_TRY(fq_run(c, d_ids, nls, B.dna.p, B.qual.p, (uint32_t)m, L, B.out.p + tcarry, out_bytes, d_err));
                 HIP_TRY(hipEventRecord(ev1, c->stream));
-                { const double t0w = mono_now(); RC_TRY(drain.put(B.out.p, (size_t)out_bytes, out_at)); t_write += mono_now() - t0w; }
+                if (!bgzf) { const double t0w = mono_now(); RC_TRY(drain.put(B.out.p, (size_t)out_bytes, out_at)); t_write += mono_now() - t0w; }
+                else {
+                    const uint64_t have = tcarry + out_bytes, full = have / DM_TEXT * DM_TEXT;
+                    if (full) {
+                        uint64_t ngz = 0;
+                        RC_TRY(buf_reserve(c, &B.gz, (size_t)dm_bound(full), 0));
+                        RC_TRY(harc_bgzf_deflate(c, B.out.p, full, 0, (uint8_t *)B.gz.p, B.gz.cap, &ngz, &gst));
+                        { const double t0w = mono_now(); RC_TRY(drain.put(B.gz.p, (size_t)ngz, gz_at)); t_write += mono_now() - t0w; }
+                        gz_at += ngz;
+                        if (have > full) HIP_TRY(hipMemcpyAsync(B.out.p, B.out.p + full, (size_t)(have - full), hipMemcpyDeviceToDevice, c->stream));     // (less than a member: no overlap)
+                    }
+                    tcarry = have - full;
+                }
                 out_at += out_bytes; npieces++;
                 HIP_TRY(hipEventSynchronize(ev1));
                 float ms = 0; (void)hipEventElapsedTime(&ms, ev0, ev1); t_kernel += 1e-3 * (double)ms;
@@ -361,8 +383,19 @@ extern "C" int harc_amd_fastq_assemble_files(const harc_amd_params *params, cons
     }
     if (out_at != out_size) { harc_set_error("fastq_assemble_files: %llu bytes assembled, the file sizes announce %llu", (unsigned long long)out_at, (unsigned long long)out_size); return HARC_AMD_EINTERNAL; }
     RC_TRY(fq_check_errors(c, d_err, L));
+    if (bgzf) {                                                       // the last member and the end-of-file marker
+        uint64_t ngz = 0;
+        RC_TRY(buf_reserve(c, &B.gz, (size_t)dm_bound(tcarry), 0));
+        RC_TRY(harc_bgzf_deflate(c, B.out.p, tcarry, 1, (uint8_t *)B.gz.p, B.gz.cap, &ngz, &gst));
+        { const double t0w = mono_now(); RC_TRY(drain.put(B.gz.p, (size_t)ngz, gz_at)); t_write += mono_now() - t0w; }
+        gz_at += ngz;
+        drain.set_final_size(gz_at);
+    }
     { const double t0 = mono_now(); RC_TRY(drain.finish()); t_write += mono_now() - t0; }
-    if (tlog) fprintf(stderr, "[fastq_out] %llu bytes in %d pieces: %.3f s in the kernel, %.3f s waiting for the readers, %.3f s waiting for the writers\n",
+    if (tlog && bgzf) fprintf(stderr, "[fastq_out] %llu bytes in %d pieces: %.3f s in the kernel, %.3f s waiting for the readers, %.3f s waiting for the writers; BGZF: %llu bytes of text -> %llu bytes in %llu members (%llu stored), %.3f s in the deflate kernels\n",
+                              (unsigned long long)out_size, npieces, t_kernel, t_read, t_write, (unsigned long long)gst.text, (unsigned long long)gz_at, (unsigned long long)gst.members,
+                              (unsigned long long)gst.stored, gst.seconds);
+    else if (tlog) fprintf(stderr, "[fastq_out] %llu bytes in %d pieces: %.3f s in the kernel, %.3f s waiting for the readers, %.3f s waiting for the writers\n",
                       (unsigned long long)out_size, npieces, t_kernel, t_read, t_write);
     outguard.ok = true;
     return HARC_AMD_OK;

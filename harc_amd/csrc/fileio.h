@@ -196,12 +196,18 @@ struct FileDrain {
     // the file's blocks are ALLOCATED ahead of the writers by a thread of its own (posix_fallocate, 64 MB at a time): a store into a mapping of a sparse file on a full
     // file system is a SIGBUS, not an error code -- this way "no space left" is an error of the call, as it was with fwrite
     std::thread alloc_th; std::condition_variable cv_alloc; uint64_t alloc_upto = 0; int alloc_err = 0;
+    // a file whose size is only bounded when it is opened (BGZF output): `bytes` of start() is the bound, blocks are allocated no further than what put() has been
+    // given (lazy), and finish() cuts the file to the size set_final_size() announced
+    std::condition_variable cv_goal; uint64_t alloc_goal = 0; bool lazy = false; bool have_final = false; uint64_t final_size = 0;
     std::string fname;
     explicit FileDrain(harc_amd_ctx *c_) : c(c_) {}
     ~FileDrain() { (void)finish(); }
     // geom == nullptr: the whole ring in the default geometry, with HARC_AMD_FEED_SLICE / HARC_AMD_FEED_THREADS read here
-    int start(const std::string &path, size_t bytes, const RingGeom *geom = nullptr)
+    void set_final_size(uint64_t n) { have_final = true; final_size = n; }
+    void raise_goal(uint64_t upto) { if (!lazy) return; { std::lock_guard<std::mutex> lk(mu); if (upto > alloc_goal) alloc_goal = upto; } cv_goal.notify_all(); }
+    int start(const std::string &path, size_t bytes, const RingGeom *geom = nullptr, bool lazy_alloc = false)
     {
+        lazy = lazy_alloc; alloc_goal = lazy_alloc ? 0 : (uint64_t)bytes;
         fd = open(path.c_str(), O_CREAT | O_RDWR | O_TRUNC, 0644);
         if (fd < 0) { harc_set_error("cannot create %s", path.c_str()); return HARC_AMD_EIO; }
         fsize = bytes; fname = path;
@@ -221,6 +227,7 @@ struct FileDrain {
         alloc_th = std::thread([this] {
             const uint64_t STEP = (uint64_t)64 << 20;
             for (uint64_t a = 0; a < (uint64_t)fsize; a += STEP) {
+                if (lazy) { std::unique_lock<std::mutex> lk(mu); cv_goal.wait(lk, [&] { return stop || alloc_goal > a; }); if (alloc_goal <= a) break; }
                 const uint64_t len = (uint64_t)fsize - a < STEP ? (uint64_t)fsize - a : STEP;
                 const int e = posix_fallocate(fd, (off_t)a, (off_t)len);
                 std::lock_guard<std::mutex> lk(mu);
@@ -257,6 +264,7 @@ struct FileDrain {
     int put(const void *d_src, size_t n, uint64_t off)
     {
         if (off + n > fsize) { harc_set_error("output file: %zu bytes at %llu do not fit its %zu bytes", n, (unsigned long long)off, fsize); return HARC_AMD_EINTERNAL; }
+        raise_goal(off + n);
         for (size_t a = 0; a < n; a += SL) {
             const size_t len = n - a < SL ? n - a : SL;
             int sl;
@@ -271,6 +279,7 @@ struct FileDrain {
     int put_host(const void *h, size_t n, uint64_t off)
     {
         if (off + n > fsize) { harc_set_error("output file: %zu bytes at %llu do not fit its %zu bytes", n, (unsigned long long)off, fsize); return HARC_AMD_EINTERNAL; }
+        raise_goal(off + n);
         if (n) {
             { std::unique_lock<std::mutex> lk(mu); cv_alloc.wait(lk, [&] { return alloc_err != 0 || alloc_upto >= off + n; }); if (alloc_err) return HARC_AMD_OK; }      // (finish() reports it)
             memcpy(map + off, h, n);
@@ -285,11 +294,15 @@ struct FileDrain {
             for (auto &t : th) t.join();
             th.clear();
         }
+        { std::lock_guard<std::mutex> lk(mu); stop = true; }
+        cv_goal.notify_all();
         if (alloc_th.joinable()) alloc_th.join();
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
         ev.clear();
         if (map) { munmap(map, fsize); map = nullptr; }
-        if (fd >= 0) { close(fd); fd = -1; }
+        bool cut_failed = false;
+        if (fd >= 0) { if (have_final && final_size < fsize && ftruncate(fd, (off_t)final_size) != 0) cut_failed = true; close(fd); fd = -1; }
+        if (cut_failed) { harc_set_error("cannot cut %s to its %llu bytes", fname.c_str(), (unsigned long long)final_size); return HARC_AMD_EIO; }
         if (alloc_err) { harc_set_error("cannot allocate %zu bytes for %s: %s", fsize, fname.c_str(), strerror(alloc_err)); const int e = alloc_err; alloc_err = 0; (void)e; return HARC_AMD_EIO; }
         return HARC_AMD_OK;
     }

@@ -243,3 +243,8 @@ struct BgzfPlan { std::vector<BgzfMember> m; uint64_t text = 0, next = 0; };    
 int harc_bgzf_plan(harc_amd_ctx *c, const uint8_t *d_in, uint64_t n, uint64_t start, uint64_t own_end, uint64_t base_off, BgzfPlan *plan);
 // their text -> d_out[0 .. plan.text); HARC_AMD_EINVAL naming the first bad member (length, CRC-32, any malformed DEFLATE data)
 int harc_bgzf_run(harc_amd_ctx *c, const uint8_t *d_in, const BgzfPlan &plan, uint64_t base_off, char *d_out);
+
+// ---- BGZF out (bgzf_out.hip): text in device memory -> members of DM_TEXT bytes of text each, deflated on the GPU (deflate_member.h), packed at d_out
+struct BgzfOutStats { uint64_t text = 0, bytes = 0, members = 0, stored = 0; double seconds = 0; };     // summed over calls; seconds: in the deflate kernels
+// flags bit 0: the end-of-file marker follows the last member.  d_out == nullptr: *n_out alone.  st may be null
+int harc_bgzf_deflate(harc_amd_ctx *c, const char *d_text, uint64_t n_bytes, int32_t flags, uint8_t *d_out, uint64_t out_capacity, uint64_t *n_out, BgzfOutStats *st);

@@ -11,7 +11,8 @@
 //   harc_amd_stage compressfq_shard <basedir> <readlen> <fastq> <num_thr> <num_chains> <num_steps> <preserve_order> <preserve_quality>
 //                                   <world> <rank> <comm_spec> [device] [replicate]    one rank of `./harc -c -g <world>` (one process per GPU)
 //   harc_amd_stage merge_shards <basedir> <world>                          the whole-job files of the archive from the rank parts
-//   harc_amd_stage fastq_out <dna> <ignored> <id> <quality> <out>            lines i of the three files -> record i of the FASTQ file <out> (./harc -d -q)
+//   harc_amd_stage fastq_out <dna> <ignored> <id> <quality> <out> [bgzf]     lines i of the three files -> record i of the FASTQ file <out> (./harc -d -q);
+//                                                                          bgzf: <out> is that text as BGZF, deflated on the GPU (./harc -d -q -z)
 // readlen / num_thr arrive as arguments instead of the compile-time macros of src/config.h (harc:52-63).
 #include <stdio.h>
 #include <stdlib.h>
@@ -30,10 +31,11 @@ int main(int argc, char **argv)
         return 0;
     }
     if (!strcmp(argv[1], "fastq_out")) {                          // the read length is the first line's of <dna>
-        if (argc < 7) { fprintf(stderr, "fastq_out needs <dna> <ignored> <id> <quality> <out>\n"); return 2; }
+        if (argc < 7) { fprintf(stderr, "fastq_out needs <dna> <ignored> <id> <quality> <out> [bgzf]\n"); return 2; }
+        if (argc > 7 && strcmp(argv[7], "bgzf")) { fprintf(stderr, "fastq_out: the sixth argument can only be 'bgzf' (got '%s')\n", argv[7]); return 2; }
         harc_amd_params PF;
         if (harc_amd_default_params(100, &PF) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
-        const int rcf = harc_amd_fastq_assemble_files(&PF, argv[2], argv[4], argv[5], argv[6]);
+        const int rcf = argc > 7 ? harc_amd_fastq_assemble_files_ex(&PF, argv[2], argv[4], argv[5], argv[6], 1) : harc_amd_fastq_assemble_files(&PF, argv[2], argv[4], argv[5], argv[6]);
         if (rcf != 0) { fprintf(stderr, "harc_amd_stage fastq_out failed (%d): %s\n", rcf, harc_amd_last_error()); return 1; }
         return 0;
     }

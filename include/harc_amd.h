@@ -167,6 +167,16 @@ int harc_amd_set_fastq_device(harc_amd_ctx *ctx, const char *d_fastq, uint64_t n
    leaves the buffer, a position where a member must start but none parses, ISIZE > 65536, a wrong length or CRC-32 or malformed DEFLATE
    data: HARC_AMD_EINVAL naming the compressed byte offset of the member. */
 int harc_amd_bgzf_inflate_device(harc_amd_ctx *ctx, const uint8_t *d_bgzf, uint64_t n_bytes, char *d_out, uint64_t out_capacity, uint64_t *n_out);
+/* The other way: text in device memory -> BGZF in device memory, deflated on the GPU.  The text is cut every 65 280 bytes (bgzip's size) into members that are
+   deflated independently, a workgroup each: matches only against the line four lines up at the same column (what repeats in FASTQ; no search), one dynamic
+   Huffman block per member, a stored block where that is not smaller (harc_amd/csrc/deflate_member.h holds the rules).  The bytes depend on the text alone.
+   flags bit 0: the 28-byte end-of-file marker follows the last member; n_bytes == 0 gives the marker alone, or nothing.  *n_out = bytes of the members (and the
+   marker).  d_out == NULL: the size alone (the members are deflated to learn it); else HARC_AMD_EINVAL naming both numbers when out_capacity is smaller.
+   harc_amd_bgzf_bound(n_bytes) is always enough.  No byte outside [d_out, d_out + *n_out) is written, whatever the alignment of d_out or d_text. */
+uint64_t harc_amd_bgzf_bound(uint64_t n_text);        /* host only: ceil(n / 65280) * (65280 + 31) + 28 */
+int harc_amd_bgzf_deflate_device(harc_amd_ctx *ctx, const char *d_text, uint64_t n_bytes, int32_t flags, uint8_t *d_out, uint64_t out_capacity, uint64_t *n_out);
+/* the same encoder run in a row on the host (host memory, no device): what the kernels must write, byte for byte.  out_capacity >= harc_amd_bgzf_bound(n_bytes) */
+int harc_amd_bgzf_deflate_host(const char *text, uint64_t n_bytes, int32_t flags, uint8_t *out, uint64_t out_capacity, uint64_t *n_out);
 /* The way back to FASTQ: n_records ids (d_ids: id_bytes of text, one id per line, any length, 0 included; a last line without its newline counts as a
    line), reads and quality values (d_dna, d_quality: n_records lines at a stride of readlen + 1, readlen 1..255 whatever the context's own read length
    is), all in device memory -> the records  id_i \n read_i \n + \n quality_i \n  at d_out.  The third line is a bare '+': preprocess.cpp drops the rest
@@ -290,6 +300,12 @@ int harc_amd_compress_fastq_files_ex(const harc_amd_params *params, const char *
    file the reference writes WITHOUT -p for an input with N reads can be a line short, and pairs ids wrongly on such inputs anyway: see README).  On any
    failure out_path is removed.  HARC_AMD_TRACE=1: one "[fastq_out]" line on stderr (bytes, pieces, seconds in the kernel / waiting for readers / writers). */
 int harc_amd_fastq_assemble_files(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out_path);
+/* harc_amd_fastq_assemble_files is this call with bgzf = 0.  bgzf = 1: out_path is the same FASTQ text as BGZF (harc_amd_bgzf_deflate_device: every assembled
+   piece is deflated where it sits in device memory; one end-of-file marker ends the file) -- a .fastq.gz that harc_amd_compress_fastq_files, bgzip -d, gzip -d and
+   samtools read.  The file is a function of the FASTQ text alone: members are cut at multiples of 65 280 bytes of the whole text, whatever the pieces
+   (HARC_AMD_FQOUT_PIECE, HARC_AMD_FEED_SLICE).  Empty inputs give the 28-byte marker.  Refusals and the removal of out_path on failure are those of the plain
+   call.  HARC_AMD_TRACE=1: the "[fastq_out]" line also names text bytes, compressed bytes, members, stored members and the seconds in the deflate kernels. */
+int harc_amd_fastq_assemble_files_ex(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out_path, int32_t bgzf);
 /* == `preprocess.out <fastq> <basedir> <preserve_order> <preserve_quality> <readlen>` (src/preprocess.cpp:22-137, harc:50),
    the N split only; host code, feeds the boundary */
 int harc_amd_preprocess_files(const char *fastq, const char *basedir, int32_t readlen);

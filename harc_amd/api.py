@@ -96,6 +96,14 @@ def lib():
     l.harc_amd_bgzf_bound.restype = C.c_uint64
     l.harc_amd_bgzf_deflate_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     l.harc_amd_bgzf_deflate_host.argtypes = [C.c_char_p, C.c_uint64, C.c_int32, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_qpack_bound.argtypes = [C.c_uint64, C.c_int32, C.c_uint32]
+    l.harc_amd_qpack_bound.restype = C.c_uint64
+    l.harc_amd_qpack_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_qunpack_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_qpack_host.argtypes = [C.c_char_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_int32, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_qunpack_host.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_qpack_files.argtypes = [PP, C.c_char_p, C.c_char_p]
+    l.harc_amd_qunpack_files.argtypes = [PP, C.c_char_p, C.c_char_p]
     l.harc_amd_decode_signature.argtypes = [ctx, C.POINTER(C.c_uint64)]
     l.harc_amd_input_signature.argtypes = [ctx, C.POINTER(C.c_uint64)]
     l.harc_amd_reads_signature_device.argtypes = [ctx, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
@@ -240,6 +248,45 @@ def bgzf_deflate_host(text, eof=True):
     return out.raw[:n.value]
 
 
+def qpack_bound(n_reads, readlen, reads_per_block=0):
+    """bytes that n_reads quality lines of readlen take at most as a packed quality file: 32 + blocks * 5 + n_reads * readlen; host only"""
+    return int(lib().harc_amd_qpack_bound(n_reads, readlen, reads_per_block))
+
+
+def qpack_host(text, readlen, reads_per_block=0, header=True):
+    """the encoder of HarcAmd.qpack_device run in a row on the host: the bytes the kernels must write (tests; no device).  text: lines of readlen quality
+    values and a newline each"""
+    n, rem = divmod(len(text), readlen + 1)
+    if rem:
+        raise HarcAmdError(-1, f"{len(text)} bytes are no multiple of the {readlen + 1} bytes of a line")
+    cap = qpack_bound(n, readlen, reads_per_block)
+    out = C.create_string_buffer(cap)
+    got = C.c_uint64(0)
+    _check(lib().harc_amd_qpack_host(text, n, readlen, reads_per_block, 1 if header else 0, out, cap, C.byref(got)))
+    return out.raw[:got.value]
+
+
+def qunpack_host(packed):
+    """a packed quality file (with its header) -> its lines, decoded on the host by the functions the kernels compile; HarcAmdError(-1) for damaged input"""
+    size = C.c_uint64(0)
+    _check(lib().harc_amd_qunpack_host(packed, len(packed), None, 0, C.byref(size)))
+    out = C.create_string_buffer(size.value + 1)
+    _check(lib().harc_amd_qunpack_host(packed, len(packed), out, size.value, C.byref(size)))
+    return out.raw[:size.value]
+
+
+def qpack_files(quality, out, device=0):
+    """the quality file `quality` (fixed-length lines) -> the packed quality file `out`, coded on the GPU (include/harc_amd.h: harc_amd_qpack_files)"""
+    p = default_params(100, device=device)
+    _check(lib().harc_amd_qpack_files(C.byref(p), os.fsencode(quality), os.fsencode(out)))
+
+
+def qunpack_files(packed, out, device=0):
+    """the packed quality file `packed` -> the quality file `out`, decoded on the GPU"""
+    p = default_params(100, device=device)
+    _check(lib().harc_amd_qunpack_files(C.byref(p), os.fsencode(packed), os.fsencode(out)))
+
+
 def pack_order(basedir, readlen=100, **kw):
     """== `pack_order.out <basedir>` (src/pack_order.cpp:11-77)"""
     p = default_params(readlen, **kw)
@@ -304,6 +351,20 @@ class HarcAmd:
                                                     C.c_void_p(d_quality) if d_quality else None, n, readlen, C.c_void_p(out_ptr) if out_ptr else None,
                                                     out_capacity, C.byref(n_out)))
         return n_out.value
+
+    def qpack_device(self, d_text, n_reads, readlen, reads_per_block=0, out_ptr=None, out_capacity=0, header=True):
+        """n_reads quality lines of readlen (+ newline) in device memory -> the packed form at out_ptr (device memory), with the 32-byte file header when
+        header; without out_ptr only the size. -> bytes.  qpack_bound(n_reads, readlen, reads_per_block) is always enough capacity"""
+        n = C.c_uint64(0)
+        _check(lib().harc_amd_qpack_device(self._ctx, C.c_void_p(d_text) if d_text else None, n_reads, readlen, reads_per_block, 1 if header else 0,
+                                           C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
+        return n.value
+
+    def qunpack_device(self, d_packed, nbytes, out_ptr=None, out_capacity=0):
+        """a packed quality file in device memory -> its lines at out_ptr (device memory); without out_ptr only their size. -> bytes of text"""
+        n = C.c_uint64(0)
+        _check(lib().harc_amd_qunpack_device(self._ctx, C.c_void_p(d_packed), nbytes, C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
+        return n.value
 
     def set_fastq_bgzf_device(self, dptr, nbytes):
         """set_fastq_device for a BGZF-compressed FASTQ in device memory (inflated on the GPU) -> complete records"""

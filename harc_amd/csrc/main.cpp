@@ -13,6 +13,8 @@
 //   harc_amd_stage merge_shards <basedir> <world>                          the whole-job files of the archive from the rank parts
 //   harc_amd_stage fastq_out <dna> <ignored> <id> <quality> <out> [bgzf]     lines i of the three files -> record i of the FASTQ file <out> (./harc -d -q);
 //                                                                          bgzf: <out> is that text as BGZF, deflated on the GPU (./harc -d -q -z)
+//   harc_amd_stage quality_pack <quality> <device> <out>                   the fixed-length lines of <quality> -> the packed quality file <out> (./harc -c -q -Q)
+//   harc_amd_stage quality_unpack <packed> <device> <out>                  ... and back (./harc -d -q when only X.quality.hq is there)
 // readlen / num_thr arrive as arguments instead of the compile-time macros of src/config.h (harc:52-63).
 #include <stdio.h>
 #include <stdlib.h>
@@ -37,6 +39,15 @@ int main(int argc, char **argv)
         if (harc_amd_default_params(100, &PF) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
         const int rcf = argc > 7 ? harc_amd_fastq_assemble_files_ex(&PF, argv[2], argv[4], argv[5], argv[6], 1) : harc_amd_fastq_assemble_files(&PF, argv[2], argv[4], argv[5], argv[6]);
         if (rcf != 0) { fprintf(stderr, "harc_amd_stage fastq_out failed (%d): %s\n", rcf, harc_amd_last_error()); return 1; }
+        return 0;
+    }
+    if (!strcmp(argv[1], "quality_pack") || !strcmp(argv[1], "quality_unpack")) {     // the read length is in the file
+        if (argc < 5) { fprintf(stderr, "%s needs <in> <device> <out>\n", argv[1]); return 2; }
+        harc_amd_params PQ;
+        if (harc_amd_default_params(100, &PQ) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
+        PQ.device = atoi(argv[3]);
+        const int rcq = !strcmp(argv[1], "quality_pack") ? harc_amd_qpack_files(&PQ, argv[2], argv[4]) : harc_amd_qunpack_files(&PQ, argv[2], argv[4]);
+        if (rcq != 0) { fprintf(stderr, "harc_amd_stage %s failed (%d): %s\n", argv[1], rcq, harc_amd_last_error()); return 1; }
         return 0;
     }
     harc_amd_params P;

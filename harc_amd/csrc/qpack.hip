@@ -1,0 +1,626 @@
+// qpack.hip -- quality lines in device memory <-> the packed quality file X.quality.hq (README: "The packed quality file"), what ./harc -c -q -Q writes and
+// ./harc -d -q reads.  Every byte of a block is decided by qv_block.h; this file spreads its functions over a workgroup per block.
+//
+// Packing.  Sizes are needed before bytes can be placed, as in bgzf_out.hip, and the way is the same: code into scratch, scan, gather.
+//   k_qp_encode   a workgroup of 256 per block, lane t owns the lines t, t + 256, ... -- which is also strand t.  Pass A: every byte against 33..126, the bitmap,
+//                 the stride check.  Pass B: the (A + 1) x A histogram with LDS atomics.  A lane per row normalises it (qv_norm_row) and the table stays in LDS as
+//                 frequency | cumulative << 16.  Then every lane codes its strand downwards into its slab of scratch (qv_strand_encode); the strand lengths are
+//                 scanned over the workgroup, the header, table and lengths are written in front of the slabs, and the block's size, stored or coded, is decided.
+//   (scan of the block sizes, prims.hip)
+//   k_qp_gather   a workgroup per block copies u32 payload_bytes, header and strands -- or the stored lines -- to their byte-granular place: whole dwords of the
+//                 destination inside the block, the bytes in front of and behind them one by one.  Nothing outside the blocks is written.
+// The lanes of a wave read 64 neighbouring lines at a stride of L + 1 bytes in all three walks over the text: the same cache lines serve the next hundred symbols.
+//
+// Unpacking.  The block offsets follow from the payload_bytes prefixes (k_qp_walk, one lane; the file call walks them on the host with pread).
+//   k_qp_decode   a workgroup per block validates head, table and strand lengths into LDS (qv_check_head, qv_load_row), then a lane per strand decodes forward
+//                 (qv_strand_decode) and writes its lines, a newline behind each.  Any violation raises the error word: block number << 8 | QV_E_*.
+#include "devutil.h"
+#include "qv_block.h"
+#include "fileio.h"
+
+#define QP_T 256
+#define QP_HDR ((14u + 2u * QV_TABLE + 4u * QV_STRANDS + 15u) & ~15u)     // the head of a coded payload in front of the block's slabs, rounded to 16
+
+struct QpShared {
+    uint32_t fc[QV_TABLE];
+    uint32_t bm[3], bad, A, err, mode;
+    uint32_t scan[QP_T / 64 + 1];
+    unsigned long long sum;
+    uint8_t sym_of[96], byte_of[96];
+};
+struct QpGather { uint32_t scan[QP_T / 64 + 1], soff[QV_STRANDS], slen[QV_STRANDS]; };
+struct QpStats { uint64_t text = 0, bytes = 0, blocks = 0, stored = 0; double seconds = 0; };
+
+// len bytes src -> dst by the nt lanes of a group (lane tid): dwords of the destination, bytes at its ends.  Up to 3 bytes behind src + len are read (never used)
+__device__ __forceinline__ void qp_copy(uint8_t *dst, const uint8_t *src, uint32_t len, uint32_t tid, uint32_t nt)
+{
+    uint32_t head = (uint32_t)((0 - (uintptr_t)dst) & 3);
+    if (head > len) head = len;
+    if (tid < head) dst[tid] = src[tid];
+    const uint32_t nd = (len - head) >> 2;
+    for (uint32_t i = tid; i < nd; i += nt) {
+        const uintptr_t u = (uintptr_t)(src + head + 4 * i);
+        const uint32_t sh = (uint32_t)(u & 3);
+        const uint32_t *sw = (const uint32_t *)(u - sh);
+        *(uint32_t *)(dst + head + 4 * i) = sh ? __builtin_amdgcn_alignbyte(sw[1], sw[0], sh) : sw[0];
+    }
+    const uint32_t done = head + 4 * nd;
+    if (tid < len - done) dst[done + tid] = src[done + tid];
+}
+
+// err[0]: stride positions that hold no newline; err[1]: newlines inside a line; err[2]: strands that did not fit their slab (never); err[3]: stored blocks
+__global__ __launch_bounds__(QP_T) void k_qp_encode(const uint8_t *text, uint64_t n_lines, uint32_t L, uint32_t RB, uint32_t nb, uint8_t *scratch, uint64_t stride,
+                                                    uint32_t slab, uint32_t *bsize, uint32_t *bmode, unsigned int *err)
+{
+    __shared__ QpShared S;
+    const uint64_t b = harc_bid();
+    if (b >= nb) return;
+    const uint32_t t = threadIdx.x;
+    const uint64_t line0 = b * (uint64_t)RB;
+    const uint32_t m = n_lines - line0 < RB ? (uint32_t)(n_lines - line0) : RB;
+    const uint8_t *tx = text + line0 * (L + 1u);
+    for (uint32_t i = t; i < QV_TABLE; i += QP_T) S.fc[i] = 0;
+    if (t < 3) S.bm[t] = 0;
+    if (t == 0) S.bad = 0;
+    __syncthreads();
+    {   // ---- A: alphabet and stride
+        uint64_t lo = 0; uint32_t hi = 0, bad = 0, e0 = 0, e1 = 0;
+        for (uint32_t i = t; i < m; i += QP_T) {
+            const uint8_t *ln = tx + (uint64_t)i * (L + 1u);
+            for (uint32_t j = 0; j < L; j++) {
+                const uint32_t v = ln[j], k = v - QV_FIRST;
+                if (k < 64u) lo |= 1ull << k; else if (k < QV_MAXA) hi |= 1u << (k - 64u); else { bad = 1; e1 += v == '\n'; }
+            }
+            e0 += ln[L] != '\n';
+        }
+        if ((uint32_t)lo) atomicOr(&S.bm[0], (uint32_t)lo);
+        if (lo >> 32) atomicOr(&S.bm[1], (uint32_t)(lo >> 32));
+        if (hi) atomicOr(&S.bm[2], hi);
+        if (bad) atomicOr(&S.bad, 1u);
+        if (e0) atomicAdd(&err[0], e0);
+        if (e1) atomicAdd(&err[1], e1);
+    }
+    __syncthreads();
+    if (S.bad) {                                                   // a byte outside the alphabet: stored
+        if (t == 0) { bsize[b] = 4u + 1u + m * L; bmode[b] = 0; atomicAdd(&err[3], 1u); }
+        return;
+    }
+    const uint32_t A = qv_rank(S.bm, 96);
+    if (t < QV_MAXA) qv_map_entry(S.bm, t, S.sym_of, S.byte_of);
+    __syncthreads();
+    // ---- B: the histogram
+    for (uint32_t i = t; i < m; i += QP_T) {
+        const uint8_t *ln = tx + (uint64_t)i * (L + 1u);
+        uint32_t ctx = A;
+        for (uint32_t j = 0; j < L; j++) { const uint32_t y = S.sym_of[ln[j] - QV_FIRST]; atomicAdd(&S.fc[ctx * A + y], 1u); ctx = y; }
+    }
+    __syncthreads();
+    if (t <= A) { qv_norm_row(S.fc + t * A, A); qv_cum_row(S.fc + t * A, A); }
+    __syncthreads();
+    // ---- the head of the payload: mode, A, bitmap, table
+    uint8_t *hdr = scratch + b * stride;
+    if (t == 0) { hdr[0] = 1; hdr[1] = (uint8_t)A; qv_put32(hdr + 2, S.bm[0]); qv_put32(hdr + 6, S.bm[1]); qv_put32(hdr + 10, S.bm[2]); }
+    for (uint32_t i = t; i < (A + 1u) * A; i += QP_T) { const uint32_t f = S.fc[i] & 0xFFFFu; hdr[14 + 2 * i] = (uint8_t)f; hdr[15 + 2 * i] = (uint8_t)(f >> 8); }
+    // ---- the strands
+    uint8_t *slab_lo = hdr + QP_HDR + (uint64_t)t * slab;
+    uint32_t len = qv_strand_encode(tx, L, m, t, S.fc, A, S.sym_of, slab_lo, slab_lo + slab);
+    if (len == QV_SLAB_OVERFLOW) { atomicAdd(&err[2], 1u); len = 0; }
+    uint32_t total;
+    (void)block_excl_scan_u32<QP_T>(len, S.scan, &total);
+    qv_put32(hdr + 14 + 2u * (A + 1u) * A + 4u * t, len);
+    if (t == 0) {
+        const int coded = qv_use_coded(A, total, m, L);
+        bsize[b] = 4u + (coded ? qv_hdr1(A) + total : 1u + m * L);
+        bmode[b] = coded ? 1u : 0u;
+        if (!coded) atomicAdd(&err[3], 1u);
+    }
+}
+
+__global__ __launch_bounds__(QP_T) void k_qp_gather(const uint8_t *text, uint64_t n_lines, uint32_t L, uint32_t RB, uint32_t nb, const uint8_t *scratch, uint64_t stride,
+                                                    uint32_t slab, const uint32_t *bsize, const uint32_t *bmode, const uint64_t *boff, uint8_t *out)
+{
+    __shared__ QpGather S;
+    const uint64_t b = harc_bid();
+    if (b >= nb) return;
+    const uint32_t t = threadIdx.x;
+    const uint64_t line0 = b * (uint64_t)RB;
+    const uint32_t m = n_lines - line0 < RB ? (uint32_t)(n_lines - line0) : RB;
+    uint8_t *dst = out + boff[b];
+    const uint32_t payload = bsize[b] - 4u;
+    if (t < 4) dst[t] = (uint8_t)(payload >> (8 * t));
+    if (!bmode[b]) {
+        const uint8_t *tx = text + line0 * (L + 1u);
+        if (t == 0) dst[4] = 0;
+        for (uint32_t j = t; j < m * L; j += QP_T) { const uint32_t i = j / L; dst[5 + j] = tx[(uint64_t)i * (L + 1u) + (j - i * L)]; }
+        return;
+    }
+    const uint8_t *hdr = scratch + b * stride;
+    const uint32_t A = hdr[1], h = qv_hdr1(A);
+    const uint32_t len = qv_le32(hdr + h - 4u * QV_STRANDS + 4u * t);
+    uint32_t total;
+    const uint32_t off = block_excl_scan_u32<QP_T>(len, S.scan, &total);
+    S.soff[t] = off; S.slen[t] = len;
+    qp_copy(dst + 4, hdr, h, t, QP_T);
+    __syncthreads();
+    const uint32_t wv = t >> 6, lane = t & 63u;
+    for (uint32_t s = wv; s < QV_STRANDS; s += QP_T / 64) {
+        const uint32_t n = S.slen[s];
+        if (n) qp_copy(dst + 4 + h + S.soff[s], hdr + QP_HDR + (uint64_t)(s + 1u) * slab - n, n, lane, 64);
+    }
+}
+
+// The offsets of the nb blocks behind the 32-byte header of p[0 .. n_bytes), relative to p + 32; off[nb] = their end.  bad[0]: 1 + the first block whose prefix
+// or payload leaves the bytes (nb + 1: bytes are left behind the last block), bad[1]: its offset
+__global__ void k_qp_walk(const uint8_t *p, uint64_t n_bytes, uint64_t nb, uint64_t *off, unsigned long long *bad)
+{
+    if (threadIdx.x || blockIdx.x) return;
+    uint64_t at = QV_FILE_HEADER;
+    for (uint64_t b = 0; b < nb; b++) {
+        off[b] = at - QV_FILE_HEADER;
+        if (n_bytes - at < 4) { bad[0] = b + 1; bad[1] = at; return; }
+        const uint64_t pb = qv_le32(p + at);
+        if (pb == 0 || n_bytes - at - 4 < pb) { bad[0] = b + 1; bad[1] = at; return; }
+        at += 4 + pb;
+    }
+    off[nb] = at - QV_FILE_HEADER;
+    if (at != n_bytes) { bad[0] = nb + 1; bad[1] = at; }
+}
+
+// blocks: block b of this call at blocks + off[b], off[b + 1] - off[b] bytes with its u32; lines [b RB, ..) of the n_lines lines at text
+__global__ __launch_bounds__(QP_T) void k_qp_decode(const uint8_t *blocks, const uint64_t *off, uint32_t nb, uint64_t n_lines, uint32_t L, uint32_t RB, uint8_t *text,
+                                                    unsigned long long *errw)
+{
+    __shared__ QpShared S;
+    const uint64_t b = harc_bid();
+    if (b >= nb) return;
+    const uint32_t t = threadIdx.x;
+    const uint64_t line0 = b * (uint64_t)RB;
+    const uint32_t m = n_lines - line0 < RB ? (uint32_t)(n_lines - line0) : RB;
+    const uint8_t *pl = blocks + off[b] + 4;
+    const uint32_t pbytes = (uint32_t)(off[b + 1] - off[b] - 4);
+    uint8_t *tx = text + line0 * (L + 1u);
+    if (t == 0) { S.sum = 0; S.A = 0; S.mode = 0; S.err = (uint32_t)qv_check_head(pl, pbytes, m, L, &S.mode, &S.A, S.bm); }
+    __syncthreads();
+    if (S.err) { if (t == 0) atomicMin(errw, ((unsigned long long)b << 8) | S.err); return; }
+    if (S.mode == 0) {
+        const uint64_t nbytes = (uint64_t)m * (L + 1u);
+        for (uint64_t j = t; j < nbytes; j += QP_T) { const uint64_t i = j / (L + 1u); const uint32_t col = (uint32_t)(j - i * (L + 1u)); tx[j] = col == L ? (uint8_t)'\n' : pl[1 + i * L + col]; }
+        return;
+    }
+    const uint32_t A = S.A, h = qv_hdr1(A), rest = pbytes - h;
+    if (t < QV_MAXA) qv_map_entry(S.bm, t, S.sym_of, S.byte_of);
+    uint32_t e = 0;
+    if (t <= A) e = (uint32_t)qv_load_row(pl + 14, t, A, S.fc + t * A);
+    uint32_t len = qv_le32(pl + h - 4u * QV_STRANDS + 4u * t);
+    if (!e && (qv_strand_lines(m, t) ? len < 4 : len != 0)) e = QV_E_SHORT;
+    if (!e && len > rest) e = QV_E_LENGTHS;
+    if (e) { atomicMax(&S.err, e); len = 0; }
+    atomicAdd(&S.sum, (unsigned long long)len);
+    __syncthreads();
+    if (t == 0 && !S.err && S.sum != rest) S.err = QV_E_LENGTHS;
+    __syncthreads();
+    if (S.err) { if (t == 0) atomicMin(errw, ((unsigned long long)b << 8) | S.err); return; }
+    uint32_t total;
+    const uint32_t at = block_excl_scan_u32<QP_T>(len, S.scan, &total);
+    e = (uint32_t)qv_strand_decode(pl + h + at, len, S.fc, A, S.byte_of, tx, L, m, t);
+    if (e) atomicMax(&S.err, e);
+    __syncthreads();
+    if (t == 0 && S.err) atomicMin(errw, ((unsigned long long)b << 8) | S.err);
+}
+
+static const char *qv_error_text(uint32_t e)
+{
+    switch (e) {
+    case QV_E_MODE: return "its mode is neither 0 nor 1";
+    case QV_E_SIZE: return "its payload size does not fit its mode";
+    case QV_E_ALPHABET: return "its symbol count is not that of its bitmap";
+    case QV_E_ROW: return "a row of its table sums to neither 0 nor 4096";
+    case QV_E_LENGTHS: return "its strand lengths do not sum to the rest of its payload";
+    case QV_E_SHORT: return "a strand with lines is shorter than 4 bytes, or one without lines is not empty";
+    case QV_E_TRUNC: return "a strand ends before its last symbol";
+    case QV_E_CONTEXT: return "a symbol is coded in a context that never occurs";
+    case QV_E_END: return "a strand does not end in the state and at the byte it must";
+    }
+    return "unknown error";
+}
+
+// ------------------------------------------------------------------------------------------------ packing: the blocks of n lines
+static int qp_check_geometry(const char *who, int32_t readlen, uint32_t *rb)
+{
+    if (readlen < 1 || readlen > 255) { harc_set_error("%s: the read length %d is not in 1..255", who, readlen); return HARC_AMD_EINVAL; }
+    if (*rb == 0) *rb = qv_default_rb((uint32_t)readlen);
+    if ((uint64_t)*rb * (uint64_t)readlen > QV_MAX_BLOCK_SYMBOLS) { harc_set_error("%s: %u reads of %d per block are more than %u quality values", who, *rb, readlen, QV_MAX_BLOCK_SYMBOLS); return HARC_AMD_EINVAL; }
+    return HARC_AMD_OK;
+}
+// the blocks alone (no file header) -> d_out[0 .. *n_out); d_out == nullptr: the size alone
+static int harc_qpack_run(harc_amd_ctx *c, const char *d_text, uint64_t n, uint32_t L, uint32_t RB, uint8_t *d_out, uint64_t out_capacity, uint64_t *n_out, QpStats *st)
+{
+    *n_out = 0;
+    const uint64_t nb64 = qv_blocks(n, RB);
+    if (nb64 > 0x7FFFFFF0ull) { harc_set_error("qpack: too many blocks for one call"); return HARC_AMD_EINVAL; }
+    const uint32_t nb = (uint32_t)nb64;
+    if (!nb) return HARC_AMD_OK;
+    PoolScope scope(c);
+    const uint32_t mmax = n < RB ? (uint32_t)n : RB, slab = qv_slab_bytes(qv_strand_lines(mmax, 0) * L);
+    const uint64_t stride = (uint64_t)QP_HDR + (uint64_t)QV_STRANDS * slab;
+    uint8_t *scratch = nullptr; uint32_t *bsize = nullptr, *bmode = nullptr; uint64_t *boff = nullptr; unsigned int *d_err = nullptr;
+    RC_TRY(dalloc(c, &scratch, (size_t)(stride * nb))); RC_TRY(dalloc(c, &bsize, (size_t)nb + 1)); RC_TRY(dalloc(c, &bmode, (size_t)nb)); RC_TRY(dalloc(c, &boff, (size_t)nb + 1));
+    RC_TRY(dalloc(c, &d_err, 4));
+    HIP_TRY(hipMemsetAsync(bsize + nb, 0, 4, c->stream));
+    HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    struct EvGuard { hipEvent_t &a, &b; ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evguard{ e0, e1 };
+    if (st) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, c->stream)); }
+    hipLaunchKernelGGL(k_qp_encode, harc_fold256(nb), dim3(QP_T), 0, c->stream, (const uint8_t *)d_text, n, L, RB, nb, scratch, stride, slab, bsize, bmode, d_err);
+    HIP_TRY(hipGetLastError());
+    RC_TRY(prim_excl_scan_u32_to_u64(c, bsize, boff, (size_t)nb + 1));
+    uint64_t total = 0; unsigned int err[4] = { 0, 0, 0, 0 };
+    HIP_TRY(hipMemcpyAsync(&total, boff + nb, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(err, d_err, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (err[0] || err[1]) {
+        harc_set_error("qpack: the text is not lines of %u quality values: %u positions on the %u-byte stride hold no newline and %u newlines are off it", L, err[0], L + 1, err[1]);
+        return HARC_AMD_EINVAL;
+    }
+    if (err[2]) { harc_set_error("qpack: %u strands did not fit their scratch", err[2]); return HARC_AMD_EINTERNAL; }
+    *n_out = total;
+    if (st) { st->text += n * (L + 1ull); st->bytes += total; st->blocks += nb; st->stored += err[3]; }
+    if (d_out) {
+        if (out_capacity < total) { harc_set_error("qpack_device: the blocks take %llu bytes, the buffer holds %llu", (unsigned long long)total, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
+        hipLaunchKernelGGL(k_qp_gather, harc_fold256(nb), dim3(QP_T), 0, c->stream, (const uint8_t *)d_text, n, L, RB, nb, (const uint8_t *)scratch, stride, slab,
+                           (const uint32_t *)bsize, (const uint32_t *)bmode, (const uint64_t *)boff, d_out);
+        HIP_TRY(hipGetLastError());
+    }
+    if (st) {
+        HIP_TRY(hipEventRecord(e1, c->stream)); HIP_TRY(hipEventSynchronize(e1));
+        float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); st->seconds += 1e-3 * (double)ms;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));                     // the scratch goes back to the pool
+    return HARC_AMD_OK;
+}
+
+extern "C" uint64_t harc_amd_qpack_bound(uint64_t n_reads, int32_t readlen, uint32_t reads_per_block)
+{
+    if (readlen < 1 || readlen > 255 || n_reads == 0) return QV_FILE_HEADER;
+    return qv_bound(n_reads, (uint32_t)readlen, reads_per_block ? reads_per_block : qv_default_rb((uint32_t)readlen));
+}
+
+extern "C" int harc_amd_qpack_device(harc_amd_ctx *c, const char *d_text, uint64_t n_reads, int32_t readlen, uint32_t reads_per_block, int32_t flags, uint8_t *d_out,
+                                     uint64_t out_capacity, uint64_t *n_out)
+{
+    if (!c || (n_reads && !d_text) || !n_out) { harc_set_error("qpack_device: bad arguments"); return HARC_AMD_EINVAL; }
+    uint32_t rb = reads_per_block;
+    RC_TRY(qp_check_geometry("qpack_device", readlen, &rb));
+    HIP_TRY(hipSetDevice(c->P.device));
+    const uint64_t head = (flags & 1) ? QV_FILE_HEADER : 0;
+    const bool trace = getenv("HARC_AMD_TRACE") != nullptr;
+    QpStats st; uint64_t nblk = 0;
+    // the size first: a buffer that is too small is refused with both numbers before a byte of it is written
+    if (d_out && out_capacity < head) { harc_set_error("qpack_device: the blocks take at least %llu bytes, the buffer holds %llu", (unsigned long long)head, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
+    const int rc = harc_qpack_run(c, d_text, n_reads, (uint32_t)readlen, rb, d_out ? d_out + head : nullptr, d_out ? out_capacity - head : 0, &nblk, trace ? &st : nullptr);
+    *n_out = head + nblk;
+    if (rc != HARC_AMD_OK) {
+        if (d_out && nblk && out_capacity - head < nblk) harc_set_error("qpack_device: the packed form takes %llu bytes, the buffer holds %llu", (unsigned long long)(head + nblk), (unsigned long long)out_capacity);
+        return rc;
+    }
+    if (d_out && head) {
+        uint8_t h[QV_FILE_HEADER];
+        if (n_reads) qv_file_header(h, (uint32_t)readlen, rb, n_reads); else qv_file_header(h, 0, 0, 0);
+        HIP_TRY(hipMemcpyAsync(d_out, h, QV_FILE_HEADER, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (trace) fprintf(stderr, "[qpack] device call: %llu bytes of text -> %llu bytes in %llu blocks (%llu stored), kernels %.3f ms (%.1f GB/s of text)\n", (unsigned long long)st.text,
+                       (unsigned long long)*n_out, (unsigned long long)st.blocks, (unsigned long long)st.stored, 1e3 * st.seconds, st.seconds > 0 ? 1e-9 * (double)st.text / st.seconds : 0.0);
+    return HARC_AMD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ unpacking
+struct QvHeader { uint32_t L, rb; uint64_t n, nb; };
+// the 32 bytes at h of a packed form of n_bytes bytes
+static int qp_parse_header(const char *who, const uint8_t *h, uint64_t n_bytes, QvHeader *H)
+{
+    if (!qv_magic_ok(h)) { harc_set_error("%s: no packed quality file: its first 8 bytes are not the magic HARCQ1", who); return HARC_AMD_EINVAL; }
+    H->L = qv_le32(h + 8); H->rb = qv_le32(h + 12); H->n = qv_le64(h + 16);
+    if (H->n == 0) {
+        if (H->L || H->rb || n_bytes != QV_FILE_HEADER) { harc_set_error("%s: the header announces no lines, but a read length, a block size or %llu bytes behind it", who, (unsigned long long)(n_bytes - QV_FILE_HEADER)); return HARC_AMD_EINVAL; }
+        H->nb = 0;
+        return HARC_AMD_OK;
+    }
+    if (H->L < 1 || H->L > 255 || H->rb < 1 || (uint64_t)H->rb * H->L > QV_MAX_BLOCK_SYMBOLS) { harc_set_error("%s: the header names a read length of %u and %u reads per block", who, H->L, H->rb); return HARC_AMD_EINVAL; }
+    H->nb = qv_blocks(H->n, H->rb);
+    if (H->nb > (n_bytes - QV_FILE_HEADER) / 5) { harc_set_error("%s: the header announces %llu blocks, %llu bytes cannot hold them", who, (unsigned long long)H->nb, (unsigned long long)n_bytes); return HARC_AMD_EINVAL; }
+    if (H->n > ((uint64_t)1 << 62) / (H->L + 1ull)) { harc_set_error("%s: the header announces %llu lines", who, (unsigned long long)H->n); return HARC_AMD_EINVAL; }
+    return HARC_AMD_OK;
+}
+// nb blocks at d_blocks with their offsets d_off[0 .. nb] -> the n lines at d_text; block0 / base: number and file offset of the first of them, for the message
+static int harc_qunpack_run(harc_amd_ctx *c, const uint8_t *d_blocks, const uint64_t *d_off, const uint64_t *h_off, uint32_t nb, uint64_t n, uint32_t L, uint32_t RB, char *d_text,
+                            uint64_t block0, uint64_t base)
+{
+    if (!nb) return HARC_AMD_OK;
+    PoolScope scope(c);
+    unsigned long long *d_errw = nullptr; RC_TRY(dalloc(c, &d_errw, 2));
+    HIP_TRY(hipMemsetAsync(d_errw, 0xFF, 8, c->stream));
+    hipLaunchKernelGGL(k_qp_decode, harc_fold256(nb), dim3(QP_T), 0, c->stream, d_blocks, d_off, nb, n, L, RB, (uint8_t *)d_text, d_errw);
+    HIP_TRY(hipGetLastError());
+    unsigned long long errw = 0;
+    HIP_TRY(hipMemcpyAsync(&errw, d_errw, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (errw != ~0ull) {
+        const uint64_t b = errw >> 8;
+        harc_set_error("qunpack: block %llu at byte %llu is damaged: %s", (unsigned long long)(block0 + b), (unsigned long long)(base + (h_off ? h_off[b] : 0)), qv_error_text((uint32_t)(errw & 0xFF)));
+        return HARC_AMD_EINVAL;
+    }
+    return HARC_AMD_OK;
+}
+
+extern "C" int harc_amd_qunpack_device(harc_amd_ctx *c, const uint8_t *d_packed, uint64_t n_bytes, char *d_text, uint64_t out_capacity, uint64_t *n_out)
+{
+    if (!c || !d_packed || !n_out) { harc_set_error("qunpack_device: bad arguments"); return HARC_AMD_EINVAL; }
+    if (n_bytes < QV_FILE_HEADER) { harc_set_error("qunpack_device: %llu bytes are fewer than the %u of the header", (unsigned long long)n_bytes, QV_FILE_HEADER); return HARC_AMD_EINVAL; }
+    HIP_TRY(hipSetDevice(c->P.device));
+    uint8_t h[QV_FILE_HEADER];
+    HIP_TRY(hipMemcpyAsync(h, d_packed, QV_FILE_HEADER, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    QvHeader H;
+    RC_TRY(qp_parse_header("qunpack_device", h, n_bytes, &H));
+    const uint64_t total = H.n * (H.L + 1ull);
+    *n_out = total;
+    if (!d_text) return HARC_AMD_OK;
+    if (out_capacity < total) { harc_set_error("qunpack_device: the lines take %llu bytes, the buffer holds %llu", (unsigned long long)total, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
+    if (!H.nb) return HARC_AMD_OK;
+    if (H.nb > 0x7FFFFFF0ull) { harc_set_error("qunpack_device: too many blocks for one call"); return HARC_AMD_EINVAL; }
+    PoolScope scope(c);
+    uint64_t *d_off = nullptr; unsigned long long *d_bad = nullptr;
+    RC_TRY(dalloc(c, &d_off, (size_t)H.nb + 1)); RC_TRY(dalloc(c, &d_bad, 2));
+    HIP_TRY(hipMemsetAsync(d_bad, 0, 16, c->stream));
+    hipLaunchKernelGGL(k_qp_walk, dim3(1), dim3(64), 0, c->stream, d_packed, n_bytes, H.nb, d_off, d_bad);
+    HIP_TRY(hipGetLastError());
+    unsigned long long bad[2] = { 0, 0 };
+    std::vector<uint64_t> h_off((size_t)H.nb + 1);
+    HIP_TRY(hipMemcpyAsync(bad, d_bad, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (bad[0]) {
+        if (bad[0] == H.nb + 1) harc_set_error("qunpack_device: block %llu ends at byte %llu, but there are %llu bytes", (unsigned long long)H.nb - 1, bad[1], (unsigned long long)n_bytes);
+        else harc_set_error("qunpack_device: block %llu at byte %llu leaves the %llu bytes of the packed form", bad[0] - 1, bad[1], (unsigned long long)n_bytes);
+        return HARC_AMD_EINVAL;
+    }
+    HIP_TRY(hipMemcpyAsync(h_off.data(), d_off, 8 * ((size_t)H.nb + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return harc_qunpack_run(c, d_packed + QV_FILE_HEADER, d_off, h_off.data(), (uint32_t)H.nb, H.n, H.L, H.rb, d_text, 0, QV_FILE_HEADER);
+}
+
+// ------------------------------------------------------------------------------------------------ the same in a row on the host: what the kernels are held to
+static int qp_host_stride_check(const char *text, uint64_t n, uint32_t L)
+{
+    uint64_t e0 = 0, e1 = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const char *ln = text + i * (L + 1ull);
+        for (uint32_t j = 0; j < L; j++) e1 += ln[j] == '\n';
+        e0 += ln[L] != '\n';
+    }
+    if (e0 || e1) {
+        harc_set_error("qpack: the text is not lines of %u quality values: %llu positions on the %u-byte stride hold no newline and %llu newlines are off it", L, (unsigned long long)e0, L + 1, (unsigned long long)e1);
+        return HARC_AMD_EINVAL;
+    }
+    return HARC_AMD_OK;
+}
+
+extern "C" int harc_amd_qpack_host(const char *text, uint64_t n_reads, int32_t readlen, uint32_t reads_per_block, int32_t flags, uint8_t *out, uint64_t cap, uint64_t *n_out)
+{
+    if ((n_reads && !text) || !n_out) { harc_set_error("qpack_host: bad arguments"); return HARC_AMD_EINVAL; }
+    uint32_t rb = reads_per_block;
+    RC_TRY(qp_check_geometry("qpack_host", readlen, &rb));
+    const uint32_t L = (uint32_t)readlen;
+    RC_TRY(qp_host_stride_check(text, n_reads, L));
+    const uint64_t head = (flags & 1) ? QV_FILE_HEADER : 0;
+    std::vector<QvWork> W(1);
+    const uint32_t mmax = n_reads < rb ? (uint32_t)n_reads : rb;
+    std::vector<uint8_t> slabs((size_t)qv_block_slabs(mmax, L)), blk;
+    uint64_t at = head;
+    for (uint64_t a = 0; a < n_reads; a += rb) {
+        const uint32_t m = n_reads - a < rb ? (uint32_t)(n_reads - a) : rb;
+        blk.resize((size_t)5 + (size_t)m * L);
+        const uint32_t sz = qv_block_encode((const uint8_t *)text + a * (L + 1ull), m, L, W[0], slabs.data(), blk.data(), blk.size(), nullptr);
+        if (!sz) { harc_set_error("qpack_host: a strand did not fit its scratch"); return HARC_AMD_EINTERNAL; }
+        if (out && at + sz <= cap) memcpy(out + at, blk.data(), sz);
+        at += sz;
+    }
+    *n_out = at;
+    if (!out) return HARC_AMD_OK;
+    if (cap < at) { harc_set_error("qpack_host: the packed form takes %llu bytes, the buffer holds %llu", (unsigned long long)at, (unsigned long long)cap); return HARC_AMD_EINVAL; }
+    if (head) { if (n_reads) qv_file_header(out, L, rb, n_reads); else qv_file_header(out, 0, 0, 0); }
+    return HARC_AMD_OK;
+}
+
+extern "C" int harc_amd_qunpack_host(const uint8_t *packed, uint64_t n_bytes, char *text, uint64_t cap, uint64_t *n_out)
+{
+    if (!packed || !n_out) { harc_set_error("qunpack_host: bad arguments"); return HARC_AMD_EINVAL; }
+    if (n_bytes < QV_FILE_HEADER) { harc_set_error("qunpack_host: %llu bytes are fewer than the %u of the header", (unsigned long long)n_bytes, QV_FILE_HEADER); return HARC_AMD_EINVAL; }
+    QvHeader H;
+    RC_TRY(qp_parse_header("qunpack_host", packed, n_bytes, &H));
+    const uint64_t total = H.n * (H.L + 1ull);
+    *n_out = total;
+    if (!text) return HARC_AMD_OK;
+    if (cap < total) { harc_set_error("qunpack_host: the lines take %llu bytes, the buffer holds %llu", (unsigned long long)total, (unsigned long long)cap); return HARC_AMD_EINVAL; }
+    std::vector<QvWork> W(1);
+    uint64_t at = QV_FILE_HEADER;
+    for (uint64_t b = 0; b < H.nb; b++) {
+        if (n_bytes - at < 4) { harc_set_error("qunpack_host: block %llu at byte %llu leaves the %llu bytes of the packed form", (unsigned long long)b, (unsigned long long)at, (unsigned long long)n_bytes); return HARC_AMD_EINVAL; }
+        const uint64_t pb = qv_le32(packed + at);
+        if (pb == 0 || n_bytes - at - 4 < pb) { harc_set_error("qunpack_host: block %llu at byte %llu leaves the %llu bytes of the packed form", (unsigned long long)b, (unsigned long long)at, (unsigned long long)n_bytes); return HARC_AMD_EINVAL; }
+        const uint64_t line0 = b * (uint64_t)H.rb;
+        const uint32_t m = H.n - line0 < H.rb ? (uint32_t)(H.n - line0) : H.rb;
+        const int e = qv_block_decode(packed + at + 4, (uint32_t)pb, m, H.L, W[0], (uint8_t *)text + line0 * (H.L + 1ull));
+        if (e) { harc_set_error("qunpack: block %llu at byte %llu is damaged: %s", (unsigned long long)b, (unsigned long long)at, qv_error_text((uint32_t)e)); return HARC_AMD_EINVAL; }
+        at += 4 + pb;
+    }
+    if (at != n_bytes) { harc_set_error("qunpack_host: block %llu ends at byte %llu, but there are %llu bytes", (unsigned long long)H.nb - 1, (unsigned long long)at, (unsigned long long)n_bytes); return HARC_AMD_EINVAL; }
+    return HARC_AMD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the files
+namespace {
+struct QpBuf { harc_amd_ctx *c; char *p = nullptr; size_t cap = 0; ~QpBuf() { if (p) harc_raw_free(c, p); } };
+int qp_reserve(QpBuf *b, size_t need)
+{
+    if (b->p && b->cap >= need) return HARC_AMD_OK;
+    HIP_TRY(hipStreamSynchronize(b->c->stream));                  // whatever still reads the old buffer has finished
+    if (b->p) { harc_raw_free(b->c, b->p); b->p = nullptr; b->cap = 0; }
+    RC_TRY(harc_raw_alloc(b->c, (void **)&b->p, need + 16));
+    b->cap = need;
+    return HARC_AMD_OK;
+}
+bool qp_file_size(const char *path, uint64_t *n) { struct stat st; if (stat(path, &st) != 0 || !S_ISREG(st.st_mode)) return false; *n = (uint64_t)st.st_size; return true; }
+struct QpOutGuard { std::string path; bool ok = false; ~QpOutGuard() { if (!ok) (void)remove(path.c_str()); } };
+struct QpCtxGuard { harc_amd_ctx *c; ~QpCtxGuard() { harc_amd_destroy(c); } };
+uint64_t qp_env_u64(const char *name, uint64_t dflt) { if (const char *e = getenv(name)) { const unsigned long long v = strtoull(e, nullptr, 10); if (v >= 1) return v; } return dflt; }
+// the context's one pinned ring in two halves of eight slices: the feeder's and the drain's
+int qp_ring(harc_amd_ctx *c, RingGeom *feed, RingGeom *drain)
+{
+    RingGeom base; harc_ring_geom_env(&base);
+    for (RingGeom *g : { feed, drain }) { g->slice = base.slice; g->nslices = 8; g->nthr = base.nthr / 2 > 0 ? base.nthr / 2 : 1; }
+    feed->ring_off = 0; drain->ring_off = 8 * base.slice;
+    return harc_ring_reserve(c, 16 * base.slice, "quality");
+}
+int qp_context(const harc_amd_params *params, int L, harc_amd_ctx **c)
+{
+    harc_amd_params P = *params;
+    if (harc_amd_default_params(L, &P) != HARC_AMD_OK) return HARC_AMD_EINVAL;
+    P.device = params->device;
+    return harc_amd_create(&P, c);
+}
+}
+
+extern "C" int harc_amd_qpack_files(const harc_amd_params *params, const char *quality_path, const char *out_path)
+{
+    if (!params || !quality_path || !out_path) { harc_set_error("qpack_files: bad arguments"); return HARC_AMD_EINVAL; }
+    uint64_t qsz = 0;
+    if (!qp_file_size(quality_path, &qsz)) { harc_set_error("cannot open %s", quality_path); return HARC_AMD_EIO; }
+    QpOutGuard outguard{ out_path };
+    // the read length is the length of the first line; everything about the sizes follows from it, before a device is touched
+    uint32_t L = 1;
+    if (qsz) {
+        char head[257];
+        FILE *f = fopen(quality_path, "rb");
+        if (!f) { harc_set_error("cannot open %s", quality_path); return HARC_AMD_EIO; }
+        const size_t got = fread(head, 1, sizeof head, f);
+        fclose(f);
+        size_t nl = 0;
+        while (nl < got && head[nl] != '\n') nl++;
+        if (nl > 255 || (nl == got && got == sizeof head)) { harc_set_error("qpack_files: the first line of %s is longer than 255 characters", quality_path); return HARC_AMD_EINVAL; }
+        if (nl == 0) { harc_set_error("qpack_files: the first line of %s is empty", quality_path); return HARC_AMD_EINVAL; }
+        L = (uint32_t)nl;
+    }
+    const uint64_t LL = L + 1ull;
+    if (qsz % LL) { harc_set_error("qpack_files: %s holds %llu bytes, no multiple of the %llu bytes of a line of %u quality values and its newline", quality_path, (unsigned long long)qsz, (unsigned long long)LL, L); return HARC_AMD_EINVAL; }
+    const uint64_t n = qsz / LL;
+    uint32_t rb = (uint32_t)qp_env_u64("HARC_AMD_QPACK_BLOCK", 0);
+    RC_TRY(qp_check_geometry("qpack_files", (int32_t)L, &rb));
+    const uint64_t piece_blocks = qp_env_u64("HARC_AMD_QPACK_PIECE", 64), piece_lines = piece_blocks * rb, nb = qv_blocks(n, rb);
+    harc_amd_ctx *c = nullptr;
+    RC_TRY(qp_context(params, (int)L, &c));
+    QpCtxGuard guard{ c };
+    RingGeom gf, gd;
+    RC_TRY(qp_ring(c, &gf, &gd));
+    QpBuf txt{ c }, out{ c };
+    const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
+    double t_read = 0, t_write = 0;
+    QpStats st;
+    uint8_t h[QV_FILE_HEADER];
+    if (n) qv_file_header(h, L, rb, n); else qv_file_header(h, 0, 0, 0);
+    uint64_t at = QV_FILE_HEADER; int npieces = 0;
+    {
+        FileDrain drain(c);
+        RC_TRY(drain.start(out_path, (size_t)(n ? qv_bound(n, L, rb) : QV_FILE_HEADER), &gd, true));
+        RC_TRY(drain.put_host(h, QV_FILE_HEADER, 0));
+        std::vector<std::pair<uint64_t, uint64_t>> pieces;
+        for (uint64_t a = 0; a < n; a += piece_lines) pieces.emplace_back(a * LL, (n - a < piece_lines ? n : a + piece_lines) * LL);
+        FileFeeder feed(c, quality_path);
+        if (!pieces.empty()) RC_TRY(feed.start(pieces, gf));
+        for (size_t p = 0; p < pieces.size(); p++) {
+            const uint64_t bytes = pieces[p].second - pieces[p].first, m = bytes / LL;
+            RC_TRY(qp_reserve(&txt, (size_t)bytes));
+            RC_TRY(qp_reserve(&out, (size_t)(qv_bound(m, L, rb) - QV_FILE_HEADER)));
+            { const double t0 = mono_now(); RC_TRY(feed.upload_piece(p, txt.p, nullptr)); t_read += mono_now() - t0; }
+            uint64_t nblk = 0;
+            RC_TRY(harc_qpack_run(c, txt.p, m, L, rb, (uint8_t *)out.p, out.cap, &nblk, &st));
+            { const double t0 = mono_now(); RC_TRY(drain.put(out.p, (size_t)nblk, at)); t_write += mono_now() - t0; }
+            at += nblk; npieces++;
+        }
+        drain.set_final_size(at);
+        { const double t0 = mono_now(); RC_TRY(drain.finish()); t_write += mono_now() - t0; }
+    }
+    if (tlog) fprintf(stderr, "[qpack] %llu bytes of text -> %llu bytes in %llu blocks (%llu stored), %d pieces: %.3f s in the kernels, %.3f s waiting for the readers, %.3f s waiting for the writers\n",
+                      (unsigned long long)qsz, (unsigned long long)at, (unsigned long long)nb, (unsigned long long)st.stored, npieces, st.seconds, t_read, t_write);
+    outguard.ok = true;
+    return HARC_AMD_OK;
+}
+
+extern "C" int harc_amd_qunpack_files(const harc_amd_params *params, const char *packed_path, const char *out_path)
+{
+    if (!params || !packed_path || !out_path) { harc_set_error("qunpack_files: bad arguments"); return HARC_AMD_EINVAL; }
+    uint64_t fsz = 0;
+    if (!qp_file_size(packed_path, &fsz)) { harc_set_error("cannot open %s", packed_path); return HARC_AMD_EIO; }
+    QpOutGuard outguard{ out_path };
+    if (fsz < QV_FILE_HEADER) { harc_set_error("qunpack_files: %s holds %llu bytes, fewer than the %u of the header", packed_path, (unsigned long long)fsz, QV_FILE_HEADER); return HARC_AMD_EINVAL; }
+    const int fd = open(packed_path, O_RDONLY);
+    if (fd < 0) { harc_set_error("cannot open %s", packed_path); return HARC_AMD_EIO; }
+    struct FdGuard { int fd; ~FdGuard() { close(fd); } } fdguard{ fd };
+    uint8_t h[QV_FILE_HEADER];
+    if (pread(fd, h, QV_FILE_HEADER, 0) != (ssize_t)QV_FILE_HEADER) { harc_set_error("cannot read %s", packed_path); return HARC_AMD_EIO; }
+    QvHeader H;
+    RC_TRY(qp_parse_header("qunpack_files", h, fsz, &H));
+    // the block offsets, from the prefixes: known, and inside the file, before a device is touched
+    std::vector<uint64_t> off((size_t)H.nb + 1);
+    uint64_t at = QV_FILE_HEADER;
+    for (uint64_t b = 0; b < H.nb; b++) {
+        off[b] = at;
+        uint8_t q[4];
+        if (fsz - at < 4) { harc_set_error("qunpack_files: block %llu at byte %llu leaves the %llu bytes of %s", (unsigned long long)b, (unsigned long long)at, (unsigned long long)fsz, packed_path); return HARC_AMD_EINVAL; }
+        if (pread(fd, q, 4, (off_t)at) != 4) { harc_set_error("cannot read %s", packed_path); return HARC_AMD_EIO; }
+        const uint64_t pb = qv_le32(q);
+        if (pb == 0 || fsz - at - 4 < pb) { harc_set_error("qunpack_files: block %llu at byte %llu leaves the %llu bytes of %s", (unsigned long long)b, (unsigned long long)at, (unsigned long long)fsz, packed_path); return HARC_AMD_EINVAL; }
+        at += 4 + pb;
+    }
+    off[H.nb] = at;
+    if (at != fsz) { harc_set_error("qunpack_files: the blocks of %s end at byte %llu, the file holds %llu", packed_path, (unsigned long long)at, (unsigned long long)fsz); return HARC_AMD_EINVAL; }
+    const uint64_t LL = H.L + 1ull, out_size = H.n * LL;
+    harc_amd_ctx *c = nullptr;
+    RC_TRY(qp_context(params, H.n ? (int)H.L : 100, &c));
+    QpCtxGuard guard{ c };
+    RingGeom gf, gd;
+    RC_TRY(qp_ring(c, &gf, &gd));
+    QpBuf pk{ c }, txt{ c }, doff{ c };
+    const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
+    double t_read = 0, t_write = 0, t_kernel = 0;
+    const uint64_t piece_blocks = qp_env_u64("HARC_AMD_QPACK_PIECE", 64);
+    int npieces = 0;
+    {
+        FileDrain drain(c);
+        RC_TRY(drain.start(out_path, (size_t)out_size, &gd, true));
+        std::vector<std::pair<uint64_t, uint64_t>> pieces;
+        for (uint64_t b = 0; b < H.nb; b += piece_blocks) pieces.emplace_back(off[b], off[H.nb - b < piece_blocks ? H.nb : b + piece_blocks]);
+        FileFeeder feed(c, packed_path);
+        if (!pieces.empty()) RC_TRY(feed.start(pieces, gf));
+        std::vector<uint64_t> rel;
+        for (size_t p = 0; p < pieces.size(); p++) {
+            const uint64_t b0 = p * piece_blocks, b1 = H.nb - b0 < piece_blocks ? H.nb : b0 + piece_blocks, bytes = pieces[p].second - pieces[p].first;
+            const uint64_t line0 = b0 * H.rb, m = (b1 == H.nb ? H.n : b1 * H.rb) - line0;
+            RC_TRY(qp_reserve(&pk, (size_t)bytes)); RC_TRY(qp_reserve(&txt, (size_t)(m * LL))); RC_TRY(qp_reserve(&doff, 8 * (size_t)(b1 - b0 + 1)));
+            { const double t0 = mono_now(); RC_TRY(feed.upload_piece(p, pk.p, nullptr)); t_read += mono_now() - t0; }
+            rel.resize((size_t)(b1 - b0 + 1));
+            for (uint64_t b = b0; b <= b1; b++) rel[(size_t)(b - b0)] = off[b] - off[b0];
+            HIP_TRY(hipMemcpyAsync(doff.p, rel.data(), 8 * rel.size(), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            { const double t0 = mono_now(); RC_TRY(harc_qunpack_run(c, (const uint8_t *)pk.p, (const uint64_t *)doff.p, rel.data(), (uint32_t)(b1 - b0), m, H.L, H.rb, txt.p, b0, off[b0])); t_kernel += mono_now() - t0; }
+            { const double t0 = mono_now(); RC_TRY(drain.put(txt.p, (size_t)(m * LL), line0 * LL)); t_write += mono_now() - t0; }
+            npieces++;
+        }
+        drain.set_final_size(out_size);
+        { const double t0 = mono_now(); RC_TRY(drain.finish()); t_write += mono_now() - t0; }
+    }
+    if (tlog) fprintf(stderr, "[qpack] unpacked %llu bytes of text from %llu bytes in %llu blocks, %d pieces: %.3f s in the kernels, %.3f s waiting for the readers, %.3f s waiting for the writers\n",
+                      (unsigned long long)out_size, (unsigned long long)fsz, (unsigned long long)H.nb, npieces, t_kernel, t_read, t_write);
+    outguard.ok = true;
+    return HARC_AMD_OK;
+}

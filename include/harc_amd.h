@@ -336,6 +336,39 @@ int harc_amd_merge_shard_files(const char *basedir, int32_t world);
 int harc_amd_compress_fastq_replicated_files(const harc_amd_params *params, const char *fastq, const char *basedir, int32_t preserve_order,
                                              int32_t preserve_quality, int32_t world, int32_t rank, const char *comm_spec);
 
+/* ---- The packed quality file X.quality.hq (./harc -c -q -Q; the format is written down in README.md, "The packed quality file"): n lines of exactly readlen
+   quality values and a newline -> a 32-byte header and blocks of reads_per_block lines, each stored or coded with order-1 static rANS in 256 strands that a
+   workgroup codes independently.  readlen is 1..255 whatever the context's own read length is; reads_per_block 0 = the default max(256, 2^22 / readlen), and
+   reads_per_block * readlen may not exceed 2^30.  The packed bytes depend on nothing but the text and reads_per_block. */
+/* Host only: bytes that n_reads lines take at most, 32 + blocks * 5 + n_reads * readlen (every block stored). */
+uint64_t harc_amd_qpack_bound(uint64_t n_reads, int32_t readlen, uint32_t reads_per_block);
+/* d_text (device memory, n_reads * (readlen + 1) bytes, any alignment) -> the packed form at d_out (device memory, any alignment), *n_out bytes; no byte outside
+   [d_out, d_out + *n_out) is written.  flags bit 0: the 32-byte file header in front of the blocks (without it: the blocks alone, for a caller that packs a file
+   in pieces).  d_out == NULL: the size alone (the blocks are coded to learn it); else HARC_AMD_EINVAL naming both numbers when out_capacity is smaller.
+   harc_amd_qpack_bound is always enough.  A byte at a (readlen + 1)-stride position that is no newline, or a newline anywhere else: HARC_AMD_EINVAL with the
+   counts.  Any other byte outside 33..126 is kept: its block is stored.  HARC_AMD_TRACE=1: one "[qpack]" line on stderr. */
+int harc_amd_qpack_device(harc_amd_ctx *ctx, const char *d_text, uint64_t n_reads, int32_t readlen, uint32_t reads_per_block, int32_t flags, uint8_t *d_out,
+                          uint64_t out_capacity, uint64_t *n_out);
+/* The packed form with its header, n_bytes in device memory -> its lines at d_text, *n_out = n * (readlen + 1) bytes, both numbers from the header.
+   d_text == NULL: the size alone; a smaller out_capacity: HARC_AMD_EINVAL naming both numbers.  Everything read is validated before it is trusted: a wrong
+   magic, a block prefix that leaves the bytes, a mode other than 0 or 1, a symbol count that is not the bitmap's, a row that sums to neither 0 nor 4096, strand
+   lengths that do not sum to the payload, a strand that ends early, a context that never occurs, a strand that does not end in state 2^23 at its last byte:
+   HARC_AMD_EINVAL naming the block and its byte offset, never an access out of bounds.  What was written to d_text by then is unspecified. */
+int harc_amd_qunpack_device(harc_amd_ctx *ctx, const uint8_t *d_packed, uint64_t n_bytes, char *d_text, uint64_t out_capacity, uint64_t *n_out);
+/* The same two calls in a row on the host, through the functions of harc_amd/csrc/qv_block.h that the kernels compile: they touch no device, and they are what the
+   kernels are held to, byte for byte (tests). */
+int harc_amd_qpack_host(const char *text, uint64_t n_reads, int32_t readlen, uint32_t reads_per_block, int32_t flags, uint8_t *out, uint64_t cap, uint64_t *n_out);
+int harc_amd_qunpack_host(const uint8_t *packed, uint64_t n_bytes, char *text, uint64_t cap, uint64_t *n_out);
+/* quality_path (what -c -q writes: fixed-length lines) -> out_path, packed on the GPU.  The read length is that of the first line (more than 255:
+   HARC_AMD_EINVAL); the file size must be a multiple of readlen + 1 (checked before a device is touched); only `device` is taken from params.  The job runs in
+   pieces of whole blocks (64 blocks; HARC_AMD_QPACK_PIECE=blocks, HARC_AMD_QPACK_BLOCK=reads per block in tests) through the pinned ring, so the file may be
+   larger than device memory; the output is the same file whatever the piece, slice or thread settings.  On any failure out_path is removed.  HARC_AMD_TRACE=1:
+   one "[qpack]" line on stderr (text bytes, packed bytes, blocks, stored blocks, pieces, seconds in the kernels / waiting for readers / for writers). */
+int harc_amd_qpack_files(const harc_amd_params *params, const char *quality_path, const char *out_path);
+/* packed_path -> the quality file at out_path, n * (readlen + 1) bytes known from the header before anything is decoded.  A short file, a wrong magic, a block
+   prefix that leaves the file or any damaged block: HARC_AMD_EINVAL; a failed read: HARC_AMD_EIO.  On any failure out_path is removed. */
+int harc_amd_qunpack_files(const harc_amd_params *params, const char *packed_path, const char *out_path);
+
 #ifdef __cplusplus
 }
 #endif

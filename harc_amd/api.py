@@ -104,6 +104,14 @@ def lib():
     l.harc_amd_qunpack_host.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
     l.harc_amd_qpack_files.argtypes = [PP, C.c_char_p, C.c_char_p]
     l.harc_amd_qunpack_files.argtypes = [PP, C.c_char_p, C.c_char_p]
+    l.harc_amd_idpack_bound.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
+    l.harc_amd_idpack_bound.restype = C.c_uint64
+    l.harc_amd_idpack_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_idunpack_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_idpack_host.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_idunpack_host.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_idpack_files.argtypes = [PP, C.c_char_p, C.c_char_p]
+    l.harc_amd_idunpack_files.argtypes = [PP, C.c_char_p, C.c_char_p]
     l.harc_amd_decode_signature.argtypes = [ctx, C.POINTER(C.c_uint64)]
     l.harc_amd_input_signature.argtypes = [ctx, C.POINTER(C.c_uint64)]
     l.harc_amd_reads_signature_device.argtypes = [ctx, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
@@ -287,6 +295,41 @@ def qunpack_files(packed, out, device=0):
     _check(lib().harc_amd_qunpack_files(C.byref(p), os.fsencode(packed), os.fsencode(out)))
 
 
+def idpack_bound(text_bytes, n_lines, lines_per_block=0):
+    """bytes that n_lines id lines in text_bytes bytes take at most as a packed id file: 32 + blocks * 9 + text_bytes; host only"""
+    return int(lib().harc_amd_idpack_bound(text_bytes, n_lines, lines_per_block))
+
+
+def idpack_host(text, lines_per_block=0, header=True):
+    """the encoder of HarcAmd.idpack_device run in a row on the host: the bytes the kernels must write (tests; no device).  text: id lines, a newline behind each"""
+    cap = idpack_bound(len(text), text.count(b"\n"), lines_per_block)
+    out = C.create_string_buffer(cap + 1)
+    got = C.c_uint64(0)
+    _check(lib().harc_amd_idpack_host(text, len(text), lines_per_block, 0 if header else 1, out, cap, C.byref(got)))
+    return out.raw[:got.value]
+
+
+def idunpack_host(packed):
+    """a packed id file (with its header) -> its text, decoded on the host by the functions the kernels compile; HarcAmdError(-1) for damaged input"""
+    size = C.c_uint64(0)
+    _check(lib().harc_amd_idunpack_host(packed, len(packed), None, 0, C.byref(size)))
+    out = C.create_string_buffer(size.value + 1)
+    _check(lib().harc_amd_idunpack_host(packed, len(packed), out, size.value, C.byref(size)))
+    return out.raw[:size.value]
+
+
+def idpack_files(ids, out, device=0):
+    """the id file `ids` -> the packed id file `out`, coded on the GPU (include/harc_amd.h: harc_amd_idpack_files)"""
+    p = default_params(100, device=device)
+    _check(lib().harc_amd_idpack_files(C.byref(p), os.fsencode(ids), os.fsencode(out)))
+
+
+def idunpack_files(packed, out, device=0):
+    """the packed id file `packed` -> the id file `out`, decoded on the GPU"""
+    p = default_params(100, device=device)
+    _check(lib().harc_amd_idunpack_files(C.byref(p), os.fsencode(packed), os.fsencode(out)))
+
+
 def pack_order(basedir, readlen=100, **kw):
     """== `pack_order.out <basedir>` (src/pack_order.cpp:11-77)"""
     p = default_params(readlen, **kw)
@@ -364,6 +407,20 @@ class HarcAmd:
         """a packed quality file in device memory -> its lines at out_ptr (device memory); without out_ptr only their size. -> bytes of text"""
         n = C.c_uint64(0)
         _check(lib().harc_amd_qunpack_device(self._ctx, C.c_void_p(d_packed), nbytes, C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
+        return n.value
+
+    def idpack_device(self, d_text, text_bytes, lines_per_block=0, out_ptr=None, out_capacity=0, header=True):
+        """an id text in device memory -> the packed form at out_ptr (device memory), with the 32-byte file header when header; without out_ptr only the
+        size. -> bytes.  idpack_bound(text_bytes, lines, lines_per_block) is always enough capacity"""
+        n = C.c_uint64(0)
+        _check(lib().harc_amd_idpack_device(self._ctx, C.c_void_p(d_text) if d_text else None, text_bytes, lines_per_block, 0 if header else 1,
+                                            C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
+        return n.value
+
+    def idunpack_device(self, d_packed, nbytes, out_ptr=None, out_capacity=0):
+        """a packed id file in device memory -> its text at out_ptr (device memory); without out_ptr only its size. -> bytes of text"""
+        n = C.c_uint64(0)
+        _check(lib().harc_amd_idunpack_device(self._ctx, C.c_void_p(d_packed), nbytes, C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
         return n.value
 
     def set_fastq_bgzf_device(self, dptr, nbytes):

@@ -230,3 +230,19 @@ template <int NT> __device__ __forceinline__ uint32_t block_excl_scan_u32(uint32
     *total = tot;
     return base + ex;
 }
+// len bytes src -> dst by the nt >= 3 lanes of a group (lane tid; qpack.hip, idpack.hip): dwords of the destination, bytes at its ends.  Up to 3 bytes behind src + len are read (never used)
+__device__ __forceinline__ void group_copy_bytes(uint8_t *dst, const uint8_t *src, uint32_t len, uint32_t tid, uint32_t nt)
+{
+    uint32_t head = (uint32_t)((0 - (uintptr_t)dst) & 3);
+    if (head > len) head = len;
+    if (tid < head) dst[tid] = src[tid];
+    const uint32_t nd = (len - head) >> 2;
+    for (uint32_t i = tid; i < nd; i += nt) {
+        const uintptr_t u = (uintptr_t)(src + head + 4 * i);
+        const uint32_t sh = (uint32_t)(u & 3);
+        const uint32_t *sw = (const uint32_t *)(u - sh);
+        *(uint32_t *)(dst + head + 4 * i) = sh ? __builtin_amdgcn_alignbyte(sw[1], sw[0], sh) : sw[0];
+    }
+    const uint32_t done = head + 4 * nd;
+    if (tid < len - done) dst[done + tid] = src[done + tid];
+}

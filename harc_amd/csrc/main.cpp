@@ -15,6 +15,8 @@
 //                                                                          bgzf: <out> is that text as BGZF, deflated on the GPU (./harc -d -q -z)
 //   harc_amd_stage quality_pack <quality> <device> <out>                   the fixed-length lines of <quality> -> the packed quality file <out> (./harc -c -q -Q)
 //   harc_amd_stage quality_unpack <packed> <device> <out>                  ... and back (./harc -d -q when only X.quality.hq is there)
+//   harc_amd_stage id_pack <id> <device> <out>                             the lines of <id> -> the packed id file <out> (./harc -c -q -I)
+//   harc_amd_stage id_unpack <packed> <device> <out>                       ... and back (./harc -d -q when only X.id.hi is there)
 // readlen / num_thr arrive as arguments instead of the compile-time macros of src/config.h (harc:52-63).
 #include <stdio.h>
 #include <stdlib.h>
@@ -48,6 +50,15 @@ int main(int argc, char **argv)
         PQ.device = atoi(argv[3]);
         const int rcq = !strcmp(argv[1], "quality_pack") ? harc_amd_qpack_files(&PQ, argv[2], argv[4]) : harc_amd_qunpack_files(&PQ, argv[2], argv[4]);
         if (rcq != 0) { fprintf(stderr, "harc_amd_stage %s failed (%d): %s\n", argv[1], rcq, harc_amd_last_error()); return 1; }
+        return 0;
+    }
+    if (!strcmp(argv[1], "id_pack") || !strcmp(argv[1], "id_unpack")) {
+        if (argc < 5) { fprintf(stderr, "%s needs <in> <device> <out>\n", argv[1]); return 2; }
+        harc_amd_params PI;
+        if (harc_amd_default_params(100, &PI) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
+        PI.device = atoi(argv[3]);
+        const int rci = !strcmp(argv[1], "id_pack") ? harc_amd_idpack_files(&PI, argv[2], argv[4]) : harc_amd_idunpack_files(&PI, argv[2], argv[4]);
+        if (rci != 0) { fprintf(stderr, "harc_amd_stage %s failed (%d): %s\n", argv[1], rci, harc_amd_last_error()); return 1; }
         return 0;
     }
     harc_amd_params P;

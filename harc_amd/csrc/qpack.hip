@@ -31,23 +31,6 @@ struct QpShared {
 struct QpGather { uint32_t scan[QP_T / 64 + 1], soff[QV_STRANDS], slen[QV_STRANDS]; };
 struct QpStats { uint64_t text = 0, bytes = 0, blocks = 0, stored = 0; double seconds = 0; };
 
-// len bytes src -> dst by the nt lanes of a group (lane tid): dwords of the destination, bytes at its ends.  Up to 3 bytes behind src + len are read (never used)
-__device__ __forceinline__ void qp_copy(uint8_t *dst, const uint8_t *src, uint32_t len, uint32_t tid, uint32_t nt)
-{
-    uint32_t head = (uint32_t)((0 - (uintptr_t)dst) & 3);
-    if (head > len) head = len;
-    if (tid < head) dst[tid] = src[tid];
-    const uint32_t nd = (len - head) >> 2;
-    for (uint32_t i = tid; i < nd; i += nt) {
-        const uintptr_t u = (uintptr_t)(src + head + 4 * i);
-        const uint32_t sh = (uint32_t)(u & 3);
-        const uint32_t *sw = (const uint32_t *)(u - sh);
-        *(uint32_t *)(dst + head + 4 * i) = sh ? __builtin_amdgcn_alignbyte(sw[1], sw[0], sh) : sw[0];
-    }
-    const uint32_t done = head + 4 * nd;
-    if (tid < len - done) dst[done + tid] = src[done + tid];
-}
-
 // err[0]: stride positions that hold no newline; err[1]: newlines inside a line; err[2]: strands that did not fit their slab (never); err[3]: stored blocks
 __global__ __launch_bounds__(QP_T) void k_qp_encode(const uint8_t *text, uint64_t n_lines, uint32_t L, uint32_t RB, uint32_t nb, uint8_t *scratch, uint64_t stride,
                                                     uint32_t slab, uint32_t *bsize, uint32_t *bmode, unsigned int *err)
@@ -140,12 +123,12 @@ __global__ __launch_bounds__(QP_T) void k_qp_gather(const uint8_t *text, uint64_
     uint32_t total;
     const uint32_t off = block_excl_scan_u32<QP_T>(len, S.scan, &total);
     S.soff[t] = off; S.slen[t] = len;
-    qp_copy(dst + 4, hdr, h, t, QP_T);
+    group_copy_bytes(dst + 4, hdr, h, t, QP_T);
     __syncthreads();
     const uint32_t wv = t >> 6, lane = t & 63u;
     for (uint32_t s = wv; s < QV_STRANDS; s += QP_T / 64) {
         const uint32_t n = S.slen[s];
-        if (n) qp_copy(dst + 4 + h + S.soff[s], hdr + QP_HDR + (uint64_t)(s + 1u) * slab - n, n, lane, 64);
+        if (n) group_copy_bytes(dst + 4 + h + S.soff[s], hdr + QP_HDR + (uint64_t)(s + 1u) * slab - n, n, lane, 64);
     }
 }
 

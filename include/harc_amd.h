@@ -369,6 +369,39 @@ int harc_amd_qpack_files(const harc_amd_params *params, const char *quality_path
    prefix that leaves the file or any damaged block: HARC_AMD_EINVAL; a failed read: HARC_AMD_EIO.  On any failure out_path is removed. */
 int harc_amd_qunpack_files(const harc_amd_params *params, const char *packed_path, const char *out_path);
 
+/* ---- The packed id file X.id.hi (./harc -c -q -I; the format is written down in README.md, "The packed id file"): an id text -- lines of any length, empty
+   ones too, every one ended by a newline (a last line without one: HARC_AMD_EINVAL) -> a 32-byte header and blocks of lines_per_block lines, each stored or
+   coded: a line against the line in front of it, token by token, as events of a static rANS stream, in 256 strands of consecutive lines that a workgroup codes
+   independently.  lines_per_block 0 = the default 2^18; the text of a block may not exceed 2^30 bytes (HARC_AMD_EINVAL naming the block).  The packed bytes
+   depend on nothing but the text and lines_per_block. */
+#define HARC_AMD_IDPACK_NO_HEADER 1
+/* Host only: bytes that n_lines lines in text_bytes bytes take at most, 32 + blocks * 9 + text_bytes (every block stored). */
+uint64_t harc_amd_idpack_bound(uint64_t text_bytes, uint64_t n_lines, uint32_t lines_per_block);
+/* d_text (device memory, text_bytes bytes, any alignment) -> the packed form at d_out (device memory, any alignment), *n_out bytes; no byte outside
+   [d_out, d_out + *n_out) is written and none outside the text is read.  flags: HARC_AMD_IDPACK_NO_HEADER writes the blocks alone, without the 32-byte file
+   header (for a caller that packs a file in pieces).  d_out == NULL: the size alone (the blocks are coded to learn it); else HARC_AMD_EINVAL naming both numbers
+   when out_capacity is smaller.  harc_amd_idpack_bound is always enough.  A byte outside 32..126 that is no newline is kept: its block is stored.
+   HARC_AMD_TRACE=1: one "[idpack]" line on stderr. */
+int harc_amd_idpack_device(harc_amd_ctx *ctx, const char *d_text, uint64_t text_bytes, uint32_t lines_per_block, int32_t flags, uint8_t *d_out, uint64_t out_capacity,
+                           uint64_t *n_out);
+/* The packed form with its header, n_bytes in device memory -> its text at d_text, *n_out bytes, the number from the header.  d_text == NULL: the size alone; a
+   smaller out_capacity: HARC_AMD_EINVAL naming both numbers.  Everything read is validated before it is trusted (README lists the checks): HARC_AMD_EINVAL
+   naming the block and its byte offset, never an access outside the packed form or the text.  What was written to d_text by then is unspecified. */
+int harc_amd_idunpack_device(harc_amd_ctx *ctx, const uint8_t *d_packed, uint64_t n_bytes, char *d_text, uint64_t out_capacity, uint64_t *n_out);
+/* The same two calls in a row on the host, through the functions of harc_amd/csrc/id_block.h that the kernels compile: they touch no device, and they are what the
+   kernels are held to, byte for byte (tests). */
+int harc_amd_idpack_host(const char *text, uint64_t text_bytes, uint32_t lines_per_block, int32_t flags, uint8_t *out, uint64_t cap, uint64_t *n_out);
+int harc_amd_idunpack_host(const uint8_t *packed, uint64_t n_bytes, char *text, uint64_t cap, uint64_t *n_out);
+/* id_path (what -c -q writes) -> out_path, packed on the GPU; only `device` is taken from params.  The text goes through the pinned ring in byte ranges; the whole
+   blocks that have arrived are packed, at most HARC_AMD_IDPACK_PIECE blocks (8) and 256 MiB of text a kernel call (one block where a block alone is longer), and the rest is carried into the next range, so the file may be
+   larger than device memory; the output is the same file whatever the piece, slice or thread settings.  HARC_AMD_IDPACK_BLOCK=lines per block (tests: it is
+   recorded in the file and changes its bytes).  On any failure out_path is removed.  HARC_AMD_TRACE=1: one "[idpack]" line on stderr (text bytes, packed bytes,
+   blocks, stored blocks, pieces, seconds in the kernels / waiting for readers / for writers). */
+int harc_amd_idpack_files(const harc_amd_params *params, const char *id_path, const char *out_path);
+/* packed_path -> the id file at out_path, its size known from the header before anything is decoded.  A short file, a wrong magic, a block prefix that leaves the
+   file or any damaged block: HARC_AMD_EINVAL; a failed read: HARC_AMD_EIO.  On any failure out_path is removed. */
+int harc_amd_idunpack_files(const harc_amd_params *params, const char *packed_path, const char *out_path);
+
 #ifdef __cplusplus
 }
 #endif

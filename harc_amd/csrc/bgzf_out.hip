@@ -16,6 +16,7 @@
 //   7 the chunk CRCs folded as a tree of products with x^(512 * 2^level); header, stream or stored text and trailer leave in 16-byte stores
 #include "devutil.h"
 #include "deflate_member.h"
+#include "fileio.h"                                               // KernelTimer
 
 #define BZ_T 1024
 #define BZ_ROW 17                        // dwords per 64-byte row of the text in LDS
@@ -286,9 +287,8 @@ int harc_bgzf_deflate(harc_amd_ctx *c, const char *d_text, uint64_t n_bytes, int
     RC_TRY(dalloc(c, &slots, (size_t)nm * BZ_SLOT)); RC_TRY(dalloc(c, &msize, (size_t)nm + 1)); RC_TRY(dalloc(c, &moff, (size_t)nm + 1)); RC_TRY(dalloc(c, &d_stat, 4));
     HIP_TRY(hipMemsetAsync(msize + nm, 0, 4, c->stream));
     HIP_TRY(hipMemsetAsync(d_stat, 0, 16, c->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    struct EvGuard { hipEvent_t &a, &b; ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evguard{ e0, e1 };
-    if (st) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, c->stream)); }
+    KernelTimer timer(st ? &st->seconds : nullptr);
+    RC_TRY(timer.begin(c->stream));
     if (nm) {
         hipLaunchKernelGGL(k_bgzf_deflate, harc_fold256(nm), dim3(BZ_T), 0, c->stream, d_text, n_bytes, nm, slots, msize, d_stat);
         HIP_TRY(hipGetLastError());
@@ -312,10 +312,7 @@ int harc_bgzf_deflate(harc_amd_ctx *c, const char *d_text, uint64_t n_bytes, int
                            nm, eof ? 1 : 0, d_out);
         HIP_TRY(hipGetLastError());
     }
-    if (st) {
-        HIP_TRY(hipEventRecord(e1, c->stream)); HIP_TRY(hipEventSynchronize(e1));
-        float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); st->seconds += 1e-3 * (double)ms;
-    }
+    RC_TRY(timer.end(c->stream));
     return HARC_AMD_OK;
 }
 

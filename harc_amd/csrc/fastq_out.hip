@@ -12,6 +12,7 @@
 // longer than a tile (an id of 40 000 bytes) is simply clipped to the tile by every workgroup it reaches into.  The first and the last 16 bytes of the whole
 // output, where the caller's buffer is not aligned or does not end on a 16-byte boundary, are stored byte by byte by the lanes that hold them.
 // The same lanes check the fixed-width inputs on the way -- a newline at every (readlen + 1)-stride position and nowhere else -- into an error counter.
+// The plumbing of the file call (probes, guards, ring split, device buffers, kernel timer, the carried tail of the id text) is fileio.h's.
 #include "devutil.h"
 #include "fileio.h"
 #include "deflate_member.h"
@@ -205,40 +206,19 @@ extern "C" int harc_amd_fastq_assemble_device(harc_amd_ctx *c, const char *d_ids
         RC_TRY(fq_run(c, d_ids, nls, d_dna, d_quality, n_records, readlen, d_out, total, d_err));
         return fq_check_errors(c, d_err, readlen);
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;                        // the tile kernel alone, for tools/fastq_out_rate.py
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evguard{ e0, e1 };
-    HIP_TRY(hipEventRecord(e0, c->stream));
+    double seconds = 0;                                           // the tile kernel alone, for tools/fastq_out_rate.py
+    KernelTimer timer(&seconds);
+    RC_TRY(timer.begin(c->stream));
     RC_TRY(fq_run(c, d_ids, nls, d_dna, d_quality, n_records, readlen, d_out, total, d_err));
-    HIP_TRY(hipEventRecord(e1, c->stream));
+    RC_TRY(timer.end_mark(c->stream));
     const int rc = fq_check_errors(c, d_err, readlen);
-    float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
+    RC_TRY(timer.end_wait());
+    const double ms = 1e3 * seconds;
     fprintf(stderr, "[fastq_out] device call: %llu bytes, tile kernel %.3f ms (%.1f GB/s of output)\n", (unsigned long long)total, ms, ms > 0 ? 1e-6 * (double)total / ms : 0.0);
     return rc;
 }
 
 // ------------------------------------------------------------------------------------------------ the files
-namespace {
-struct DevBuf { char *p = nullptr; size_t cap = 0; };
-struct DevBufs {
-    harc_amd_ctx *c; DevBuf id[2], dna, qual, out, gz;
-    ~DevBufs() { for (DevBuf *b : { &id[0], &id[1], &dna, &qual, &out, &gz }) if (b->p) harc_raw_free(c, b->p); }
-};
-// at least `need` bytes, the first `keep` of them kept
-int buf_reserve(harc_amd_ctx *c, DevBuf *b, size_t need, size_t keep)
-{
-    if (b->p && b->cap >= need) return HARC_AMD_OK;
-    char *np = nullptr; const size_t cap = need + (keep ? need / 4 : 0);
-    RC_TRY(harc_raw_alloc(c, (void **)&np, cap + 16));
-    if (keep) HIP_TRY(hipMemcpyAsync(np, b->p, keep, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));                     // whatever still reads the old buffer has finished
-    if (b->p) harc_raw_free(c, b->p);
-    b->p = np; b->cap = cap;
-    return HARC_AMD_OK;
-}
-bool file_size(const char *path, uint64_t *n) { struct stat st; if (stat(path, &st) != 0 || !S_ISREG(st.st_mode)) return false; *n = (uint64_t)st.st_size; return true; }
-}
-
 extern "C" int harc_amd_fastq_assemble_files(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out_path)
 {
     return harc_amd_fastq_assemble_files_ex(params, dna_path, id_path, quality_path, out_path, 0);
@@ -255,81 +235,51 @@ extern "C" int harc_amd_fastq_assemble_files_ex(const harc_amd_params *params, c
     if (!file_size(id_path, &isz)) { harc_set_error("cannot open %s", id_path); return HARC_AMD_EIO; }
     if (!file_size(quality_path, &qsz)) { harc_set_error("cannot open %s", quality_path); return HARC_AMD_EIO; }
     // the read length is the length of the first read; everything else about the sizes follows from it, before a device is touched
-    int L = 1; bool id_open_tail = false;
-    {
-        char head[257]; size_t got = 0;
-        FILE *f = fopen(dna_path, "rb");
-        if (!f) { harc_set_error("cannot open %s", dna_path); return HARC_AMD_EIO; }
-        got = fread(head, 1, sizeof head, f);
-        fclose(f);
-        size_t nl = 0;
-        while (nl < got && head[nl] != '\n') nl++;
-        if (dsz) {
-            if (nl == got && got == sizeof head) { harc_set_error("fastq_assemble_files: the first line of %s is longer than 255 characters", dna_path); return HARC_AMD_EINVAL; }
-            if (nl == 0) { harc_set_error("fastq_assemble_files: the first line of %s is empty", dna_path); return HARC_AMD_EINVAL; }
-            if (nl > 255) { harc_set_error("fastq_assemble_files: the first line of %s is longer than 255 characters", dna_path); return HARC_AMD_EINVAL; }
-            L = (int)nl;
-        }
-        if (isz) {
-            FILE *g = fopen(id_path, "rb"); char last = '\n';
-            if (!g || fseeko(g, (off_t)isz - 1, SEEK_SET) != 0 || fread(&last, 1, 1, g) != 1) { if (g) fclose(g); harc_set_error("cannot read %s", id_path); return HARC_AMD_EIO; }
-            fclose(g);
-            id_open_tail = last != '\n';
-        }
-    }
+    uint32_t L1 = 1; bool id_closed = true;
+    if (dsz) RC_TRY(first_line_length(dna_path, "fastq_assemble_files", &L1));
+    if (isz) RC_TRY(last_byte_is_newline(id_path, &id_closed));
+    const int L = (int)L1; const bool id_open_tail = !id_closed;
     const uint64_t LL = (uint64_t)L + 1, K = 2ull * (uint64_t)L + 4;
     if (dsz % LL) { harc_set_error("fastq_assemble_files: %s holds %llu bytes, no multiple of the %llu bytes of a read of %d characters and its newline", dna_path, (unsigned long long)dsz, (unsigned long long)LL, L); return HARC_AMD_EINVAL; }
     if (qsz != dsz) { harc_set_error("fastq_assemble_files: %s holds %llu bytes and %s %llu: not a quality line per read", quality_path, (unsigned long long)qsz, dna_path, (unsigned long long)dsz); return HARC_AMD_EINVAL; }
     const uint64_t n = dsz / LL;
     if (n > 4294967290ull) { harc_set_error("Too many reads. HARC supports at most 4294967290 reads"); return HARC_AMD_EINVAL; }
     const uint64_t out_size = isz + (id_open_tail ? 1 : 0) + n * K;    // known before a byte is read: the output is sized and mapped up front
-    harc_amd_params P = *params;
-    if (harc_amd_default_params(L, &P) != HARC_AMD_OK) return HARC_AMD_EINVAL;
-    P.device = params->device;
-    harc_amd_ctx *c = nullptr;
-    RC_TRY(harc_amd_create(&P, &c));
-    struct Guard { harc_amd_ctx *c; ~Guard() { harc_amd_destroy(c); } } guard{ c };
+    CtxGuard guard;
+    RC_TRY(side_context(params, L, &guard.c));
+    harc_amd_ctx *c = guard.c;
     // Three feeders (ids, reads, quality values) and the drain are alive at the same time and the context has ONE pinned ring: it is split into four quarters of four
     // slices each -- quarter 0: the id feeder, 1: the read feeder, 2: the quality feeder, 3: the drain -- and reserved whole before any of them starts.  With the default
     // slice of 64 MB that is the 1 GiB the ring always had.  HARC_AMD_FEED_SLICE sets the slice, HARC_AMD_FEED_THREADS the host threads of all four together.
     RingGeom gq[4];
-    {
-        RingGeom base; harc_ring_geom_env(&base);
-        for (int k = 0; k < 4; k++) { gq[k].slice = base.slice; gq[k].nslices = 4; gq[k].nthr = base.nthr / 4 > 0 ? base.nthr / 4 : 1; gq[k].ring_off = (size_t)k * 4 * base.slice; }
-        RC_TRY(harc_ring_reserve(c, 16 * base.slice, "FASTQ output"));
-    }
-    struct OutGuard { std::string path; bool ok = false; ~OutGuard() { if (!ok) (void)remove(path.c_str()); } } outguard{ out_path };   // declared in front of the drain: it goes after the drain has closed the file
-    DevBufs B{ c };
+    RC_TRY(ring_split(c, 4, 4, "FASTQ output", gq));
+    OutFileGuard outguard{ out_path };
+    CarriedText ids(c); DevBuf dna{ c }, qual{ c }, out{ c }, gz{ c };
     const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
     double t_kernel = 0, t_read = 0, t_write = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    HIP_TRY(hipEventCreate(&ev0)); HIP_TRY(hipEventCreate(&ev1));
-    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evguard{ ev0, ev1 };
+    KernelTimer timer(&t_kernel);
     PoolScope scope(c);
     unsigned int *d_err = nullptr; RC_TRY(dalloc(c, &d_err, 4));
     HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
     FileDrain drain(c);
     RC_TRY(drain.start(out_path, bgzf ? (size_t)dm_bound(out_size) : (size_t)out_size, &gq[3], bgzf != 0));
-    BgzfOutStats gst; uint64_t gz_at = 0, tcarry = 0;                  // bgzf: bytes of the file so far; text in front of B.out that no member holds yet
+    BgzfOutStats gst; uint64_t gz_at = 0, tcarry = 0;                  // bgzf: bytes of the file so far; text in front of `out` that no member holds yet
     // the job is driven by the id file: a piece is a byte range of it; what follows the piece's last newline is carried into the next piece
-    uint64_t piece = (uint64_t)256 << 20;
-    if (const char *e = getenv("HARC_AMD_FQOUT_PIECE")) { const unsigned long long v = strtoull(e, nullptr, 10); if (v >= 1) piece = v; }
+    const uint64_t piece = env_u64("HARC_AMD_FQOUT_PIECE", (uint64_t)256 << 20);
     std::vector<std::pair<uint64_t, uint64_t>> pieces;
     for (uint64_t a = 0; a < isz; a += piece) pieces.emplace_back(a, isz - a < piece ? isz : a + piece);
     FileFeeder idf(c, id_path);
     if (!pieces.empty()) RC_TRY(idf.start(pieces, gq[0]));
-    uint64_t carry = 0, r0 = 0, lines_seen = 0, out_at = 0; int cur = 0, npieces = 0; bool over = false;
+    uint64_t r0 = 0, lines_seen = 0, out_at = 0; int npieces = 0; bool over = false;
     for (size_t p = 0; p < pieces.size(); p++) {
-        const uint64_t len = pieces[p].second - pieces[p].first; const bool lastp = p + 1 == pieces.size();
-        RC_TRY(buf_reserve(c, &B.id[cur], (size_t)(carry + len), (size_t)carry));          // the carried bytes sit at its front
-        { const double t0 = mono_now(); RC_TRY(idf.upload_piece(p, B.id[cur].p + carry, nullptr)); t_read += mono_now() - t0; }
-        const uint64_t total = carry + len;
-        const char *d_ids = B.id[cur].p;
+        const uint64_t len = pieces[p].second - pieces[p].first, total = ids.carry + len; const bool lastp = p + 1 == pieces.size();
+        RC_TRY(ids.take(idf, p, len, &t_read));                                              // the carried bytes sit at its front
+        const char *d_ids = ids.text();
         PoolScope piece_scope(c);
         const uint64_t *nls = nullptr; uint64_t lines = 0; bool open_tail = false;
         RC_TRY(fq_index(c, d_ids, total, &nls, &lines, &open_tail));
         const uint64_t m = lines - ((open_tail && !lastp) ? 1 : 0);                        // whole lines; a last line of the FILE without its newline is one
-        if (m == 0 && !lastp) { carry = total; continue; }                                   // not one whole line yet: the piece grows by the next one
+        if (m == 0 && !lastp) { ids.carry = total; continue; }                               // not one whole line yet: the piece grows by the next one
         uint64_t cut = total;
         if (open_tail && !lastp) {
             HIP_TRY(hipMemcpyAsync(&cut, nls + (m - 1), 8, hipMemcpyDeviceToHost, c->stream));
@@ -340,42 +290,37 @@ extern "C" int harc_amd_fastq_assemble_files_ex(const harc_amd_params *params, c
         if (r0 + m > n) over = true;                                                         // more ids than reads: the lines are still counted, for the message
         if (!over && m) {
             const uint64_t nb = m * LL, out_bytes = cut + ((lastp && open_tail) ? 1 : 0) + m * K;
-            RC_TRY(buf_reserve(c, &B.dna, (size_t)nb, 0)); RC_TRY(buf_reserve(c, &B.qual, (size_t)nb, 0)); RC_TRY(buf_reserve(c, &B.out, (size_t)(tcarry + out_bytes), (size_t)tcarry));
+            RC_TRY(dev_reserve(&dna, (size_t)nb)); RC_TRY(dev_reserve(&qual, (size_t)nb)); RC_TRY(dev_reserve(&out, (size_t)(tcarry + out_bytes), (size_t)tcarry));
             {   // lines [r0, r0 + m) of the two fixed-width files, by offset
                 FileFeeder fd(c, dna_path), fq(c, quality_path);
                 RC_TRY(fd.start({ { r0 * LL, (r0 + m) * LL } }, gq[1])); RC_TRY(fq.start({ { r0 * LL, (r0 + m) * LL } }, gq[2]));
                 const double t0 = mono_now();
-                RC_TRY(fd.upload_piece(0, B.dna.p, nullptr)); RC_TRY(fq.upload_piece(0, B.qual.p, nullptr));
+                RC_TRY(fd.upload_piece(0, dna.p, nullptr)); RC_TRY(fq.upload_piece(0, qual.p, nullptr));
                 t_read += mono_now() - t0;
-                HIP_TRY(hipEventRecord(ev0, c->stream));
-                RC_TRY(fq_run(c, d_ids, nls, B.dna.p, B.qual.p, (uint32_t)m, L, B.out.p + tcarry, out_bytes, d_err));
-                HIP_TRY(hipEventRecord(ev1, c->stream));
-                if (!bgzf) { const double t0w = mono_now(); RC_TRY(drain.put(B.out.p, (size_t)out_bytes, out_at)); t_write += mono_now() - t0w; }
+                RC_TRY(timer.begin(c->stream));
+                RC_TRY(fq_run(c, d_ids, nls, dna.p, qual.p, (uint32_t)m, L, out.p + tcarry, out_bytes, d_err));
+                RC_TRY(timer.end_mark(c->stream));
+                if (!bgzf) { const double t0w = mono_now(); RC_TRY(drain.put(out.p, (size_t)out_bytes, out_at)); t_write += mono_now() - t0w; }
                 else {
                     const uint64_t have = tcarry + out_bytes, full = have / DM_TEXT * DM_TEXT;
                     if (full) {
                         uint64_t ngz = 0;
-                        RC_TRY(buf_reserve(c, &B.gz, (size_t)dm_bound(full), 0));
-                        RC_TRY(harc_bgzf_deflate(c, B.out.p, full, 0, (uint8_t *)B.gz.p, B.gz.cap, &ngz, &gst));
-                        { const double t0w = mono_now(); RC_TRY(drain.put(B.gz.p, (size_t)ngz, gz_at)); t_write += mono_now() - t0w; }
+                        RC_TRY(dev_reserve(&gz, (size_t)dm_bound(full)));
+                        RC_TRY(harc_bgzf_deflate(c, out.p, full, 0, (uint8_t *)gz.p, gz.cap, &ngz, &gst));
+                        { const double t0w = mono_now(); RC_TRY(drain.put(gz.p, (size_t)ngz, gz_at)); t_write += mono_now() - t0w; }
                         gz_at += ngz;
-                        if (have > full) HIP_TRY(hipMemcpyAsync(B.out.p, B.out.p + full, (size_t)(have - full), hipMemcpyDeviceToDevice, c->stream));     // (less than a member: no overlap)
+                        if (have > full) HIP_TRY(hipMemcpyAsync(out.p, out.p + full, (size_t)(have - full), hipMemcpyDeviceToDevice, c->stream));     // (less than a member: no overlap)
                     }
                     tcarry = have - full;
                 }
                 out_at += out_bytes; npieces++;
-                HIP_TRY(hipEventSynchronize(ev1));
-                float ms = 0; (void)hipEventElapsedTime(&ms, ev0, ev1); t_kernel += 1e-3 * (double)ms;
+                RC_TRY(timer.end_wait());
             }                                                                                // (the feeders wait for the stream when they go)
         }
         if (!over) r0 += m;
         const uint64_t rest = total - cut;
-        if (rest) {
-            RC_TRY(buf_reserve(c, &B.id[cur ^ 1], (size_t)rest, 0));
-            HIP_TRY(hipMemcpyAsync(B.id[cur ^ 1].p, d_ids + cut, (size_t)rest, hipMemcpyDeviceToDevice, c->stream));
-            cur ^= 1;
-        }
-        carry = rest;
+        if (rest) RC_TRY(ids.carry_from(cut, rest));
+        else ids.carry = 0;
     }
     if (over || r0 != n) {
         harc_set_error("fastq_assemble_files: %s holds %llu lines, %s %llu reads", id_path, (unsigned long long)lines_seen, dna_path, (unsigned long long)n);
@@ -385,9 +330,9 @@ extern "C" int harc_amd_fastq_assemble_files_ex(const harc_amd_params *params, c
     RC_TRY(fq_check_errors(c, d_err, L));
     if (bgzf) {                                                       // the last member and the end-of-file marker
         uint64_t ngz = 0;
-        RC_TRY(buf_reserve(c, &B.gz, (size_t)dm_bound(tcarry), 0));
-        RC_TRY(harc_bgzf_deflate(c, B.out.p, tcarry, 1, (uint8_t *)B.gz.p, B.gz.cap, &ngz, &gst));
-        { const double t0w = mono_now(); RC_TRY(drain.put(B.gz.p, (size_t)ngz, gz_at)); t_write += mono_now() - t0w; }
+        RC_TRY(dev_reserve(&gz, (size_t)dm_bound(tcarry)));
+        RC_TRY(harc_bgzf_deflate(c, out.p, tcarry, 1, (uint8_t *)gz.p, gz.cap, &ngz, &gst));
+        { const double t0w = mono_now(); RC_TRY(drain.put(gz.p, (size_t)ngz, gz_at)); t_write += mono_now() - t0w; }
         gz_at += ngz;
         drain.set_final_size(gz_at);
     }

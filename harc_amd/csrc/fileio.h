@@ -1,6 +1,7 @@
-// fileio.h -- the two file <-> HBM movers of the library, shared by ingest.hip (FASTQ in), verify.hip (decoded reads out) and fastq_out.hip (both at once):
-// FileFeeder reads a file into device memory, FileDrain writes device memory into a file, each through pinned slices of the context's ring (c->feed_ring)
-// worked by a few host threads.
+// fileio.h -- the two file <-> HBM movers of the library, shared by ingest.hip (FASTQ in), verify.hip (decoded reads out), fastq_out.hip (both at once) and, through
+// packfile.h, qpack.hip and idpack.hip: FileFeeder reads a file into device memory, FileDrain writes device memory into a file, each through pinned slices of the
+// context's ring (c->feed_ring) worked by a few host threads.  Around them, once each, what every file-level call needs: the probes of a file (size, first line, last
+// byte), the guards of an output file and of a context, the split of the ring, an owning device buffer, a kernel timer, and a text whose cut tail is carried on.
 #pragma once
 #include "internal.h"
 #include <string>
@@ -38,6 +39,104 @@ static inline void harc_ring_geom_env(RingGeom *g)
 }
 
 static inline double mono_now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
+
+// ------------------------------------------------------------------------------------------------ what the file-level calls share
+static inline bool file_size(const char *path, uint64_t *n) { struct stat st; if (stat(path, &st) != 0 || !S_ISREG(st.st_mode)) return false; *n = (uint64_t)st.st_size; return true; }   // regular files only
+// the length of the first line of a file that is not empty, for `who`: 1 .. 255
+static inline int first_line_length(const char *path, const char *who, uint32_t *L)
+{
+    char head[257];
+    FILE *f = fopen(path, "rb");
+    if (!f) { harc_set_error("cannot open %s", path); return HARC_AMD_EIO; }
+    const size_t got = fread(head, 1, sizeof head, f);
+    fclose(f);
+    size_t nl = 0;
+    while (nl < got && head[nl] != '\n') nl++;
+    if (nl > 255) { harc_set_error("%s: the first line of %s is longer than 255 characters", who, path); return HARC_AMD_EINVAL; }
+    if (nl == 0) { harc_set_error("%s: the first line of %s is empty", who, path); return HARC_AMD_EINVAL; }
+    *L = (uint32_t)nl;
+    return HARC_AMD_OK;
+}
+// of a file that is not empty
+static inline int last_byte_is_newline(const char *path, bool *yes)
+{
+    FILE *g = fopen(path, "rb"); char last = 0;
+    if (!g || fseeko(g, -1, SEEK_END) != 0 || fread(&last, 1, 1, g) != 1) { if (g) fclose(g); harc_set_error("cannot read %s", path); return HARC_AMD_EIO; }
+    fclose(g);
+    *yes = last == '\n';
+    return HARC_AMD_OK;
+}
+// The output file is removed unless the call reaches its end.  Declare it in front of the FileDrain: it goes after the drain has closed the file
+struct OutFileGuard { std::string path; bool ok = false; ~OutFileGuard() { if (!ok) (void)remove(path.c_str()); } };
+struct CtxGuard { harc_amd_ctx *c = nullptr; ~CtxGuard() { harc_amd_destroy(c); } };
+static inline uint64_t env_u64(const char *name, uint64_t dflt) { if (const char *e = getenv(name)) { const unsigned long long v = strtoull(e, nullptr, 10); if (v >= 1) return v; } return dflt; }
+// a context of its own for a call on side files: the default parameters of read length L over *params, the caller's device kept
+static inline int side_context(const harc_amd_params *params, int L, harc_amd_ctx **c)
+{
+    harc_amd_params P = *params;
+    if (harc_amd_default_params(L, &P) != HARC_AMD_OK) return HARC_AMD_EINVAL;
+    P.device = params->device;
+    return harc_amd_create(&P, c);
+}
+// The context's ONE pinned ring in `parts` disjoint parts of `slices_each` slices, out[0 .. parts), for movers that are alive at the same time; the host threads are
+// shared out among them.  The ring is reserved whole before any of them starts.  HARC_AMD_FEED_SLICE sets the slice, HARC_AMD_FEED_THREADS the threads of all together
+static inline int ring_split(harc_amd_ctx *c, int parts, int slices_each, const char *what, RingGeom *out)
+{
+    RingGeom base; harc_ring_geom_env(&base);
+    for (int k = 0; k < parts; k++) { out[k].slice = base.slice; out[k].nslices = slices_each; out[k].nthr = base.nthr / parts > 0 ? base.nthr / parts : 1; out[k].ring_off = (size_t)k * slices_each * base.slice; }
+    return harc_ring_reserve(c, (size_t)parts * slices_each * base.slice, what);
+}
+
+// A device buffer that a file-level call owns and grows piece by piece
+struct DevBuf { harc_amd_ctx *c; char *p = nullptr; size_t cap = 0; ~DevBuf() { if (p) harc_raw_free(c, p); } };
+// at least `need` bytes, the first `keep` of them kept.  Nothing to keep: the old buffer goes first (the peak stays lower) and the new one is exactly `need`; otherwise
+// a quarter more than `need`, and the old one goes when its bytes have been copied
+static inline int dev_reserve(DevBuf *b, size_t need, size_t keep = 0)
+{
+    if (b->p && b->cap >= need) return HARC_AMD_OK;
+    harc_amd_ctx *c = b->c;
+    if (!keep) {
+        HIP_TRY(hipStreamSynchronize(c->stream));                 // whatever still reads the old buffer has finished
+        if (b->p) { harc_raw_free(c, b->p); b->p = nullptr; b->cap = 0; }
+        RC_TRY(harc_raw_alloc(c, (void **)&b->p, need + 16));
+        b->cap = need;
+        return HARC_AMD_OK;
+    }
+    char *np = nullptr; const size_t cap = need + need / 4;
+    RC_TRY(harc_raw_alloc(c, (void **)&np, cap + 16));
+    hipError_t e = hipMemcpyAsync(np, b->p, keep, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);     // ... and whatever still reads the old buffer has finished
+    if (e != hipSuccess) { harc_raw_free(c, np); harc_set_error("growing a device buffer to %zu bytes failed: %s", cap, hipGetErrorString(e)); return HARC_AMD_ENODEVICE; }
+    harc_raw_free(c, b->p);
+    b->p = np; b->cap = cap;
+    return HARC_AMD_OK;
+}
+
+// Seconds between two points of a stream, added to *sum; sum == nullptr: every call does nothing.  The events go on every way out
+struct KernelTimer {
+    double *sum; hipEvent_t e0 = nullptr, e1 = nullptr;
+    explicit KernelTimer(double *sum_) : sum(sum_) {}
+    KernelTimer(const KernelTimer &) = delete;
+    ~KernelTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    int begin(hipStream_t s)
+    {
+        if (!sum) return HARC_AMD_OK;
+        if (!e0) HIP_TRY(hipEventCreate(&e0));
+        if (!e1) HIP_TRY(hipEventCreate(&e1));
+        HIP_TRY(hipEventRecord(e0, s));
+        return HARC_AMD_OK;
+    }
+    // end() in two halves, for a caller that enqueues more work before it waits
+    int end_mark(hipStream_t s) { if (sum) HIP_TRY(hipEventRecord(e1, s)); return HARC_AMD_OK; }
+    int end_wait()
+    {
+        if (!sum) return HARC_AMD_OK;
+        HIP_TRY(hipEventSynchronize(e1));
+        float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); *sum += 1e-3 * (double)ms;
+        return HARC_AMD_OK;
+    }
+    int end(hipStream_t s) { RC_TRY(end_mark(s)); return end_wait(); }
+};
 
 // File -> HBM at the rate of the host's memory system instead of one core's (round 6; round 3's ./harc -c spent most of its 6 s on 100 M reads in a
 // single-threaded fread into one pinned buffer): reader threads pread() slices of the file into a ring of pinned slices kept by the context, the calling
@@ -304,6 +403,31 @@ struct FileDrain {
         if (fd >= 0) { if (have_final && final_size < fsize && ftruncate(fd, (off_t)final_size) != 0) cut_failed = true; close(fd); fd = -1; }
         if (cut_failed) { harc_set_error("cannot cut %s to its %llu bytes", fname.c_str(), (unsigned long long)final_size); return HARC_AMD_EIO; }
         if (alloc_err) { harc_set_error("cannot allocate %zu bytes for %s: %s", fsize, fname.c_str(), strerror(alloc_err)); const int e = alloc_err; alloc_err = 0; (void)e; return HARC_AMD_EIO; }
+        return HARC_AMD_OK;
+    }
+};
+
+// A text that arrives in pieces and is worked in whole units (lines, blocks): what lies behind the last whole unit of a piece is carried to the front of the next.
+// Two buffers take turns: the carried bytes are copied device to device on the stream, behind the kernels that still read the piece they are cut from.
+struct CarriedText {
+    DevBuf buf[2]; int cur = 0; uint64_t carry = 0;               // carry: bytes at the front of text() that the last piece left
+    explicit CarriedText(harc_amd_ctx *c) : buf{ { c }, { c } } {}
+    char *text() const { return buf[cur].p; }
+    // piece p of the feeder, `len` bytes, behind what was carried: text()[0 .. carry + len).  *t_read: seconds in the upload
+    int take(FileFeeder &feed, size_t p, uint64_t len, double *t_read)
+    {
+        RC_TRY(dev_reserve(&buf[cur], (size_t)(carry + len), (size_t)carry));
+        const double t0 = mono_now();
+        RC_TRY(feed.upload_piece(p, buf[cur].p + carry, nullptr));
+        *t_read += mono_now() - t0;
+        return HARC_AMD_OK;
+    }
+    // the `rest` bytes from byte `cut` of text() on are carried: they become the front of the other buffer
+    int carry_from(uint64_t cut, uint64_t rest)
+    {
+        RC_TRY(dev_reserve(&buf[cur ^ 1], (size_t)rest));
+        HIP_TRY(hipMemcpyAsync(buf[cur ^ 1].p, buf[cur].p + cut, (size_t)rest, hipMemcpyDeviceToDevice, buf[cur].c->stream));
+        cur ^= 1; carry = rest;
         return HARC_AMD_OK;
     }
 };

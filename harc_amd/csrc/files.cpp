@@ -6,8 +6,7 @@
 //                                                       writes read_{seq,pos,noise,noisepos,rev}.txt.<e>(+.tail), read_singleton.txt(+.tail),
 //                                                              read_order.bin, read_order_N_pe.bin, input_N.dna (rewritten), read_meta.txt
 //   pack_order.out <basedir> src/pack_order.cpp:11-77  rewrites read_order.bin, writes read_order.bin.tail
-#include "internal.h"
-#include <string>
+#include "fileio.h"
 
 static bool slurp(const std::string &path, std::vector<char> &out, bool must_exist)
 {
@@ -35,8 +34,6 @@ static int spit_stream(harc_amd_ctx *c, int id, int shard, const std::string &pa
     RC_TRY(harc_amd_get_stream(c, id, shard, &p, &n));
     return spit(path, p, n);
 }
-
-struct CtxGuard { harc_amd_ctx *c = nullptr; ~CtxGuard() { harc_amd_destroy(c); } };
 
 static int load_clean(harc_amd_ctx *c, const std::string &od)
 {

@@ -292,6 +292,16 @@ QV_HD int id_load_row(const uint8_t *tab, const uint32_t *bm, uint32_t r, uint32
     if (qv_load_row(tab + 2u * id_rows_before(bm, r), 0, A, row)) return ID_E_ROW;
     return (row[A - 1u] >> 16) + (row[A - 1u] & 0xFFFFu) == QV_TOT ? ID_OK : ID_E_ROW;
 }
+// The prefix of a block, u32 payload_bytes and the mode and block_text_bytes that every payload starts with, at q with `left` bytes of the packed form from q on
+// (fewer than ID_PREFIX: none of q is read) and text_left bytes of the text not yet claimed by the blocks in front: -> 1 with the size of a payload that holds its head
+// and fits what is left behind the u32, and text bytes within the bound of a block and within text_left, or 0
+#define ID_PREFIX (4u + ID_HEAD0)
+QV_HD int id_prefix(const uint8_t *q, uint64_t left, uint64_t text_left, uint64_t *payload_bytes, uint64_t *text_bytes)
+{
+    if (left < ID_PREFIX) return 0;
+    *payload_bytes = qv_le32(q); *text_bytes = qv_le32(q + 5);
+    return *payload_bytes >= ID_HEAD0 && *payload_bytes <= left - 4u && *text_bytes <= ID_MAX_BLOCK_TEXT && *text_bytes <= text_left;
+}
 // the head of a payload of pbytes bytes: -> ID_OK with *mode and *tbytes, and for mode 1 bm[4] and *hdr1, the bytes in front of the strands
 QV_HD int id_check_head(const uint8_t *pl, uint32_t pbytes, uint32_t *mode, uint32_t *tbytes, uint32_t *bm, uint32_t *hdr1)
 {

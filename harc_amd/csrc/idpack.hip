@@ -13,14 +13,16 @@
 //                 of the destination inside the block, the bytes in front of and behind them one by one.  Nothing outside the blocks is written.
 // A lane's walk over its own lines is byte-serial and not coalesced: neighbouring lanes read text q lines apart.  That is accepted here (NOTES.md has the rate).
 //
-// Unpacking.  The block offsets follow from the payload_bytes prefixes and the places in the text from the block_text_bytes behind them (k_ip_walk, one lane;
-// the file call walks them on the host with pread).
+// Unpacking.  The block offsets follow from the payload_bytes prefixes and the places in the text from the block_text_bytes behind them (id_prefix: k_ip_walk,
+// one lane; on the host the walk of packfile.h).
 //   k_ip_decode   a workgroup per block validates head, bitmap, rows and strand sizes into LDS (id_check_head, id_load_row, id_check_strand), then a lane per
 //                 strand decodes forward (id_strand_decode) and writes its text at its prefix-summed offset.  Any violation raises the error word:
 //                 block number << 8 | ID_E_*.
+// The plumbing of the file calls (probes, guards, ring split, device buffers, kernel timer, the carried tail of the text) is fileio.h's; the drivers of the way back
+// -- the run of k_ip_decode, the device call and the file call -- are packfile.h's, shared with qpack.hip: this file hands them ID_FORMAT.
 #include "devutil.h"
 #include "id_block.h"
-#include "fileio.h"
+#include "packfile.h"
 
 #define IP_T 256
 #define IP_HDR ((ID_HEAD1 + 2u * ID_TABLE + 15u) & ~15u)          // the head and table of a coded payload, rounded to 16
@@ -144,9 +146,8 @@ __global__ void k_ip_walk(const uint8_t *p, uint64_t n_bytes, uint64_t nb, uint6
     uint64_t at = ID_FILE_HEADER, tat = 0;
     for (uint64_t b = 0; b < nb; b++) {
         off[b] = at - ID_FILE_HEADER; toff[b] = tat;
-        if (n_bytes - at < 4u + ID_HEAD0) { bad[0] = b + 1; bad[1] = at; return; }
-        const uint64_t pb = qv_le32(p + at), tb = qv_le32(p + at + 5);
-        if (pb < ID_HEAD0 || n_bytes - at - 4 < pb || tb > ID_MAX_BLOCK_TEXT || tb > text_bytes - tat) { bad[0] = b + 1; bad[1] = at; return; }
+        uint64_t pb = 0, tb = 0;
+        if (!id_prefix(p + at, n_bytes - at, text_bytes - tat, &pb, &tb)) { bad[0] = b + 1; bad[1] = at; return; }
         at += 4 + pb; tat += tb;
     }
     off[nb] = at - ID_FILE_HEADER; toff[nb] = tat;
@@ -246,9 +247,8 @@ static int harc_idpack_run(harc_amd_ctx *c, const char *d_text, const uint64_t *
     HIP_TRY(hipMemsetAsync(bsize + nb, 0, 4, c->stream));
     HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
     HIP_TRY(hipMemsetAsync(d_err, 0xFF, 4, c->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    struct EvGuard { hipEvent_t &a, &b; ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evguard{ e0, e1 };
-    if (st) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, c->stream)); }
+    KernelTimer timer(st ? &st->seconds : nullptr);
+    RC_TRY(timer.begin(c->stream));
     hipLaunchKernelGGL(k_ip_encode, harc_fold256(nb), dim3(IP_T), 0, c->stream, (const uint8_t *)d_text, nls, t0, n, RB, nb, events, slabs, heads, sat, btext, bsize, bmode, d_err);
     HIP_TRY(hipGetLastError());
     RC_TRY(prim_excl_scan_u32_to_u64(c, bsize, boff, (size_t)nb + 1));
@@ -266,10 +266,7 @@ static int harc_idpack_run(harc_amd_ctx *c, const char *d_text, const uint64_t *
                            (const uint64_t *)btext, (const uint32_t *)bsize, (const uint32_t *)bmode, (const uint64_t *)boff, d_out);
         HIP_TRY(hipGetLastError());
     }
-    if (st) {
-        HIP_TRY(hipEventRecord(e1, c->stream)); HIP_TRY(hipEventSynchronize(e1));
-        float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); st->seconds += 1e-3 * (double)ms;
-    }
+    RC_TRY(timer.end(c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));                     // the scratch goes back to the pool
     return HARC_AMD_OK;
 }
@@ -321,9 +318,8 @@ extern "C" int harc_amd_idpack_device(harc_amd_ctx *c, const char *d_text, uint6
 }
 
 // ------------------------------------------------------------------------------------------------ unpacking
-struct IdHeader { uint32_t rb; uint64_t n, text, nb; };
 // the 32 bytes at h of a packed form of n_bytes bytes
-static int ip_parse_header(const char *who, const uint8_t *h, uint64_t n_bytes, IdHeader *H)
+static int ip_parse_header(const char *who, const uint8_t *h, uint64_t n_bytes, PackHeader *H)
 {
     if (!id_magic_ok(h)) { harc_set_error("%s: no packed id file: its first 8 bytes are not the magic HARCI1", who); return HARC_AMD_EINVAL; }
     H->rb = qv_le32(h + 8); H->n = qv_le64(h + 16); H->text = qv_le64(h + 24);
@@ -339,62 +335,21 @@ static int ip_parse_header(const char *who, const uint8_t *h, uint64_t n_bytes, 
     if (H->text < H->n || H->text > H->nb * (uint64_t)ID_MAX_BLOCK_TEXT) { harc_set_error("%s: the header announces %llu lines in %llu bytes of text", who, (unsigned long long)H->n, (unsigned long long)H->text); return HARC_AMD_EINVAL; }
     return HARC_AMD_OK;
 }
-// nb blocks at d_blocks with their offsets d_off[0 .. nb] and text offsets d_toff[0 .. nb] -> the n lines at d_text; block0 / base: number and file offset of the
-// first of them, for the message
-static int harc_idunpack_run(harc_amd_ctx *c, const uint8_t *d_blocks, const uint64_t *d_off, const uint64_t *d_toff, const uint64_t *h_off, uint32_t nb, uint64_t n, uint32_t RB,
-                             char *d_text, uint64_t block0, uint64_t base)
-{
-    if (!nb) return HARC_AMD_OK;
-    PoolScope scope(c);
-    unsigned long long *d_errw = nullptr; RC_TRY(dalloc(c, &d_errw, 2));
-    HIP_TRY(hipMemsetAsync(d_errw, 0xFF, 8, c->stream));
-    hipLaunchKernelGGL(k_ip_decode, harc_fold256(nb), dim3(IP_T), 0, c->stream, d_blocks, d_off, d_toff, nb, n, RB, (uint8_t *)d_text, d_errw);
-    HIP_TRY(hipGetLastError());
-    unsigned long long errw = 0;
-    HIP_TRY(hipMemcpyAsync(&errw, d_errw, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (errw != ~0ull) {
-        const uint64_t b = errw >> 8;
-        harc_set_error("idunpack: block %llu at byte %llu is damaged: %s", (unsigned long long)(block0 + b), (unsigned long long)(base + (h_off ? h_off[b] : 0)), id_error_text((uint32_t)(errw & 0xFF)));
-        return HARC_AMD_EINVAL;
-    }
-    return HARC_AMD_OK;
-}
+static const PackFormat ID_FORMAT = {
+    "id", "id", "HARC_AMD_IDPACK_PIECE", 8, ID_PREFIX, ip_parse_header,
+    [](const PackHeader &, uint64_t, const uint8_t *q, uint64_t left, uint64_t text_left, uint64_t *pb, uint64_t *tb) { return id_prefix(q, left, text_left, pb, tb); },
+    [](harc_amd_ctx *c, const uint8_t *d_packed, uint64_t n_bytes, const PackHeader &H, uint64_t *d_off, uint64_t *d_toff, unsigned long long *d_bad) {
+        hipLaunchKernelGGL(k_ip_walk, dim3(1), dim3(64), 0, c->stream, d_packed, n_bytes, H.nb, H.text, d_off, d_toff, d_bad);
+    },
+    [](harc_amd_ctx *c, const uint8_t *d_blocks, const uint64_t *d_off, const uint64_t *d_toff, uint32_t nb, uint64_t n, const PackHeader &H, char *d_text, unsigned long long *d_errw) {
+        hipLaunchKernelGGL(k_ip_decode, harc_fold256(nb), dim3(IP_T), 0, c->stream, d_blocks, d_off, d_toff, nb, n, H.rb, (uint8_t *)d_text, d_errw);
+    },
+    id_error_text,
+};
 
 extern "C" int harc_amd_idunpack_device(harc_amd_ctx *c, const uint8_t *d_packed, uint64_t n_bytes, char *d_text, uint64_t out_capacity, uint64_t *n_out)
 {
-    if (!c || !d_packed || !n_out) { harc_set_error("idunpack_device: bad arguments"); return HARC_AMD_EINVAL; }
-    if (n_bytes < ID_FILE_HEADER) { harc_set_error("idunpack_device: %llu bytes are fewer than the %u of the header", (unsigned long long)n_bytes, ID_FILE_HEADER); return HARC_AMD_EINVAL; }
-    HIP_TRY(hipSetDevice(c->P.device));
-    uint8_t h[ID_FILE_HEADER];
-    HIP_TRY(hipMemcpyAsync(h, d_packed, ID_FILE_HEADER, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    IdHeader H;
-    RC_TRY(ip_parse_header("idunpack_device", h, n_bytes, &H));
-    *n_out = H.text;
-    if (!d_text) return HARC_AMD_OK;
-    if (out_capacity < H.text) { harc_set_error("idunpack_device: the text takes %llu bytes, the buffer holds %llu", (unsigned long long)H.text, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
-    if (!H.nb) return HARC_AMD_OK;
-    if (H.nb > 0x7FFFFFF0ull) { harc_set_error("idunpack_device: too many blocks for one call"); return HARC_AMD_EINVAL; }
-    PoolScope scope(c);
-    uint64_t *d_off = nullptr, *d_toff = nullptr; unsigned long long *d_bad = nullptr;
-    RC_TRY(dalloc(c, &d_off, (size_t)H.nb + 1)); RC_TRY(dalloc(c, &d_toff, (size_t)H.nb + 1)); RC_TRY(dalloc(c, &d_bad, 2));
-    HIP_TRY(hipMemsetAsync(d_bad, 0, 16, c->stream));
-    hipLaunchKernelGGL(k_ip_walk, dim3(1), dim3(64), 0, c->stream, d_packed, n_bytes, H.nb, H.text, d_off, d_toff, d_bad);
-    HIP_TRY(hipGetLastError());
-    unsigned long long bad[2] = { 0, 0 };
-    std::vector<uint64_t> h_off((size_t)H.nb + 1);
-    HIP_TRY(hipMemcpyAsync(bad, d_bad, 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (bad[0]) {
-        if (bad[0] == H.nb + 2) harc_set_error("idunpack_device: block %llu ends the text at byte %llu, the header announces %llu", (unsigned long long)H.nb - 1, bad[1], (unsigned long long)H.text);
-        else if (bad[0] == H.nb + 1) harc_set_error("idunpack_device: block %llu ends at byte %llu, but there are %llu bytes", (unsigned long long)H.nb - 1, bad[1], (unsigned long long)n_bytes);
-        else harc_set_error("idunpack_device: block %llu at byte %llu leaves the %llu bytes of the packed form or the %llu bytes of its text", bad[0] - 1, bad[1], (unsigned long long)n_bytes, (unsigned long long)H.text);
-        return HARC_AMD_EINVAL;
-    }
-    HIP_TRY(hipMemcpyAsync(h_off.data(), d_off, 8 * ((size_t)H.nb + 1), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return harc_idunpack_run(c, d_packed + ID_FILE_HEADER, d_off, d_toff, h_off.data(), (uint32_t)H.nb, H.n, H.rb, d_text, 0, ID_FILE_HEADER);
+    return pack_unpack_device(ID_FORMAT, c, d_packed, n_bytes, d_text, out_capacity, n_out);
 }
 
 // ------------------------------------------------------------------------------------------------ the same in a row on the host: what the kernels are held to
@@ -425,123 +380,66 @@ extern "C" int harc_amd_idpack_host(const char *text, uint64_t text_bytes, uint3
     return HARC_AMD_OK;
 }
 
-// the u32 and the head of block b at byte `at` of a packed form of n_bytes bytes, read into q[9]: its payload and text bytes, checked against what is left
-static int ip_check_prefix(const char *who, const uint8_t *q, uint64_t b, uint64_t at, uint64_t n_bytes, uint64_t text_left, uint64_t *pb, uint64_t *tb)
-{
-    *pb = qv_le32(q); *tb = qv_le32(q + 5);
-    if (*pb < ID_HEAD0 || n_bytes - at - 4 < *pb || *tb > ID_MAX_BLOCK_TEXT || *tb > text_left) {
-        harc_set_error("%s: block %llu at byte %llu leaves the %llu bytes of the packed form or the bytes of its text", who, (unsigned long long)b, (unsigned long long)at, (unsigned long long)n_bytes);
-        return HARC_AMD_EINVAL;
-    }
-    return HARC_AMD_OK;
-}
-
 extern "C" int harc_amd_idunpack_host(const uint8_t *packed, uint64_t n_bytes, char *text, uint64_t cap, uint64_t *n_out)
 {
     if (!packed || !n_out) { harc_set_error("idunpack_host: bad arguments"); return HARC_AMD_EINVAL; }
     if (n_bytes < ID_FILE_HEADER) { harc_set_error("idunpack_host: %llu bytes are fewer than the %u of the header", (unsigned long long)n_bytes, ID_FILE_HEADER); return HARC_AMD_EINVAL; }
-    IdHeader H;
+    PackHeader H;
     RC_TRY(ip_parse_header("idunpack_host", packed, n_bytes, &H));
     *n_out = H.text;
     if (!text) return HARC_AMD_OK;
     if (cap < H.text) { harc_set_error("idunpack_host: the text takes %llu bytes, the buffer holds %llu", (unsigned long long)H.text, (unsigned long long)cap); return HARC_AMD_EINVAL; }
     std::vector<IdWork> W(1);
-    uint64_t at = ID_FILE_HEADER, tat = 0;
-    for (uint64_t b = 0; b < H.nb; b++) {
-        if (n_bytes - at < 4u + ID_HEAD0) { harc_set_error("idunpack_host: block %llu at byte %llu leaves the %llu bytes of the packed form", (unsigned long long)b, (unsigned long long)at, (unsigned long long)n_bytes); return HARC_AMD_EINVAL; }
-        uint64_t pb = 0, tb = 0;
-        RC_TRY(ip_check_prefix("idunpack_host", packed + at, b, at, n_bytes, H.text - tat, &pb, &tb));
-        const uint64_t line0 = b * (uint64_t)H.rb;
-        const uint32_t m = H.n - line0 < H.rb ? (uint32_t)(H.n - line0) : H.rb;
-        const int e = id_block_decode(packed + at + 4, (uint32_t)pb, m, W[0], (uint8_t *)text + tat);
-        if (e) { harc_set_error("idunpack: block %llu at byte %llu is damaged: %s", (unsigned long long)b, (unsigned long long)at, id_error_text((uint32_t)e)); return HARC_AMD_EINVAL; }
-        at += 4 + pb; tat += tb;
-    }
-    if (at != n_bytes) { harc_set_error("idunpack_host: block %llu ends at byte %llu, but there are %llu bytes", (unsigned long long)H.nb - 1, (unsigned long long)at, (unsigned long long)n_bytes); return HARC_AMD_EINVAL; }
-    if (tat != H.text) { harc_set_error("idunpack_host: block %llu ends the text at byte %llu, the header announces %llu", (unsigned long long)H.nb - 1, (unsigned long long)tat, (unsigned long long)H.text); return HARC_AMD_EINVAL; }
-    return HARC_AMD_OK;
+    return pack_walk(ID_FORMAT, "idunpack_host", "the packed form", H, n_bytes,
+                     [&](uint64_t at, uint8_t *q, size_t k) { memcpy(q, packed + at, k); return HARC_AMD_OK; },
+                     [&](uint64_t b, uint64_t at, uint64_t pb, uint64_t tat) {
+                         const int e = id_block_decode(packed + at + 4, (uint32_t)pb, pack_block_lines(H, b), W[0], (uint8_t *)text + tat);
+                         return e ? pack_refuse_damaged(ID_FORMAT, b, at, (uint32_t)e) : HARC_AMD_OK;
+                     }, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------ the files
-namespace {
-struct IpBuf { harc_amd_ctx *c; char *p = nullptr; size_t cap = 0; ~IpBuf() { if (p) harc_raw_free(c, p); } };
-// at least `need` bytes, the first `keep` of them kept
-int ip_reserve(IpBuf *b, size_t need, size_t keep)
-{
-    if (b->p && b->cap >= need) return HARC_AMD_OK;
-    char *np = nullptr; const size_t cap = need + (keep ? need / 4 : 0);
-    RC_TRY(harc_raw_alloc(b->c, (void **)&np, cap + 16));
-    if (keep && hipMemcpyAsync(np, b->p, keep, hipMemcpyDeviceToDevice, b->c->stream) != hipSuccess) { harc_raw_free(b->c, np); harc_set_error("idpack_files: a device copy failed"); return HARC_AMD_ENODEVICE; }
-    if (hipStreamSynchronize(b->c->stream) != hipSuccess) { harc_raw_free(b->c, np); harc_set_error("idpack_files: the device failed"); return HARC_AMD_ENODEVICE; }      // whatever still reads the old buffer has finished
-    if (b->p) harc_raw_free(b->c, b->p);
-    b->p = np; b->cap = cap;
-    return HARC_AMD_OK;
-}
-bool ip_file_size(const char *path, uint64_t *n) { struct stat st; if (stat(path, &st) != 0 || !S_ISREG(st.st_mode)) return false; *n = (uint64_t)st.st_size; return true; }
-struct IpOutGuard { std::string path; bool ok = false; ~IpOutGuard() { if (!ok) (void)remove(path.c_str()); } };
-struct IpCtxGuard { harc_amd_ctx *c; ~IpCtxGuard() { harc_amd_destroy(c); } };
-uint64_t ip_env_u64(const char *name, uint64_t dflt) { if (const char *e = getenv(name)) { const unsigned long long v = strtoull(e, nullptr, 10); if (v >= 1) return v; } return dflt; }
-// the context's one pinned ring in two halves of eight slices: the feeder's and the drain's
-int ip_ring(harc_amd_ctx *c, RingGeom *feed, RingGeom *drain)
-{
-    RingGeom base; harc_ring_geom_env(&base);
-    for (RingGeom *g : { feed, drain }) { g->slice = base.slice; g->nslices = 8; g->nthr = base.nthr / 2 > 0 ? base.nthr / 2 : 1; }
-    feed->ring_off = 0; drain->ring_off = 8 * base.slice;
-    return harc_ring_reserve(c, 16 * base.slice, "id");
-}
-int ip_context(const harc_amd_params *params, harc_amd_ctx **c)
-{
-    harc_amd_params P = *params;
-    if (harc_amd_default_params(100, &P) != HARC_AMD_OK) return HARC_AMD_EINVAL;
-    P.device = params->device;
-    return harc_amd_create(&P, c);
-}
-}
-
 // The text goes through the ring in byte ranges of about `piece_blocks` blocks of ids of 80 bytes (4 KiB .. 256 MiB).  The line index of what has arrived says how
 // many whole blocks it holds: they are packed, at most piece_blocks and at most IP_CALL_TEXT bytes of text a call (one block where a block alone is longer), and the
-// rest is carried to the front of the next range, as fastq_out.hip carries a cut line.  The event scratch and the slabs are five bytes per byte of text: 1.25 GiB a
+// rest is carried to the front of the next range (CarriedText, as fastq_out.hip carries a cut line).  The event scratch and the slabs are five bytes per byte of text: 1.25 GiB a
 // call with ids of any length, and 5 GiB in the one case that cannot be cut, a single block of the 2^30 bytes a block may hold
 extern "C" int harc_amd_idpack_files(const harc_amd_params *params, const char *id_path, const char *out_path)
 {
     if (!params || !id_path || !out_path) { harc_set_error("idpack_files: bad arguments"); return HARC_AMD_EINVAL; }
     uint64_t isz = 0;
-    if (!ip_file_size(id_path, &isz)) { harc_set_error("cannot open %s", id_path); return HARC_AMD_EIO; }
-    IpOutGuard outguard{ out_path };
+    if (!file_size(id_path, &isz)) { harc_set_error("cannot open %s", id_path); return HARC_AMD_EIO; }
+    OutFileGuard outguard{ out_path };
     if (isz) {                                                    // before a device is touched
-        FILE *g = fopen(id_path, "rb"); char last = 0;
-        if (!g || fseeko(g, (off_t)isz - 1, SEEK_SET) != 0 || fread(&last, 1, 1, g) != 1) { if (g) fclose(g); harc_set_error("cannot read %s", id_path); return HARC_AMD_EIO; }
-        fclose(g);
-        if (last != '\n') { harc_set_error("idpack_files: the last line of %s does not end in a newline", id_path); return HARC_AMD_EINVAL; }
+        bool closed = false;
+        RC_TRY(last_byte_is_newline(id_path, &closed));
+        if (!closed) { harc_set_error("idpack_files: the last line of %s does not end in a newline", id_path); return HARC_AMD_EINVAL; }
     }
-    const uint32_t rb = (uint32_t)ip_env_u64("HARC_AMD_IDPACK_BLOCK", ID_DEFAULT_RB);
-    const uint64_t piece_blocks = ip_env_u64("HARC_AMD_IDPACK_PIECE", 8), call_text = ip_env_u64("HARC_AMD_IDPACK_CALL_TEXT", IP_CALL_TEXT);
+    const uint32_t rb = (uint32_t)env_u64("HARC_AMD_IDPACK_BLOCK", ID_DEFAULT_RB);
+    const uint64_t piece_blocks = env_u64(ID_FORMAT.piece_env, ID_FORMAT.piece_default), call_text = env_u64("HARC_AMD_IDPACK_CALL_TEXT", IP_CALL_TEXT);
     uint64_t piece = piece_blocks * rb * 80ull;
     if (piece < 4096) piece = 4096;
     if (piece > ((uint64_t)256 << 20)) piece = (uint64_t)256 << 20;
-    harc_amd_ctx *c = nullptr;
-    RC_TRY(ip_context(params, &c));
-    IpCtxGuard guard{ c };
-    RingGeom gf, gd;
-    RC_TRY(ip_ring(c, &gf, &gd));
-    IpBuf txt[2] = { { c }, { c } }, out{ c };
+    CtxGuard guard;
+    RC_TRY(side_context(params, 100, &guard.c));
+    harc_amd_ctx *c = guard.c;
+    RingGeom g[2];                                                // the feeder's and the drain's
+    RC_TRY(ring_split(c, 2, 8, ID_FORMAT.ring, g));
+    CarriedText txt(c); DevBuf out{ c };
     const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
     double t_read = 0, t_write = 0;
     IpStats st;
     uint64_t at = ID_FILE_HEADER, n = 0, nb = 0; int npieces = 0;
     {
         FileDrain drain(c);
-        RC_TRY(drain.start(out_path, (size_t)id_bound(isz, isz, rb), &gd, true));      // (no more lines than bytes)
+        RC_TRY(drain.start(out_path, (size_t)id_bound(isz, isz, rb), &g[1], true));      // (no more lines than bytes)
         std::vector<std::pair<uint64_t, uint64_t>> pieces;
         for (uint64_t a = 0; a < isz; a += piece) pieces.emplace_back(a, isz - a < piece ? isz : a + piece);
         FileFeeder feed(c, id_path);
-        if (!pieces.empty()) RC_TRY(feed.start(pieces, gf));
-        uint64_t carry = 0; int cur = 0;
+        if (!pieces.empty()) RC_TRY(feed.start(pieces, g[0]));
         for (size_t p = 0; p < pieces.size(); p++) {
-            const uint64_t len = pieces[p].second - pieces[p].first, total = carry + len; const bool lastp = p + 1 == pieces.size();
-            RC_TRY(ip_reserve(&txt[cur], (size_t)total, (size_t)carry));                     // the carried bytes sit at its front
-            { const double t0 = mono_now(); RC_TRY(feed.upload_piece(p, txt[cur].p + carry, nullptr)); t_read += mono_now() - t0; }
-            const char *d_ids = txt[cur].p;
+            const uint64_t len = pieces[p].second - pieces[p].first, total = txt.carry + len; const bool lastp = p + 1 == pieces.size();
+            RC_TRY(txt.take(feed, p, len, &t_read));                                         // the carried bytes sit at its front
+            const char *d_ids = txt.text();
             PoolScope piece_scope(c);
             const uint64_t *nls = nullptr; uint64_t lines = 0;
             RC_TRY(build_line_index(c, d_ids, total, &nls, &lines));
@@ -564,7 +462,7 @@ extern "C" int harc_amd_idpack_files(const harc_amd_params *params, const char *
                     const uint64_t half = (id_blocks(m, rb) / 2) * rb;
                     m = half < rb ? rb : half;
                 }
-                RC_TRY(ip_reserve(&out, (size_t)(id_bound(end - cut, m, rb) - ID_FILE_HEADER), 0));
+                RC_TRY(dev_reserve(&out, (size_t)(id_bound(end - cut, m, rb) - ID_FILE_HEADER)));
                 uint64_t nblk = 0;
                 RC_TRY(harc_idpack_run(c, d_ids, nls + l0, cut, end, m, rb, (uint8_t *)out.p, out.cap, &nblk, nb, &st));
                 { const double t0 = mono_now(); RC_TRY(drain.put(out.p, (size_t)nblk, at)); t_write += mono_now() - t0; }
@@ -572,12 +470,8 @@ extern "C" int harc_amd_idpack_files(const harc_amd_params *params, const char *
                 l0 += m; cut = end;
             }
             const uint64_t rest = total - cut;
-            if (rest && cut) {
-                RC_TRY(ip_reserve(&txt[cur ^ 1], (size_t)rest, 0));
-                HIP_TRY(hipMemcpyAsync(txt[cur ^ 1].p, d_ids + cut, (size_t)rest, hipMemcpyDeviceToDevice, c->stream));
-                cur ^= 1;
-            }
-            carry = rest;
+            if (rest && cut) RC_TRY(txt.carry_from(cut, rest));
+            else txt.carry = rest;                                                           // nothing, or not one whole block yet: the piece grows by the next one
         }
         uint8_t h[ID_FILE_HEADER];
         id_file_header(h, rb, n, isz);
@@ -593,69 +487,5 @@ extern "C" int harc_amd_idpack_files(const harc_amd_params *params, const char *
 
 extern "C" int harc_amd_idunpack_files(const harc_amd_params *params, const char *packed_path, const char *out_path)
 {
-    if (!params || !packed_path || !out_path) { harc_set_error("idunpack_files: bad arguments"); return HARC_AMD_EINVAL; }
-    uint64_t fsz = 0;
-    if (!ip_file_size(packed_path, &fsz)) { harc_set_error("cannot open %s", packed_path); return HARC_AMD_EIO; }
-    IpOutGuard outguard{ out_path };
-    if (fsz < ID_FILE_HEADER) { harc_set_error("idunpack_files: %s holds %llu bytes, fewer than the %u of the header", packed_path, (unsigned long long)fsz, ID_FILE_HEADER); return HARC_AMD_EINVAL; }
-    const int fd = open(packed_path, O_RDONLY);
-    if (fd < 0) { harc_set_error("cannot open %s", packed_path); return HARC_AMD_EIO; }
-    struct FdGuard { int fd; ~FdGuard() { close(fd); } } fdguard{ fd };
-    uint8_t h[ID_FILE_HEADER];
-    if (pread(fd, h, ID_FILE_HEADER, 0) != (ssize_t)ID_FILE_HEADER) { harc_set_error("cannot read %s", packed_path); return HARC_AMD_EIO; }
-    IdHeader H;
-    RC_TRY(ip_parse_header("idunpack_files", h, fsz, &H));
-    // the block offsets and the places in the text, from the prefixes: known, and inside the file, before a device is touched
-    std::vector<uint64_t> off((size_t)H.nb + 1), toff((size_t)H.nb + 1);
-    uint64_t at = ID_FILE_HEADER, tat = 0;
-    for (uint64_t b = 0; b < H.nb; b++) {
-        off[b] = at; toff[b] = tat;
-        uint8_t q[4 + ID_HEAD0];
-        if (fsz - at < sizeof q) { harc_set_error("idunpack_files: block %llu at byte %llu leaves the %llu bytes of %s", (unsigned long long)b, (unsigned long long)at, (unsigned long long)fsz, packed_path); return HARC_AMD_EINVAL; }
-        if (pread(fd, q, sizeof q, (off_t)at) != (ssize_t)sizeof q) { harc_set_error("cannot read %s", packed_path); return HARC_AMD_EIO; }
-        uint64_t pb = 0, tb = 0;
-        RC_TRY(ip_check_prefix("idunpack_files", q, b, at, fsz, H.text - tat, &pb, &tb));
-        at += 4 + pb; tat += tb;
-    }
-    off[H.nb] = at; toff[H.nb] = tat;
-    if (at != fsz) { harc_set_error("idunpack_files: the blocks of %s end at byte %llu, the file holds %llu", packed_path, (unsigned long long)at, (unsigned long long)fsz); return HARC_AMD_EINVAL; }
-    if (tat != H.text) { harc_set_error("idunpack_files: block %llu of %s ends the text at byte %llu, its header announces %llu", (unsigned long long)H.nb - 1, packed_path, (unsigned long long)tat, (unsigned long long)H.text); return HARC_AMD_EINVAL; }
-    harc_amd_ctx *c = nullptr;
-    RC_TRY(ip_context(params, &c));
-    IpCtxGuard guard{ c };
-    RingGeom gf, gd;
-    RC_TRY(ip_ring(c, &gf, &gd));
-    IpBuf pk{ c }, txt{ c }, doff{ c };
-    const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
-    double t_read = 0, t_write = 0, t_kernel = 0;
-    const uint64_t piece_blocks = ip_env_u64("HARC_AMD_IDPACK_PIECE", 8);
-    int npieces = 0;
-    {
-        FileDrain drain(c);
-        RC_TRY(drain.start(out_path, (size_t)H.text, &gd, true));
-        std::vector<std::pair<uint64_t, uint64_t>> pieces;
-        for (uint64_t b = 0; b < H.nb; b += piece_blocks) pieces.emplace_back(off[b], off[H.nb - b < piece_blocks ? H.nb : b + piece_blocks]);
-        FileFeeder feed(c, packed_path);
-        if (!pieces.empty()) RC_TRY(feed.start(pieces, gf));
-        std::vector<uint64_t> rel;
-        for (size_t p = 0; p < pieces.size(); p++) {
-            const uint64_t b0 = p * piece_blocks, b1 = H.nb - b0 < piece_blocks ? H.nb : b0 + piece_blocks, bytes = pieces[p].second - pieces[p].first, k = b1 - b0 + 1;
-            const uint64_t line0 = b0 * H.rb, m = (b1 == H.nb ? H.n : b1 * H.rb) - line0, tbytes = toff[b1] - toff[b0];
-            RC_TRY(ip_reserve(&pk, (size_t)bytes, 0)); RC_TRY(ip_reserve(&txt, (size_t)tbytes + 1, 0)); RC_TRY(ip_reserve(&doff, 16 * (size_t)k, 0));
-            { const double t0 = mono_now(); RC_TRY(feed.upload_piece(p, pk.p, nullptr)); t_read += mono_now() - t0; }
-            rel.resize((size_t)(2 * k));
-            for (uint64_t b = b0; b <= b1; b++) { rel[(size_t)(b - b0)] = off[b] - off[b0]; rel[(size_t)(k + b - b0)] = toff[b] - toff[b0]; }
-            HIP_TRY(hipMemcpyAsync(doff.p, rel.data(), 8 * rel.size(), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            { const double t0 = mono_now(); RC_TRY(harc_idunpack_run(c, (const uint8_t *)pk.p, (const uint64_t *)doff.p, (const uint64_t *)doff.p + k, rel.data(), (uint32_t)(b1 - b0), m, H.rb, txt.p, b0, off[b0])); t_kernel += mono_now() - t0; }
-            { const double t0 = mono_now(); RC_TRY(drain.put(txt.p, (size_t)tbytes, toff[b0])); t_write += mono_now() - t0; }
-            npieces++;
-        }
-        drain.set_final_size(H.text);
-        { const double t0 = mono_now(); RC_TRY(drain.finish()); t_write += mono_now() - t0; }
-    }
-    if (tlog) fprintf(stderr, "[idpack] unpacked %llu bytes of text from %llu bytes in %llu blocks, %d pieces: %.3f s in the kernels, %.3f s waiting for the readers, %.3f s waiting for the writers\n",
-                      (unsigned long long)H.text, (unsigned long long)fsz, (unsigned long long)H.nb, npieces, t_kernel, t_read, t_write);
-    outguard.ok = true;
-    return HARC_AMD_OK;
+    return pack_unpack_files(ID_FORMAT, params, packed_path, out_path);
 }

@@ -11,12 +11,14 @@
 //                 destination inside the block, the bytes in front of and behind them one by one.  Nothing outside the blocks is written.
 // The lanes of a wave read 64 neighbouring lines at a stride of L + 1 bytes in all three walks over the text: the same cache lines serve the next hundred symbols.
 //
-// Unpacking.  The block offsets follow from the payload_bytes prefixes (k_qp_walk, one lane; the file call walks them on the host with pread).
+// Unpacking.  The block offsets follow from the payload_bytes prefixes (qv_prefix: k_qp_walk, one lane; on the host the walk of packfile.h).
 //   k_qp_decode   a workgroup per block validates head, table and strand lengths into LDS (qv_check_head, qv_load_row), then a lane per strand decodes forward
 //                 (qv_strand_decode) and writes its lines, a newline behind each.  Any violation raises the error word: block number << 8 | QV_E_*.
+// The plumbing of the file calls (probes, guards, ring split, device buffers, kernel timer) is fileio.h's; the drivers of the way back -- the run of k_qp_decode, the
+// device call and the file call -- are packfile.h's, shared with idpack.hip: this file hands them QV_FORMAT.
 #include "devutil.h"
 #include "qv_block.h"
-#include "fileio.h"
+#include "packfile.h"
 
 #define QP_T 256
 #define QP_HDR ((14u + 2u * QV_TABLE + 4u * QV_STRANDS + 15u) & ~15u)     // the head of a coded payload in front of the block's slabs, rounded to 16
@@ -140,9 +142,8 @@ __global__ void k_qp_walk(const uint8_t *p, uint64_t n_bytes, uint64_t nb, uint6
     uint64_t at = QV_FILE_HEADER;
     for (uint64_t b = 0; b < nb; b++) {
         off[b] = at - QV_FILE_HEADER;
-        if (n_bytes - at < 4) { bad[0] = b + 1; bad[1] = at; return; }
-        const uint64_t pb = qv_le32(p + at);
-        if (pb == 0 || n_bytes - at - 4 < pb) { bad[0] = b + 1; bad[1] = at; return; }
+        uint64_t pb = 0;
+        if (!qv_prefix(p + at, n_bytes - at, &pb)) { bad[0] = b + 1; bad[1] = at; return; }
         at += 4 + pb;
     }
     off[nb] = at - QV_FILE_HEADER;
@@ -231,9 +232,8 @@ static int harc_qpack_run(harc_amd_ctx *c, const char *d_text, uint64_t n, uint3
     RC_TRY(dalloc(c, &d_err, 4));
     HIP_TRY(hipMemsetAsync(bsize + nb, 0, 4, c->stream));
     HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    struct EvGuard { hipEvent_t &a, &b; ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evguard{ e0, e1 };
-    if (st) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, c->stream)); }
+    KernelTimer timer(st ? &st->seconds : nullptr);
+    RC_TRY(timer.begin(c->stream));
     hipLaunchKernelGGL(k_qp_encode, harc_fold256(nb), dim3(QP_T), 0, c->stream, (const uint8_t *)d_text, n, L, RB, nb, scratch, stride, slab, bsize, bmode, d_err);
     HIP_TRY(hipGetLastError());
     RC_TRY(prim_excl_scan_u32_to_u64(c, bsize, boff, (size_t)nb + 1));
@@ -254,10 +254,7 @@ static int harc_qpack_run(harc_amd_ctx *c, const char *d_text, uint64_t n, uint3
                            (const uint32_t *)bsize, (const uint32_t *)bmode, (const uint64_t *)boff, d_out);
         HIP_TRY(hipGetLastError());
     }
-    if (st) {
-        HIP_TRY(hipEventRecord(e1, c->stream)); HIP_TRY(hipEventSynchronize(e1));
-        float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); st->seconds += 1e-3 * (double)ms;
-    }
+    RC_TRY(timer.end(c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));                     // the scratch goes back to the pool
     return HARC_AMD_OK;
 }
@@ -298,78 +295,39 @@ extern "C" int harc_amd_qpack_device(harc_amd_ctx *c, const char *d_text, uint64
 }
 
 // ------------------------------------------------------------------------------------------------ unpacking
-struct QvHeader { uint32_t L, rb; uint64_t n, nb; };
 // the 32 bytes at h of a packed form of n_bytes bytes
-static int qp_parse_header(const char *who, const uint8_t *h, uint64_t n_bytes, QvHeader *H)
+static int qp_parse_header(const char *who, const uint8_t *h, uint64_t n_bytes, PackHeader *H)
 {
     if (!qv_magic_ok(h)) { harc_set_error("%s: no packed quality file: its first 8 bytes are not the magic HARCQ1", who); return HARC_AMD_EINVAL; }
     H->L = qv_le32(h + 8); H->rb = qv_le32(h + 12); H->n = qv_le64(h + 16);
     if (H->n == 0) {
         if (H->L || H->rb || n_bytes != QV_FILE_HEADER) { harc_set_error("%s: the header announces no lines, but a read length, a block size or %llu bytes behind it", who, (unsigned long long)(n_bytes - QV_FILE_HEADER)); return HARC_AMD_EINVAL; }
-        H->nb = 0;
+        H->nb = 0; H->text = 0;
         return HARC_AMD_OK;
     }
     if (H->L < 1 || H->L > 255 || H->rb < 1 || (uint64_t)H->rb * H->L > QV_MAX_BLOCK_SYMBOLS) { harc_set_error("%s: the header names a read length of %u and %u reads per block", who, H->L, H->rb); return HARC_AMD_EINVAL; }
     H->nb = qv_blocks(H->n, H->rb);
     if (H->nb > (n_bytes - QV_FILE_HEADER) / 5) { harc_set_error("%s: the header announces %llu blocks, %llu bytes cannot hold them", who, (unsigned long long)H->nb, (unsigned long long)n_bytes); return HARC_AMD_EINVAL; }
     if (H->n > ((uint64_t)1 << 62) / (H->L + 1ull)) { harc_set_error("%s: the header announces %llu lines", who, (unsigned long long)H->n); return HARC_AMD_EINVAL; }
+    H->text = H->n * (H->L + 1ull);
     return HARC_AMD_OK;
 }
-// nb blocks at d_blocks with their offsets d_off[0 .. nb] -> the n lines at d_text; block0 / base: number and file offset of the first of them, for the message
-static int harc_qunpack_run(harc_amd_ctx *c, const uint8_t *d_blocks, const uint64_t *d_off, const uint64_t *h_off, uint32_t nb, uint64_t n, uint32_t L, uint32_t RB, char *d_text,
-                            uint64_t block0, uint64_t base)
-{
-    if (!nb) return HARC_AMD_OK;
-    PoolScope scope(c);
-    unsigned long long *d_errw = nullptr; RC_TRY(dalloc(c, &d_errw, 2));
-    HIP_TRY(hipMemsetAsync(d_errw, 0xFF, 8, c->stream));
-    hipLaunchKernelGGL(k_qp_decode, harc_fold256(nb), dim3(QP_T), 0, c->stream, d_blocks, d_off, nb, n, L, RB, (uint8_t *)d_text, d_errw);
-    HIP_TRY(hipGetLastError());
-    unsigned long long errw = 0;
-    HIP_TRY(hipMemcpyAsync(&errw, d_errw, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (errw != ~0ull) {
-        const uint64_t b = errw >> 8;
-        harc_set_error("qunpack: block %llu at byte %llu is damaged: %s", (unsigned long long)(block0 + b), (unsigned long long)(base + (h_off ? h_off[b] : 0)), qv_error_text((uint32_t)(errw & 0xFF)));
-        return HARC_AMD_EINVAL;
-    }
-    return HARC_AMD_OK;
-}
+// (the text bytes of a block follow from its number, lines of H.L and their newlines, not from its prefix)
+static const PackFormat QV_FORMAT = {
+    "q", "quality", "HARC_AMD_QPACK_PIECE", 64, QV_PREFIX, qp_parse_header,
+    [](const PackHeader &H, uint64_t b, const uint8_t *q, uint64_t left, uint64_t, uint64_t *pb, uint64_t *tb) { *tb = pack_block_lines(H, b) * (H.L + 1ull); return qv_prefix(q, left, pb); },
+    [](harc_amd_ctx *c, const uint8_t *d_packed, uint64_t n_bytes, const PackHeader &H, uint64_t *d_off, uint64_t *, unsigned long long *d_bad) {
+        hipLaunchKernelGGL(k_qp_walk, dim3(1), dim3(64), 0, c->stream, d_packed, n_bytes, H.nb, d_off, d_bad);
+    },
+    [](harc_amd_ctx *c, const uint8_t *d_blocks, const uint64_t *d_off, const uint64_t *, uint32_t nb, uint64_t n, const PackHeader &H, char *d_text, unsigned long long *d_errw) {
+        hipLaunchKernelGGL(k_qp_decode, harc_fold256(nb), dim3(QP_T), 0, c->stream, d_blocks, d_off, nb, n, H.L, H.rb, (uint8_t *)d_text, d_errw);
+    },
+    qv_error_text,
+};
 
 extern "C" int harc_amd_qunpack_device(harc_amd_ctx *c, const uint8_t *d_packed, uint64_t n_bytes, char *d_text, uint64_t out_capacity, uint64_t *n_out)
 {
-    if (!c || !d_packed || !n_out) { harc_set_error("qunpack_device: bad arguments"); return HARC_AMD_EINVAL; }
-    if (n_bytes < QV_FILE_HEADER) { harc_set_error("qunpack_device: %llu bytes are fewer than the %u of the header", (unsigned long long)n_bytes, QV_FILE_HEADER); return HARC_AMD_EINVAL; }
-    HIP_TRY(hipSetDevice(c->P.device));
-    uint8_t h[QV_FILE_HEADER];
-    HIP_TRY(hipMemcpyAsync(h, d_packed, QV_FILE_HEADER, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    QvHeader H;
-    RC_TRY(qp_parse_header("qunpack_device", h, n_bytes, &H));
-    const uint64_t total = H.n * (H.L + 1ull);
-    *n_out = total;
-    if (!d_text) return HARC_AMD_OK;
-    if (out_capacity < total) { harc_set_error("qunpack_device: the lines take %llu bytes, the buffer holds %llu", (unsigned long long)total, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
-    if (!H.nb) return HARC_AMD_OK;
-    if (H.nb > 0x7FFFFFF0ull) { harc_set_error("qunpack_device: too many blocks for one call"); return HARC_AMD_EINVAL; }
-    PoolScope scope(c);
-    uint64_t *d_off = nullptr; unsigned long long *d_bad = nullptr;
-    RC_TRY(dalloc(c, &d_off, (size_t)H.nb + 1)); RC_TRY(dalloc(c, &d_bad, 2));
-    HIP_TRY(hipMemsetAsync(d_bad, 0, 16, c->stream));
-    hipLaunchKernelGGL(k_qp_walk, dim3(1), dim3(64), 0, c->stream, d_packed, n_bytes, H.nb, d_off, d_bad);
-    HIP_TRY(hipGetLastError());
-    unsigned long long bad[2] = { 0, 0 };
-    std::vector<uint64_t> h_off((size_t)H.nb + 1);
-    HIP_TRY(hipMemcpyAsync(bad, d_bad, 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (bad[0]) {
-        if (bad[0] == H.nb + 1) harc_set_error("qunpack_device: block %llu ends at byte %llu, but there are %llu bytes", (unsigned long long)H.nb - 1, bad[1], (unsigned long long)n_bytes);
-        else harc_set_error("qunpack_device: block %llu at byte %llu leaves the %llu bytes of the packed form", bad[0] - 1, bad[1], (unsigned long long)n_bytes);
-        return HARC_AMD_EINVAL;
-    }
-    HIP_TRY(hipMemcpyAsync(h_off.data(), d_off, 8 * ((size_t)H.nb + 1), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return harc_qunpack_run(c, d_packed + QV_FILE_HEADER, d_off, h_off.data(), (uint32_t)H.nb, H.n, H.L, H.rb, d_text, 0, QV_FILE_HEADER);
+    return pack_unpack_device(QV_FORMAT, c, d_packed, n_bytes, d_text, out_capacity, n_out);
 }
 
 // ------------------------------------------------------------------------------------------------ the same in a row on the host: what the kernels are held to
@@ -419,93 +377,42 @@ extern "C" int harc_amd_qunpack_host(const uint8_t *packed, uint64_t n_bytes, ch
 {
     if (!packed || !n_out) { harc_set_error("qunpack_host: bad arguments"); return HARC_AMD_EINVAL; }
     if (n_bytes < QV_FILE_HEADER) { harc_set_error("qunpack_host: %llu bytes are fewer than the %u of the header", (unsigned long long)n_bytes, QV_FILE_HEADER); return HARC_AMD_EINVAL; }
-    QvHeader H;
+    PackHeader H;
     RC_TRY(qp_parse_header("qunpack_host", packed, n_bytes, &H));
-    const uint64_t total = H.n * (H.L + 1ull);
-    *n_out = total;
+    *n_out = H.text;
     if (!text) return HARC_AMD_OK;
-    if (cap < total) { harc_set_error("qunpack_host: the lines take %llu bytes, the buffer holds %llu", (unsigned long long)total, (unsigned long long)cap); return HARC_AMD_EINVAL; }
+    if (cap < H.text) { harc_set_error("qunpack_host: the text takes %llu bytes, the buffer holds %llu", (unsigned long long)H.text, (unsigned long long)cap); return HARC_AMD_EINVAL; }
     std::vector<QvWork> W(1);
-    uint64_t at = QV_FILE_HEADER;
-    for (uint64_t b = 0; b < H.nb; b++) {
-        if (n_bytes - at < 4) { harc_set_error("qunpack_host: block %llu at byte %llu leaves the %llu bytes of the packed form", (unsigned long long)b, (unsigned long long)at, (unsigned long long)n_bytes); return HARC_AMD_EINVAL; }
-        const uint64_t pb = qv_le32(packed + at);
-        if (pb == 0 || n_bytes - at - 4 < pb) { harc_set_error("qunpack_host: block %llu at byte %llu leaves the %llu bytes of the packed form", (unsigned long long)b, (unsigned long long)at, (unsigned long long)n_bytes); return HARC_AMD_EINVAL; }
-        const uint64_t line0 = b * (uint64_t)H.rb;
-        const uint32_t m = H.n - line0 < H.rb ? (uint32_t)(H.n - line0) : H.rb;
-        const int e = qv_block_decode(packed + at + 4, (uint32_t)pb, m, H.L, W[0], (uint8_t *)text + line0 * (H.L + 1ull));
-        if (e) { harc_set_error("qunpack: block %llu at byte %llu is damaged: %s", (unsigned long long)b, (unsigned long long)at, qv_error_text((uint32_t)e)); return HARC_AMD_EINVAL; }
-        at += 4 + pb;
-    }
-    if (at != n_bytes) { harc_set_error("qunpack_host: block %llu ends at byte %llu, but there are %llu bytes", (unsigned long long)H.nb - 1, (unsigned long long)at, (unsigned long long)n_bytes); return HARC_AMD_EINVAL; }
-    return HARC_AMD_OK;
+    return pack_walk(QV_FORMAT, "qunpack_host", "the packed form", H, n_bytes,
+                     [&](uint64_t at, uint8_t *q, size_t k) { memcpy(q, packed + at, k); return HARC_AMD_OK; },
+                     [&](uint64_t b, uint64_t at, uint64_t pb, uint64_t tat) {
+                         const int e = qv_block_decode(packed + at + 4, (uint32_t)pb, pack_block_lines(H, b), H.L, W[0], (uint8_t *)text + tat);
+                         return e ? pack_refuse_damaged(QV_FORMAT, b, at, (uint32_t)e) : HARC_AMD_OK;
+                     }, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------ the files
-namespace {
-struct QpBuf { harc_amd_ctx *c; char *p = nullptr; size_t cap = 0; ~QpBuf() { if (p) harc_raw_free(c, p); } };
-int qp_reserve(QpBuf *b, size_t need)
-{
-    if (b->p && b->cap >= need) return HARC_AMD_OK;
-    HIP_TRY(hipStreamSynchronize(b->c->stream));                  // whatever still reads the old buffer has finished
-    if (b->p) { harc_raw_free(b->c, b->p); b->p = nullptr; b->cap = 0; }
-    RC_TRY(harc_raw_alloc(b->c, (void **)&b->p, need + 16));
-    b->cap = need;
-    return HARC_AMD_OK;
-}
-bool qp_file_size(const char *path, uint64_t *n) { struct stat st; if (stat(path, &st) != 0 || !S_ISREG(st.st_mode)) return false; *n = (uint64_t)st.st_size; return true; }
-struct QpOutGuard { std::string path; bool ok = false; ~QpOutGuard() { if (!ok) (void)remove(path.c_str()); } };
-struct QpCtxGuard { harc_amd_ctx *c; ~QpCtxGuard() { harc_amd_destroy(c); } };
-uint64_t qp_env_u64(const char *name, uint64_t dflt) { if (const char *e = getenv(name)) { const unsigned long long v = strtoull(e, nullptr, 10); if (v >= 1) return v; } return dflt; }
-// the context's one pinned ring in two halves of eight slices: the feeder's and the drain's
-int qp_ring(harc_amd_ctx *c, RingGeom *feed, RingGeom *drain)
-{
-    RingGeom base; harc_ring_geom_env(&base);
-    for (RingGeom *g : { feed, drain }) { g->slice = base.slice; g->nslices = 8; g->nthr = base.nthr / 2 > 0 ? base.nthr / 2 : 1; }
-    feed->ring_off = 0; drain->ring_off = 8 * base.slice;
-    return harc_ring_reserve(c, 16 * base.slice, "quality");
-}
-int qp_context(const harc_amd_params *params, int L, harc_amd_ctx **c)
-{
-    harc_amd_params P = *params;
-    if (harc_amd_default_params(L, &P) != HARC_AMD_OK) return HARC_AMD_EINVAL;
-    P.device = params->device;
-    return harc_amd_create(&P, c);
-}
-}
-
 extern "C" int harc_amd_qpack_files(const harc_amd_params *params, const char *quality_path, const char *out_path)
 {
     if (!params || !quality_path || !out_path) { harc_set_error("qpack_files: bad arguments"); return HARC_AMD_EINVAL; }
     uint64_t qsz = 0;
-    if (!qp_file_size(quality_path, &qsz)) { harc_set_error("cannot open %s", quality_path); return HARC_AMD_EIO; }
-    QpOutGuard outguard{ out_path };
+    if (!file_size(quality_path, &qsz)) { harc_set_error("cannot open %s", quality_path); return HARC_AMD_EIO; }
+    OutFileGuard outguard{ out_path };
     // the read length is the length of the first line; everything about the sizes follows from it, before a device is touched
     uint32_t L = 1;
-    if (qsz) {
-        char head[257];
-        FILE *f = fopen(quality_path, "rb");
-        if (!f) { harc_set_error("cannot open %s", quality_path); return HARC_AMD_EIO; }
-        const size_t got = fread(head, 1, sizeof head, f);
-        fclose(f);
-        size_t nl = 0;
-        while (nl < got && head[nl] != '\n') nl++;
-        if (nl > 255 || (nl == got && got == sizeof head)) { harc_set_error("qpack_files: the first line of %s is longer than 255 characters", quality_path); return HARC_AMD_EINVAL; }
-        if (nl == 0) { harc_set_error("qpack_files: the first line of %s is empty", quality_path); return HARC_AMD_EINVAL; }
-        L = (uint32_t)nl;
-    }
+    if (qsz) RC_TRY(first_line_length(quality_path, "qpack_files", &L));
     const uint64_t LL = L + 1ull;
     if (qsz % LL) { harc_set_error("qpack_files: %s holds %llu bytes, no multiple of the %llu bytes of a line of %u quality values and its newline", quality_path, (unsigned long long)qsz, (unsigned long long)LL, L); return HARC_AMD_EINVAL; }
     const uint64_t n = qsz / LL;
-    uint32_t rb = (uint32_t)qp_env_u64("HARC_AMD_QPACK_BLOCK", 0);
+    uint32_t rb = (uint32_t)env_u64("HARC_AMD_QPACK_BLOCK", 0);
     RC_TRY(qp_check_geometry("qpack_files", (int32_t)L, &rb));
-    const uint64_t piece_blocks = qp_env_u64("HARC_AMD_QPACK_PIECE", 64), piece_lines = piece_blocks * rb, nb = qv_blocks(n, rb);
-    harc_amd_ctx *c = nullptr;
-    RC_TRY(qp_context(params, (int)L, &c));
-    QpCtxGuard guard{ c };
-    RingGeom gf, gd;
-    RC_TRY(qp_ring(c, &gf, &gd));
-    QpBuf txt{ c }, out{ c };
+    const uint64_t piece_blocks = env_u64(QV_FORMAT.piece_env, QV_FORMAT.piece_default), piece_lines = piece_blocks * rb, nb = qv_blocks(n, rb);
+    CtxGuard guard;
+    RC_TRY(side_context(params, (int)L, &guard.c));
+    harc_amd_ctx *c = guard.c;
+    RingGeom g[2];                                                // the feeder's and the drain's
+    RC_TRY(ring_split(c, 2, 8, QV_FORMAT.ring, g));
+    DevBuf txt{ c }, out{ c };
     const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
     double t_read = 0, t_write = 0;
     QpStats st;
@@ -514,16 +421,16 @@ extern "C" int harc_amd_qpack_files(const harc_amd_params *params, const char *q
     uint64_t at = QV_FILE_HEADER; int npieces = 0;
     {
         FileDrain drain(c);
-        RC_TRY(drain.start(out_path, (size_t)(n ? qv_bound(n, L, rb) : QV_FILE_HEADER), &gd, true));
+        RC_TRY(drain.start(out_path, (size_t)(n ? qv_bound(n, L, rb) : QV_FILE_HEADER), &g[1], true));
         RC_TRY(drain.put_host(h, QV_FILE_HEADER, 0));
         std::vector<std::pair<uint64_t, uint64_t>> pieces;
         for (uint64_t a = 0; a < n; a += piece_lines) pieces.emplace_back(a * LL, (n - a < piece_lines ? n : a + piece_lines) * LL);
         FileFeeder feed(c, quality_path);
-        if (!pieces.empty()) RC_TRY(feed.start(pieces, gf));
+        if (!pieces.empty()) RC_TRY(feed.start(pieces, g[0]));
         for (size_t p = 0; p < pieces.size(); p++) {
             const uint64_t bytes = pieces[p].second - pieces[p].first, m = bytes / LL;
-            RC_TRY(qp_reserve(&txt, (size_t)bytes));
-            RC_TRY(qp_reserve(&out, (size_t)(qv_bound(m, L, rb) - QV_FILE_HEADER)));
+            RC_TRY(dev_reserve(&txt, (size_t)bytes));
+            RC_TRY(dev_reserve(&out, (size_t)(qv_bound(m, L, rb) - QV_FILE_HEADER)));
             { const double t0 = mono_now(); RC_TRY(feed.upload_piece(p, txt.p, nullptr)); t_read += mono_now() - t0; }
             uint64_t nblk = 0;
             RC_TRY(harc_qpack_run(c, txt.p, m, L, rb, (uint8_t *)out.p, out.cap, &nblk, &st));
@@ -541,69 +448,5 @@ extern "C" int harc_amd_qpack_files(const harc_amd_params *params, const char *q
 
 extern "C" int harc_amd_qunpack_files(const harc_amd_params *params, const char *packed_path, const char *out_path)
 {
-    if (!params || !packed_path || !out_path) { harc_set_error("qunpack_files: bad arguments"); return HARC_AMD_EINVAL; }
-    uint64_t fsz = 0;
-    if (!qp_file_size(packed_path, &fsz)) { harc_set_error("cannot open %s", packed_path); return HARC_AMD_EIO; }
-    QpOutGuard outguard{ out_path };
-    if (fsz < QV_FILE_HEADER) { harc_set_error("qunpack_files: %s holds %llu bytes, fewer than the %u of the header", packed_path, (unsigned long long)fsz, QV_FILE_HEADER); return HARC_AMD_EINVAL; }
-    const int fd = open(packed_path, O_RDONLY);
-    if (fd < 0) { harc_set_error("cannot open %s", packed_path); return HARC_AMD_EIO; }
-    struct FdGuard { int fd; ~FdGuard() { close(fd); } } fdguard{ fd };
-    uint8_t h[QV_FILE_HEADER];
-    if (pread(fd, h, QV_FILE_HEADER, 0) != (ssize_t)QV_FILE_HEADER) { harc_set_error("cannot read %s", packed_path); return HARC_AMD_EIO; }
-    QvHeader H;
-    RC_TRY(qp_parse_header("qunpack_files", h, fsz, &H));
-    // the block offsets, from the prefixes: known, and inside the file, before a device is touched
-    std::vector<uint64_t> off((size_t)H.nb + 1);
-    uint64_t at = QV_FILE_HEADER;
-    for (uint64_t b = 0; b < H.nb; b++) {
-        off[b] = at;
-        uint8_t q[4];
-        if (fsz - at < 4) { harc_set_error("qunpack_files: block %llu at byte %llu leaves the %llu bytes of %s", (unsigned long long)b, (unsigned long long)at, (unsigned long long)fsz, packed_path); return HARC_AMD_EINVAL; }
-        if (pread(fd, q, 4, (off_t)at) != 4) { harc_set_error("cannot read %s", packed_path); return HARC_AMD_EIO; }
-        const uint64_t pb = qv_le32(q);
-        if (pb == 0 || fsz - at - 4 < pb) { harc_set_error("qunpack_files: block %llu at byte %llu leaves the %llu bytes of %s", (unsigned long long)b, (unsigned long long)at, (unsigned long long)fsz, packed_path); return HARC_AMD_EINVAL; }
-        at += 4 + pb;
-    }
-    off[H.nb] = at;
-    if (at != fsz) { harc_set_error("qunpack_files: the blocks of %s end at byte %llu, the file holds %llu", packed_path, (unsigned long long)at, (unsigned long long)fsz); return HARC_AMD_EINVAL; }
-    const uint64_t LL = H.L + 1ull, out_size = H.n * LL;
-    harc_amd_ctx *c = nullptr;
-    RC_TRY(qp_context(params, H.n ? (int)H.L : 100, &c));
-    QpCtxGuard guard{ c };
-    RingGeom gf, gd;
-    RC_TRY(qp_ring(c, &gf, &gd));
-    QpBuf pk{ c }, txt{ c }, doff{ c };
-    const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
-    double t_read = 0, t_write = 0, t_kernel = 0;
-    const uint64_t piece_blocks = qp_env_u64("HARC_AMD_QPACK_PIECE", 64);
-    int npieces = 0;
-    {
-        FileDrain drain(c);
-        RC_TRY(drain.start(out_path, (size_t)out_size, &gd, true));
-        std::vector<std::pair<uint64_t, uint64_t>> pieces;
-        for (uint64_t b = 0; b < H.nb; b += piece_blocks) pieces.emplace_back(off[b], off[H.nb - b < piece_blocks ? H.nb : b + piece_blocks]);
-        FileFeeder feed(c, packed_path);
-        if (!pieces.empty()) RC_TRY(feed.start(pieces, gf));
-        std::vector<uint64_t> rel;
-        for (size_t p = 0; p < pieces.size(); p++) {
-            const uint64_t b0 = p * piece_blocks, b1 = H.nb - b0 < piece_blocks ? H.nb : b0 + piece_blocks, bytes = pieces[p].second - pieces[p].first;
-            const uint64_t line0 = b0 * H.rb, m = (b1 == H.nb ? H.n : b1 * H.rb) - line0;
-            RC_TRY(qp_reserve(&pk, (size_t)bytes)); RC_TRY(qp_reserve(&txt, (size_t)(m * LL))); RC_TRY(qp_reserve(&doff, 8 * (size_t)(b1 - b0 + 1)));
-            { const double t0 = mono_now(); RC_TRY(feed.upload_piece(p, pk.p, nullptr)); t_read += mono_now() - t0; }
-            rel.resize((size_t)(b1 - b0 + 1));
-            for (uint64_t b = b0; b <= b1; b++) rel[(size_t)(b - b0)] = off[b] - off[b0];
-            HIP_TRY(hipMemcpyAsync(doff.p, rel.data(), 8 * rel.size(), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            { const double t0 = mono_now(); RC_TRY(harc_qunpack_run(c, (const uint8_t *)pk.p, (const uint64_t *)doff.p, rel.data(), (uint32_t)(b1 - b0), m, H.L, H.rb, txt.p, b0, off[b0])); t_kernel += mono_now() - t0; }
-            { const double t0 = mono_now(); RC_TRY(drain.put(txt.p, (size_t)(m * LL), line0 * LL)); t_write += mono_now() - t0; }
-            npieces++;
-        }
-        drain.set_final_size(out_size);
-        { const double t0 = mono_now(); RC_TRY(drain.finish()); t_write += mono_now() - t0; }
-    }
-    if (tlog) fprintf(stderr, "[qpack] unpacked %llu bytes of text from %llu bytes in %llu blocks, %d pieces: %.3f s in the kernels, %.3f s waiting for the readers, %.3f s waiting for the writers\n",
-                      (unsigned long long)out_size, (unsigned long long)fsz, (unsigned long long)H.nb, npieces, t_kernel, t_read, t_write);
-    outguard.ok = true;
-    return HARC_AMD_OK;
+    return pack_unpack_files(QV_FORMAT, params, packed_path, out_path);
 }

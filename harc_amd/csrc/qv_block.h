@@ -192,6 +192,15 @@ QV_HD int qv_in_alphabet(uint32_t v) { return v - QV_FIRST < QV_MAXA; }
 // a block whose bytes all lie in 33..126 is coded when that is smaller
 QV_HD int qv_use_coded(uint32_t A, uint32_t strand_bytes, uint32_t m, uint32_t L) { return qv_hdr1(A) + strand_bytes < 1u + m * L; }
 
+// The prefix of a block, u32 payload_bytes, at q with `left` bytes of the packed form from q on (fewer than QV_PREFIX: none of q is read): -> 1 with the size of a
+// payload that is not empty and fits what is left behind the prefix, or 0
+#define QV_PREFIX 4u
+QV_HD int qv_prefix(const uint8_t *q, uint64_t left, uint64_t *payload_bytes)
+{
+    if (left < QV_PREFIX) return 0;
+    *payload_bytes = qv_le32(q);
+    return *payload_bytes >= 1 && *payload_bytes <= left - QV_PREFIX;
+}
 // the head of a payload of pbytes bytes for m lines of L: -> QV_OK with *mode, and for mode 1 *A and bm[3]
 QV_HD int qv_check_head(const uint8_t *pl, uint32_t pbytes, uint32_t m, uint32_t L, uint32_t *mode, uint32_t *A, uint32_t *bm)
 {

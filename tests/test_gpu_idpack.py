@@ -206,6 +206,31 @@ def test_file_calls_are_a_function_of_the_text_and_the_block_size_alone(tmp_path
     assert (tmp_path / "e.back").read_bytes() == b""
 
 
+def test_a_damaged_block_of_a_later_piece_is_named_by_its_number_and_byte_in_the_file(tmp_path, monkeypatch):
+    """three blocks in three pieces, the mode byte of the last set to 2 (refused by rule): the file call and the host twin name block 2 and its byte in the file"""
+    import harc_amd
+    text = ic.text(list(ic.illumina_ids()[:700]))
+    bad = bytearray(harc_amd.idpack_host(text, 300))
+    off, at = [], 32                                               # the blocks behind the 32-byte header, by their u32 payload sizes
+    while at < len(bad):
+        off.append(at)
+        at += 4 + int.from_bytes(bad[at:at + 4], "little")
+    assert at == len(bad) and len(off) == 3
+    bad[off[2] + 4] = 2                                            # the first byte of the payload
+    monkeypatch.setenv("HARC_AMD_IDPACK_BLOCK", "300")
+    monkeypatch.setenv("HARC_AMD_IDPACK_PIECE", "1")
+    monkeypatch.setenv("HARC_AMD_FEED_SLICE", "4096")
+    (tmp_path / "bad.packed").write_bytes(bytes(bad))
+    back = tmp_path / "bad.back"
+    with pytest.raises(harc_amd.HarcAmdError) as e:
+        harc_amd.idunpack_files(str(tmp_path / "bad.packed"), str(back))
+    with pytest.raises(harc_amd.HarcAmdError) as eh:
+        harc_amd.idunpack_host(bytes(bad))
+    for err in (e.value, eh.value):
+        assert err.code == EINVAL and "block 2 " in str(err) and "byte %d " % off[2] in str(err) and "is damaged" in str(err), str(err)
+    assert not back.exists()
+
+
 # ------------------------------------------------------------------------------------------------ ./harc
 def _harc(args, env):
     return subprocess.run([os.path.join(ROOT, "harc")] + args, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

@@ -70,12 +70,13 @@ static inline int last_byte_is_newline(const char *path, bool *yes)
 struct OutFileGuard { std::string path; bool ok = false; ~OutFileGuard() { if (!ok) (void)remove(path.c_str()); } };
 struct CtxGuard { harc_amd_ctx *c = nullptr; ~CtxGuard() { harc_amd_destroy(c); } };
 static inline uint64_t env_u64(const char *name, uint64_t dflt) { if (const char *e = getenv(name)) { const unsigned long long v = strtoull(e, nullptr, 10); if (v >= 1) return v; } return dflt; }
-// a context of its own for a call on side files: the default parameters of read length L over *params, the caller's device kept
-static inline int side_context(const harc_amd_params *params, int L, harc_amd_ctx **c)
+// a context of its own for a call on side files: the default parameters of read length L over *params, the caller's device kept; num_thr: the shards of an archive
+static inline int side_context(const harc_amd_params *params, int L, harc_amd_ctx **c, int num_thr = 0)
 {
     harc_amd_params P = *params;
     if (harc_amd_default_params(L, &P) != HARC_AMD_OK) return HARC_AMD_EINVAL;
     P.device = params->device;
+    if (num_thr) P.num_thr = num_thr;
     return harc_amd_create(&P, c);
 }
 // The context's ONE pinned ring in `parts` disjoint parts of `slices_each` slices, out[0 .. parts), for movers that are alive at the same time; the host threads are

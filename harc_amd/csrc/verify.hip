@@ -7,16 +7,6 @@
 // xored: an order-independent signature of the decoded multiset that is compared with the same signature of the input reads.
 #include "devutil.h"
 #include "fileio.h"
-#include <string>
-#include <stdlib.h>
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-#include <condition_variable>
-#include <deque>
-#include <mutex>
-#include <thread>
 
 __device__ __forceinline__ uint64_t read_hash_step(uint64_t h, int code) { return (h ^ (uint64_t)code) * 1099511628211ULL; }   // FNV-1a over codes A0 C1 G2 T3 N4
 #define READ_HASH_INIT 1469598103934665603ULL
@@ -65,35 +55,47 @@ __global__ void k_nl_positions(const uint8_t *noise, const uint32_t *rank, uint6
     const uint64_t i = harc_gid();
     if (i < n && noise[i] == '\n') nlpos[rank[i]] = i;
 }
-// one thread per read of a shard: decode, hash
+// Read i of a shard into buf[0 .. L) as codes A0 C1 G2 T3 N4, in the direction of the consensus; *rev: the read is its reverse complement (decoder.cpp:109-129).
+// false: the read's span does not lie inside the consensus stream, nothing was decoded.  That, a mismatch position outside the read and a noise code outside
+// '0'..'3' are each counted into *err: the host refuses the archive.  nlpos[i] and the noisepos bytes of the read exist because the host has checked the line
+// count of `noise` and the length of `noisepos` before the launch (shard_prepare).
+__device__ __forceinline__ bool decode_read(const uint8_t *seqb, uint64_t seqlen, const uint64_t *possum, const uint8_t *noise, const uint8_t *noisepos,
+                                            const uint64_t *nlpos, const uint8_t *revb, uint64_t nrevb, const uint8_t *revtail, uint32_t i, int L,
+                                            uint8_t *buf, bool *rev, bool *hasN, unsigned int *err)
+{
+    const uint64_t start = possum[i] - (uint64_t)L;                           // decoder.cpp:93-98
+    if (possum[i] < (uint64_t)L || start + L > seqlen) { atomicAdd(err, 1u); return false; }
+    for (int j = 0; j < L; j++) buf[j] = seqb[start + j];
+    const uint64_t n0 = i ? nlpos[i - 1] + 1 : 0, n1 = nlpos[i];
+    uint64_t np = n0 - i;                                                     // noisepos bytes consumed by earlier reads
+    int p = 0; bool anyN = false;
+    for (uint64_t k = n0; k < n1; k++) {                                      // decoder.cpp:100-108
+        if (p < L) p += noisepos[np];                                         // (a position past the read stays there: p never exceeds L + 254, buf is never indexed with it)
+        np++;
+        const int code = noise[k] - '0';
+        if (p >= L || (unsigned)code > 3u) { atomicAdd(err, 1u); continue; }
+        const int ref = buf[p] & 3;
+        // dec_noise (decoder.cpp setglobalarrays): A:{C,G,T,N} C:{A,G,T,N} G:{T,A,C,N} T:{G,C,A,N}
+        const unsigned tab = ref == 0 ? 0x4321u : ref == 1 ? 0x4320u : ref == 2 ? 0x4103u : 0x4012u;
+        buf[p] = (uint8_t)((tab >> (4 * code)) & 0xF); anyN |= buf[p] == 4;
+    }
+    *rev = i < 8 * nrevb ? ((revb[i >> 3] >> (i & 7)) & 1) : (revtail[i - 8 * nrevb] == 'r');
+    *hasN = anyN;
+    return true;
+}
+// one thread per read of a shard: decode, hash; a read that could not be decoded is left out of the signature
 __global__ void k_decode_sig(const uint8_t *seqb, uint64_t seqlen, const uint64_t *possum, const uint8_t *noise, const uint8_t *noisepos,
                              const uint64_t *nlpos, const uint8_t *revb, uint64_t nrevb, const uint8_t *revtail, uint32_t n, int L,
                              unsigned long long *sig, unsigned int *err)
 {
     const uint32_t i = harc_gid32();
     uint64_t h = READ_HASH_INIT;
-    bool ok = i < n;
+    uint8_t buf[256]; bool rev = false, hasN;
+    const bool ok = i < n && decode_read(seqb, seqlen, possum, noise, noisepos, nlpos, revb, nrevb, revtail, i, L, buf, &rev, &hasN, err);
     if (ok) {
-        const uint64_t start = possum[i] - (uint64_t)L;                       // decoder.cpp:93-98
-        if (possum[i] < (uint64_t)L || start + L > seqlen) { atomicAdd(err, 1u); ok = false; }
-        else {
-            uint8_t buf[256];
-            for (int j = 0; j < L; j++) buf[j] = seqb[start + j];
-            const uint64_t n0 = i ? nlpos[i - 1] + 1 : 0, n1 = nlpos[i];
-            uint64_t np = n0 - i;                                             // noisepos bytes consumed by earlier reads
-            int p = 0;
-            for (uint64_t k = n0; k < n1; k++) {                              // decoder.cpp:100-108
-                p += noisepos[np++];
-                const int ref = buf[p] & 3, code = noise[k] - '0';
-                // dec_noise (decoder.cpp setglobalarrays): A:{C,G,T,N} C:{A,G,T,N} G:{T,A,C,N} T:{G,C,A,N}
-                const unsigned tab = ref == 0 ? 0x4321u : ref == 1 ? 0x4320u : ref == 2 ? 0x4103u : 0x4012u;
-                if (p < L) buf[p] = (uint8_t)((tab >> (4 * code)) & 0xF); else atomicAdd(err, 1u);
-            }
-            const bool rev = i < 8 * nrevb ? ((revb[i >> 3] >> (i & 7)) & 1) : (revtail[i - 8 * nrevb] == 'r');
-            if (!rev) for (int j = 0; j < L; j++) h = read_hash_step(h, buf[j]);
-            else for (int j = L - 1; j >= 0; j--) h = read_hash_step(h, buf[j] == 4 ? 4 : 3 - buf[j]);   // decoder.cpp:109-129
-            h = mix64(h);
-        }
+        if (!rev) for (int j = 0; j < L; j++) h = read_hash_step(h, buf[j]);
+        else for (int j = L - 1; j >= 0; j--) h = read_hash_step(h, buf[j] == 4 ? 4 : 3 - buf[j]);   // decoder.cpp:109-129
+        h = mix64(h);
     }
     sig_accumulate(h, ok, sig);
 }
@@ -105,99 +107,7 @@ __global__ void k_sig_codes(const uint8_t *codes, uint32_t n, int L, unsigned lo
     if (i < n) { for (int j = 0; j < L; j++) h = read_hash_step(h, codes[(size_t)i * L + j]); h = mix64(h); }
     sig_accumulate(h, i < n, sig);
 }
-
-#define G256(n) harc_grid256((uint64_t)(n)), dim3(256), 0, c->stream
-
-static bool get_out(harc_amd_ctx *c, int id, int shard, const uint8_t **p, size_t *n)
-{
-    auto it = c->out.find(std::make_pair(id, shard));
-    if (it == c->out.end()) return false;
-    if (it->second.ptr) { *p = it->second.ptr; *n = it->second.len; } else { *p = it->second.own.data(); *n = it->second.own.size(); }
-    return true;
-}
-static int up(harc_amd_ctx *c, const uint8_t *h, size_t n, uint8_t **d)
-{
-    RC_TRY(dalloc(c, d, n + 16));
-    if (n) HIP_TRY(hipMemcpyAsync(*d, h, n, hipMemcpyHostToDevice, c->stream));
-    return HARC_AMD_OK;
-}
-
-extern "C" int harc_amd_reads_signature_device(harc_amd_ctx *c, const char *d_ascii, uint32_t n, uint32_t stride, uint64_t *sig3)
-{
-    if (!c || !sig3 || (n && !d_ascii) || stride < (uint32_t)c->P.readlen) return HARC_AMD_EINVAL;
-    HIP_TRY(hipSetDevice(c->P.device));
-    const harc_mark_t mk = harc_pool_mark(c);
-    unsigned long long *d_sig = nullptr; RC_TRY(dalloc(c, &d_sig, 4));
-    HIP_TRY(hipMemsetAsync(d_sig, 0, 32, c->stream));
-    if (n) hipLaunchKernelGGL(k_sig_ascii, G256(n), d_ascii, n, stride, c->P.readlen, d_sig);
-    HIP_TRY(hipMemcpyAsync(sig3, d_sig, 24, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    harc_pool_release(c, mk);
-    return HARC_AMD_OK;
-}
-
-extern "C" int harc_amd_decode_signature(harc_amd_ctx *c, uint64_t *sig3)
-{
-    if (!c || !sig3) return HARC_AMD_EINVAL;
-    if (!c->have_s2) { harc_set_error("harc_amd_decode_signature: encode first"); return HARC_AMD_ESTATE; }
-    HIP_TRY(hipSetDevice(c->P.device));
-    const int L = c->P.readlen;
-    const harc_mark_t mk0 = harc_pool_mark(c);
-    unsigned long long *d_sig = nullptr; unsigned int *d_err = nullptr;
-    RC_TRY(dalloc(c, &d_sig, 4)); RC_TRY(dalloc(c, &d_err, 4));
-    HIP_TRY(hipMemsetAsync(d_sig, 0, 32, c->stream)); HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
-    for (int e = 0; e < c->P.num_thr; e++) {
-        const uint8_t *seq, *seqt, *pos, *noise, *npz, *rev, *revt; size_t nseq, nseqt, npos, nnoise, nnp, nrev, nrevt;
-        if (!get_out(c, HARC_AMD_S2_SEQ, e, &seq, &nseq) || !get_out(c, HARC_AMD_S2_SEQ_TAIL, e, &seqt, &nseqt) || !get_out(c, HARC_AMD_S2_POS, e, &pos, &npos) ||
-            !get_out(c, HARC_AMD_S2_NOISE, e, &noise, &nnoise) || !get_out(c, HARC_AMD_S2_NOISEPOS, e, &npz, &nnp) ||
-            !get_out(c, HARC_AMD_S2_REV, e, &rev, &nrev) || !get_out(c, HARC_AMD_S2_REV_TAIL, e, &revt, &nrevt)) { harc_set_error("shard %d streams missing", e); return HARC_AMD_ESTATE; }
-        if (npos == 0) continue;
-        if (npos > 0xFFFFFFFFull || 8 * nrev + nrevt != npos) { harc_set_error("shard %d: rev stream does not match pos stream", e); return HARC_AMD_EIO; }
-        const harc_mark_t mk = harc_pool_mark(c);
-        const uint32_t n = (uint32_t)npos;
-        uint8_t *d_seq, *d_seqt, *d_pos, *d_noise, *d_np, *d_rev, *d_revt, *seqb; uint64_t *p64, *possum, *nlpos; uint32_t *fl, *rk;
-        RC_TRY(up(c, seq, nseq, &d_seq)); RC_TRY(up(c, seqt, nseqt, &d_seqt)); RC_TRY(up(c, pos, npos, &d_pos)); RC_TRY(up(c, noise, nnoise, &d_noise));
-        RC_TRY(up(c, npz, nnp, &d_np)); RC_TRY(up(c, rev, nrev, &d_rev)); RC_TRY(up(c, revt, nrevt, &d_revt));
-        const uint64_t seqlen = 4 * (uint64_t)nseq + nseqt;
-        RC_TRY(dalloc(c, &seqb, (size_t)seqlen + 16)); RC_TRY(dalloc(c, &p64, (size_t)n + 1)); RC_TRY(dalloc(c, &possum, (size_t)n + 1));
-        RC_TRY(dalloc(c, &nlpos, (size_t)n + 1)); RC_TRY(dalloc(c, &fl, nnoise + 1)); RC_TRY(dalloc(c, &rk, nnoise + 1));
-        if (seqlen) hipLaunchKernelGGL(k_unpack_seq, G256(seqlen), d_seq, (uint64_t)nseq, d_seqt, (uint64_t)nseqt, seqb);
-        hipLaunchKernelGGL(k_pos_to_u64, G256(n), d_pos, n, p64);
-        RC_TRY(prim_incl_scan_u64(c, p64, possum, n));
-        if (nnoise) {
-            hipLaunchKernelGGL(k_nl_flags, G256(nnoise), d_noise, (uint64_t)nnoise, fl);
-            RC_TRY(prim_excl_scan_u32(c, fl, rk, nnoise));
-            hipLaunchKernelGGL(k_nl_positions, G256(nnoise), d_noise, rk, (uint64_t)nnoise, nlpos);
-        }
-        hipLaunchKernelGGL(k_decode_sig, G256(n), seqb, seqlen, possum, d_noise, d_np, nlpos, d_rev, (uint64_t)nrev, d_revt, n, L, d_sig, d_err);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        harc_pool_release(c, mk);
-    }
-    {   // unaligned singletons and unaligned N reads (decoder.cpp:148-169)
-        const uint8_t *sg, *sgt, *nt; size_t nsg, nsgt, nnt;
-        if (!get_out(c, HARC_AMD_S2_SINGLETON, 0, &sg, &nsg) || !get_out(c, HARC_AMD_S2_SINGLETON_TAIL, 0, &sgt, &nsgt) || !get_out(c, HARC_AMD_S2_INPUT_N, 0, &nt, &nnt)) {
-            harc_set_error("singleton streams missing"); return HARC_AMD_ESTATE;
-        }
-        const uint64_t nb = 4 * (uint64_t)nsg + nsgt;
-        uint8_t *d_sg, *d_sgt, *codes, *d_nt;
-        RC_TRY(up(c, sg, nsg, &d_sg)); RC_TRY(up(c, sgt, nsgt, &d_sgt)); RC_TRY(up(c, nt, nnt, &d_nt)); RC_TRY(dalloc(c, &codes, (size_t)nb + 16));
-        if (nb) hipLaunchKernelGGL(k_unpack_seq, G256(nb), d_sg, (uint64_t)nsg, d_sgt, (uint64_t)nsgt, codes);
-        const uint32_t ns = (uint32_t)(nb / L), nn = (uint32_t)(nnt / (L + 1));
-        if (ns) hipLaunchKernelGGL(k_sig_codes, G256(ns), codes, ns, L, d_sig);
-        if (nn) hipLaunchKernelGGL(k_sig_ascii, G256(nn), (const char *)d_nt, nn, (uint32_t)L + 1, L, d_sig);
-    }
-    unsigned int err = 0;
-    HIP_TRY(hipMemcpyAsync(sig3, d_sig, 24, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    harc_pool_release(c, mk0);
-    if (err) { harc_set_error("decode: %u reads with inconsistent pos/noise streams", err); return HARC_AMD_EIO; }
-    return HARC_AMD_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ decoder.out drop-in (non -p)
-// Same decode as k_decode_sig, but the read is written as a text line into tmp[i] and flagged when it contains N
+// the two file decoders: the same decode as k_decode_sig, but the read is written as a text line into tmp[i] and flagged when it contains N
 // (decoder.cpp:110-129 routes those to a separate file that is appended after the singletons, :141-169).
 __global__ void k_decode_text(const uint8_t *seqb, uint64_t seqlen, const uint64_t *possum, const uint8_t *noise, const uint8_t *noisepos,
                               const uint64_t *nlpos, const uint8_t *revb, uint64_t nrevb, const uint8_t *revtail, uint32_t n, int L,
@@ -205,21 +115,11 @@ __global__ void k_decode_text(const uint8_t *seqb, uint64_t seqlen, const uint64
 {
     const uint32_t i = harc_gid32();
     if (i >= n) return;
-    const uint64_t start = possum[i] - (uint64_t)L;
     char *o = tmp + (size_t)i * (L + 1);
-    if (possum[i] < (uint64_t)L || start + L > seqlen) { atomicAdd(err, 1u); isN[i] = 0; for (int j = 0; j < L; j++) o[j] = 'A'; o[L] = '\n'; return; }
-    uint8_t buf[256];
-    for (int j = 0; j < L; j++) buf[j] = seqb[start + j];
-    const uint64_t n0 = i ? nlpos[i - 1] + 1 : 0, n1 = nlpos[i];
-    uint64_t np = n0 - i;
-    int p = 0; bool hasN = false;
-    for (uint64_t k = n0; k < n1; k++) {
-        p += noisepos[np++];
-        const int ref = buf[p < L ? p : 0] & 3, code = noise[k] - '0';
-        const unsigned tab = ref == 0 ? 0x4321u : ref == 1 ? 0x4320u : ref == 2 ? 0x4103u : 0x4012u;
-        if (p < L) { buf[p] = (uint8_t)((tab >> (4 * code)) & 0xF); hasN |= buf[p] == 4; } else atomicAdd(err, 1u);
+    uint8_t buf[256]; bool rev, hasN;
+    if (!decode_read(seqb, seqlen, possum, noise, noisepos, nlpos, revb, nrevb, revtail, i, L, buf, &rev, &hasN, err)) {
+        isN[i] = 0; for (int j = 0; j < L; j++) o[j] = 'A'; o[L] = '\n'; return;       // a line all the same: the host refuses the archive (*err)
     }
-    const bool rev = i < 8 * nrevb ? ((revb[i >> 3] >> (i & 7)) & 1) : (revtail[i - 8 * nrevb] == 'r');
     if (!rev) for (int j = 0; j < L; j++) o[j] = "ACGTN"[buf[j]];
     else for (int j = 0; j < L; j++) { const int b = buf[L - 1 - j]; o[j] = "ACGTN"[b == 4 ? 4 : 3 - b]; }
     o[L] = '\n';
@@ -244,6 +144,18 @@ __global__ void k_codes_to_lines(const uint8_t *codes, uint32_t n, int L, char *
     out[gid] = j == (uint32_t)L ? '\n' : "ACGT"[codes[(uint64_t)i * L + j] & 3];
 }
 
+#define G256(n) harc_grid256((uint64_t)(n)), dim3(256), 0, c->stream
+
+// ------------------------------------------------------------------------------------------------ one shard: its streams, on the device, as lines
+struct View { const uint8_t *p = nullptr; size_t n = 0; };        // host memory somebody else owns
+static View view_of(const std::vector<uint8_t> &v) { return View{ v.data(), v.size() }; }
+static bool get_out(harc_amd_ctx *c, int id, int shard, View *v)
+{
+    auto it = c->out.find(std::make_pair(id, shard));
+    if (it == c->out.end()) return false;
+    *v = it->second.ptr ? View{ it->second.ptr, it->second.len } : view_of(it->second.own);
+    return true;
+}
 static bool slurp_file(const std::string &path, std::vector<uint8_t> &out)
 {
     out.clear();
@@ -255,102 +167,223 @@ static bool slurp_file(const std::string &path, std::vector<uint8_t> &out)
     fclose(f);
     return ok;
 }
+static int up(harc_amd_ctx *c, View h, uint8_t **d)
+{
+    RC_TRY(dalloc(c, d, h.n + 16));
+    if (h.n) HIP_TRY(hipMemcpyAsync(*d, h.p, h.n, hipMemcpyHostToDevice, c->stream));
+    return HARC_AMD_OK;
+}
 
-static size_t file_size_or_zero(const std::string &path) { struct stat st; return stat(path.c_str(), &st) == 0 ? (size_t)st.st_size : 0; }
+// the seven streams of a shard, out of the context that has just encoded them or out of output/read_*.txt.<e>
+enum { S_SEQ, S_SEQ_TAIL, S_POS, S_NOISE, S_NOISEPOS, S_REV, S_REV_TAIL, S_COUNT };
+struct ShardStreams { View v[S_COUNT]; std::vector<uint8_t> own[S_COUNT]; };      // own: what streams_from_files read
+static int streams_from_context(harc_amd_ctx *c, int e, ShardStreams *s)
+{
+    static const int id[S_COUNT] = { HARC_AMD_S2_SEQ, HARC_AMD_S2_SEQ_TAIL, HARC_AMD_S2_POS, HARC_AMD_S2_NOISE, HARC_AMD_S2_NOISEPOS, HARC_AMD_S2_REV, HARC_AMD_S2_REV_TAIL };
+    for (int k = 0; k < S_COUNT; k++)
+        if (!get_out(c, id[k], e, &s->v[k])) { harc_set_error("shard %d streams missing", e); return HARC_AMD_ESTATE; }
+    return HARC_AMD_OK;
+}
+static int streams_from_files(const std::string &od, int e, ShardStreams *s)
+{
+    static const char *const stem[S_COUNT] = { "read_seq.txt", "read_seq.txt", "read_pos.txt", "read_noise.txt", "read_noisepos.txt", "read_rev.txt", "read_rev.txt" };
+    for (int k = 0; k < S_COUNT; k++) {
+        const bool tail = k == S_SEQ_TAIL || k == S_REV_TAIL;
+        if (!slurp_file(od + stem[k] + "." + std::to_string(e) + (tail ? ".tail" : ""), s->own[k])) { harc_set_error("shard %d: stream files missing", e); return HARC_AMD_EIO; }
+        s->v[k] = view_of(s->own[k]);
+    }
+    return HARC_AMD_OK;
+}
+
+// What the decode kernels read of a shard, in the order of their arguments.  n == 0: a shard without reads, nothing to decode
+struct ShardDev { uint8_t *seqb; uint64_t seqlen; uint64_t *possum; uint8_t *noise, *noisepos; uint64_t *nlpos; uint8_t *rev; uint64_t nrev; uint8_t *revtail; uint32_t n = 0; };
+#define SHARD_ARGS(d) (d).seqb, (d).seqlen, (d).possum, (d).noise, (d).noisepos, (d).nlpos, (d).rev, (d).nrev, (d).revtail, (d).n
+// The streams of shard e on the device: consensus unpacked to a code per byte, possum[i] = sum of the pos bytes up to read i, nlpos[i] = where the i-th '\n' of
+// read_noise sits.  The streams come from outside the program: that they announce the same number of reads three times over -- a pos byte, a rev bit or tail
+// byte and a line of read_noise per read, a read_noisepos byte for every other byte of read_noise -- is decided here, on the host, and the decode kernels are
+// launched behind it: they index nlpos by the read and read_noisepos by (bytes of read_noise in front of the read) - (lines in front of it).
+// Pool memory: the caller's PoolScope.  Synchronises the stream once
+static int shard_prepare(harc_amd_ctx *c, int e, const ShardStreams &s, ShardDev *d)
+{
+    const View &seq = s.v[S_SEQ], &seqt = s.v[S_SEQ_TAIL], &pos = s.v[S_POS], &noise = s.v[S_NOISE], &npz = s.v[S_NOISEPOS], &rev = s.v[S_REV], &revt = s.v[S_REV_TAIL];
+    d->n = 0;
+    if (pos.n == 0) return HARC_AMD_OK;
+    if (pos.n > 0xFFFFFFFFull || 8 * rev.n + revt.n != pos.n) { harc_set_error("shard %d: rev stream does not match pos stream", e); return HARC_AMD_EIO; }
+    const uint32_t n = (uint32_t)pos.n;
+    const size_t nnoise = noise.n;
+    uint8_t *d_seq, *d_seqt, *d_pos; uint64_t *p64; uint32_t *fl, *rk;
+    RC_TRY(up(c, seq, &d_seq)); RC_TRY(up(c, seqt, &d_seqt)); RC_TRY(up(c, pos, &d_pos)); RC_TRY(up(c, noise, &d->noise));
+    RC_TRY(up(c, npz, &d->noisepos)); RC_TRY(up(c, rev, &d->rev)); RC_TRY(up(c, revt, &d->revtail));
+    d->seqlen = 4 * (uint64_t)seq.n + seqt.n; d->nrev = rev.n;
+    RC_TRY(dalloc(c, &d->seqb, (size_t)d->seqlen + 16)); RC_TRY(dalloc(c, &p64, (size_t)n + 1)); RC_TRY(dalloc(c, &d->possum, (size_t)n + 1));
+    RC_TRY(dalloc(c, &d->nlpos, (size_t)n + 1)); RC_TRY(dalloc(c, &fl, nnoise + 1)); RC_TRY(dalloc(c, &rk, nnoise + 1));
+    hipLaunchKernelGGL(k_unpack_seq, G256(d->seqlen), d_seq, (uint64_t)seq.n, d_seqt, (uint64_t)seqt.n, d->seqb);
+    hipLaunchKernelGGL(k_pos_to_u64, G256(n), d_pos, n, p64);
+    RC_TRY(prim_incl_scan_u64(c, p64, d->possum, n));
+    // rank of every '\n' among the '\n's; one flag more, a zero, and its rank is their number
+    hipLaunchKernelGGL(k_nl_flags, G256(nnoise), d->noise, (uint64_t)nnoise, fl);
+    HIP_TRY(hipMemsetAsync(fl + nnoise, 0, 4, c->stream));
+    RC_TRY(prim_excl_scan_u32(c, fl, rk, nnoise + 1));
+    uint32_t lines = 0;
+    HIP_TRY(hipMemcpyAsync(&lines, rk + nnoise, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (lines != n) { harc_set_error("shard %d: read_noise holds %u lines, read_pos %u reads", e, lines, n); return HARC_AMD_EIO; }
+    if (npz.n != nnoise - n) { harc_set_error("shard %d: read_noisepos holds %zu bytes, read_noise announces %zu", e, npz.n, nnoise - n); return HARC_AMD_EIO; }
+    hipLaunchKernelGGL(k_nl_positions, G256(nnoise), d->noise, rk, (uint64_t)nnoise, d->nlpos);         // (n lines: every nlpos[0 .. n) is written, none beyond)
+    HIP_TRY(hipGetLastError());
+    d->n = n;
+    return HARC_AMD_OK;
+}
+
+// A prepared shard as text, for the two file decoders: nA lines without N in outA and nN lines with N in outN, each in stream order (decoder.cpp:110-129 routes
+// the reads with N to a file of their own).  Pool memory: the caller's PoolScope.  The stream has been synchronised on return
+struct ShardLines { char *outA, *outN; uint32_t nA, nN; };
+static int shard_to_lines(harc_amd_ctx *c, const ShardDev &d, int L, unsigned int *d_err, ShardLines *out)
+{
+    const uint32_t n = d.n; const size_t LL = (size_t)L + 1;
+    uint32_t *isN, *rkN; char *tmp;
+    RC_TRY(dalloc(c, &isN, (size_t)n + 1)); RC_TRY(dalloc(c, &rkN, (size_t)n + 1));
+    RC_TRY(dalloc(c, &tmp, (size_t)n * LL + 16)); RC_TRY(dalloc(c, &out->outA, (size_t)n * LL + 16)); RC_TRY(dalloc(c, &out->outN, (size_t)n * LL + 16));
+    HIP_TRY(hipMemsetAsync(isN, 0, ((size_t)n + 1) * 4, c->stream));
+    hipLaunchKernelGGL(k_decode_text, G256(n), SHARD_ARGS(d), L, tmp, isN, d_err);
+    RC_TRY(prim_excl_scan_u32(c, isN, rkN, (size_t)n + 1));
+    hipLaunchKernelGGL(k_split_lines, G256((uint64_t)n * LL), tmp, isN, rkN, n, L, out->outA, out->outN);
+    HIP_TRY(hipMemcpyAsync(&out->nN, rkN + n, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    out->nA = n - out->nN;
+    return HARC_AMD_OK;
+}
+
+// unaligned singletons, 2-bit packed + ASCII tail, L bases each (decoder.cpp:148-158): *ns of them as a code per byte, and as text lines when `lines` is given
+static int singletons_unpack(harc_amd_ctx *c, View sg, View sgt, int L, uint32_t *ns, uint8_t **codes, char **lines)
+{
+    const uint64_t nb = 4 * (uint64_t)sg.n + sgt.n;
+    *ns = (uint32_t)(nb / L);
+    if (!*ns) return HARC_AMD_OK;
+    uint8_t *d_sg, *d_sgt;
+    RC_TRY(up(c, sg, &d_sg)); RC_TRY(up(c, sgt, &d_sgt)); RC_TRY(dalloc(c, codes, (size_t)nb + 16));
+    hipLaunchKernelGGL(k_unpack_seq, G256(nb), d_sg, (uint64_t)sg.n, d_sgt, (uint64_t)sgt.n, *codes);
+    if (lines) {
+        RC_TRY(dalloc(c, lines, (size_t)*ns * (L + 1) + 16));
+        hipLaunchKernelGGL(k_codes_to_lines, G256((uint64_t)*ns * (L + 1)), *codes, *ns, L, *lines);
+    }
+    return HARC_AMD_OK;
+}
+
+// the archive under <basedir>/output/ for one of the two file decoders: read length out of read_meta.txt (getDataParams, decoder.cpp:324-333), a context of its own
+static int open_archive(const harc_amd_params *params, const char *basedir, int32_t num_thr_e, std::string *od, int *L, harc_amd_ctx **c)
+{
+    if (!params || !basedir || num_thr_e < 1) return HARC_AMD_EINVAL;
+    *od = std::string(basedir) + "/output/";
+    std::vector<uint8_t> meta;
+    if (!slurp_file(*od + "read_meta.txt", meta)) { harc_set_error("cannot read %sread_meta.txt", od->c_str()); return HARC_AMD_EIO; }
+    meta.push_back(0);
+    *L = atoi((const char *)meta.data());
+    return side_context(params, *L, c, num_thr_e);
+}
+
+extern "C" int harc_amd_reads_signature_device(harc_amd_ctx *c, const char *d_ascii, uint32_t n, uint32_t stride, uint64_t *sig3)
+{
+    if (!c || !sig3 || (n && !d_ascii) || stride < (uint32_t)c->P.readlen) return HARC_AMD_EINVAL;
+    HIP_TRY(hipSetDevice(c->P.device));
+    PoolScope scope(c);
+    unsigned long long *d_sig = nullptr; RC_TRY(dalloc(c, &d_sig, 4));
+    HIP_TRY(hipMemsetAsync(d_sig, 0, 32, c->stream));
+    if (n) hipLaunchKernelGGL(k_sig_ascii, G256(n), d_ascii, n, stride, c->P.readlen, d_sig);
+    HIP_TRY(hipMemcpyAsync(sig3, d_sig, 24, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return HARC_AMD_OK;
+}
+
+extern "C" int harc_amd_decode_signature(harc_amd_ctx *c, uint64_t *sig3)
+{
+    if (!c || !sig3) return HARC_AMD_EINVAL;
+    if (!c->have_s2) { harc_set_error("harc_amd_decode_signature: encode first"); return HARC_AMD_ESTATE; }
+    HIP_TRY(hipSetDevice(c->P.device));
+    const int L = c->P.readlen;
+    PoolScope scope(c);                                            // the caller's context lives on: whatever way this call ends, the pool is as it found it
+    unsigned long long *d_sig = nullptr; unsigned int *d_err = nullptr;
+    RC_TRY(dalloc(c, &d_sig, 4)); RC_TRY(dalloc(c, &d_err, 4));
+    HIP_TRY(hipMemsetAsync(d_sig, 0, 32, c->stream)); HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
+    for (int e = 0; e < c->P.num_thr; e++) {
+        ShardStreams s; ShardDev d;
+        RC_TRY(streams_from_context(c, e, &s));
+        PoolScope shard(c);
+        RC_TRY(shard_prepare(c, e, s, &d));
+        if (!d.n) continue;
+        hipLaunchKernelGGL(k_decode_sig, G256(d.n), SHARD_ARGS(d), L, d_sig, d_err);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    {   // unaligned singletons and unaligned N reads (decoder.cpp:148-169)
+        View sg, sgt, nt;
+        if (!get_out(c, HARC_AMD_S2_SINGLETON, 0, &sg) || !get_out(c, HARC_AMD_S2_SINGLETON_TAIL, 0, &sgt) || !get_out(c, HARC_AMD_S2_INPUT_N, 0, &nt)) {
+            harc_set_error("singleton streams missing"); return HARC_AMD_ESTATE;
+        }
+        uint32_t ns = 0; uint8_t *codes = nullptr, *d_nt = nullptr;
+        RC_TRY(singletons_unpack(c, sg, sgt, L, &ns, &codes, nullptr));
+        if (ns) hipLaunchKernelGGL(k_sig_codes, G256(ns), codes, ns, L, d_sig);
+        const uint32_t nn = (uint32_t)(nt.n / (L + 1));
+        if (nn) {
+            RC_TRY(up(c, nt, &d_nt));
+            hipLaunchKernelGGL(k_sig_ascii, G256(nn), (const char *)d_nt, nn, (uint32_t)L + 1, L, d_sig);
+        }
+    }
+    unsigned int err = 0;
+    HIP_TRY(hipMemcpyAsync(sig3, d_sig, 24, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (err) { harc_set_error("decode: %u reads with inconsistent pos/noise streams", err); return HARC_AMD_EIO; }
+    return HARC_AMD_OK;
+}
 
 // decoder.out <basedir> <num_thr> <num_thr_e>  (src/decoder.cpp:44-172, harc:188): writes output/output.dna
 extern "C" int harc_amd_decoder_files(const harc_amd_params *params, const char *basedir, int32_t num_thr_e)
 {
-    if (!params || !basedir || num_thr_e < 1) return HARC_AMD_EINVAL;
-    const std::string od = std::string(basedir) + "/output/";
-    std::vector<uint8_t> meta;
-    if (!slurp_file(od + "read_meta.txt", meta)) { harc_set_error("cannot read %sread_meta.txt", od.c_str()); return HARC_AMD_EIO; }
-    meta.push_back(0);
-    const int L = atoi((const char *)meta.data());                              // getDataParams, decoder.cpp:324-333
-    harc_amd_params P = *params;
-    if (harc_amd_default_params(L, &P) != HARC_AMD_OK) return HARC_AMD_EINVAL;
-    P.device = params->device; P.num_thr = num_thr_e;
-    harc_amd_ctx *c = nullptr;
-    RC_TRY(harc_amd_create(&P, &c));
-    struct Guard { harc_amd_ctx *c; ~Guard() { harc_amd_destroy(c); } } guard{ c };
+    std::string od; int L = 0; CtxGuard guard;
+    RC_TRY(open_archive(params, basedir, num_thr_e, &od, &L, &guard.c));
+    harc_amd_ctx *c = guard.c;
     // output.dna holds one line per read: its length is known before a byte is decoded -- a read per byte of read_pos.txt.<e> (decoder.cpp:96), the singletons
     // (4 bases per byte + tail, :148-158), input_N.dna as it is (:166-168)
-    const size_t LLo = (size_t)L + 1;
-    size_t total_out = file_size_or_zero(od + "input_N.dna");
-    for (int e = 0; e < num_thr_e; e++) total_out += file_size_or_zero(od + "read_pos.txt." + std::to_string(e)) * LLo;
-    total_out += ((4 * file_size_or_zero(od + "read_singleton.txt") + file_size_or_zero(od + "read_singleton.txt.tail")) / (size_t)L) * LLo;
+    const size_t LL = (size_t)L + 1;
+    auto size_of = [&od](const std::string &name) { uint64_t n = 0; (void)file_size((od + name).c_str(), &n); return (size_t)n; };     // 0: no such regular file
+    size_t total_out = size_of("input_N.dna");
+    for (int e = 0; e < num_thr_e; e++) total_out += size_of("read_pos.txt." + std::to_string(e)) * LL;
+    total_out += ((4 * size_of("read_singleton.txt") + size_of("read_singleton.txt.tail")) / (size_t)L) * LL;
     // the N reads of every shard come behind the singletons (decoder.cpp:159-165): they wait in device memory of their own (declared in front of the
     // drain: it goes after the drain has written what it still holds)
     struct NParts { harc_amd_ctx *c; std::vector<std::pair<char *, size_t>> v; ~NParts() { for (auto &x : v) if (x.first) harc_raw_free(c, x.first); } } nparts{ c, {} };
-    auto wall = []() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
-    const double td0 = wall(); double t_slurp = 0, t_put = 0;
+    const double td0 = mono_now(); double t_slurp = 0, t_put = 0;
     FileDrain drain(c);
     RC_TRY(drain.start(od + "output.dna", total_out));
-    const double td1 = wall();
+    const double td1 = mono_now();
     uint64_t out_at = 0;
     unsigned int *d_err = nullptr; RC_TRY(dalloc(c, &d_err, 4));
     HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
     for (int e = 0; e < num_thr_e; e++) {
-        const std::string sfx = "." + std::to_string(e);
-        std::vector<uint8_t> seq, seqt, pos, noise, npz, rev, revt;
-        const double ts0 = wall();
-        if (!slurp_file(od + "read_seq.txt" + sfx, seq) || !slurp_file(od + "read_seq.txt" + sfx + ".tail", seqt) || !slurp_file(od + "read_pos.txt" + sfx, pos) ||
-            !slurp_file(od + "read_noise.txt" + sfx, noise) || !slurp_file(od + "read_noisepos.txt" + sfx, npz) ||
-            !slurp_file(od + "read_rev.txt" + sfx, rev) || !slurp_file(od + "read_rev.txt" + sfx + ".tail", revt)) { harc_set_error("shard %d: stream files missing", e); return HARC_AMD_EIO; }
-        t_slurp += wall() - ts0;
-        if (pos.empty()) continue;
-        if (pos.size() > 0xFFFFFFFFull || 8 * rev.size() + revt.size() != pos.size()) { harc_set_error("shard %d: rev stream does not match pos stream", e); return HARC_AMD_EIO; }
-        const harc_mark_t mk = harc_pool_mark(c);
-        const uint32_t n = (uint32_t)pos.size();
-        uint8_t *d_seq, *d_seqt, *d_pos, *d_noise, *d_np, *d_rev, *d_revt, *seqb; uint64_t *p64, *possum, *nlpos; uint32_t *fl, *rk, *isN, *rkN; char *tmp, *outA, *outN;
-        RC_TRY(up(c, seq.data(), seq.size(), &d_seq)); RC_TRY(up(c, seqt.data(), seqt.size(), &d_seqt)); RC_TRY(up(c, pos.data(), pos.size(), &d_pos));
-        RC_TRY(up(c, noise.data(), noise.size(), &d_noise)); RC_TRY(up(c, npz.data(), npz.size(), &d_np)); RC_TRY(up(c, rev.data(), rev.size(), &d_rev)); RC_TRY(up(c, revt.data(), revt.size(), &d_revt));
-        const uint64_t seqlen = 4 * (uint64_t)seq.size() + seqt.size();
-        const size_t nnoise = noise.size(), LL = (size_t)L + 1;
-        RC_TRY(dalloc(c, &seqb, (size_t)seqlen + 16)); RC_TRY(dalloc(c, &p64, (size_t)n + 1)); RC_TRY(dalloc(c, &possum, (size_t)n + 1)); RC_TRY(dalloc(c, &nlpos, (size_t)n + 1));
-        RC_TRY(dalloc(c, &fl, nnoise + 1)); RC_TRY(dalloc(c, &rk, nnoise + 1)); RC_TRY(dalloc(c, &isN, (size_t)n + 1)); RC_TRY(dalloc(c, &rkN, (size_t)n + 1));
-        RC_TRY(dalloc(c, &tmp, (size_t)n * LL + 16)); RC_TRY(dalloc(c, &outA, (size_t)n * LL + 16)); RC_TRY(dalloc(c, &outN, (size_t)n * LL + 16));
-        if (seqlen) hipLaunchKernelGGL(k_unpack_seq, G256(seqlen), d_seq, (uint64_t)seq.size(), d_seqt, (uint64_t)seqt.size(), seqb);
-        hipLaunchKernelGGL(k_pos_to_u64, G256(n), d_pos, n, p64);
-        RC_TRY(prim_incl_scan_u64(c, p64, possum, n));
-        if (nnoise) {
-            hipLaunchKernelGGL(k_nl_flags, G256(nnoise), d_noise, (uint64_t)nnoise, fl);
-            RC_TRY(prim_excl_scan_u32(c, fl, rk, nnoise));
-            hipLaunchKernelGGL(k_nl_positions, G256(nnoise), d_noise, rk, (uint64_t)nnoise, nlpos);
-        }
-        HIP_TRY(hipMemsetAsync(isN, 0, ((size_t)n + 1) * 4, c->stream));
-        hipLaunchKernelGGL(k_decode_text, G256(n), seqb, seqlen, possum, d_noise, d_np, nlpos, d_rev, (uint64_t)rev.size(), d_revt, n, L, tmp, isN, d_err);
-        RC_TRY(prim_excl_scan_u32(c, isN, rkN, (size_t)n + 1));
-        hipLaunchKernelGGL(k_split_lines, G256((uint64_t)n * LL), tmp, isN, rkN, n, L, outA, outN);
-        uint32_t nN = 0;
-        HIP_TRY(hipMemcpyAsync(&nN, rkN + n, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        const size_t bytesA = (size_t)(n - nN) * LL, bytesN = (size_t)nN * LL;
+        ShardStreams s; ShardDev d; ShardLines ln;
+        { const double ts0 = mono_now(); RC_TRY(streams_from_files(od, e, &s)); t_slurp += mono_now() - ts0; }
+        PoolScope shard(c);                                        // (the copies out of outA / outN are on the stream in front of whatever takes their place)
+        RC_TRY(shard_prepare(c, e, s, &d));
+        if (!d.n) continue;
+        RC_TRY(shard_to_lines(c, d, L, d_err, &ln));
+        const size_t bytesA = (size_t)ln.nA * LL, bytesN = (size_t)ln.nN * LL;
         if (bytesN) {
             char *keep = nullptr;
             RC_TRY(harc_raw_alloc(c, (void **)&keep, bytesN + 16));
             nparts.v.emplace_back(keep, bytesN);
-            HIP_TRY(hipMemcpyAsync(keep, outN, bytesN, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(keep, ln.outN, bytesN, hipMemcpyDeviceToDevice, c->stream));
         }
-        { const double tp0 = wall(); if (bytesA) { RC_TRY(drain.put(outA, bytesA, out_at)); out_at += bytesA; } t_put += wall() - tp0; }
-        harc_pool_release(c, mk);                                  // (the copies out of outA / outN are on the stream in front of whatever takes their place)
+        { const double tp0 = mono_now(); if (bytesA) { RC_TRY(drain.put(ln.outA, bytesA, out_at)); out_at += bytesA; } t_put += mono_now() - tp0; }
     }
     {   // singletons (decoder.cpp:148-158), then the N reads of every shard (:159-165), then input_N.dna (:166-168)
         std::vector<uint8_t> sg, sgt, nt;
         if (!slurp_file(od + "read_singleton.txt", sg) || !slurp_file(od + "read_singleton.txt.tail", sgt)) { harc_set_error("singleton files missing"); return HARC_AMD_EIO; }
         slurp_file(od + "input_N.dna", nt);
-        const uint64_t nb = 4 * (uint64_t)sg.size() + sgt.size();
-        const uint32_t ns = (uint32_t)(nb / L);
-        if (ns) {
-            const harc_mark_t mk = harc_pool_mark(c);
-            uint8_t *d_sg, *d_sgt, *codes; char *lines;
-            RC_TRY(up(c, sg.data(), sg.size(), &d_sg)); RC_TRY(up(c, sgt.data(), sgt.size(), &d_sgt)); RC_TRY(dalloc(c, &codes, (size_t)nb + 16));
-            RC_TRY(dalloc(c, &lines, (size_t)ns * (L + 1) + 16));
-            hipLaunchKernelGGL(k_unpack_seq, G256(nb), d_sg, (uint64_t)sg.size(), d_sgt, (uint64_t)sgt.size(), codes);
-            hipLaunchKernelGGL(k_codes_to_lines, G256((uint64_t)ns * (L + 1)), codes, ns, L, lines);
-            RC_TRY(drain.put(lines, (size_t)ns * (L + 1), out_at)); out_at += (size_t)ns * (L + 1);
-            harc_pool_release(c, mk);
-        }
+        PoolScope scope(c);
+        uint32_t ns = 0; uint8_t *codes = nullptr; char *lines = nullptr;
+        RC_TRY(singletons_unpack(c, view_of(sg), view_of(sgt), L, &ns, &codes, &lines));
+        if (ns) { RC_TRY(drain.put(lines, (size_t)ns * LL, out_at)); out_at += (size_t)ns * LL; }
         for (auto &p : nparts.v) { RC_TRY(drain.put(p.first, p.second, out_at)); out_at += p.second; }
         RC_TRY(drain.put_host(nt.data(), nt.size(), out_at)); out_at += nt.size();
     }
@@ -358,9 +391,9 @@ extern "C" int harc_amd_decoder_files(const harc_amd_params *params, const char 
     unsigned int err = 0;
     HIP_TRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const double tf0 = wall();
+    const double tf0 = mono_now();
     RC_TRY(drain.finish());
-    if (getenv("HARC_AMD_TRACE")) fprintf(stderr, "[decoder] %.3f s: output mapped and ring ready %.3f, stream files read %.3f, waiting for ring slices %.3f, last slices written %.3f\n", wall() - td0, td1 - td0, t_slurp, t_put, wall() - tf0);
+    if (getenv("HARC_AMD_TRACE")) fprintf(stderr, "[decoder] %.3f s: output mapped and ring ready %.3f, stream files read %.3f, waiting for ring slices %.3f, last slices written %.3f\n", mono_now() - td0, td1 - td0, t_slurp, t_put, mono_now() - tf0);
     if (err) { harc_set_error("decoder: %u reads with inconsistent pos/noise streams", err); return HARC_AMD_EIO; }
     printf("Decoding done\n");                                                 // decoder.cpp:170
     return HARC_AMD_OK;
@@ -400,14 +433,13 @@ extern "C" int harc_amd_input_signature(harc_amd_ctx *c, uint64_t *sig3)
 {
     if (!c || !sig3) return HARC_AMD_EINVAL;
     HIP_TRY(hipSetDevice(c->P.device));
-    const harc_mark_t mk = harc_pool_mark(c);
+    PoolScope scope(c);
     unsigned long long *d_sig = nullptr; RC_TRY(dalloc(c, &d_sig, 4));
     HIP_TRY(hipMemsetAsync(d_sig, 0, 32, c->stream));
     if (c->N && c->d_reads) hipLaunchKernelGGL(k_sig_packed2, G256(c->N), c->d_reads, c->N, c->P.readlen, c->W, d_sig);
     if (c->NN && c->d_nreads3) hipLaunchKernelGGL(k_sig_packed3, G256(c->NN), c->d_nreads3, c->NN, c->P.readlen, c->W3, d_sig);
     HIP_TRY(hipMemcpyAsync(sig3, d_sig, 24, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    harc_pool_release(c, mk);
     return HARC_AMD_OK;
 }
 
@@ -460,20 +492,12 @@ __global__ void k_merge_lines(const char *clean, const char *withN, const uint32
 
 extern "C" int harc_amd_decoder_preserve_files(const harc_amd_params *params, const char *basedir, int32_t num_thr_e)
 {
-    if (!params || !basedir || num_thr_e < 1) return HARC_AMD_EINVAL;
-    const std::string od = std::string(basedir) + "/output/";
-    std::vector<uint8_t> meta, pord, ptail, ordNpe, ordN;
-    if (!slurp_file(od + "read_meta.txt", meta)) { harc_set_error("cannot read %sread_meta.txt", od.c_str()); return HARC_AMD_EIO; }
-    meta.push_back(0);
-    const int L = atoi((const char *)meta.data());
-    harc_amd_params P = *params;
-    if (harc_amd_default_params(L, &P) != HARC_AMD_OK) return HARC_AMD_EINVAL;
-    P.device = params->device; P.num_thr = num_thr_e;
+    std::string od; int L = 0; CtxGuard guard;
+    RC_TRY(open_archive(params, basedir, num_thr_e, &od, &L, &guard.c));
+    harc_amd_ctx *c = guard.c;
+    std::vector<uint8_t> pord, ptail, ordNpe, ordN;
     if (!slurp_file(od + "read_order.bin", pord) || !slurp_file(od + "read_order.bin.tail", ptail) || !slurp_file(od + "read_order_N_pe.bin", ordNpe) ||
         !slurp_file(od + "read_order_N.bin", ordN)) { harc_set_error("order files missing: was the archive made with -p?"); return HARC_AMD_EIO; }
-    harc_amd_ctx *c = nullptr;
-    RC_TRY(harc_amd_create(&P, &c));
-    struct Guard { harc_amd_ctx *c; ~Guard() { harc_amd_destroy(c); } } guard{ c };
     const size_t LL = (size_t)L + 1;
     // ---- unpack_order
     uint32_t nC = 0; int numbits = 0;
@@ -490,11 +514,10 @@ extern "C" int harc_amd_decoder_preserve_files(const harc_amd_params *params, co
     RC_TRY(dalloc(c, &flag, (size_t)total + 1)); RC_TRY(dalloc(c, &rankN, (size_t)total + 1));
     HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
     if (ng) {
-        const harc_mark_t mk = harc_pool_mark(c);
-        uint8_t *d_p = nullptr; RC_TRY(up(c, pord.data() + 8, (size_t)ng * numbits * 4, &d_p));
+        PoolScope scope(c);
+        uint8_t *d_p = nullptr; RC_TRY(up(c, View{ pord.data() + 8, (size_t)ng * numbits * 4 }, &d_p));
         hipLaunchKernelGGL(k_unpack_order, G256((uint64_t)ng * 32), (const uint32_t *)d_p, ng, numbits, d_order);
         HIP_TRY(hipStreamSynchronize(c->stream));
-        harc_pool_release(c, mk);
     }
     if (ntail) HIP_TRY(hipMemcpyAsync(d_order + (size_t)ng * 32, ptail.data(), (size_t)ntail * 4, hipMemcpyHostToDevice, c->stream));
     if (nN) { HIP_TRY(hipMemcpyAsync(d_ordNpe, ordNpe.data(), (size_t)nN * 4, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_ordN, ordN.data(), (size_t)nN * 4, hipMemcpyHostToDevice, c->stream)); }
@@ -511,7 +534,7 @@ extern "C" int harc_amd_decoder_preserve_files(const harc_amd_params *params, co
     // fall into it -- decoding is cheap, no temporary file, host memory bounded by one output chunk.
     uint64_t bin_lines;
     {
-        const int mgb = P.decode_memory_gb > 3 ? P.decode_memory_gb : (P.decode_memory_gb == 0 ? 7 : 3);     // harc:225 default 7; decoder_preserve.cpp:249-252
+        const int mgb = c->P.decode_memory_gb > 3 ? c->P.decode_memory_gb : (c->P.decode_memory_gb == 0 ? 7 : 3);     // harc:225 default 7; decoder_preserve.cpp:249-252
         bin_lines = (uint64_t)mgb * 200000000ull / 7ull;
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
@@ -520,8 +543,8 @@ extern "C" int harc_amd_decoder_preserve_files(const harc_amd_params *params, co
             // bytes per read of the shard) is needed whatever the bin size, and is taken off before the bin gets its quarter
             uint64_t nmax = 0;
             for (int e = 0; e < num_thr_e; e++) {
-                FILE *fp = fopen((od + "read_pos.txt." + std::to_string(e)).c_str(), "rb");
-                if (fp) { if (fseek(fp, 0, SEEK_END) == 0) { const long sz = ftell(fp); if (sz > 0 && (uint64_t)sz > nmax) nmax = (uint64_t)sz; } fclose(fp); }
+                uint64_t sz = 0;
+                if (file_size((od + "read_pos.txt." + std::to_string(e)).c_str(), &sz) && sz > nmax) nmax = sz;
             }
             const double shard_scratch = (double)nmax * (3.0 * (double)LL + 64.0);
             if (shard_scratch > 0.9 * (double)fr) {
@@ -541,9 +564,16 @@ extern "C" int harc_amd_decoder_preserve_files(const harc_amd_params *params, co
     std::vector<uint8_t> sg, sgt, nt;                             // singletons and unaligned N reads: read once
     if (!slurp_file(od + "read_singleton.txt", sg) || !slurp_file(od + "read_singleton.txt.tail", sgt)) { harc_set_error("singleton files missing"); return HARC_AMD_EIO; }
     slurp_file(od + "input_N.dna", nt);
-    const harc_mark_t mark_bins = harc_pool_mark(c);
+    // what the kernels have counted into d_err so far refuses the archive
+    auto refuse_counted = [&]() -> int {
+        unsigned int err = 0;
+        HIP_TRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (err) { harc_set_error("decoder -p: %u inconsistent order / stream entries", err); return HARC_AMD_EIO; }
+        return HARC_AMD_OK;
+    };
     for (uint64_t p0 = 0; p0 < total || (total == 0 && p0 == 0); p0 += bin_lines) {
-        harc_pool_release(c, mark_bins);
+        PoolScope bin(c);                                         // what a bin allocates goes with it
         const uint32_t pn = (uint32_t)(total - p0 < bin_lines ? total - p0 : bin_lines);
         uint32_t r0 = 0, r1 = 0;
         HIP_TRY(hipMemcpyAsync(&r0, rankN + p0, 4, hipMemcpyDeviceToHost, c->stream));
@@ -556,70 +586,33 @@ extern "C" int harc_amd_decoder_preserve_files(const harc_amd_params *params, co
         //      restore_order_N (:212-244)
         uint64_t cA = 0, cN = 0;
         for (int e = 0; e < num_thr_e; e++) {
-            const std::string sfx = "." + std::to_string(e);
-            std::vector<uint8_t> seq, seqt, pos, noise, npz, rev, revt;
-            if (!slurp_file(od + "read_seq.txt" + sfx, seq) || !slurp_file(od + "read_seq.txt" + sfx + ".tail", seqt) || !slurp_file(od + "read_pos.txt" + sfx, pos) ||
-                !slurp_file(od + "read_noise.txt" + sfx, noise) || !slurp_file(od + "read_noisepos.txt" + sfx, npz) ||
-                !slurp_file(od + "read_rev.txt" + sfx, rev) || !slurp_file(od + "read_rev.txt" + sfx + ".tail", revt)) { harc_set_error("shard %d: stream files missing", e); return HARC_AMD_EIO; }
-            if (pos.empty()) continue;
-            if (pos.size() > 0xFFFFFFFFull || 8 * rev.size() + revt.size() != pos.size()) { harc_set_error("shard %d: rev stream does not match pos stream", e); return HARC_AMD_EIO; }
-            const harc_mark_t mk = harc_pool_mark(c);
-            const uint32_t n = (uint32_t)pos.size();
-            uint8_t *d_seq, *d_seqt, *d_pos, *d_noise, *d_np, *d_rev, *d_revt, *seqb; uint64_t *p64, *possum, *nlpos; uint32_t *fl, *rk, *isN, *rkN; char *tmp, *outA, *outN;
-            RC_TRY(up(c, seq.data(), seq.size(), &d_seq)); RC_TRY(up(c, seqt.data(), seqt.size(), &d_seqt)); RC_TRY(up(c, pos.data(), pos.size(), &d_pos));
-            RC_TRY(up(c, noise.data(), noise.size(), &d_noise)); RC_TRY(up(c, npz.data(), npz.size(), &d_np)); RC_TRY(up(c, rev.data(), rev.size(), &d_rev)); RC_TRY(up(c, revt.data(), revt.size(), &d_revt));
-            const uint64_t seqlen = 4 * (uint64_t)seq.size() + seqt.size();
-            const size_t nnoise = noise.size();
-            RC_TRY(dalloc(c, &seqb, (size_t)seqlen + 16)); RC_TRY(dalloc(c, &p64, (size_t)n + 1)); RC_TRY(dalloc(c, &possum, (size_t)n + 1)); RC_TRY(dalloc(c, &nlpos, (size_t)n + 1));
-            RC_TRY(dalloc(c, &fl, nnoise + 1)); RC_TRY(dalloc(c, &rk, nnoise + 1)); RC_TRY(dalloc(c, &isN, (size_t)n + 1)); RC_TRY(dalloc(c, &rkN, (size_t)n + 1));
-            RC_TRY(dalloc(c, &tmp, (size_t)n * LL + 16)); RC_TRY(dalloc(c, &outA, (size_t)n * LL + 16)); RC_TRY(dalloc(c, &outN, (size_t)n * LL + 16));
-            if (seqlen) hipLaunchKernelGGL(k_unpack_seq, G256(seqlen), d_seq, (uint64_t)seq.size(), d_seqt, (uint64_t)seqt.size(), seqb);
-            hipLaunchKernelGGL(k_pos_to_u64, G256(n), d_pos, n, p64);
-            RC_TRY(prim_incl_scan_u64(c, p64, possum, n));
-            if (nnoise) {
-                hipLaunchKernelGGL(k_nl_flags, G256(nnoise), d_noise, (uint64_t)nnoise, fl);
-                RC_TRY(prim_excl_scan_u32(c, fl, rk, nnoise));
-                hipLaunchKernelGGL(k_nl_positions, G256(nnoise), d_noise, rk, (uint64_t)nnoise, nlpos);
-            }
-            HIP_TRY(hipMemsetAsync(isN, 0, ((size_t)n + 1) * 4, c->stream));
-            hipLaunchKernelGGL(k_decode_text, G256(n), seqb, seqlen, possum, d_noise, d_np, nlpos, d_rev, (uint64_t)rev.size(), d_revt, n, L, tmp, isN, d_err);
-            RC_TRY(prim_excl_scan_u32(c, isN, rkN, (size_t)n + 1));
-            hipLaunchKernelGGL(k_split_lines, G256((uint64_t)n * LL), tmp, isN, rkN, n, L, outA, outN);
-            uint32_t nNs = 0;
-            HIP_TRY(hipMemcpyAsync(&nNs, rkN + n, 4, hipMemcpyDeviceToHost, c->stream));
+            ShardStreams s; ShardDev d; ShardLines ln;
+            RC_TRY(streams_from_files(od, e, &s));
+            PoolScope shard(c);
+            RC_TRY(shard_prepare(c, e, s, &d));
+            if (!d.n) continue;
+            RC_TRY(shard_to_lines(c, d, L, d_err, &ln));
+            if (cA + ln.nA > nC || cN + ln.nN > nN) { harc_set_error("streams hold more reads than the order files"); return HARC_AMD_EIO; }
+            if (ln.nA) hipLaunchKernelGGL(k_permute_lines, G256((uint64_t)ln.nA * LL), ln.outA, d_order + cA, ln.nA, L, clp, clo, chi, nC, d_err);
+            if (ln.nN) hipLaunchKernelGGL(k_permute_lines, G256((uint64_t)ln.nN * LL), ln.outN, d_ordNpe + cN, ln.nN, L, nlp, nlo, nhi, nN, d_err);
             HIP_TRY(hipStreamSynchronize(c->stream));
-            const uint32_t nAs = n - nNs;
-            if (cA + nAs > nC || cN + nNs > nN) { harc_set_error("streams hold more reads than the order files"); return HARC_AMD_EIO; }
-            if (nAs) hipLaunchKernelGGL(k_permute_lines, G256((uint64_t)nAs * LL), outA, d_order + cA, nAs, L, clp, clo, chi, nC, d_err);
-            if (nNs) hipLaunchKernelGGL(k_permute_lines, G256((uint64_t)nNs * LL), outN, d_ordNpe + cN, nNs, L, nlp, nlo, nhi, nN, d_err);
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            cA += nAs; cN += nNs;
-            harc_pool_release(c, mk);
+            cA += ln.nA; cN += ln.nN;
         }
+        RC_TRY(refuse_counted());                                 // (in front of the counts below: a read that could not be decoded is a line without N, whatever it was)
         {   // singletons, then the N reads that were not aligned (decoder_preserve.cpp:160-197)
-            const harc_mark_t mk = harc_pool_mark(c);
-            const uint64_t nb = 4 * (uint64_t)sg.size() + sgt.size();
-            const uint32_t ns = (uint32_t)(nb / L), nu = (uint32_t)(nt.size() / LL);
+            PoolScope scope(c);
+            uint32_t ns = 0; uint8_t *codes = nullptr; char *sl = nullptr;
+            RC_TRY(singletons_unpack(c, view_of(sg), view_of(sgt), L, &ns, &codes, &sl));
+            const uint32_t nu = (uint32_t)(nt.size() / LL);
             if (cA + ns != nC || cN + nu != nN) { harc_set_error("read counts do not add up: clean %llu+%u vs %u, N %llu+%u vs %u", (unsigned long long)cA, ns, nC, (unsigned long long)cN, nu, nN); return HARC_AMD_EIO; }
-            if (ns) {
-                uint8_t *d_sg, *d_sgt, *codes; char *sl;
-                RC_TRY(up(c, sg.data(), sg.size(), &d_sg)); RC_TRY(up(c, sgt.data(), sgt.size(), &d_sgt)); RC_TRY(dalloc(c, &codes, (size_t)nb + 16)); RC_TRY(dalloc(c, &sl, (size_t)ns * LL + 16));
-                hipLaunchKernelGGL(k_unpack_seq, G256(nb), d_sg, (uint64_t)sg.size(), d_sgt, (uint64_t)sgt.size(), codes);
-                hipLaunchKernelGGL(k_codes_to_lines, G256((uint64_t)ns * LL), codes, ns, L, sl);
-                hipLaunchKernelGGL(k_permute_lines, G256((uint64_t)ns * LL), sl, d_order + cA, ns, L, clp, clo, chi, nC, d_err);
-            }
+            if (ns) hipLaunchKernelGGL(k_permute_lines, G256((uint64_t)ns * LL), sl, d_order + cA, ns, L, clp, clo, chi, nC, d_err);
             if (nu) {
-                uint8_t *d_nt; RC_TRY(up(c, nt.data(), (size_t)nu * LL, &d_nt));
+                uint8_t *d_nt; RC_TRY(up(c, View{ nt.data(), (size_t)nu * LL }, &d_nt));
                 hipLaunchKernelGGL(k_permute_lines, G256((uint64_t)nu * LL), (const char *)d_nt, d_ordNpe + cN, nu, L, nlp, nlo, nhi, nN, d_err);
             }
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            harc_pool_release(c, mk);
         }
+        RC_TRY(refuse_counted());
         // ---- merge_N for the lines of the bin, written in pieces of at most 256 MiB
-        unsigned int err = 0;
-        HIP_TRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (err) { harc_set_error("decoder -p: %u inconsistent order / stream entries", err); return HARC_AMD_EIO; }
         const uint32_t piece = (uint32_t)(((size_t)256 << 20) / LL);
         char *outl = nullptr; RC_TRY(dalloc(c, &outl, (size_t)piece * LL + 16));
         std::vector<uint8_t> host;

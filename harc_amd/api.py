@@ -127,6 +127,8 @@ def lib():
     l.harc_amd_merge_shard_files.argtypes = [C.c_char_p, C.c_int32]
     l.harc_amd_stream_digest.argtypes = [ctx, C.POINTER(C.c_uint64)]
     l.harc_amd_selftest_launch.argtypes = [ctx, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    l.harc_amd_selftest_index.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     l.harc_amd_build_id.restype = C.c_char_p
     _lib = l
     return l
@@ -512,6 +514,23 @@ class HarcAmd:
         v, x = C.c_uint64(0), C.c_uint64(0)
         _check(lib().harc_amd_selftest_launch(self._ctx, n, C.byref(v), C.byref(x)))
         return int(v.value), int(x.value)
+
+    def selftest_index(self, keys, slots_per_read=0, bigthresh=0, want_large=False):
+        """the index build of the stages over `keys` (unscrambled u64, ids 0 .. n-1): (cap, nbins, slots, ids, large).  slots is a structured array of
+        cap (key u64, start u32, count u32), large the list of (slot << 1) | 1 of the bins of more than 16 keys, or None when not asked for"""
+        import numpy as np
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        n = int(keys.size)
+        cap, nbins, nl = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        _check(lib().harc_amd_selftest_index(self._ctx, keys.ctypes.data, n, slots_per_read, bigthresh, 0, C.byref(cap), None, None, None, None, 0, None))
+        slots = np.zeros(cap.value, dtype=np.dtype([("key", "<u8"), ("start", "<u4"), ("count", "<u4")]))
+        ids = np.zeros(n, dtype=np.uint32)
+        large = np.zeros(n // 16 + 16, dtype=np.uint64)
+        _check(lib().harc_amd_selftest_index(self._ctx, keys.ctypes.data, n, slots_per_read, bigthresh, 1 if want_large else 0, C.byref(cap), C.byref(nbins),
+                                             slots.ctypes.data, ids.ctypes.data, large.ctypes.data, large.size, C.byref(nl)))
+        if want_large and nl.value > large.size:
+            raise HarcAmdError(-1, "harc_amd_selftest_index lists %d large bins among %d keys" % (nl.value, n))
+        return int(cap.value), int(nbins.value), slots, ids, (large[:nl.value].copy() if want_large else None)
 
     def stream_digest(self):
         """four 64-bit words over the stage-II streams of the last encode(), folded on the device (params.stream_digest = 1)"""

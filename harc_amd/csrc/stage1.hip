@@ -2849,6 +2849,65 @@ void harc_dict_free(harc_amd_ctx *c, DictDev *d)
     d->slots = nullptr; d->ids = nullptr; d->d_nbins = nullptr; d->cap = 0;
 }
 
+// ---- self-test of the index build (include/harc_amd.h; tests/test_gpu_index.py holds the table to its contract): harc_dict_alloc + harc_dict_build as
+// the stages call them, over keys from the host, the table and ids[] copied back
+__global__ void k_selftest_ids(uint32_t *ids, uint32_t n)
+{
+    const uint32_t i = harc_gid32();
+    if (i < n) ids[i] = i;                                        // as k_keygen2 makes them
+}
+static int selftest_index(harc_amd_ctx *c, const uint64_t *keys, uint32_t n, uint32_t bigthresh, bool want_large, uint64_t *cap, uint32_t *nbins, void *slots,
+                          uint32_t *ids, uint64_t *large, uint64_t large_capacity, uint64_t *n_large)
+{
+    PoolScope scope(c);                                           // table, ids and temporaries go on every way out
+    DictDev d;
+    RC_TRY(harc_dict_alloc(c, &d, n, 0));
+    const uint64_t room = *cap;
+    *cap = d.cap;
+    if (!slots) return HARC_AMD_OK;
+    if (room < d.cap) { harc_set_error("harc_amd_selftest_index: the table has %llu slots, the caller's buffer %llu", (unsigned long long)d.cap, (unsigned long long)room); return HARC_AMD_EINVAL; }
+    uint64_t *k0 = nullptr; uint32_t *i0 = nullptr; unsigned long long *d_large = nullptr; unsigned int *d_nlarge = nullptr;
+    const uint32_t maxlarge = 2 * (n / HARC_LARGEBIN) + 16;       // as stage1_run_w sizes it
+    RC_TRY(dalloc(c, &k0, n)); RC_TRY(dalloc(c, &i0, n));
+    if (want_large) {
+        RC_TRY(dalloc(c, &d_large, maxlarge)); RC_TRY(dalloc(c, &d_nlarge, 4));
+        HIP_TRY(hipMemsetAsync(d_nlarge, 0, 16, c->stream));
+        d.large_list = d_large; d.large_n = d_nlarge; d.large_max = maxlarge; d.large_tag = 1u;
+    }
+    d.bigthresh = bigthresh;
+    HIP_TRY(hipMemcpyAsync(k0, keys, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_selftest_ids, harc_grid256(n), dim3(256), 0, c->stream, i0, n);
+    HIP_TRY(hipMemsetAsync(d.slots, 0xA5, d.cap * sizeof(HashSlot), c->stream));      // stale bytes: whatever the build leaves unwritten shows
+    HIP_TRY(hipMemsetAsync(d.ids, 0xA5, (size_t)n * 4, c->stream));
+    RC_TRY(harc_dict_build(c, &d, k0, i0, n, 64));
+    *nbins = d.nbins;
+    HIP_TRY(hipMemcpyAsync(slots, d.slots, d.cap * sizeof(HashSlot), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(ids, d.ids, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    unsigned int nl = 0;
+    if (want_large) HIP_TRY(hipMemcpyAsync(&nl, d_nlarge, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (want_large) {
+        *n_large = nl;
+        uint64_t take = nl < maxlarge ? nl : maxlarge;
+        if (take > large_capacity) take = large_capacity;
+        if (take) HIP_TRY(hipMemcpy(large, d_large, (size_t)take * 8, hipMemcpyDeviceToHost));
+    }
+    return HARC_AMD_OK;
+}
+extern "C" int harc_amd_selftest_index(harc_amd_ctx *c, const uint64_t *keys, uint64_t n, int32_t slots_per_read, uint32_t bigthresh, int32_t want_large,
+                                       uint64_t *cap, uint32_t *nbins, void *slots, uint32_t *ids, uint64_t *large, uint64_t large_capacity, uint64_t *n_large)
+{
+    if (!c || !cap || n == 0 || n > 0xFFFFFFF0ull || (slots_per_read != 0 && (slots_per_read < 2 || slots_per_read > 4))) { harc_set_error("harc_amd_selftest_index: bad arguments"); return HARC_AMD_EINVAL; }
+    if (slots && (!keys || !nbins || !ids || (want_large && (!n_large || (!large && large_capacity))))) { harc_set_error("harc_amd_selftest_index: a NULL output"); return HARC_AMD_EINVAL; }
+    HIP_TRY(hipSetDevice(c->P.device));
+    const int32_t spr = c->P.table_slots_per_read;
+    c->P.table_slots_per_read = slots_per_read;
+    const int rc = selftest_index(c, keys, (uint32_t)n, bigthresh, want_large != 0, cap, nbins, slots, ids, large, large_capacity, n_large);
+    c->P.table_slots_per_read = spr;
+    if (rc != HARC_AMD_OK) (void)hipStreamSynchronize(c->stream);                     // nothing of a failed build is still running when its memory is reused
+    return rc;
+}
+
 static std::vector<uint16_t> make_probe_table(const harc_amd_params &P)
 {
     // reorder.cpp:517-649: for j: forward l=0,1 (skip if dict_end[l]+j >= readlen), reverse l=0,1 (skip if dict_start[l] <= j)

@@ -266,6 +266,15 @@ int harc_amd_build_has(const char *feature);
 /* Self-test of the library's launch geometry (one thread per item over n items through harc_gid / harc_gid32, and four lanes per item in folded workgroups, n beyond 2^32 included: a one-dimensional grid of 2^32 and more
  * work-items is cut short without an error on this platform).  *visited == n and *index_sum == n (n - 1) / 2 mod 2^64 when every item was visited once. */
 int harc_amd_selftest_launch(harc_amd_ctx *ctx, uint64_t n, uint64_t *visited, uint64_t *index_sum);
+/* Self-test of the index build: the very harc_dict_alloc + harc_dict_build the stages run, over n UNSCRAMBLED 64-bit keys in host memory with the ids
+ * 0 .. n-1, into a slot array that holds a non-zero byte pattern beforehand (the build must not depend on cleared memory).  slots_per_read 2..4, 0 = the
+ * library's choice; bigthresh as DictDev.bigthresh (0 = no SLOT_BIG); want_large != 0 lists the bins of more than 16 keys as (slot << 1) | 1.
+ * slots == NULL: size query, *cap alone (with slots_per_read = 0 the library chooses by the memory free at that moment: a later call may choose another
+ * cap, and then refuses a buffer that is too small).  Else *cap holds on entry how many 16-byte slots `slots` has room for (HARC_AMD_EINVAL when the table is larger),
+ * and out come *cap, *nbins, slots[*cap] (key u64, start u32, count u32), ids[n], and -- with want_large -- large[min(*n_large, large_capacity)] and
+ * *n_large.  Nothing stays allocated, and after an error return the context is as usable as before. */
+int harc_amd_selftest_index(harc_amd_ctx *ctx, const uint64_t *keys, uint64_t n, int32_t slots_per_read, uint32_t bigthresh, int32_t want_large,
+                            uint64_t *cap, uint32_t *nbins, void *slots, uint32_t *ids, uint64_t *large, uint64_t large_capacity, uint64_t *n_large);
 
 /* Where the wall time of this process's last harc_amd_compress_fastq_files_ex went, in seconds (the end-to-end leg of bench.py; preprocess.cpp:81-121 + harc:50-69):
  * out[0] context + device pool, [1] ingest (file -> HBM -> packed stores; reads, uploads and kernels overlapped), [2] of it the calling thread waiting for

@@ -284,3 +284,86 @@ def reads_text_bigbin_stage2_at(seed, L, n_clean=4000, n_dupN=3000, genome_len=8
     allr = np.concatenate([clean, dup])
     rs.shuffle(allr)
     return lines_of(allr)
+
+
+def reads_text_table_end(seed, n=3000, genome_len=30000, n_plant=12, err=0.01, L=100):
+    """k-mers that live at the very END of both stage-I dictionaries.  At L = 100 both dictionary windows (bases 18-49 and 50-81) are 32 bases, a full
+    64-bit key: n_plant crafted 32-mers -- each the unscrambled value of a scrambled key whose high word is 0xFFFFFFFF, the last bucket of any table,
+    spelled in the 2-bit code of the packed reads (A 0, G 1, C 2, T 3, base j at bits 2j) -- are planted at well-separated loci of a random genome.
+    n reads as reads_array samples them, plus error-free reads that start at locus - 18 + d and locus - 50 + d for d = -6 .. 6 (those with odd d
+    reverse-complemented): each planted k-mer is a bin of both dictionaries and is probed at several shifts and in both orientations.
+    -> (text, planted unscrambled keys)"""
+    from tests import index_ref as ix
+    assert L == 100
+    rs = np.random.RandomState(seed)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    genome = acgt[rs.randint(0, 4, size=genome_len)].copy()
+    h = np.uint64(0xFFFFFFFF00000000) + np.unique(rs.randint(0, 1 << 32, size=4 * n_plant, dtype=np.uint64))[:n_plant]
+    keys = ix.unscramble(rs.permutation(h))
+    loci = 1000 + np.arange(n_plant) * ((genome_len - 2000) // n_plant)
+    agct = np.frombuffer(b"AGCT", dtype=np.uint8)
+    for key, at in zip(keys, loci):
+        genome[at:at + 32] = agct[((np.uint64(key) >> (np.uint64(2) * np.arange(32, dtype=np.uint64))) & np.uint64(3)).astype(np.int64)]
+    starts = rs.randint(0, genome_len - L, size=n)
+    r = genome[starts[:, None] + np.arange(L)[None, :]].copy()
+    e = rs.random_sample((n, L)) < err
+    isN = e & (rs.random_sample((n, L)) < 0.25)
+    sub = e & ~isN
+    r[sub] = acgt[(np.searchsorted(acgt, r[sub]) + rs.randint(1, 4, size=int(sub.sum()))) % 4]
+    r[isN] = ord("N")
+    odd = np.arange(n) % 2 == 1
+    r[odd] = _COMP[r[odd][:, ::-1]]
+    exact = np.array([at - w + d for at in loci for w in (18, 50) for d in range(-6, 7)])
+    x = genome[exact[:, None] + np.arange(L)[None, :]].copy()
+    rev = np.array([d % 2 != 0 for at in loci for w in (18, 50) for d in range(-6, 7)])      # d = 0 stays forward: the planted k-mer itself is a key
+    x[rev] = _COMP[x[rev][:, ::-1]]
+    allr = np.concatenate([r, x])
+    return lines_of(allr[rs.permutation(allr.shape[0])]), keys
+
+
+_CODE3 = np.zeros(256, dtype=np.uint64)                               # the 3-bit read store: A 0, N 1, G 2, C 4, T 6, base j at bits 3j
+for _ch, _v in zip(b"ANGCT", (0, 1, 2, 4, 6)):
+    _CODE3[_ch] = _v
+
+
+def keys3(reads, start, nbases=21):
+    """[n, L] uint8 reads -> the 3-bit-coded key of bases [start, start + nbases) of each (stage II's dictionaries: bases 0-20 and 21-41 above 50 bp)"""
+    return (_CODE3[reads[:, start:start + nbases]] << (np.uint64(3) * np.arange(nbases, dtype=np.uint64))).sum(axis=1, dtype=np.uint64)
+
+
+def reads_text_table_end_stage2(seed, n=3000, genome_len=30000, n_plant=12, err=0.01, L=100, max_buckets=2048):
+    """k-mers that live at the very END of both STAGE-II dictionaries (built over the singletons and the reads with N, keyed by the 3-bit-coded bases 0-20
+    and 21-41).  A key there is 21 three-bit codes, not any 64-bit value, so the k-mers are drawn by rejection: random 21-mers whose scrambled key has its
+    high word in the top 1 / max_buckets of the range -- the last bucket of every table of at most max_buckets buckets.  n_plant 42-mers made of two such
+    21-mers are planted in a random genome, the odd ones reverse-complemented; for each, three reads that BEGIN with the 42-mer (the odd ones read from the
+    other strand) and carry one N behind it.  Reads with N never enter stage I: all of them are candidates of stage II, where the consensus of the n reads
+    sampled around them (reads_array's way) has to find them.  -> (text, the planted 42-mers as [n_plant, 42] uint8)"""
+    from tests import index_ref as ix
+    rs = np.random.RandomState(seed)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    genome = acgt[rs.randint(0, 4, size=genome_len)].copy()
+    found = []
+    while sum(len(f) for f in found) < 2 * n_plant:
+        c = acgt[rs.randint(0, 4, size=(200000, 21))]
+        top = ix.scramble(keys3(c, 0)) >> np.uint64(32)
+        found.append(c[top >= np.uint64((1 << 32) - (1 << 32) // max_buckets)])
+    mers = np.concatenate(found)[:2 * n_plant].reshape(n_plant, 42)
+    loci = 1000 + np.arange(n_plant) * ((genome_len - 2000) // n_plant)
+    planted = []
+    for i, (p, at) in enumerate(zip(mers, loci)):
+        genome[at:at + 42] = p if i % 2 == 0 else _COMP[p[::-1]]
+        for k in range(3):
+            r = genome[at:at + L].copy() if i % 2 == 0 else _COMP[genome[at + 42 - L:at + 42][::-1]]
+            r[42 + 7 * k + i] = ord("N")
+            planted.append(r)
+    starts = rs.randint(0, genome_len - L, size=n)
+    r = genome[starts[:, None] + np.arange(L)[None, :]].copy()
+    e = rs.random_sample((n, L)) < err
+    isN = e & (rs.random_sample((n, L)) < 0.25)
+    sub = e & ~isN
+    r[sub] = acgt[(np.searchsorted(acgt, r[sub]) + rs.randint(1, 4, size=int(sub.sum()))) % 4]
+    r[isN] = ord("N")
+    odd = np.arange(n) % 2 == 1
+    r[odd] = _COMP[r[odd][:, ::-1]]
+    allr = np.concatenate([r, np.array(planted)])
+    return lines_of(allr[rs.permutation(allr.shape[0])]), mers

@@ -1,7 +1,7 @@
 // fileio.h -- the two file <-> HBM movers of the library, shared by ingest.hip (FASTQ in), verify.hip (decoded reads out), fastq_out.hip (both at once) and, through
 // packfile.h, qpack.hip and idpack.hip: FileFeeder reads a file into device memory, FileDrain writes device memory into a file, each through pinned slices of the
 // context's ring (c->feed_ring) worked by a few host threads.  Around them, once each, what every file-level call needs: the probes of a file (size, first line, last
-// byte), the guards of an output file and of a context, the split of the ring, an owning device buffer, a kernel timer, and a text whose cut tail is carried on.
+// byte), whole files read and written, the guards of an output file and of a context, the split of the ring, an owning device buffer, a kernel timer, and a text whose cut tail is carried on.
 #pragma once
 #include "internal.h"
 #include <string>
@@ -39,6 +39,11 @@ static inline void harc_ring_geom_env(RingGeom *g)
 }
 
 static inline double mono_now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
+// HARC_AMD_TRACE: "<tag> <what>: <seconds since the last lap> s" on stderr
+struct LapTimer {
+    const char *tag; bool on = getenv("HARC_AMD_TRACE") != nullptr; double t = mono_now();
+    void lap(const char *what) { if (on) { const double n = mono_now(); fprintf(stderr, "%s %s: %.3f s\n", tag, what, n - t); t = n; } }
+};
 
 // ------------------------------------------------------------------------------------------------ what the file-level calls share
 static inline bool file_size(const char *path, uint64_t *n) { struct stat st; if (stat(path, &st) != 0 || !S_ISREG(st.st_mode)) return false; *n = (uint64_t)st.st_size; return true; }   // regular files only
@@ -65,6 +70,34 @@ static inline int last_byte_is_newline(const char *path, bool *yes)
     fclose(g);
     *yes = last == '\n';
     return HARC_AMD_OK;
+}
+// A whole file into host memory.  A file that is not there: an error when it must exist, otherwise an empty `out` and true with no error set
+template <class T> static inline bool slurp_file(const std::string &path, std::vector<T> &out, bool must_exist)
+{
+    out.clear();
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) { if (must_exist) harc_set_error("cannot open %s", path.c_str()); return !must_exist; }
+    fseek(f, 0, SEEK_END); long n = ftell(f); fseek(f, 0, SEEK_SET);
+    out.resize((size_t)n);
+    const bool ok = n == 0 || fread(out.data(), 1, (size_t)n, f) == (size_t)n;
+    fclose(f);
+    if (!ok) harc_set_error("short read on %s", path.c_str());
+    return ok;
+}
+// Host memory, or a stream of the context, as a whole file
+static inline int spit_file(const std::string &path, const void *p, size_t n)
+{
+    FILE *o = fopen(path.c_str(), "wb");
+    if (!o) { harc_set_error("cannot create %s", path.c_str()); return HARC_AMD_EIO; }
+    if (n && fwrite(p, 1, n, o) != n) { fclose(o); harc_set_error("short write on %s", path.c_str()); return HARC_AMD_EIO; }
+    fclose(o);
+    return HARC_AMD_OK;
+}
+static inline int spit_stream(harc_amd_ctx *c, int id, int shard, const std::string &path)
+{
+    const void *p = nullptr; size_t n = 0;
+    RC_TRY(harc_amd_get_stream(c, id, shard, &p, &n));
+    return spit_file(path, p, n);
 }
 // The output file is removed unless the call reaches its end.  Declare it in front of the FileDrain: it goes after the drain has closed the file
 struct OutFileGuard { std::string path; bool ok = false; ~OutFileGuard() { if (!ok) (void)remove(path.c_str()); } };

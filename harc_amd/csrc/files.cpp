@@ -8,40 +8,13 @@
 //   pack_order.out <basedir> src/pack_order.cpp:11-77  rewrites read_order.bin, writes read_order.bin.tail
 #include "fileio.h"
 
-static bool slurp(const std::string &path, std::vector<char> &out, bool must_exist)
-{
-    out.clear();
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) { if (must_exist) harc_set_error("cannot open %s", path.c_str()); return !must_exist; }
-    fseek(f, 0, SEEK_END); long n = ftell(f); fseek(f, 0, SEEK_SET);
-    out.resize((size_t)n);
-    bool ok = n == 0 || fread(out.data(), 1, (size_t)n, f) == (size_t)n;
-    fclose(f);
-    if (!ok) harc_set_error("short read on %s", path.c_str());
-    return ok;
-}
-static int spit(const std::string &path, const void *p, size_t n)
-{
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f) { harc_set_error("cannot create %s", path.c_str()); return HARC_AMD_EIO; }
-    if (n && fwrite(p, 1, n, f) != n) { fclose(f); harc_set_error("short write on %s", path.c_str()); return HARC_AMD_EIO; }
-    fclose(f);
-    return HARC_AMD_OK;
-}
-static int spit_stream(harc_amd_ctx *c, int id, int shard, const std::string &path)
-{
-    const void *p = nullptr; size_t n = 0;
-    RC_TRY(harc_amd_get_stream(c, id, shard, &p, &n));
-    return spit(path, p, n);
-}
-
 static int load_clean(harc_amd_ctx *c, const std::string &od)
 {
     const int L = c->P.readlen;
     std::vector<char> nb, dna;
-    if (!slurp(od + "numreads.bin", nb, true) || nb.size() < 4) { harc_set_error("numreads.bin missing or short"); return HARC_AMD_EIO; }
+    if (!slurp_file(od + "numreads.bin", nb, true) || nb.size() < 4) { harc_set_error("numreads.bin missing or short"); return HARC_AMD_EIO; }
     uint32_t N; memcpy(&N, nb.data(), 4);                                          // reorder.cpp:112-113
-    if (!slurp(od + "input_clean.dna", dna, true)) return HARC_AMD_EIO;
+    if (!slurp_file(od + "input_clean.dna", dna, true)) return HARC_AMD_EIO;
     if (dna.size() < (size_t)N * (L + 1)) { harc_set_error("input_clean.dna holds fewer than %u lines of %d bases", N, L); return HARC_AMD_EIO; }
     return harc_amd_set_reads_ascii(c, dna.data(), N, (uint32_t)L + 1);             // (readlen+1) stride, reorder.cpp:252
 }
@@ -49,7 +22,7 @@ static int load_N(harc_amd_ctx *c, const std::string &od)
 {
     const int L = c->P.readlen;
     std::vector<char> n;
-    if (!slurp(od + "input_N.dna", n, false)) return HARC_AMD_EIO;
+    if (!slurp_file(od + "input_N.dna", n, false)) return HARC_AMD_EIO;
     return harc_amd_set_nreads_ascii(c, n.data(), (uint32_t)(n.size() / (L + 1)), (uint32_t)L + 1);   // encoder.cpp:804-808
 }
 static int write_stage1(harc_amd_ctx *c, const std::string &od)
@@ -63,25 +36,49 @@ static int write_stage1(harc_amd_ctx *c, const std::string &od)
     RC_TRY(spit_stream(c, HARC_AMD_S1_ORDER_SINGLETON, 0, od + "read_order.bin.singleton"));
     return HARC_AMD_OK;
 }
+// ---- the archive's stage-II files, stated once: the per-shard family read_{seq,pos,noise,noisepos,rev}.txt.<first_shard + e> (+ .tail) of
+// encoder.cpp:190-196, then the six files that exist once per job.
+// The family goes stream by stream, the largest first: when HARC_AMD_READY_FD names an open descriptor (./harc passes a pipe), the name of every stream is
+// written to it as soon as all its shard files are closed, and ./harc starts that stream's stage-III coder (harc:102-109) while the next
+// stream is still being written.
+static void announce_stream(const char *stem)
+{
+    const char *e = getenv("HARC_AMD_READY_FD");
+    if (!e) return;
+    const int fd = atoi(e);
+    if (fd < 3) return;
+    const std::string line = std::string(stem) + "\n";
+    (void)!write(fd, line.data(), line.size());
+}
+// the stream files of the context's encoder shards [e_lo, e_hi) (e_hi < 0: all) as read_*.txt.<first_shard + e>
+int write_shard_family(harc_amd_ctx *c, const std::string &od, int first_shard, int e_lo, int e_hi)
+{
+    if (e_hi < 0) e_hi = c->P.num_thr;
+    static const struct { int id; const char *name; int tail; } files[] = {
+        { HARC_AMD_S2_SEQ, "read_seq", HARC_AMD_S2_SEQ_TAIL }, { HARC_AMD_S2_POS, "read_pos", -1 }, { HARC_AMD_S2_NOISE, "read_noise", -1 },
+        { HARC_AMD_S2_NOISEPOS, "read_noisepos", -1 }, { HARC_AMD_S2_REV, "read_rev", HARC_AMD_S2_REV_TAIL } };
+    for (auto &fd : files) {
+        for (int e = e_lo; e < e_hi; e++) {
+            const std::string path = od + fd.name + ".txt." + std::to_string(first_shard + e);
+            RC_TRY(spit_stream(c, fd.id, e, path));
+            if (fd.tail >= 0) RC_TRY(spit_stream(c, fd.tail, e, path + ".tail"));
+        }
+        if (first_shard == 0) announce_stream(fd.name);
+    }
+    return HARC_AMD_OK;
+}
+int write_whole_job_files(harc_amd_ctx *c, const std::string &od)
+{
+    static const struct { int id; const char *name; } whole[] = {
+        { HARC_AMD_S2_ORDER, "read_order.bin" }, { HARC_AMD_S2_ORDER_N_PE, "read_order_N_pe.bin" }, { HARC_AMD_S2_INPUT_N, "input_N.dna" },
+        { HARC_AMD_S2_META, "read_meta.txt" }, { HARC_AMD_S2_SINGLETON, "read_singleton.txt" }, { HARC_AMD_S2_SINGLETON_TAIL, "read_singleton.txt.tail" } };
+    for (auto &fd : whole) RC_TRY(spit_stream(c, fd.id, 0, od + fd.name));
+    return HARC_AMD_OK;
+}
 static int write_stage2(harc_amd_ctx *c, const std::string &od)
 {
-    for (int e = 0; e < c->P.num_thr; e++) {
-        const std::string s = "." + std::to_string(e);
-        RC_TRY(spit_stream(c, HARC_AMD_S2_SEQ, e, od + "read_seq.txt" + s));
-        RC_TRY(spit_stream(c, HARC_AMD_S2_SEQ_TAIL, e, od + "read_seq.txt" + s + ".tail"));
-        RC_TRY(spit_stream(c, HARC_AMD_S2_POS, e, od + "read_pos.txt" + s));
-        RC_TRY(spit_stream(c, HARC_AMD_S2_NOISE, e, od + "read_noise.txt" + s));
-        RC_TRY(spit_stream(c, HARC_AMD_S2_NOISEPOS, e, od + "read_noisepos.txt" + s));
-        RC_TRY(spit_stream(c, HARC_AMD_S2_REV, e, od + "read_rev.txt" + s));
-        RC_TRY(spit_stream(c, HARC_AMD_S2_REV_TAIL, e, od + "read_rev.txt" + s + ".tail"));
-    }
-    RC_TRY(spit_stream(c, HARC_AMD_S2_ORDER, 0, od + "read_order.bin"));
-    RC_TRY(spit_stream(c, HARC_AMD_S2_ORDER_N_PE, 0, od + "read_order_N_pe.bin"));
-    RC_TRY(spit_stream(c, HARC_AMD_S2_INPUT_N, 0, od + "input_N.dna"));
-    RC_TRY(spit_stream(c, HARC_AMD_S2_META, 0, od + "read_meta.txt"));
-    RC_TRY(spit_stream(c, HARC_AMD_S2_SINGLETON, 0, od + "read_singleton.txt"));
-    RC_TRY(spit_stream(c, HARC_AMD_S2_SINGLETON_TAIL, 0, od + "read_singleton.txt.tail"));
-    return HARC_AMD_OK;
+    RC_TRY(write_shard_family(c, od, 0, 0, -1));
+    return write_whole_job_files(c, od);
 }
 
 extern "C" int harc_amd_reorder_files(const harc_amd_params *params, const char *basedir)
@@ -104,9 +101,9 @@ extern "C" int harc_amd_encoder_files(const harc_amd_params *params, const char 
     const int L = params->readlen;
     const std::string od = std::string(basedir) + "/output/";
     std::vector<char> dna, flag, pos, order, rc, dna_s, order_s;
-    if (!slurp(od + "temp.dna", dna, true) || !slurp(od + "tempflag.txt", flag, true) || !slurp(od + "temppos.txt", pos, true) ||
-        !slurp(od + "read_order.bin", order, true) || !slurp(od + "read_rev.txt", rc, true) ||
-        !slurp(od + "temp.dna.singleton", dna_s, true) || !slurp(od + "read_order.bin.singleton", order_s, true)) return HARC_AMD_EIO;
+    if (!slurp_file(od + "temp.dna", dna, true) || !slurp_file(od + "tempflag.txt", flag, true) || !slurp_file(od + "temppos.txt", pos, true) ||
+        !slurp_file(od + "read_order.bin", order, true) || !slurp_file(od + "read_rev.txt", rc, true) ||
+        !slurp_file(od + "temp.dna.singleton", dna_s, true) || !slurp_file(od + "read_order.bin.singleton", order_s, true)) return HARC_AMD_EIO;
     const uint32_t M = (uint32_t)(order.size() / 4), S = (uint32_t)(dna_s.size() / (L + 1));           // encoder.cpp:781-803
     if (dna.size() < (size_t)M * (L + 1) || flag.size() < M || pos.size() < M || rc.size() < M || order_s.size() < (size_t)S * 4) {
         harc_set_error("stage-I files are inconsistent"); return HARC_AMD_EIO;
@@ -146,7 +143,7 @@ extern "C" int harc_amd_pack_order_files(const harc_amd_params *params, const ch
     CtxGuard g; RC_TRY(harc_amd_create(params, &g.c));
     const std::string od = std::string(basedir) + "/output/";
     std::vector<char> in;
-    if (!slurp(od + "read_order.bin", in, true)) return HARC_AMD_EIO;
+    if (!slurp_file(od + "read_order.bin", in, true)) return HARC_AMD_EIO;
     std::vector<uint8_t> &b = out_buf(g.c, HARC_AMD_S2_ORDER, 0);
     b.assign(in.begin(), in.end());
     g.c->have_s2 = true;
@@ -198,7 +195,7 @@ extern "C" int harc_amd_preprocess_files(const char *fastq, const char *basedir,
     if (rc != HARC_AMD_OK) return rc;
     if (readnum > 4294967290ull) { printf("Too many reads. HARC supports at most 4294967290 reads\n"); harc_set_error("too many reads"); return HARC_AMD_EINVAL; }   // :122-126
     const uint32_t n32 = (uint32_t)nclean;
-    RC_TRY(spit(od + "numreads.bin", &n32, 4));
+    RC_TRY(spit_file(od + "numreads.bin", &n32, 4));
     printf("Read length: %d\nTotal number of reads: %llu\nTotal number of reads without N: %llu\nPreprocessing Done!\n", readlen,
            (unsigned long long)readnum, (unsigned long long)nclean);
     return HARC_AMD_OK;
@@ -239,7 +236,7 @@ extern "C" int harc_amd_merge_shard_files(const char *basedir, int32_t world)
     int L = 0; unsigned long long nrec = 0, nclean = 0, unmatched = 0, al_s = 0, al_N = 0;
     for (int r = 0; r < world; r++) {
         std::vector<char> st;
-        if (!slurp(part("stats", r), st, true)) { harc_set_error("rank %d left no result under %s", r, sd.c_str()); return HARC_AMD_EIO; }
+        if (!slurp_file(part("stats", r), st, true)) { harc_set_error("rank %d left no result under %s", r, sd.c_str()); return HARC_AMD_EIO; }
         st.push_back(0);
         int l = 0; unsigned long long v[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
         if (sscanf(st.data(), "%d %llu %llu %llu %llu %llu %llu %llu %llu", &l, &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7]) != 9) { harc_set_error("stats of rank %d unreadable", r); return HARC_AMD_EIO; }
@@ -265,7 +262,7 @@ extern "C" int harc_amd_merge_shard_files(const char *basedir, int32_t world)
         std::vector<char> in, tail; std::vector<uint8_t> outb;
         auto code = [](char ch) -> unsigned { return ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : 3u; };
         for (int r = 0; r < world; r++) {
-            if (!slurp(part("singleton", r), in, true) || !slurp(part("singleton_tail", r), tail, true)) return HARC_AMD_EIO;
+            if (!slurp_file(part("singleton", r), in, true) || !slurp_file(part("singleton_tail", r), tail, true)) return HARC_AMD_EIO;
             if (npend == 0) RC_TRY(sg.add(in.data(), in.size()));
             else {
                 outb.resize(in.size());
@@ -279,10 +276,10 @@ extern "C" int harc_amd_merge_shard_files(const char *basedir, int32_t world)
             }
         }
         char t[4]; for (int k = 0; k < npend; k++) t[k] = "ACGT"[(pend >> (2 * k)) & 3];
-        RC_TRY(spit(od + "read_singleton.txt.tail", t, (size_t)npend));
+        RC_TRY(spit_file(od + "read_singleton.txt.tail", t, (size_t)npend));
     }
-    { const uint32_t n32 = (uint32_t)nclean; RC_TRY(spit(od + "numreads.bin", &n32, 4)); }
-    { char m[32]; const int ml = snprintf(m, sizeof m, "%d\n", L); RC_TRY(spit(od + "read_meta.txt", m, (size_t)ml)); }
+    { const uint32_t n32 = (uint32_t)nclean; RC_TRY(spit_file(od + "numreads.bin", &n32, 4)); }
+    { char m[32]; const int ml = snprintf(m, sizeof m, "%d\n", L); RC_TRY(spit_file(od + "read_meta.txt", m, (size_t)ml)); }
     {   // -q -p: quality values and ids in file order = the slices in rank order
         FILE *probe = fopen(part("quality", 0).c_str(), "rb");
         if (probe) {

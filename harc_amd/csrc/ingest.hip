@@ -6,16 +6,6 @@
 #include "devutil.h"
 #include "inflate_member.h"
 #include "fileio.h"
-#include <string>
-#include <sys/stat.h>
-#include <unistd.h>
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <atomic>
-#include <condition_variable>
-#include <deque>
-#include <mutex>
-#include <thread>
 
 // line index in two levels: newlines per 4096-byte tile -> scan of the tile counts -> positions written tile by tile
 #define NL_TILE 4096
@@ -93,7 +83,7 @@ __global__ void k_ingest_pack3(const char *txt, const uint64_t *nl, const uint32
 #define G256(n) harc_grid256((uint64_t)(n)), dim3(256), 0, c->stream
 
 // nls[k] = byte position of the newline that ends line k (a last line without one ends at nbytes); nls[-1] = (u64)-1 so that line k
-// starts at nls[k-1]+1 for every k.  Pool memory: the caller brackets it with harc_pool_mark / release.
+// starts at nls[k-1]+1 for every k.  Pool memory: the caller brackets it with a PoolScope.
 int build_line_index(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const uint64_t **nls_out, uint64_t *total_lines_out)
 {
     const uint64_t ntiles = (nbytes + NL_TILE - 1) / NL_TILE;
@@ -124,10 +114,10 @@ int build_line_index(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const 
 struct IngestState {
     uint64_t nC = 0, nN = 0, nrec = 0, nfull = 0;                 // clean reads, reads with N, reads, complete records so far
     std::vector<uint32_t> orderN;                                 // read_order_N.bin: record number of every read with N (preprocess.cpp:102)
-    // -q without -p on a file that does not stay in HBM (emit_quality_and_ids_streamed): the length of every id line, the lines the file holds
+    uint64_t total_lines = 0;                                     // the lines the text holds (-q without -p, q_plan: a last record may be cut short)
+    // -q without -p on a file that does not stay in HBM (emit_quality_and_ids_streamed): the length of every id line
     bool want_idlen = false;
     std::vector<uint32_t> idlen;
-    uint64_t total_lines = 0;
 };
 __global__ void k_q_idlen(const uint64_t *nls, uint32_t nid, uint32_t *len)
 {
@@ -160,8 +150,7 @@ static int ingest_append(harc_amd_ctx *c, IngestState &st, const char *d_txt, ui
 {
     if (nbytes == 0) return HARC_AMD_OK;
     const int L = c->P.readlen;
-    const harc_mark_t mk = harc_pool_mark(c);
-    struct Rel { harc_amd_ctx *c; harc_mark_t mk; ~Rel() { harc_pool_release(c, mk); } } rel{ c, mk };       // scratch goes on every way out
+    PoolScope scope(c);                                           // scratch goes on every way out
     const uint64_t *nls = nullptr; uint64_t total_lines = 0;
     RC_TRY(build_line_index(c, d_txt, nbytes, &nls, &total_lines));
     if (!last && (total_lines % 4)) { harc_set_error("FASTQ: a piece of the file does not hold whole 4-line records (%llu lines)", (unsigned long long)total_lines); return HARC_AMD_EINVAL; }
@@ -244,6 +233,16 @@ extern "C" int harc_amd_set_fastq_device(harc_amd_ctx *c, const char *d_txt, uin
 // ------------------------------------------------------------------------------------------------ -q: ids and quality values
 // preprocess.cpp:61-118 + reorder_quality.cpp as gathers over the line index.  `rec[p]` names the record whose
 // line `k` (0 = id, 3 = quality) becomes output line p.
+// the N flags of k_classify again, from read_order_N.bin
+__global__ void k_q_scatter_flag(const uint32_t *idx, uint32_t n, uint32_t lim, uint32_t *flag, unsigned int *err)
+{
+    const uint32_t i = harc_gid32();
+    if (i >= n) return;
+    const uint32_t r = idx[i];
+    if (r >= lim) { atomicAdd(err, 1u); return; }
+    flag[r] = 1u;
+}
+__global__ void k_q_not(const uint32_t *isN, uint32_t n, uint32_t *isC) { const uint32_t r = harc_gid32(); if (r < n) isC[r] = isN[r] ? 0u : 1u; }
 __global__ void k_q_idflags(const uint32_t *isN, uint32_t nid, uint32_t *idC, uint32_t *idN)
 {
     const uint32_t r = harc_gid32();
@@ -287,15 +286,27 @@ __global__ __launch_bounds__(256) void k_q_copy(const char *txt, const uint64_t 
     if (lane == 0) o[l] = '\n';
 }
 
+// device memory -> an open file, behind what is on the stream
+static int write_device_range(harc_amd_ctx *c, const char *d, size_t n, FILE *fo)
+{
+    std::vector<uint8_t> host;
+    const size_t CH = (size_t)256 << 20;
+    for (size_t at = 0; at < n; at += CH) {
+        const size_t m = n - at < CH ? n - at : CH;
+        RC_TRY(harc_d2h(c, host, d + at, m));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (fwrite(host.data(), 1, m, fo) != m) { harc_set_error("short write"); return HARC_AMD_EIO; }
+    }
+    return HARC_AMD_OK;
+}
+
 static int emit_lines(harc_amd_ctx *c, const char *d_txt, const uint64_t *nls, const uint32_t *rec, uint64_t n, int k, int want, FILE *fo)
 {
     const uint32_t CH = 1u << 23;
     unsigned int *d_err = nullptr; RC_TRY(dalloc(c, &d_err, 4));
     HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
-    std::vector<uint8_t> host;
     for (uint64_t at = 0; at < n; at += CH) {
-        const harc_mark_t mk = harc_pool_mark(c);
-        struct Rel { harc_amd_ctx *c; harc_mark_t mk; ~Rel() { harc_pool_release(c, mk); } } rel{ c, mk };
+        PoolScope scope(c);
         const uint32_t m = (uint32_t)(n - at < CH ? n - at : CH);
         uint32_t *len = nullptr; uint64_t *off = nullptr;
         RC_TRY(dalloc(c, &len, (size_t)m + 1)); RC_TRY(dalloc(c, &off, (size_t)m + 1));
@@ -309,9 +320,7 @@ static int emit_lines(harc_amd_ctx *c, const char *d_txt, const uint64_t *nls, c
         if (err) { harc_set_error("-q without -p needs quality lines of exactly readlen characters (%u differ)", err); return HARC_AMD_EINVAL; }
         char *out = nullptr; RC_TRY(dalloc(c, &out, (size_t)total + 16));
         hipLaunchKernelGGL(k_q_copy, dim3((m + 3) / 4), dim3(256), 0, c->stream, d_txt, nls, rec + at, (const uint64_t *)off, m, k, out);
-        RC_TRY(harc_d2h(c, host, out, (size_t)total));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (total && fwrite(host.data(), 1, (size_t)total, fo) != (size_t)total) { harc_set_error("short write"); return HARC_AMD_EIO; }
+        RC_TRY(write_device_range(c, out, (size_t)total, fo));
     }
     return HARC_AMD_OK;
 }
@@ -320,8 +329,7 @@ static int emit_lines(harc_amd_ctx *c, const char *d_txt, const uint64_t *nls, c
 static int emit_q_fileorder(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, FILE *fq, FILE *fi)
 {
     if (nbytes == 0) return HARC_AMD_OK;
-    const harc_mark_t mk = harc_pool_mark(c);
-    struct Rel { harc_amd_ctx *c; harc_mark_t mk; ~Rel() { harc_pool_release(c, mk); } } rel{ c, mk };
+    PoolScope scope(c);
     const uint64_t *nls = nullptr; uint64_t total_lines = 0;
     RC_TRY(build_line_index(c, d_txt, nbytes, &nls, &total_lines));
     const uint32_t nrec = (uint32_t)(total_lines / 4);
@@ -379,39 +387,60 @@ static int q_routes(harc_amd_ctx *c, const uint32_t *isN, const uint32_t *isC, u
     return HARC_AMD_OK;
 }
 
-static int emit_quality_and_ids(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, bool preserve_order, const std::string &od, const char *qname, const char *iname)
+// output.quality and output.id of an archive, or the quality / id parts of a rank: both are there or the call fails, both are closed on every way out
+struct QIdFiles {
+    FILE *fq = nullptr, *fi = nullptr;
+    ~QIdFiles() { if (fq) fclose(fq); if (fi) fclose(fi); }
+    bool open2(const std::string &q, const std::string &i) { fq = fopen(q.c_str(), "wb"); fi = fopen(i.c_str(), "wb"); return fq && fi; }
+    int open(const std::string &od)
+    {
+        if (open2(od + "output.quality", od + "output.id")) return HARC_AMD_OK;
+        harc_set_error("cannot create %soutput.quality / output.id", od.c_str()); return HARC_AMD_EIO;
+    }
+    int open_parts(const std::string &sd, const std::string &r)
+    {
+        if (open2(sd + "quality" + r, sd + "id" + r)) return HARC_AMD_OK;
+        harc_set_error("cannot create the quality / id parts under %s", sd.c_str()); return HARC_AMD_EIO;
+    }
+};
+
+// -q without -p, what the walk over the resident text and the walk over the streamed file share: the refusal of a truncated last record, the counts, the
+// per-record flags (from read_order_N.bin as the ingest kept it) and the routes.  Pool memory of the caller's bracket.
+struct QPlan { uint32_t nrec = 0, nid = 0, nidN = 0; uint32_t *qrec = nullptr, *irec = nullptr; unsigned int *d_err = nullptr; };     // d_err: zero on return
+static int q_plan(harc_amd_ctx *c, const IngestState &st, QPlan *q)
 {
-    FILE *fq = fopen((od + qname).c_str(), "wb"), *fi = fopen((od + iname).c_str(), "wb");
-    struct Closer { FILE *a, *b; ~Closer() { if (a) fclose(a); if (b) fclose(b); } } closer{ fq, fi };
-    if (!fq || !fi) { harc_set_error("cannot create %soutput.quality / output.id", od.c_str()); return HARC_AMD_EIO; }
-    if (nbytes == 0) return HARC_AMD_OK;
-    const int L = c->P.readlen;
-    const harc_mark_t mk = harc_pool_mark(c);
-    struct Rel { harc_amd_ctx *c; harc_mark_t mk; ~Rel() { harc_pool_release(c, mk); } } rel{ c, mk };
-    const uint64_t *nls = nullptr; uint64_t total_lines = 0;
-    RC_TRY(build_line_index(c, d_txt, nbytes, &nls, &total_lines));
-    const uint32_t nrec = (uint32_t)(total_lines / 4);
-    const uint32_t nid = nrec + (total_lines % 4 ? 1u : 0u);       // the id line of a truncated last record is still written (case 0 of the getline loop)
-    if (!preserve_order && (total_lines % 4) >= 2) {               // that read has no quality line: reorder_quality.cpp would walk off its arrays
+    if ((st.total_lines % 4) >= 2) {                              // that read has no quality line: reorder_quality.cpp would walk off its arrays
         harc_set_error("-q without -p: the last FASTQ record is truncated (its read is kept, its quality line is missing)"); return HARC_AMD_EINVAL;
     }
-    if (preserve_order) {                                          // preprocess.cpp:64-69: both files in file order
-        uint32_t *rec = nullptr; RC_TRY(dalloc(c, &rec, (size_t)nid + 1));
-        hipLaunchKernelGGL(k_q_iota, G256((size_t)nid + 1), rec, nid + 1);
-        RC_TRY(emit_lines(c, d_txt, nls, rec, nrec, 3, -1, fq));
-        RC_TRY(emit_lines(c, d_txt, nls, rec, nid, 0, -1, fi));
-        return HARC_AMD_OK;
-    }
-    uint32_t *isN, *isC; unsigned int *d_err;
-    RC_TRY(dalloc(c, &isN, (size_t)nid + 1)); RC_TRY(dalloc(c, &isC, (size_t)nid + 1)); RC_TRY(dalloc(c, &d_err, 4));
-    HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
+    const uint32_t nrec = (uint32_t)st.nfull;
+    const uint32_t nid = nrec + (st.total_lines % 4 ? 1u : 0u);    // the id line of a truncated last record is still written (case 0 of the getline loop)
+    uint32_t *isN, *isC;
+    RC_TRY(dalloc(c, &isN, (size_t)nid + 1)); RC_TRY(dalloc(c, &isC, (size_t)nid + 1)); RC_TRY(dalloc(c, &q->d_err, 4));
+    HIP_TRY(hipMemsetAsync(q->d_err, 0, 16, c->stream));
     HIP_TRY(hipMemsetAsync(isN, 0, ((size_t)nid + 1) * 4, c->stream)); HIP_TRY(hipMemsetAsync(isC, 0, ((size_t)nid + 1) * 4, c->stream));
-    if (nrec) hipLaunchKernelGGL(k_classify, G256(nrec), d_txt, nls, nrec, L, isN, isC, d_err);
-    uint32_t *qrec = nullptr, *irec = nullptr, nidN = 0;
-    RC_TRY(q_routes(c, isN, isC, nrec, nid, d_err, &qrec, &irec, &nidN));
-    const uint32_t nC = c->N, nN = c->NN;
-    RC_TRY(emit_lines(c, d_txt, nls, qrec, (uint64_t)nC + nN, 3, L, fq));
-    RC_TRY(emit_lines(c, d_txt, nls, irec, (uint64_t)nC + nidN, 0, -1, fi));
+    {
+        PoolScope tmp(c);
+        const uint32_t nN = (uint32_t)st.orderN.size();
+        uint32_t *d_on = nullptr; RC_TRY(dalloc(c, &d_on, (size_t)nN + 1));
+        if (nN) { HIP_TRY(hipMemcpyAsync(d_on, st.orderN.data(), (size_t)nN * 4, hipMemcpyHostToDevice, c->stream)); hipLaunchKernelGGL(k_q_scatter_flag, G256(nN), d_on, nN, nrec, isN, q->d_err); }
+        if (nrec) hipLaunchKernelGGL(k_q_not, G256(nrec), isN, nrec, isC);
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    q->nrec = nrec; q->nid = nid;
+    return q_routes(c, isN, isC, nrec, nid, q->d_err, &q->qrec, &q->irec, &q->nidN);
+}
+
+// the text is resident: the line index of the whole text, the output lines gathered through it
+static int emit_quality_and_ids(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const IngestState &st, const std::string &od)
+{
+    QIdFiles out; RC_TRY(out.open(od));
+    if (nbytes == 0) return HARC_AMD_OK;
+    PoolScope scope(c);
+    QPlan q; RC_TRY(q_plan(c, st, &q));
+    const uint64_t *nls = nullptr; uint64_t total_lines = 0;
+    RC_TRY(build_line_index(c, d_txt, nbytes, &nls, &total_lines));
+    RC_TRY(emit_lines(c, d_txt, nls, q.qrec, (uint64_t)c->N + c->NN, 3, c->P.readlen, out.fq));
+    RC_TRY(emit_lines(c, d_txt, nls, q.irec, (uint64_t)c->N + q.nidN, 0, -1, out.fi));
     return HARC_AMD_OK;
 }
 
@@ -420,15 +449,6 @@ static int emit_quality_and_ids(harc_amd_ctx *c, const char *d_txt, uint64_t nby
 // flags and the id-line lengths kept by the ingest; the OUTPUT is cut into bins that fit HBM, and for every bin the FASTQ file is streamed
 // through the GPU once more, piece by piece, every line that belongs to the bin copied to its place (quality lines have a fixed stride -- they
 // must be readlen long, reorder_quality.cpp:78-79 -- id lines go by a prefix sum of their lengths).  Quality and id bins share a pass.
-__global__ void k_q_scatter_flag(const uint32_t *idx, uint32_t n, uint32_t lim, uint32_t *flag, unsigned int *err)
-{
-    const uint32_t i = harc_gid32();
-    if (i >= n) return;
-    const uint32_t r = idx[i];
-    if (r >= lim) { atomicAdd(err, 1u); return; }
-    flag[r] = 1u;
-}
-__global__ void k_q_not(const uint32_t *isN, uint32_t n, uint32_t *isC) { const uint32_t r = harc_gid32(); if (r < n) isC[r] = isN[r] ? 0u : 1u; }
 __global__ void k_q_invert(const uint32_t *rec, uint32_t n, uint32_t *pos) { const uint32_t p = harc_gid32(); if (p < n) pos[rec[p]] = p; }
 __global__ void k_q_outlen(const uint32_t *idlen, const uint32_t *rec, uint32_t n, uint32_t *len) { const uint32_t p = harc_gid32(); if (p < n) len[p] = idlen[rec[p]] + 1u; }
 // first p in [lo, n] with off[p] - off[lo] > budget, minus one (at least lo + 1 when lo < n): the end of the bin that starts at lo
@@ -470,7 +490,6 @@ __global__ __launch_bounds__(256) void k_q_place(const char *txt, const uint64_t
         }
     }
 }
-static int load_file_range(harc_amd_ctx *c, FILE *f, const char *name, uint64_t lo, uint64_t hi, char **d_txt);
 static int record_start_at_or_after(FILE *f, uint64_t pos, uint64_t fsz, uint64_t *out);
 template <class F> static int text_pieces(harc_amd_ctx *c, FILE *f, const char *name, uint64_t lo, uint64_t end, uint64_t fsz, bool bgzf,
                                           double *t_wait, double *t_inflate, F &&fn);
@@ -478,47 +497,18 @@ template <class F> static int text_pieces(harc_amd_ctx *c, FILE *f, const char *
 // member and a piece of 1 GiB holds ~27 000 of them, too few to fill the chip (NOTES.md, BGZF); HARC_AMD_INGEST_CHUNK in tests (pieces of a few records)
 static uint64_t ingest_piece_bytes(bool bgzf)
 {
-    uint64_t piece = (uint64_t)1 << (bgzf ? 32 : 30);
-    if (const char *e = getenv("HARC_AMD_INGEST_CHUNK")) { piece = strtoull(e, nullptr, 10); if (piece < 16) piece = 16; }
-    return piece;
+    const uint64_t piece = env_u64("HARC_AMD_INGEST_CHUNK", (uint64_t)1 << (bgzf ? 32 : 30));
+    return piece < 16 ? 16 : piece;
 }
-static int write_device_range(harc_amd_ctx *c, const char *d, size_t n, FILE *fo)
+static int emit_quality_and_ids_streamed(harc_amd_ctx *c, FILE *f, const char *name, uint64_t fsz, bool bgzf, const IngestState &st, const std::string &od)
 {
-    std::vector<uint8_t> host;
-    const size_t CH = (size_t)256 << 20;
-    for (size_t at = 0; at < n; at += CH) {
-        const size_t m = n - at < CH ? n - at : CH;
-        RC_TRY(harc_d2h(c, host, d + at, m));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (fwrite(host.data(), 1, m, fo) != m) { harc_set_error("short write"); return HARC_AMD_EIO; }
-    }
-    return HARC_AMD_OK;
-}
-static int emit_quality_and_ids_streamed(harc_amd_ctx *c, FILE *f, const char *name, uint64_t fsz, bool bgzf, const IngestState &st, const std::string &od, const char *qname, const char *iname)
-{
-    FILE *fq = fopen((od + qname).c_str(), "wb"), *fi = fopen((od + iname).c_str(), "wb");
-    struct Closer { FILE *a, *b; ~Closer() { if (a) fclose(a); if (b) fclose(b); } } closer{ fq, fi };
-    if (!fq || !fi) { harc_set_error("cannot create %soutput.quality / output.id", od.c_str()); return HARC_AMD_EIO; }
+    QIdFiles out; RC_TRY(out.open(od));
     if (fsz == 0) return HARC_AMD_OK;
     const int L = c->P.readlen;
-    if ((st.total_lines % 4) >= 2) { harc_set_error("-q without -p: the last FASTQ record is truncated (its read is kept, its quality line is missing)"); return HARC_AMD_EINVAL; }
-    const uint32_t nrec = (uint32_t)st.nfull, nid = nrec + (st.total_lines % 4 ? 1u : 0u);
-    if (st.idlen.size() != (size_t)nid) { harc_set_error("-q: %zu id lines recorded, %u expected", st.idlen.size(), nid); return HARC_AMD_EINTERNAL; }
     PoolScope scope(c);
-    uint32_t *isN, *isC; unsigned int *d_err;
-    RC_TRY(dalloc(c, &isN, (size_t)nid + 1)); RC_TRY(dalloc(c, &isC, (size_t)nid + 1)); RC_TRY(dalloc(c, &d_err, 4));
-    HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
-    HIP_TRY(hipMemsetAsync(isN, 0, ((size_t)nid + 1) * 4, c->stream)); HIP_TRY(hipMemsetAsync(isC, 0, ((size_t)nid + 1) * 4, c->stream));
-    {   // the N flags of k_classify, from read_order_N.bin
-        PoolScope tmp(c);
-        const uint32_t nN = (uint32_t)st.orderN.size();
-        uint32_t *d_on = nullptr; RC_TRY(dalloc(c, &d_on, (size_t)nN + 1));
-        if (nN) { HIP_TRY(hipMemcpyAsync(d_on, st.orderN.data(), (size_t)nN * 4, hipMemcpyHostToDevice, c->stream)); hipLaunchKernelGGL(k_q_scatter_flag, G256(nN), d_on, nN, nrec, isN, d_err); }
-        if (nrec) hipLaunchKernelGGL(k_q_not, G256(nrec), isN, nrec, isC);
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    uint32_t *qrec = nullptr, *irec = nullptr, nidN = 0;
-    RC_TRY(q_routes(c, isN, isC, nrec, nid, d_err, &qrec, &irec, &nidN));
+    QPlan q; RC_TRY(q_plan(c, st, &q));
+    const uint32_t nrec = q.nrec, nid = q.nid, nidN = q.nidN, *qrec = q.qrec, *irec = q.irec; unsigned int *d_err = q.d_err;
+    if (st.idlen.size() != (size_t)nid) { harc_set_error("-q: %zu id lines recorded, %u expected", st.idlen.size(), nid); return HARC_AMD_EINTERNAL; }
     const uint32_t nC = c->N, nN = c->NN, nQ = nC + nN, nI = nC + nidN;
     uint32_t *posQ, *posI, *d_idlen, *lenI, *d_end; uint64_t *offI;
     RC_TRY(dalloc(c, &posQ, (size_t)nrec + 1)); RC_TRY(dalloc(c, &posI, (size_t)nid + 1)); RC_TRY(dalloc(c, &d_idlen, (size_t)nid + 1));
@@ -538,7 +528,7 @@ static int emit_quality_and_ids_streamed(harc_amd_ctx *c, FILE *f, const char *n
         budget = (size_t)(0.25 * (double)fr);
         if (budget > ((size_t)32 << 30)) budget = (size_t)32 << 30;
         if (budget < ((size_t)64 << 20)) budget = (size_t)64 << 20;
-        if (const char *e = getenv("HARC_AMD_Q_BIN")) { const unsigned long long v = strtoull(e, nullptr, 10); if (v >= 1) budget = (size_t)v; }       // tests: bins of a few lines
+        budget = (size_t)env_u64("HARC_AMD_Q_BIN", budget);        // tests: bins of a few lines
     }
     uint32_t q0 = 0, i0 = 0; int passes = 0;
     while (q0 < nQ || i0 < nI) {
@@ -575,7 +565,7 @@ static int emit_quality_and_ids_streamed(harc_amd_ctx *c, FILE *f, const char *n
         HIP_TRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (err) { harc_set_error("-q without -p needs quality lines of exactly readlen characters (%u differ)", err); return HARC_AMD_EINVAL; }
-        RC_TRY(write_device_range(c, outQ, bytesQ, fq)); RC_TRY(write_device_range(c, outI, bytesI, fi));
+        RC_TRY(write_device_range(c, outQ, bytesQ, out.fq)); RC_TRY(write_device_range(c, outI, bytesI, out.fi));
         q0 = q1; i0 = i1; passes++;
     }
     if (getenv("HARC_AMD_TRACE")) fprintf(stderr, "[-q] quality values and ids permuted in %d passes over the FASTQ file (%zu bytes of each per pass)\n", passes, budget);
@@ -594,67 +584,31 @@ extern "C" int harc_amd_last_fastq_timing(double *out, int32_t n)
     for (int i = 0; i < n; i++) out[i] = i < 9 ? g_fastq_timing[i] : 0.0;
     return HARC_AMD_OK;
 }
-// bytes [lo, hi) of the file -> device memory; *d_txt is a raw allocation of the context
-static int load_file_range(harc_amd_ctx *c, FILE *f, const char *name, uint64_t lo, uint64_t hi, char **d_txt)
+// bytes [lo, hi) of the file -> device memory
+static int load_file_range(harc_amd_ctx *c, const char *name, uint64_t lo, uint64_t hi, DevBuf *b)
 {
-    (void)f;
-    *d_txt = nullptr;
     const uint64_t n = hi - lo;
-    RC_TRY(harc_raw_alloc(c, (void **)d_txt, (size_t)n + 16));
-    int rc = HARC_AMD_OK;
+    RC_TRY(dev_reserve(b, (size_t)n));
     if (n) {
         FileFeeder fd(c, name);
-        rc = fd.start({ { lo, hi } });
-        if (rc == HARC_AMD_OK) rc = fd.upload_piece(0, *d_txt, nullptr);
+        RC_TRY(fd.start({ { lo, hi } }));
+        RC_TRY(fd.upload_piece(0, b->p, nullptr));
     }
-    if (rc == HARC_AMD_OK && hipStreamSynchronize(c->stream) != hipSuccess) { harc_set_error("upload of %s failed", name); rc = HARC_AMD_ENODEVICE; }
-    if (rc != HARC_AMD_OK) { harc_raw_free(c, *d_txt); *d_txt = nullptr; }
-    return rc;
-}
-static int spit_file(const std::string &path, const void *p, size_t n)
-{
-    FILE *o = fopen(path.c_str(), "wb");
-    if (!o) { harc_set_error("cannot create %s", path.c_str()); return HARC_AMD_EIO; }
-    if (n && fwrite(p, 1, n, o) != n) { fclose(o); harc_set_error("short write on %s", path.c_str()); return HARC_AMD_EIO; }
-    fclose(o);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) { harc_set_error("upload of %s failed", name); return HARC_AMD_ENODEVICE; }
     return HARC_AMD_OK;
 }
-static int spit_stream_to(harc_amd_ctx *c, int id, int shard, const std::string &path)
-{
-    const void *p; size_t n;
-    RC_TRY(harc_amd_get_stream(c, id, shard, &p, &n));
-    return spit_file(path, p, n);
-}
-// read_{seq,pos,noise,noisepos,rev}.txt.<first_shard + e> (+ .tail): the per-shard family of encoder.cpp:190-196
-// Stream by stream, the largest first: when HARC_AMD_READY_FD names an open descriptor (./harc passes a pipe), the name of every stream is
-// written to it as soon as all its shard files are closed, and ./harc starts that stream's stage-III coder (harc:102-109) while the next
-// stream is still being written.
-static void announce_stream(const char *stem)
-{
-    const char *e = getenv("HARC_AMD_READY_FD");
-    if (!e) return;
-    const int fd = atoi(e);
-    if (fd < 3) return;
-    const std::string line = std::string(stem) + "\n";
-    (void)!write(fd, line.data(), line.size());
-}
-// the stream files of the context's encoder shards [e_lo, e_hi) (default: all) as read_*.txt.<first_shard + e>
-static int write_shard_family(harc_amd_ctx *c, const std::string &od, int first_shard, int e_lo = 0, int e_hi = -1)
-{
-    if (e_hi < 0) e_hi = c->P.num_thr;
-    static const struct { int id; const char *name; int tail; } files[] = {
-        { HARC_AMD_S2_SEQ, "read_seq", HARC_AMD_S2_SEQ_TAIL }, { HARC_AMD_S2_POS, "read_pos", -1 }, { HARC_AMD_S2_NOISE, "read_noise", -1 },
-        { HARC_AMD_S2_NOISEPOS, "read_noisepos", -1 }, { HARC_AMD_S2_REV, "read_rev", HARC_AMD_S2_REV_TAIL } };
-    for (auto &fd : files) {
-        for (int e = e_lo; e < e_hi; e++) {
-            const std::string path = od + fd.name + ".txt." + std::to_string(first_shard + e);
-            RC_TRY(spit_stream_to(c, fd.id, e, path));
-            if (fd.tail >= 0) RC_TRY(spit_stream_to(c, fd.tail, e, path + ".tail"));
-        }
-        if (first_shard == 0) announce_stream(fd.name);
+// the FASTQ input of a file-level call: open for the looks at the record boundaries (record_start_at_or_after), its size, closed on every way out
+struct InFile {
+    FILE *f = nullptr; uint64_t size = 0;
+    ~InFile() { if (f) fclose(f); }
+    int open(const char *path)
+    {
+        f = fopen(path, "rb");
+        if (!f) { harc_set_error("cannot open %s", path); return HARC_AMD_EIO; }
+        fseeko(f, 0, SEEK_END); size = (uint64_t)ftello(f);
+        return HARC_AMD_OK;
     }
-    return HARC_AMD_OK;
-}
+};
 
 // first byte >= pos at which a FASTQ record starts: a line that begins with '@' whose second successor begins with '+'.  (A quality
 // line may begin with '@' too, but then the line two further on is a sequence line, which never begins with '+'.)
@@ -709,9 +663,7 @@ template <class F> static int text_pieces(harc_amd_ctx *c, FILE *f, const char *
                                           double *t_wait, double *t_inflate, F &&fn)
 {
     const uint64_t piece = ingest_piece_bytes(bgzf);
-    const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
-    double tl = mono_now();
-    auto lap = [&](const char *what) { if (tlog) { const double t = mono_now(); fprintf(stderr, "[ingest] %s: %.3f s\n", what, t - tl); tl = t; } };
+    LapTimer tm{ "[ingest]" };
     const uint64_t SLOP = 65536;                                  // BGZF: a member is at most BSIZE + 1 = 65536 bytes
     // the pieces first, so that the readers can run ahead over all of them
     std::vector<std::pair<uint64_t, uint64_t>> pieces;            // file ranges that are read
@@ -732,35 +684,30 @@ template <class F> static int text_pieces(harc_amd_ctx *c, FILE *f, const char *
         }
     }
     if (pieces.empty()) return HARC_AMD_OK;
-    lap("piece boundaries");
+    tm.lap("piece boundaries");
     // two device buffers: piece i + 1 is uploaded (behind piece i's kernels on the stream) while the host still waits for piece i's counts
-    struct Bufs { harc_amd_ctx *c; char *p[4] = { nullptr, nullptr, nullptr, nullptr }; ~Bufs() { for (char *x : p) if (x) harc_raw_free(c, x); } } db{ c };
-    RC_TRY(harc_raw_alloc(c, (void **)&db.p[0], (size_t)maxlen + 16));
-    if (pieces.size() > 1) RC_TRY(harc_raw_alloc(c, (void **)&db.p[1], (size_t)maxlen + 16));
-    size_t tcap[2] = { 0, 0 };                                    // BGZF: the text buffers db.p[2 + (p & 1)], grown as needed
-    lap("two device buffers");
+    DevBuf db[4] = { { c }, { c }, { c }, { c } };                // BGZF: the text buffers db[2 + (p & 1)], grown as needed
+    RC_TRY(dev_reserve(&db[0], (size_t)maxlen));
+    if (pieces.size() > 1) RC_TRY(dev_reserve(&db[1], (size_t)maxlen));
+    tm.lap("two device buffers");
     FileFeeder feed(c, name);
     RC_TRY(feed.start(pieces));
-    lap("feeder started (file mapped, ring pinned, readers running)");
+    tm.lap("feeder started (file mapped, ring pinned, readers running)");
     uint64_t next = lo, carry = 0; const char *carry_at = nullptr;   // BGZF: where the next member starts; the text carried into the next piece
     for (size_t p = 0; p < pieces.size(); p++) {
         const uint64_t a = pieces[p].first, hi = pieces[p].second;
-        char *d_in = db.p[p & 1];
+        char *d_in = db[p & 1].p;
         const double tu = mono_now();
-        RC_TRY(feed.upload_piece(p, d_in, p + 1 < pieces.size() ? db.p[(p + 1) & 1] : nullptr));
+        RC_TRY(feed.upload_piece(p, d_in, p + 1 < pieces.size() ? db[(p + 1) & 1].p : nullptr));
         if (t_wait) *t_wait += mono_now() - tu;
         if (!bgzf) { RC_TRY(fn((const char *)d_in, hi - a, hi == fsz, a)); continue; }
         const double ti = mono_now();
         BgzfPlan plan;
         RC_TRY(harc_bgzf_plan(c, (const uint8_t *)d_in, hi - a, next - a, owned[p] - a, a, &plan));
-        const size_t need = (size_t)(carry + plan.text) + 16;
-        char *&tb = db.p[2 + (p & 1)];
-        if (tcap[p & 1] < need) {
-            if (tb) harc_raw_free(c, tb);
-            tb = nullptr; tcap[p & 1] = 0;
-            RC_TRY(harc_raw_alloc(c, (void **)&tb, need + need / 4));
-            tcap[p & 1] = need + need / 4;
-        }
+        const size_t need = (size_t)(carry + plan.text);
+        DevBuf &tbuf = db[2 + (p & 1)];
+        if (!tbuf.p || tbuf.cap < need) RC_TRY(dev_reserve(&tbuf, need + need / 4));   // a quarter of headroom: a slightly longer piece does not reallocate
+        char *const tb = tbuf.p;
         if (carry) HIP_TRY(hipMemcpyAsync(tb, carry_at, (size_t)carry, hipMemcpyDeviceToDevice, c->stream));
         RC_TRY(harc_bgzf_run(c, (const uint8_t *)d_in, plan, a, tb + carry));
         if (t_inflate) *t_inflate += mono_now() - ti;
@@ -775,7 +722,7 @@ template <class F> static int text_pieces(harc_amd_ctx *c, FILE *f, const char *
         if (cut) RC_TRY(fn((const char *)tb, cut, false, a));
         carry = total - cut; carry_at = tb + cut;
     }
-    lap("pieces uploaded and processed");
+    tm.lap("pieces uploaded and processed");
     return HARC_AMD_OK;
 }
 // The records of bytes [lo, end) of the file, a piece at a time: every piece goes to HBM, is indexed, classified and packed, then makes room
@@ -829,18 +776,14 @@ extern "C" int harc_amd_compress_fastq_files_ex(const harc_amd_params *params, c
     const int gz = gzip_kind(fastq, &ratio);
     if (gz < 0) { harc_set_error("%s is gzip but not BGZF: recompress it with bgzip or decompress it first", fastq); return HARC_AMD_EINVAL; }
     const bool bgzf = gz > 0;
-    harc_amd_ctx *c = nullptr;
-    RC_TRY(harc_amd_create(params, &c));
-    struct Guard { harc_amd_ctx *c; ~Guard() { harc_amd_destroy(c); } } guard{ c };
+    CtxGuard guard; RC_TRY(harc_amd_create(params, &guard.c));
+    harc_amd_ctx *const c = guard.c;
     g_fastq_timing[0] = mono_now() - t_begin;
     const double t_ingest = mono_now();
-    FILE *f = fopen(fastq, "rb");
-    if (!f) { harc_set_error("cannot open %s", fastq); return HARC_AMD_EIO; }
-    struct FClose { FILE *f; ~FClose() { fclose(f); } } fcl{ f };
-    fseeko(f, 0, SEEK_END); const uint64_t fsz = (uint64_t)ftello(f);
+    InFile in; RC_TRY(in.open(fastq));
+    FILE *const f = in.f; const uint64_t fsz = in.size;
     const std::string od = std::string(basedir) + "/output/";
-    char *d_txt = nullptr;                                        // -q without -p: the whole text stays in HBM until the orders are known
-    struct FreeTxt { harc_amd_ctx *c; char **p; ~FreeTxt() { if (*p) harc_raw_free(c, *p); } } freetxt{ c, &d_txt };
+    DevBuf d_txt{ c };                                            // -q without -p: the whole text stays in HBM until the orders are known
     IngestState st;
     // -q without -p: the text stays in HBM until the orders are known when it fits next to everything else; a larger file is ingested in pieces
     // like any other and streamed again, once per bin of output, when the orders are there (emit_quality_and_ids_streamed)
@@ -855,71 +798,52 @@ extern "C" int harc_amd_compress_fastq_files_ex(const harc_amd_params *params, c
     }
     if (preserve_quality && !preserve_order && !stream_q) {
         if (bgzf) {                                               // the text pieces appended into one buffer
-            size_t cap = 0; tsz = 0;
-            {   // sized once from the estimate; grown (with a copy) only where the estimate was short
-                cap = (size_t)(1.02 * ratio * (double)fsz) + ((size_t)1 << 20);
-                RC_TRY(harc_raw_alloc(c, (void **)&d_txt, cap));
-            }
+            tsz = 0;
+            // sized once from the estimate; grown (with a copy) only where the estimate was short
+            RC_TRY(dev_reserve(&d_txt, (size_t)(1.02 * ratio * (double)fsz) + ((size_t)1 << 20)));
             RC_TRY(text_pieces(c, f, fastq, 0, fsz, fsz, true, &g_fastq_timing[2], &g_fastq_timing[8], [&](const char *p, uint64_t n, bool, uint64_t) -> int {
-                if (tsz + n + 16 > cap) {
-                    const size_t ncap = (size_t)(tsz + n + 16) + (size_t)(tsz + n) / 2;
-                    char *nb = nullptr; RC_TRY(harc_raw_alloc(c, (void **)&nb, ncap));
-                    if (tsz) HIP_TRY(hipMemcpyAsync(nb, d_txt, (size_t)tsz, hipMemcpyDeviceToDevice, c->stream));
-                    HIP_TRY(hipStreamSynchronize(c->stream));
-                    if (d_txt) harc_raw_free(c, d_txt);
-                    d_txt = nb; cap = ncap;
-                }
-                HIP_TRY(hipMemcpyAsync(d_txt + tsz, p, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+                RC_TRY(dev_reserve(&d_txt, (size_t)(tsz + n), (size_t)tsz));
+                HIP_TRY(hipMemcpyAsync(d_txt.p + tsz, p, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
                 HIP_TRY(hipStreamSynchronize(c->stream));
                 tsz += n;
                 return HARC_AMD_OK;
             }));
-        } else RC_TRY(load_file_range(c, f, fastq, 0, fsz, &d_txt));
+        } else RC_TRY(load_file_range(c, fastq, 0, fsz, &d_txt));
         RC_TRY(ingest_begin(c, st));
-        RC_TRY(ingest_append(c, st, d_txt, tsz, true, 0, 0));
+        RC_TRY(ingest_append(c, st, d_txt.p, tsz, true, 0, 0));
         RC_TRY(ingest_finish(c, st));
     } else {
-        FILE *fq = nullptr, *fi = nullptr;
-        struct Closer { FILE **a, **b; ~Closer() { if (*a) fclose(*a); if (*b) fclose(*b); } } closer{ &fq, &fi };
-        if (preserve_quality && preserve_order) {                  // file order: written while the pieces pass through
-            fq = fopen((od + "output.quality").c_str(), "wb"); fi = fopen((od + "output.id").c_str(), "wb");
-            if (!fq || !fi) { harc_set_error("cannot create %soutput.quality / output.id", od.c_str()); return HARC_AMD_EIO; }
-        }
+        QIdFiles out;
+        if (preserve_quality && preserve_order) RC_TRY(out.open(od));          // file order: written while the pieces pass through
         st.want_idlen = stream_q;
-        RC_TRY(ingest_file_range(c, f, fastq, 0, fsz, fsz, bgzf, st, fq, fi));
+        RC_TRY(ingest_file_range(c, f, fastq, 0, fsz, fsz, bgzf, st, out.fq, out.fi));
     }
     g_fastq_timing[1] = mono_now() - t_ingest;
     printf("Read length: %d\nTotal number of reads: %llu\nTotal number of reads without N: %llu\nPreprocessing Done!\n", params->readlen,
            (unsigned long long)st.nfull, (unsigned long long)c->N);                                       // preprocess.cpp:133-136
-    const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
-    auto now = []() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
-    double tl0 = now();
-    auto lap = [&](const char *what) { if (tlog) { const double t = now(); fprintf(stderr, "[compress_fastq] %s: %.3f s\n", what, t - tl0); tl0 = t; } };
-    RC_TRY(spit_stream_to(c, HARC_AMD_IN_ORDER_N, 0, od + "read_order_N.bin"));
+    LapTimer tm{ "[compress_fastq]" };
+    RC_TRY(spit_stream(c, HARC_AMD_IN_ORDER_N, 0, od + "read_order_N.bin"));
     { const uint32_t n32 = c->N; RC_TRY(spit_file(od + "numreads.bin", &n32, 4)); }
     double t_ph = mono_now();
     RC_TRY(harc_amd_reorder(c));
-    lap("reorder");
+    tm.lap("reorder");
     g_fastq_timing[4] = mono_now() - t_ph; t_ph = mono_now();
     RC_TRY(harc_amd_encode(c));
-    lap("encode");
+    tm.lap("encode");
     g_fastq_timing[5] = mono_now() - t_ph; t_ph = mono_now();
     harc_amd_counters C; harc_amd_get_counters(c, &C);
     printf("Reordering done, %llu were unmatched\n", (unsigned long long)C.unmatched);
     printf("Encoding done:\n%llu singleton reads were aligned\n%llu reads with N were aligned\n", (unsigned long long)C.aligned_singletons, (unsigned long long)C.aligned_N);
     RC_TRY(write_shard_family(c, od, 0));
-    lap("stream files");
-    static const struct { int id; const char *name; } whole[] = {
-        { HARC_AMD_S2_ORDER, "read_order.bin" }, { HARC_AMD_S2_ORDER_N_PE, "read_order_N_pe.bin" }, { HARC_AMD_S2_INPUT_N, "input_N.dna" },
-        { HARC_AMD_S2_META, "read_meta.txt" }, { HARC_AMD_S2_SINGLETON, "read_singleton.txt" }, { HARC_AMD_S2_SINGLETON_TAIL, "read_singleton.txt.tail" } };
-    for (auto &fd : whole) RC_TRY(spit_stream_to(c, fd.id, 0, od + fd.name));
+    tm.lap("stream files");
+    RC_TRY(write_whole_job_files(c, od));
     g_fastq_timing[6] = mono_now() - t_ph; g_fastq_timing[7] = mono_now() - t_begin;
     if (preserve_quality && !preserve_order) {
         printf("Reordering quality values and ids\n");                                                      // harc:122
-        lap("whole-job files");
-        if (stream_q) RC_TRY(emit_quality_and_ids_streamed(c, f, fastq, fsz, bgzf, st, od, "output.quality", "output.id"));
-        else RC_TRY(emit_quality_and_ids(c, d_txt, tsz, false, od, "output.quality", "output.id"));
-        lap("quality values and ids");
+        tm.lap("whole-job files");
+        if (stream_q) RC_TRY(emit_quality_and_ids_streamed(c, f, fastq, fsz, bgzf, st, od));
+        else RC_TRY(emit_quality_and_ids(c, d_txt.p, tsz, st, od));
+        tm.lap("quality values and ids");
     }
     return HARC_AMD_OK;
 }
@@ -974,13 +898,10 @@ static int compress_fastq_rank(const harc_amd_params *params, const char *fastq,
     if (!params || !fastq || !basedir || world < 1 || rank < 0 || rank >= world) { harc_set_error("compress_fastq_shard: bad arguments"); return HARC_AMD_EINVAL; }
     if (preserve_quality && !preserve_order) { harc_set_error("multi-GPU -q needs -p (quality values and ids stay in file order)"); return HARC_AMD_EINVAL; }
     if (gzip_kind(fastq, nullptr) != 0) { harc_set_error("multi-GPU runs read a plain FASTQ: %s is gzip / BGZF, expand it first", fastq); return HARC_AMD_EINVAL; }
-    harc_amd_ctx *c = nullptr;
-    RC_TRY(harc_amd_create(params, &c));
-    struct Guard { harc_amd_ctx *c; ~Guard() { harc_amd_destroy(c); } } guard{ c };
-    FILE *f = fopen(fastq, "rb");
-    if (!f) { harc_set_error("cannot open %s", fastq); return HARC_AMD_EIO; }
-    struct FClose { FILE *f; ~FClose() { fclose(f); } } fcl{ f };
-    fseeko(f, 0, SEEK_END); const uint64_t fsz = (uint64_t)ftello(f);
+    CtxGuard guard; RC_TRY(harc_amd_create(params, &guard.c));
+    harc_amd_ctx *const c = guard.c;
+    InFile in; RC_TRY(in.open(fastq));
+    FILE *const f = in.f; const uint64_t fsz = in.size;
     uint64_t lo = 0, hi = fsz;
     RC_TRY(record_start_at_or_after(f, fsz / (uint64_t)world * (uint64_t)rank, fsz, &lo));
     if (rank + 1 < world) RC_TRY(record_start_at_or_after(f, fsz / (uint64_t)world * (uint64_t)(rank + 1), fsz, &hi));
@@ -988,13 +909,9 @@ static int compress_fastq_rank(const harc_amd_params *params, const char *fastq,
     (void)mkdir(sd.c_str(), 0777);                                // every rank tries; the first one wins
     IngestState st;
     {
-        FILE *fq = nullptr, *fi = nullptr;
-        struct Closer { FILE **a, **b; ~Closer() { if (*a) fclose(*a); if (*b) fclose(*b); } } closer{ &fq, &fi };
-        if (preserve_quality) {                                   // file order (preprocess.cpp:64-69): the slices are concatenated by the merge
-            fq = fopen((sd + "quality" + r).c_str(), "wb"); fi = fopen((sd + "id" + r).c_str(), "wb");
-            if (!fq || !fi) { harc_set_error("cannot create the quality / id parts under %s", sd.c_str()); return HARC_AMD_EIO; }
-        }
-        RC_TRY(ingest_file_range(c, f, fastq, lo, hi, fsz, false, st, fq, fi));
+        QIdFiles out;
+        if (preserve_quality) RC_TRY(out.open_parts(sd, r));      // file order (preprocess.cpp:64-69): the slices are concatenated by the merge
+        RC_TRY(ingest_file_range(c, f, fastq, lo, hi, fsz, false, st, out.fq, out.fi));
     }
     const uint64_t nrec_full = st.nfull;
     const uint64_t n_clean_own = c->N_own;

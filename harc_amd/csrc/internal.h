@@ -234,6 +234,11 @@ int harc_d2h(harc_amd_ctx *c, std::vector<uint8_t> &dst, const void *d_src, size
 // nbytes and counts as a line); nls[-1] = (u64)-1, so that line k starts at nls[k-1] + 1 for every k.  nbytes > 0.  Pool memory: the caller brackets it
 int build_line_index(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const uint64_t **nls_out, uint64_t *total_lines_out);
 
+// ---- the archive's stage-II files under `od` (files.cpp): the stream files of the context's encoder shards [e_lo, e_hi) (e_hi < 0: all) as
+// read_*.txt.<first_shard + e>, stream by stream, each stream announced on HARC_AMD_READY_FD when first_shard == 0; then the six files of the whole job
+int write_shard_family(harc_amd_ctx *c, const std::string &od, int first_shard, int e_lo = 0, int e_hi = -1);
+int write_whole_job_files(harc_amd_ctx *c, const std::string &od);
+
 // ---- BGZF (bgzf.hip): the member chain of a buffer of compressed bytes in device memory, then every member inflated on its own
 struct BgzfCand { uint64_t off; uint32_t bsize, hdr, isize, crc; };                   // a member header that parses at `off`
 struct BgzfMember { uint64_t cdata, text; uint32_t clen, isize, crc, hdr; };          // CDATA at cdata (clen bytes) -> text[text .. + isize)

@@ -156,17 +156,6 @@ static bool get_out(harc_amd_ctx *c, int id, int shard, View *v)
     *v = it->second.ptr ? View{ it->second.ptr, it->second.len } : view_of(it->second.own);
     return true;
 }
-static bool slurp_file(const std::string &path, std::vector<uint8_t> &out)
-{
-    out.clear();
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) return false;
-    fseek(f, 0, SEEK_END); long n = ftell(f); fseek(f, 0, SEEK_SET);
-    out.resize((size_t)n);
-    const bool ok = n == 0 || fread(out.data(), 1, (size_t)n, f) == (size_t)n;
-    fclose(f);
-    return ok;
-}
 static int up(harc_amd_ctx *c, View h, uint8_t **d)
 {
     RC_TRY(dalloc(c, d, h.n + 16));
@@ -189,7 +178,7 @@ static int streams_from_files(const std::string &od, int e, ShardStreams *s)
     static const char *const stem[S_COUNT] = { "read_seq.txt", "read_seq.txt", "read_pos.txt", "read_noise.txt", "read_noisepos.txt", "read_rev.txt", "read_rev.txt" };
     for (int k = 0; k < S_COUNT; k++) {
         const bool tail = k == S_SEQ_TAIL || k == S_REV_TAIL;
-        if (!slurp_file(od + stem[k] + "." + std::to_string(e) + (tail ? ".tail" : ""), s->own[k])) { harc_set_error("shard %d: stream files missing", e); return HARC_AMD_EIO; }
+        if (!slurp_file(od + stem[k] + "." + std::to_string(e) + (tail ? ".tail" : ""), s->own[k], true)) { harc_set_error("shard %d: stream files missing", e); return HARC_AMD_EIO; }
         s->v[k] = view_of(s->own[k]);
     }
     return HARC_AMD_OK;
@@ -276,7 +265,7 @@ static int open_archive(const harc_amd_params *params, const char *basedir, int3
     if (!params || !basedir || num_thr_e < 1) return HARC_AMD_EINVAL;
     *od = std::string(basedir) + "/output/";
     std::vector<uint8_t> meta;
-    if (!slurp_file(*od + "read_meta.txt", meta)) { harc_set_error("cannot read %sread_meta.txt", od->c_str()); return HARC_AMD_EIO; }
+    if (!slurp_file(*od + "read_meta.txt", meta, true)) { harc_set_error("cannot read %sread_meta.txt", od->c_str()); return HARC_AMD_EIO; }
     meta.push_back(0);
     *L = atoi((const char *)meta.data());
     return side_context(params, *L, c, num_thr_e);
@@ -378,8 +367,8 @@ extern "C" int harc_amd_decoder_files(const harc_amd_params *params, const char 
     }
     {   // singletons (decoder.cpp:148-158), then the N reads of every shard (:159-165), then input_N.dna (:166-168)
         std::vector<uint8_t> sg, sgt, nt;
-        if (!slurp_file(od + "read_singleton.txt", sg) || !slurp_file(od + "read_singleton.txt.tail", sgt)) { harc_set_error("singleton files missing"); return HARC_AMD_EIO; }
-        slurp_file(od + "input_N.dna", nt);
+        if (!slurp_file(od + "read_singleton.txt", sg, true) || !slurp_file(od + "read_singleton.txt.tail", sgt, true)) { harc_set_error("singleton files missing"); return HARC_AMD_EIO; }
+        (void)slurp_file(od + "input_N.dna", nt, false);
         PoolScope scope(c);
         uint32_t ns = 0; uint8_t *codes = nullptr; char *lines = nullptr;
         RC_TRY(singletons_unpack(c, view_of(sg), view_of(sgt), L, &ns, &codes, &lines));
@@ -496,8 +485,8 @@ extern "C" int harc_amd_decoder_preserve_files(const harc_amd_params *params, co
     RC_TRY(open_archive(params, basedir, num_thr_e, &od, &L, &guard.c));
     harc_amd_ctx *c = guard.c;
     std::vector<uint8_t> pord, ptail, ordNpe, ordN;
-    if (!slurp_file(od + "read_order.bin", pord) || !slurp_file(od + "read_order.bin.tail", ptail) || !slurp_file(od + "read_order_N_pe.bin", ordNpe) ||
-        !slurp_file(od + "read_order_N.bin", ordN)) { harc_set_error("order files missing: was the archive made with -p?"); return HARC_AMD_EIO; }
+    if (!slurp_file(od + "read_order.bin", pord, true) || !slurp_file(od + "read_order.bin.tail", ptail, true) || !slurp_file(od + "read_order_N_pe.bin", ordNpe, true) ||
+        !slurp_file(od + "read_order_N.bin", ordN, true)) { harc_set_error("order files missing: was the archive made with -p?"); return HARC_AMD_EIO; }
     const size_t LL = (size_t)L + 1;
     // ---- unpack_order
     uint32_t nC = 0; int numbits = 0;
@@ -562,8 +551,8 @@ extern "C" int harc_amd_decoder_preserve_files(const harc_amd_params *params, co
     if (!fo) { harc_set_error("cannot create %soutput.dna", od.c_str()); return HARC_AMD_EIO; }
     struct FClose { FILE *f; ~FClose() { if (f) fclose(f); } } fcl{ fo };
     std::vector<uint8_t> sg, sgt, nt;                             // singletons and unaligned N reads: read once
-    if (!slurp_file(od + "read_singleton.txt", sg) || !slurp_file(od + "read_singleton.txt.tail", sgt)) { harc_set_error("singleton files missing"); return HARC_AMD_EIO; }
-    slurp_file(od + "input_N.dna", nt);
+    if (!slurp_file(od + "read_singleton.txt", sg, true) || !slurp_file(od + "read_singleton.txt.tail", sgt, true)) { harc_set_error("singleton files missing"); return HARC_AMD_EIO; }
+    (void)slurp_file(od + "input_N.dna", nt, false);
     // what the kernels have counted into d_err so far refuses the archive
     auto refuse_counted = [&]() -> int {
         unsigned int err = 0;

@@ -761,6 +761,56 @@ def test_quality_ids_match_oracle_any_schedule(K, S, E, trunc, stream, oracle, t
 
 
 @pytest.mark.parametrize("stream", [False, True])
+@pytest.mark.parametrize("where,dangling", [(None, False), (0, False), (-1, True), (-1, False)])
+def test_quality_ids_flag_edges_match_oracle(where, dangling, stream, oracle, tmp_path, monkeypatch, capfd):
+    """both -q walks take their per-record N flags from read_order_N.bin as the ingest kept it (ingest.hip q_plan), not from the text: the edges of
+    that list against the oracle -- no read holds N (no flag is scattered at all), only the first record, only the last complete record with a dangling
+    id line behind it (that id is routed by the last flag, nid = nrec + 1), and the same without the dangling line"""
+    import re
+    import numpy as np
+    import harc_amd
+    L, n, CHUNK, BIN = 40, 600, 16000, 8000
+    reads = [bytearray(r) for r in gen.reads_text(77, n, L, 4000, err=0.01, n_frac=0.0).split()]
+    assert not any(b"N" in r for r in reads)
+    if where is not None:
+        reads[where][17] = ord("N")
+    rs = np.random.RandomState(9)
+    recs = []
+    for i, r in enumerate(reads):
+        q = bytes(35 if c == 78 else 40 + int(x) for c, x in zip(r, rs.randint(0, 30, L)))
+        recs.append(b"@r%d %s\n%s\n+\n%s\n" % (i, b"y" * int(rs.randint(0, 12)), bytes(r), q))
+    fq = b"".join(recs) + (b"@dangling id\n" if dangling else b"")
+    if stream:
+        # a piece ends at the first record start at or after CHUNK bytes, a pass holds BIN // (L + 1) quality lines; every id line is shorter than
+        # a quality line, so the id file never needs more passes than the quality file
+        assert len(fq) > 2 * (CHUNK + max(len(x) for x in recs))            # at least three pieces
+        monkeypatch.setenv("HARC_AMD_Q_STREAM", "1"); monkeypatch.setenv("HARC_AMD_INGEST_CHUNK", str(CHUNK)); monkeypatch.setenv("HARC_AMD_Q_BIN", str(BIN))
+        monkeypatch.setenv("HARC_AMD_TRACE", "1")
+    else:
+        monkeypatch.setenv("HARC_AMD_Q_STREAM", "0")
+    (tmp_path / "in.fastq").write_bytes(fq)
+    os.makedirs(tmp_path / "output")
+    capfd.readouterr()
+    harc_amd.compress_fastq(str(tmp_path / "in.fastq"), str(tmp_path), L, num_thr=2, num_chains=1, preserve_quality=True)
+    err = capfd.readouterr().err
+    if stream:
+        m = re.search(r"\[-q\] quality values and ids permuted in (\d+) passes", err)
+        assert m, err
+        want_passes = -(-n // (BIN // (L + 1)))
+        assert want_passes >= 3 and int(m.group(1)) == want_passes
+    got = ol.read_dir(str(tmp_path))
+    assert got["read_order_N.bin"] == (b"" if where is None else (where % n).to_bytes(4, "little"))
+    o = tmp_path / "o"
+    ol.stage_dir(o, {f: got[f] for f in ("read_order.bin", "read_order_N_pe.bin")})
+    assert oracle.harc_oracle_quality(fq, len(fq), L, 0, str(o).encode()) == 0
+    exp = ol.read_dir(str(o))
+    assert got["output.quality"] == exp["output.quality"]
+    assert got["output.id"] == exp["output.id"]
+    if dangling:                                                    # routed by the last record's flag: the list of the N side, appended as it is
+        assert got["output.id"].endswith(b"\n@dangling id\n")
+
+
+@pytest.mark.parametrize("stream", [False, True])
 def test_quality_wrong_length_rejected(stream, tmp_path, monkeypatch):
     import harc_amd
     _q_stream_env(monkeypatch, stream)

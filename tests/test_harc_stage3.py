@@ -109,7 +109,7 @@ def test_stage3_failing_job_fails_the_run(tmp_path):
 
 
 def test_stage3_starts_while_the_stage_program_still_writes(tmp_path):
-    """the stage program names a stream on descriptor HARC_AMD_READY_FD when all its shard files are closed (ingest.hip write_shard_family); the
+    """the stage program names a stream on descriptor HARC_AMD_READY_FD when all its shard files are closed (files.cpp write_shard_family); the
     driver must start that stream's tar + coder at once: the stand-in announces read_seq, waits, and finds read_seq.tar(.xz) already there
     before it writes the next stream.  A failing stage program still fails the run with jobs in flight."""
     fq, env = _setup(tmp_path)

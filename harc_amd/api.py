@@ -112,6 +112,16 @@ def lib():
     l.harc_amd_idunpack_host.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
     l.harc_amd_idpack_files.argtypes = [PP, C.c_char_p, C.c_char_p]
     l.harc_amd_idunpack_files.argtypes = [PP, C.c_char_p, C.c_char_p]
+    l.harc_amd_spack_bound.argtypes = [C.c_uint64, C.c_uint32]
+    l.harc_amd_spack_bound.restype = C.c_uint64
+    l.harc_amd_spack_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_sunpack_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_spack_host.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_sunpack_host.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    l.harc_amd_spack_files.argtypes = [PP, C.c_char_p, C.c_char_p]
+    l.harc_amd_sunpack_files.argtypes = [PP, C.c_char_p, C.c_char_p]
+    l.harc_amd_spack_file_list.argtypes = [PP, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
+    l.harc_amd_sunpack_file_list.argtypes = [PP, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
     l.harc_amd_decode_signature.argtypes = [ctx, C.POINTER(C.c_uint64)]
     l.harc_amd_input_signature.argtypes = [ctx, C.POINTER(C.c_uint64)]
     l.harc_amd_reads_signature_device.argtypes = [ctx, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
@@ -332,6 +342,57 @@ def idunpack_files(packed, out, device=0):
     _check(lib().harc_amd_idunpack_files(C.byref(p), os.fsencode(packed), os.fsencode(out)))
 
 
+def spack_bound(text_bytes, block_bytes=0):
+    """bytes that text_bytes bytes take at most as a packed stream file: 32 + text_bytes + 13 * blocks; host only"""
+    return int(lib().harc_amd_spack_bound(text_bytes, block_bytes))
+
+
+def spack_host(text, block_bytes=0, header=True):
+    """the encoder of HarcAmd.spack_device run in a row on the host: the bytes the kernels must write (tests; no device).  text: any bytes"""
+    cap = spack_bound(len(text), block_bytes)
+    out = C.create_string_buffer(cap + 1)
+    got = C.c_uint64(0)
+    _check(lib().harc_amd_spack_host(text, len(text), block_bytes, 1 if header else 0, out, cap, C.byref(got)))
+    return out.raw[:got.value]
+
+
+def sunpack_host(packed):
+    """a packed stream file (with its header) -> its text, decoded on the host by the functions the kernels compile; HarcAmdError(-1) for damaged input"""
+    size = C.c_uint64(0)
+    _check(lib().harc_amd_sunpack_host(packed, len(packed), None, 0, C.byref(size)))
+    out = C.create_string_buffer(size.value + 1)
+    _check(lib().harc_amd_sunpack_host(packed, len(packed), out, size.value, C.byref(size)))
+    return out.raw[:size.value]
+
+
+def spack_files(path, out, device=0):
+    """the file `path` -> the packed stream file `out`, coded on the GPU (include/harc_amd.h: harc_amd_spack_files)"""
+    p = default_params(100, device=device)
+    _check(lib().harc_amd_spack_files(C.byref(p), os.fsencode(path), os.fsencode(out)))
+
+
+def sunpack_files(packed, out, device=0):
+    """the packed stream file `packed` -> the file `out`, decoded on the GPU"""
+    p = default_params(100, device=device)
+    _check(lib().harc_amd_sunpack_files(C.byref(p), os.fsencode(packed), os.fsencode(out)))
+
+
+def _path_list(paths):
+    return (C.c_char_p * len(paths))(*[os.fsencode(x) for x in paths])
+
+
+def spack_file_list(pairs, device=0):
+    """spack_files over (path, out) pairs, one after the other on one side context"""
+    p = default_params(100, device=device)
+    _check(lib().harc_amd_spack_file_list(C.byref(p), len(pairs), _path_list([a for a, _ in pairs]), _path_list([b for _, b in pairs])))
+
+
+def sunpack_file_list(pairs, device=0):
+    """sunpack_files over (packed, out) pairs, one after the other on one side context"""
+    p = default_params(100, device=device)
+    _check(lib().harc_amd_sunpack_file_list(C.byref(p), len(pairs), _path_list([a for a, _ in pairs]), _path_list([b for _, b in pairs])))
+
+
 def pack_order(basedir, readlen=100, **kw):
     """== `pack_order.out <basedir>` (src/pack_order.cpp:11-77)"""
     p = default_params(readlen, **kw)
@@ -423,6 +484,20 @@ class HarcAmd:
         """a packed id file in device memory -> its text at out_ptr (device memory); without out_ptr only its size. -> bytes of text"""
         n = C.c_uint64(0)
         _check(lib().harc_amd_idunpack_device(self._ctx, C.c_void_p(d_packed), nbytes, C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
+        return n.value
+
+    def spack_device(self, d_text, text_bytes, block_bytes=0, out_ptr=None, out_capacity=0, header=True):
+        """text_bytes bytes in device memory -> the packed stream form at out_ptr (device memory), with the 32-byte file header when header; without out_ptr
+        only the size. -> bytes.  spack_bound(text_bytes, block_bytes) is always enough capacity"""
+        n = C.c_uint64(0)
+        _check(lib().harc_amd_spack_device(self._ctx, C.c_void_p(d_text) if d_text else None, text_bytes, block_bytes, 1 if header else 0,
+                                           C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
+        return n.value
+
+    def sunpack_device(self, d_packed, nbytes, out_ptr=None, out_capacity=0):
+        """a packed stream file in device memory -> its text at out_ptr (device memory); without out_ptr only its size. -> bytes of text"""
+        n = C.c_uint64(0)
+        _check(lib().harc_amd_sunpack_device(self._ctx, C.c_void_p(d_packed), nbytes, C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
         return n.value
 
     def set_fastq_bgzf_device(self, dptr, nbytes):

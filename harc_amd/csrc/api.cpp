@@ -488,6 +488,7 @@ extern "C" const char *harc_amd_build_id(void) { return HARC_AMD_BUILD_ID; }
 extern "C" int harc_amd_build_has(const char *feature)
 {
     if (!feature) return 0;
+    if (!strcmp(feature, "spack")) return 1;                      // the packed stream file (spack.hip): ./harc -c -S
 #ifdef HARC_AMD_TEST_TRANSPORT
     if (!strcmp(feature, "test_transport")) return 1;
 #endif

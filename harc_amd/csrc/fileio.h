@@ -113,10 +113,13 @@ static inline int side_context(const harc_amd_params *params, int L, harc_amd_ct
     return harc_amd_create(&P, c);
 }
 // The context's ONE pinned ring in `parts` disjoint parts of `slices_each` slices, out[0 .. parts), for movers that are alive at the same time; the host threads are
-// shared out among them.  The ring is reserved whole before any of them starts.  HARC_AMD_FEED_SLICE sets the slice, HARC_AMD_FEED_THREADS the threads of all together
-static inline int ring_split(harc_amd_ctx *c, int parts, int slices_each, const char *what, RingGeom *out)
+// shared out among them.  The ring is reserved whole before any of them starts.  HARC_AMD_FEED_SLICE sets the slice, HARC_AMD_FEED_THREADS the threads of all together.
+// slice: the caller's own slice size where the environment names none (spack.hip: files of a few MB do not pin a ring of 1 GiB); 0: the default
+static inline int ring_split(harc_amd_ctx *c, int parts, int slices_each, const char *what, RingGeom *out, size_t slice = 0)
 {
-    RingGeom base; harc_ring_geom_env(&base);
+    RingGeom base;
+    if (slice) base.slice = slice;
+    harc_ring_geom_env(&base);
     for (int k = 0; k < parts; k++) { out[k].slice = base.slice; out[k].nslices = slices_each; out[k].nthr = base.nthr / parts > 0 ? base.nthr / parts : 1; out[k].ring_off = (size_t)k * slices_each * base.slice; }
     return harc_ring_reserve(c, (size_t)parts * slices_each * base.slice, what);
 }

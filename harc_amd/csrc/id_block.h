@@ -262,10 +262,9 @@ QV_HD uint32_t id_rows_before(const uint32_t *bm, uint32_t r)
 // symbols.  A row of 256 can hold more entries lifted to 1 than its largest frequency (39 common differences and 154 rare ones: 107 < 154): then the excess
 // is taken from all entries in turn, in ascending symbol order, a sixteenth of each, then an eighth, a quarter and halves until it is gone.  f >> shift < f, so an entry stays
 // >= 1; the sum is above 4096 >= 16 A, so some entry is >= 17 and every round takes something
-QV_HD int id_norm_row(uint32_t *fc, uint32_t r)
+// (id_norm_counts: the rule over any row of A <= 256 counts -- sv_block.h normalises its rows of 256 byte values with it)
+QV_HD int id_norm_counts(uint32_t *row, uint32_t A)
 {
-    uint32_t *row = fc + id_row_off(r);
-    const uint32_t A = id_row_width(r);
     uint64_t T = 0; uint32_t best = 0;
     for (uint32_t y = 0; y < A; y++) { const uint32_t c = row[y]; T += c; if (c > best) best = c; }
     if (!T) return 0;
@@ -283,6 +282,7 @@ QV_HD int id_norm_row(uint32_t *fc, uint32_t r)
     qv_cum_row(row, A);
     return 1;
 }
+QV_HD int id_norm_row(uint32_t *fc, uint32_t r) { return id_norm_counts(fc + id_row_off(r), id_row_width(r)); }
 // row r of the table at tab (the present rows, u16 frequencies) -> fc; an absent row is all zero: no slot of it belongs to a symbol
 QV_HD int id_load_row(const uint8_t *tab, const uint32_t *bm, uint32_t r, uint32_t *fc)
 {

@@ -17,6 +17,8 @@
 //   harc_amd_stage quality_unpack <packed> <device> <out>                  ... and back (./harc -d -q when only X.quality.hq is there)
 //   harc_amd_stage id_pack <id> <device> <out>                             the lines of <id> -> the packed id file <out> (./harc -c -q -I)
 //   harc_amd_stage id_unpack <packed> <device> <out>                       ... and back (./harc -d -q when only X.id.hi is there)
+//   harc_amd_stage streams_pack <device> <in> <out> [<in> <out> ...]       every <in> -> the packed stream file <out>, one after the other on one context (./harc -c -S)
+//   harc_amd_stage streams_unpack <device> <in> <out> [<in> <out> ...]     ... and back (./harc -d when the archive holds .hs files)
 // readlen / num_thr arrive as arguments instead of the compile-time macros of src/config.h (harc:52-63).
 #include <stdio.h>
 #include <stdlib.h>
@@ -50,6 +52,20 @@ int main(int argc, char **argv)
         PQ.device = atoi(argv[3]);
         const int rcq = !strcmp(argv[1], "quality_pack") ? harc_amd_qpack_files(&PQ, argv[2], argv[4]) : harc_amd_qunpack_files(&PQ, argv[2], argv[4]);
         if (rcq != 0) { fprintf(stderr, "harc_amd_stage %s failed (%d): %s\n", argv[1], rcq, harc_amd_last_error()); return 1; }
+        return 0;
+    }
+    if (!strcmp(argv[1], "streams_pack") || !strcmp(argv[1], "streams_unpack")) {
+        if (argc < 5 || (argc - 3) % 2) { fprintf(stderr, "%s needs <device> <in> <out> [<in> <out> ...]\n", argv[1]); return 2; }
+        harc_amd_params PS;
+        if (harc_amd_default_params(100, &PS) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
+        PS.device = atoi(argv[2]);
+        const int np = (argc - 3) / 2;
+        const char **in = (const char **)malloc(sizeof(char *) * 2 * (size_t)np), **out = in + np;
+        if (!in) return 1;
+        for (int k = 0; k < np; k++) { in[k] = argv[3 + 2 * k]; out[k] = argv[4 + 2 * k]; }
+        const int rcs = !strcmp(argv[1], "streams_pack") ? harc_amd_spack_file_list(&PS, np, in, out) : harc_amd_sunpack_file_list(&PS, np, in, out);
+        free(in);
+        if (rcs != 0) { fprintf(stderr, "harc_amd_stage %s failed (%d): %s\n", argv[1], rcs, harc_amd_last_error()); return 1; }
         return 0;
     }
     if (!strcmp(argv[1], "id_pack") || !strcmp(argv[1], "id_unpack")) {

@@ -115,8 +115,9 @@ static int pack_unpack_device(const PackFormat &F, harc_amd_ctx *c, const uint8_
     return pack_unpack_run(c, F, H, d_packed + PF_HEADER, d_off, d_toff, h_off.data(), (uint32_t)H.nb, H.n, d_text, 0, PF_HEADER);
 }
 
-// harc_amd_<tag>unpack_files: the packed file goes through the feeder's half of the ring in pieces of whole blocks, its text through the drain's
-static int pack_unpack_files(const PackFormat &F, const harc_amd_params *params, const char *packed_path, const char *out_path)
+// harc_amd_<tag>unpack_files: the packed file goes through the feeder's half of the ring in pieces of whole blocks, its text through the drain's.
+// shared: a side context of the caller's that serves several files one after the other, slice: its slice of the ring (spack.hip); nullptr, 0: the call's own, the default
+static int pack_unpack_files(const PackFormat &F, const harc_amd_params *params, const char *packed_path, const char *out_path, harc_amd_ctx *shared = nullptr, size_t slice = 0)
 {
     char who[32]; snprintf(who, sizeof who, "%sunpack_files", F.tag);
     if (!params || !packed_path || !out_path) { harc_set_error("%s: bad arguments", who); return HARC_AMD_EINVAL; }
@@ -136,10 +137,10 @@ static int pack_unpack_files(const PackFormat &F, const harc_amd_params *params,
     std::vector<uint64_t> off((size_t)H.nb + 1), toff((size_t)H.nb + 1);
     RC_TRY(pack_walk(F, who, packed_path, H, fsz, read, [](uint64_t, uint64_t, uint64_t, uint64_t) { return HARC_AMD_OK; }, off.data(), toff.data()));
     CtxGuard guard;
-    RC_TRY(side_context(params, H.L ? (int)H.L : 100, &guard.c));
-    harc_amd_ctx *c = guard.c;
+    if (!shared) RC_TRY(side_context(params, H.L ? (int)H.L : 100, &guard.c));
+    harc_amd_ctx *c = shared ? shared : guard.c;
     RingGeom g[2];                                                // the feeder's and the drain's
-    RC_TRY(ring_split(c, 2, 8, F.ring, g));
+    RC_TRY(ring_split(c, 2, 8, F.ring, g, slice));
     DevBuf pk{ c }, txt{ c }, doff{ c };
     const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
     double t_read = 0, t_write = 0, t_kernel = 0;

@@ -411,6 +411,40 @@ int harc_amd_idpack_files(const harc_amd_params *params, const char *id_path, co
    file or any damaged block: HARC_AMD_EINVAL; a failed read: HARC_AMD_EIO.  On any failure out_path is removed. */
 int harc_amd_idunpack_files(const harc_amd_params *params, const char *packed_path, const char *out_path);
 
+/* ---- The packed stream file X.hs (./harc -c -S; the format is written down in README.md, "The packed stream file"): text_bytes bytes of any values -> a
+   32-byte header and blocks of block_bytes text bytes, each stored or coded with static rANS in 256 strands of consecutive bytes that a workgroup codes
+   independently: with one table (order 0) or with a table per previous byte (order 1), whichever payload is smallest, and with the CRC-32 of its text.
+   block_bytes 0 = the default 2^22, at most 2^30.  The packed bytes depend on nothing but the text and block_bytes. */
+/* Host only: bytes that text_bytes bytes take at most, 32 + text_bytes + 13 * blocks (every block stored). */
+uint64_t harc_amd_spack_bound(uint64_t text_bytes, uint32_t block_bytes);
+/* d_text (device memory, any alignment) -> the packed form at d_out (device memory, any alignment), *n_out bytes; no byte outside [d_out, d_out + *n_out) is
+   written and none outside the text is read.  flags bit 0: the 32-byte file header in front of the blocks (without it: the blocks alone, for a caller that
+   packs a file in pieces).  d_out == NULL: the size alone (the blocks are coded to learn it); else HARC_AMD_EINVAL naming both numbers when out_capacity is
+   smaller.  harc_amd_spack_bound is always enough.  HARC_AMD_TRACE=1: one "[spack]" line on stderr. */
+int harc_amd_spack_device(harc_amd_ctx *ctx, const uint8_t *d_text, uint64_t text_bytes, uint32_t block_bytes, int32_t flags, uint8_t *d_out, uint64_t out_capacity,
+                          uint64_t *n_out);
+/* The packed form with its header, n_bytes in device memory -> its text at d_text, *n_out bytes, the number from the header.  d_text == NULL: the size alone; a
+   smaller out_capacity: HARC_AMD_EINVAL naming both numbers.  Everything read is validated before it is trusted (README lists the checks): HARC_AMD_EINVAL
+   naming the block and its byte offset, never an access outside the packed form or the text.  What was written to d_text by then is unspecified. */
+int harc_amd_sunpack_device(harc_amd_ctx *ctx, const uint8_t *d_packed, uint64_t n_bytes, uint8_t *d_text, uint64_t out_capacity, uint64_t *n_out);
+/* The same two calls in a row on the host, through the functions of harc_amd/csrc/sv_block.h that the kernels compile: they touch no device, and they are what the
+   kernels are held to, byte for byte (tests). */
+int harc_amd_spack_host(const uint8_t *text, uint64_t text_bytes, uint32_t block_bytes, int32_t flags, uint8_t *out, uint64_t cap, uint64_t *n_out);
+int harc_amd_sunpack_host(const uint8_t *packed, uint64_t n_bytes, uint8_t *text, uint64_t cap, uint64_t *n_out);
+/* in_path (any file) -> out_path, packed on the GPU; only `device` is taken from params.  The job runs in pieces of whole blocks (64 blocks;
+   HARC_AMD_SPACK_PIECE=blocks; HARC_AMD_SPACK_BLOCK=text bytes per block in tests: it is recorded in the file and changes its bytes) through the pinned ring, so
+   the file may be larger than device memory; the output is the same file whatever the piece, slice or thread settings.  On any failure out_path is removed.
+   HARC_AMD_TRACE=1: one "[spack]" line on stderr (text bytes, packed bytes, blocks of each mode, pieces, seconds in the kernels / waiting for readers / for
+   writers). */
+int harc_amd_spack_files(const harc_amd_params *params, const char *in_path, const char *out_path);
+/* packed_path -> the file at out_path, its size known from the header before anything is decoded.  A short file, a wrong magic, a block prefix that leaves the
+   file or any damaged block: HARC_AMD_EINVAL; a failed read: HARC_AMD_EIO.  On any failure out_path is removed. */
+int harc_amd_sunpack_files(const harc_amd_params *params, const char *packed_path, const char *out_path);
+/* The two file calls over n_files pairs of paths, one after the other on one side context (harc_amd_stage streams_pack / streams_unpack).  Every input is
+   looked for before a device is touched; the first failure ends the call: its output is removed, the outputs in front of it and all inputs stay. */
+int harc_amd_spack_file_list(const harc_amd_params *params, int32_t n_files, const char *const *in_paths, const char *const *out_paths);
+int harc_amd_sunpack_file_list(const harc_amd_params *params, int32_t n_files, const char *const *packed_paths, const char *const *out_paths);
+
 #ifdef __cplusplus
 }
 #endif

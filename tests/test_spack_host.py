@@ -1,0 +1,339 @@
+"""The packed stream file without a GPU: the block coder of harc_amd/csrc/sv_block.h (the source the kernels compile) built for the host with g++,
+AddressSanitizer and UBSan as a stand-alone program; what the library's host twin writes read back by a decoder in plain Python written from the README's
+format text; damaged files refused; the bound and the empty file; the size of the seven streams of a run against xz."""
+import lzma
+import os
+import shutil
+import struct
+import subprocess
+import zlib
+
+import pytest
+
+from tests import stream_cases as sc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EINVAL = -1
+MAGIC = b"HARCS1\0\0"
+
+DRIVER = r"""
+#include "sv_block.h"
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+// enc: cases [u32 n][u32 B][n bytes] -> [u32 status][u32 bytes][the blocks, no file header].  Every buffer is a heap block of exactly its size: a read or write
+// past it is an AddressSanitizer report.  status: 1 a second run into a block of the exact size differs or a capacity one byte short is not refused,
+// 2 sv_block_decode does not return the text
+// dec: files [u32 bytes][the file] -> [u32 code][u32 text bytes][text]; code 0, an SV_E_* of the first bad block, 100 a prefix that leaves the file, 101 the header
+static uint32_t one_block(const uint8_t *bytes, uint32_t m, FILE *o, uint32_t *total)
+{
+    uint32_t st = 0;
+    uint8_t *text = (uint8_t *)malloc(m);                          // the block's text alone
+    memcpy(text, bytes, m);
+    SvWork *W = (SvWork *)malloc(sizeof(SvWork));
+    uint8_t *slabs = (uint8_t *)malloc(sv_block_slabs(m));
+    uint8_t *big = (uint8_t *)malloc(SV_PREFIX + (size_t)m);
+    int mode = 0;
+    const uint32_t size = sv_block_encode(text, m, *W, slabs, big, SV_PREFIX + (size_t)m, &mode);
+    if (!size) return 4;
+    uint8_t *exact = (uint8_t *)malloc(size);
+    if (sv_block_encode(text, m, *W, slabs, exact, size, &mode) != size || memcmp(big, exact, size)) st |= 1;
+    if (sv_block_encode(text, m, *W, slabs, exact, size - 1, &mode) != 0) st |= 1;
+    uint8_t *payload = (uint8_t *)malloc(size - 4);
+    memcpy(payload, exact + 4, size - 4);
+    uint8_t *back = (uint8_t *)malloc(m);
+    if (qv_le32(exact) != size - 4 || sv_block_decode(payload, size - 4, m, *W, back) != SV_OK || memcmp(back, text, m)) st |= 2;
+    fwrite(exact, 1, size, o); *total += size;
+    free(back); free(payload); free(exact); free(big); free(slabs); free(W); free(text);
+    return st;
+}
+static uint32_t one_file(const uint8_t *f, uint32_t nbytes, FILE *o)
+{
+    uint32_t code = 0, tb = 0;
+    uint8_t *text = NULL;
+    if (nbytes < 32 || !sv_magic_ok(f) || qv_le32(f + 12) || qv_le64(f + 24)) code = 101;
+    else {
+        const uint32_t B = qv_le32(f + 8); const uint64_t n = qv_le64(f + 16);
+        if (n == 0) code = nbytes == 32 && B == 0 ? 0 : 101;
+        else if (B < 1 || B > SV_MAX_B || n > 10000000) code = 101;
+        else {
+            tb = (uint32_t)n;
+            text = (uint8_t *)malloc(tb);
+            memset(text, 0, tb);
+            SvWork *W = (SvWork *)malloc(sizeof(SvWork));
+            uint64_t at = 32;
+            for (uint64_t b = 0; b < sv_blocks(n, B) && !code; b++) {
+                const uint32_t m = sv_block_text(n, B, b);
+                uint64_t pb = 0, t = 0;
+                uint8_t q[SV_PREFIX];
+                if (nbytes - at >= SV_PREFIX) memcpy(q, f + at, SV_PREFIX);
+                if (!sv_prefix(q, nbytes - at, m, &pb, &t)) { code = 100; break; }
+                uint8_t *payload = (uint8_t *)malloc(pb), *out = (uint8_t *)malloc(m);
+                memcpy(payload, f + at + 4, pb);
+                memset(out, 0, m);
+                code = (uint32_t)sv_block_decode(payload, (uint32_t)pb, m, *W, out);
+                memcpy(text + b * B, out, m);
+                free(out); free(payload);
+                at += 4 + pb;
+            }
+            if (!code && at != nbytes) code = 100;
+            free(W);
+        }
+    }
+    fwrite(&code, 4, 1, o); fwrite(&tb, 4, 1, o);
+    if (tb) fwrite(text, 1, tb, o);
+    free(text);
+    return code;
+}
+int main(int argc, char **argv)
+{
+    if (argc < 4) return 2;
+    FILE *f = fopen(argv[2], "rb"), *o = fopen(argv[3], "wb");
+    if (!f || !o) return 2;
+    uint32_t n;
+    if (!strcmp(argv[1], "dec")) {
+        while (fread(&n, 4, 1, f) == 1) {
+            uint8_t *p = (uint8_t *)malloc(n ? n : 1);
+            if (n && fread(p, 1, n, f) != n) return 3;
+            one_file(p, n, o);
+            free(p);
+        }
+    } else {
+        while (fread(&n, 4, 1, f) == 1) {
+            uint32_t B;
+            if (fread(&B, 4, 1, f) != 1) return 3;
+            uint8_t *p = (uint8_t *)malloc(n ? n : 1);
+            if (n && fread(p, 1, n, f) != n) return 3;
+            if (!B) B = SV_DEFAULT_B;
+            uint32_t st = 0, total = 0;
+            const long head = ftell(o);
+            fwrite(&st, 4, 1, o); fwrite(&total, 4, 1, o);
+            for (uint32_t a = 0; a < n; a += B) st |= one_block(p + a, n - a < B ? n - a : B, o, &total);
+            fseek(o, head, SEEK_SET); fwrite(&st, 4, 1, o); fwrite(&total, 4, 1, o); fseek(o, 0, SEEK_END);
+            free(p);
+        }
+    }
+    fclose(o); fclose(f);
+    return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    if not shutil.which("g++"):
+        pytest.fail("g++ is needed to build the host form of sv_block.h")
+    d = tmp_path_factory.mktemp("sv")
+    src = d / "drv.cpp"
+    src.write_text(DRIVER)
+    exe = d / "drv"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                           "-Wall", "-Werror", "-I", os.path.join(ROOT, "harc_amd", "csrc"), str(src), "-o", str(exe)])
+
+    def run(mode, blob):
+        cin, cout = d / "in.bin", d / "out.bin"
+        cin.write_bytes(blob)
+        r = subprocess.run([str(exe), mode, str(cin), str(cout)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                           env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+        assert r.returncode == 0 and r.stderr == "", r.stderr[-3000:]                  # the sanitizers are silent
+        return cout.read_bytes()
+    return run
+
+
+@pytest.fixture(scope="module")
+def cases():
+    return sc.small_cases()
+
+
+def _header(text, B):
+    return MAGIC + (struct.pack("<IIQQ", B or 1 << 22, 0, len(text), 0) if text else bytes(24))
+
+
+# ------------------------------------------------------------------------------------------------ the decoder of the README, in plain Python
+def _row(p, at):
+    """the row at p[at:]: 32 bytes of bitmap, the u16 frequencies of its symbols -> (freq[256], cum[256], the bytes it takes)"""
+    bits = int.from_bytes(p[at:at + 32], "little")
+    syms = [y for y in range(256) if bits >> y & 1]
+    assert syms
+    f = struct.unpack_from("<%dH" % len(syms), p, at + 32)
+    assert all(v >= 1 for v in f) and sum(f) == 4096
+    freq, cum, c = [0] * 256, [0] * 256, 0
+    for y in range(256):
+        cum[y] = c
+        if bits >> y & 1:
+            freq[y] = f[syms.index(y)]
+            c += freq[y]
+    return freq, cum, 32 + 2 * len(syms)
+
+
+def readme_decode(f):
+    """-> (text, modes).  Asserts the constraints the format text states"""
+    assert f[:8] == MAGIC
+    B, zero, n, zero2 = struct.unpack_from("<IIQQ", f, 8)
+    assert zero == 0 and zero2 == 0
+    if n == 0:
+        assert B == 0 and len(f) == 32
+        return b"", []
+    assert 1 <= B <= 1 << 30
+    at, out, modes = 32, [], []
+    for b0 in range(0, n, B):
+        m = min(n, b0 + B) - b0
+        size, = struct.unpack_from("<I", f, at)
+        p = f[at + 4:at + 4 + size]
+        assert len(p) == size
+        at += 4 + size
+        mode, tb, crc = struct.unpack_from("<BII", p, 0)
+        assert tb == m and mode in (0, 1, 2)
+        modes.append(mode)
+        if mode == 0:
+            assert size == 9 + m
+            text = p[9:]
+        else:
+            rows, pos = {}, 9
+            if mode == 1:
+                fr, cu, k = _row(p, pos)
+                rows, pos = {r: (fr, cu) for r in range(256)}, pos + k
+            else:
+                present = int.from_bytes(p[9:41], "little")
+                pos = 41
+                for r in range(256):
+                    if present >> r & 1:
+                        fr, cu, k = _row(p, pos)
+                        rows[r], pos = (fr, cu), pos + k
+            lens = struct.unpack_from("<256I", p, pos)
+            pos += 1024
+            assert pos + sum(lens) == size
+            q = (m + 255) // 256
+            text = bytearray()
+            for s in range(256):
+                data, pos = p[pos:pos + lens[s]], pos + lens[s]
+                ns = min(m, (s + 1) * q) - min(m, s * q)
+                if ns == 0:
+                    assert not data
+                    continue
+                assert len(data) >= 4
+                x, k, ctx = int.from_bytes(data[:4], "big"), 4, 0
+                for _ in range(ns):
+                    freq, cum = rows[ctx]                          # an absent row: a KeyError
+                    slot = x & 4095
+                    y = next(y for y in range(256) if freq[y] and cum[y] <= slot < cum[y] + freq[y])
+                    x = freq[y] * (x >> 12) + slot - cum[y]
+                    while x < 1 << 23:
+                        x, k = x << 8 | data[k], k + 1
+                    text.append(y)
+                    ctx = y if mode == 2 else 0
+                assert x == 1 << 23 and k == len(data)             # the end of a strand
+            text = bytes(text)
+        assert len(text) == m and zlib.crc32(text) == crc
+        out.append(text)
+    assert at == len(f)
+    return b"".join(out), modes
+
+
+def test_every_case_round_trips_in_the_sanitizer_build(driver, cases):
+    import harc_amd
+    names = sorted(cases)
+    out = driver("enc", b"".join(struct.pack("<II", len(cases[k][0]), cases[k][1]) + cases[k][0] for k in names))
+    at = 0
+    for k in names:
+        st, n = struct.unpack_from("<II", out, at)
+        blocks, at = out[at + 8:at + 8 + n], at + 8 + n
+        assert st == 0, (k, st)
+        text, B = cases[k]
+        assert _header(text, B) + blocks == harc_amd.spack_host(text, B), k            # the library's host twin is this code
+    assert at == len(out)
+
+
+def test_a_decoder_written_from_the_readme_reads_every_case(cases):
+    import harc_amd
+    for k, (text, B) in sorted(cases.items()):
+        f = harc_amd.spack_host(text, B)
+        got, modes = readme_decode(f)
+        assert got == text, k
+        assert k not in sc.MODES or modes == sc.MODES[k], (k, modes)
+        assert harc_amd.sunpack_host(f) == text, k
+        nb = (len(text) + (B or 1 << 22) - 1) // (B or 1 << 22)
+        assert len(f) <= harc_amd.spack_bound(len(text), B) == 32 + len(text) + 13 * nb, k
+    sc.check_modes(harc_amd.spack_host)                           # every mode is exercised
+    # what some cases are there for
+    f = harc_amd.spack_host(*cases["repeated_byte"])
+    assert len(f) == 32 + 4 + 9 + 32 + 2 + 1024 + 4 * 242                              # one frequency of 4096; 242 strands of their 4 state bytes
+    f = harc_amd.spack_host(*cases["context_0_rule"])
+    rows = int.from_bytes(f[45:77], "little")
+    assert rows == 1 << 0 | 1 << 97 | 1 << 98 | 1 << 99                                # row 0 is there although no byte of the text is 0
+
+
+def test_corruption_is_refused(driver):
+    import harc_amd
+    blobs, texts = {}, sc.corruption_texts()
+    for mode, text in sorted(texts.items()):
+        packed = harc_amd.spack_host(text)
+        assert [m for _, m, _ in sc.blocks_of(packed)] == [mode]
+        for k, v in sc.flips(packed).items():
+            blobs["m%d_%s" % (mode, k)] = v
+        if mode == 2:
+            for k, v in sc.header_violations(packed).items():
+                blobs["m2_" + k] = v
+    names = sorted(blobs)
+    out = driver("dec", b"".join(struct.pack("<I", len(blobs[k])) + blobs[k] for k in names))       # the sanitizer build reports nothing on any of them
+    at = 0
+    for k in names:
+        code, tb = struct.unpack_from("<II", out, at)
+        at += 8 + tb
+        assert code != 0, k                                        # every single-bit flip too: the CRC-32 leaves none undetected
+        with pytest.raises(harc_amd.HarcAmdError) as e:
+            harc_amd.sunpack_host(blobs[k])
+        assert e.value.code == EINVAL, (k, str(e.value))
+        if "flip" in k or k[3:] in sc.NAMES_BLOCK_0:
+            assert "block 0 at byte 32" in str(e.value), (k, str(e.value))
+    assert at == len(out)
+
+
+def test_bound_header_flag_and_the_empty_file():
+    import harc_amd
+    assert harc_amd.spack_bound(0) == 32 and harc_amd.spack_bound(1) == 32 + 13 + 1
+    assert harc_amd.spack_bound(1 << 22) == 32 + 13 + (1 << 22) and harc_amd.spack_bound((1 << 22) + 1) == 32 + 26 + (1 << 22) + 1
+    assert harc_amd.spack_bound(3005, 1000) == 32 + 4 * 13 + 3005
+    text = sc.markov(36005, seed=6)
+    f = harc_amd.spack_host(text, 12000)
+    assert f == _header(text, 12000) + harc_amd.spack_host(text, 12000, header=False)
+    assert f != harc_amd.spack_host(text) and harc_amd.sunpack_host(harc_amd.spack_host(text)) == text
+    # block b of the file is the file of its text alone
+    assert f[32:] == b"".join(harc_amd.spack_host(text[a:a + 12000], 12000, header=False) for a in range(0, 36005, 12000))
+    empty = harc_amd.spack_host(b"")
+    assert empty == MAGIC + bytes(24) and harc_amd.sunpack_host(empty) == b""
+    with pytest.raises(harc_amd.HarcAmdError) as e:
+        harc_amd.spack_host(b"abc", (1 << 30) + 1)
+    assert e.value.code == EINVAL
+    assert harc_amd.build_has("spack")
+
+
+STREAMS = ["read_seq.txt.0", "read_pos.txt.0", "read_noise.txt.0", "read_noisepos.txt.0", "read_rev.txt.0", "read_singleton.txt", "input_N.dna"]
+
+
+def test_the_streams_of_a_run_pack_to_the_size_of_xz(tmp_path):
+    """The seven streams of gen.reads_text(7, 300000, 100, 1500000, err=0.01, n_frac=0.02) at K = 64, S = 16, E = 1, made by the CPU oracle: every packed
+    stream within its bound, and their sum within 1.03 of xz -6 (the ideal code lengths of the best mode per stream give 0.983; the margin covers the 12-bit
+    frequencies and the strands' state, about 1 KiB per coded block).  Measured: the sum is 1 139 525 bytes against 1 150 360 for xz -6, a ratio of 0.9906."""
+    import harc_amd
+    from tests import gen
+    from tests import oracle_lib as ol
+    oracle = ol.load()
+    L = 100
+    txt = gen.reads_text(7, 300000, L, 1500000, err=0.01, n_frac=0.02)
+    base = ol.stage_dir(tmp_path, {})
+    assert oracle.harc_oracle_preprocess(txt, len(txt), L, base.encode()) == 0
+    assert oracle.harc_oracle_reorder(base.encode(), L, 64, 16, None, None) == 0
+    assert oracle.harc_oracle_encoder(base.encode(), L, 1, None, None) == 0
+    files = ol.read_dir(base)
+    ours = xz = 0
+    print("| stream | bytes | packed | modes | xz -6 |\n|---|---|---|---|---|")
+    for s in STREAMS:
+        packed = harc_amd.spack_host(files[s])
+        assert harc_amd.sunpack_host(packed) == files[s]
+        assert len(packed) <= harc_amd.spack_bound(len(files[s])), s
+        z = len(lzma.compress(files[s], preset=6))
+        print("| %s | %d | %d | %s | %d |" % (s, len(files[s]), len(packed), [m for _, m, _ in sc.blocks_of(packed)], z))
+        ours += len(packed); xz += z
+    print("| sum | | %d | | %d | ratio %.4f" % (ours, xz, ours / xz))
+    assert ours <= 1.03 * xz

@@ -201,7 +201,8 @@ int prim_excl_scan_u32_to_u64(harc_amd_ctx *c, const uint32_t *in, uint64_t *out
 int prim_excl_scan_u8_to_u64(harc_amd_ctx *c, const uint8_t *in, uint64_t *out, size_t n);
 int prim_incl_scan_u64(harc_amd_ctx *c, const uint64_t *in, uint64_t *out, size_t n);
 int prim_incl_max_u32(harc_amd_ctx *c, const uint32_t *in, uint32_t *out, size_t n);
-int prim_incl_max_u64(harc_amd_ctx *c, const uint64_t *in, uint64_t *out, size_t n);
+// sorted keys -> binstart[b], q[b] = max over the bins j <= b of (home_j + n - j), *nbins (prims.hip; k_table_place reads them)
+int prim_bins_scan(harc_amd_ctx *c, const uint64_t *skeys, size_t n, uint64_t cap, uint32_t *binstart, uint64_t *q, uint32_t *nbins, void *scratch, size_t scratch_bytes);
 
 // ---- stages
 int s1_pack_ascii(harc_amd_ctx *c, const char *d_ascii, uint32_t n, uint32_t stride, uint64_t *d_out);               // 2-bit
@@ -219,7 +220,9 @@ int stage1_make_oriented(harc_amd_ctx *c, uint32_t i0 = 0, uint32_t i1 = 0xFFFFF
 int s1_orient(harc_amd_ctx *c, const uint64_t *reads, const uint32_t *order, const uint8_t *rc, uint32_t m, uint64_t *out);
 // exact key->bin table over n keys (ids must hold 0..n-1 on entry); allocates d->slots / d->ids / d->d_nbins
 int harc_dict_alloc(harc_amd_ctx *c, DictDev *d, uint32_t n, uint64_t cap_like);   // cap_like != 0: that many slots
-int harc_dict_build(harc_amd_ctx *c, DictDev *d, uint64_t *keys, uint32_t *ids, uint32_t n, unsigned kbits);   // after harc_dict_alloc
+enum { HARC_KEYS_RAW = 0, HARC_KEYS_SORTABLE = 1 };              // what harc_dict_build is handed: the keys, or key_scramble(key) rotated left by harc_dict_sort_bits(n)
+unsigned harc_dict_sort_bits(uint32_t n);
+int harc_dict_build(harc_amd_ctx *c, DictDev *d, uint64_t *keys, uint32_t *ids, uint32_t n, unsigned kbits, int keys_are);   // after harc_dict_alloc
 void harc_dict_free(harc_amd_ctx *c, DictDev *d);
 int stage2_run(harc_amd_ctx *c);
 int pack_order_run(harc_amd_ctx *c);

@@ -80,10 +80,82 @@ int prim_incl_max_u32(harc_amd_ctx *c, const uint32_t *in, uint32_t *out, size_t
     return HARC_AMD_OK;
 }
 
-int prim_incl_max_u64(harc_amd_ctx *c, const uint64_t *in, uint64_t *out, size_t n)
+// ---- the index build's bins and slots from ONE scan of the sorted keys (harc_dict_build; the linear-probing rule above k_table_place).
+// Element i: c = 1 for a head (i == 0 or a key unlike the one before), m = its home slot, -2^62 for any other element.  A part of the sequence sums
+// up to c = its heads and m = max over its heads of (home - number of heads before it INSIDE the part): (a, b) -> c = a.c + b.c,
+// m = max(a.m, b.m - a.c) -- associative, not commutative.  At head i, with b = c - 1 its bin: binstart[b] = i and
+// q[b] = m + n = max over the bins j <= b of (home_j + n - j), what k_table_place turns into slots (q[b] - n + b).
+// Reduce, then scan: a wave walks one segment of the keys, 64 at a time, and leaves the segment's part; the library scans the parts (a few
+// hundred thousand at most); the same walk again, started from the parts in front of the segment, writes.  28 n bytes; no workgroup waits for
+// another.  (rocprim::inclusive_scan over the 16-byte parts with an output iterator that stores at the heads did all of it in one pass and was
+// SLOWER than the four passes it replaced -- profiles/README.md, r09.)
+struct BinPart { long long m; uint32_t c, pad; };
+struct BinPartOp {
+    __host__ __device__ BinPart operator()(const BinPart &a, const BinPart &b) const
+    {
+        const long long bm = b.m - (long long)a.c;
+        return BinPart{ a.m > bm ? a.m : bm, a.c + b.c, 0u };
+    }
+};
+#define BINS_NONE (-(1ll << 62))
+#define BINS_SEG_MIN 2048u        // keys of a segment, at least; segments are whole multiples of 64 * BINS_UNROLL keys
+#define BINS_UNROLL 4             // chunks of 64 keys whose loads are under way together
+template <bool WRITE> __global__ __launch_bounds__(256) void k_bins_pass(const uint64_t *k, uint32_t n, uint64_t cap, uint32_t seg, uint32_t nseg, BinPart *part,
+                                                                       uint32_t *binstart, uint64_t *q, uint32_t *nbins)
+{
+    const uint32_t w = (blockIdx.x * 256u + threadIdx.x) >> 6;   // a wave per segment: everything below is wave-uniform but the lane's own key
+    if (w >= nseg) return;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = ((unsigned long long)1 << lane) - 1;
+    uint32_t C = 0; long long M = BINS_NONE;                      // heads so far; WRITE: the max so far, else the lane's own max so far
+    if (WRITE) { C = part[w].c; M = part[w].m; }                  // (the parts in front of the segment, scanned)
+    const uint64_t base = (uint64_t)w * seg, end = base + seg < n ? base + seg : (uint64_t)n;
+    uint64_t carry = base ? k[base - 1] : 0;                      // the key in front of the chunk
+    for (uint64_t at = base; at < end; at += 64u * BINS_UNROLL) {
+        uint64_t key[BINS_UNROLL];
+#pragma unroll
+        for (int u = 0; u < BINS_UNROLL; u++) { const uint64_t i = at + 64u * u + lane; key[u] = i < end ? k[i] : 0; }
+#pragma unroll
+        for (int u = 0; u < BINS_UNROLL; u++) {
+            const uint64_t i = at + 64u * u + lane;
+            uint64_t prev = __shfl_up(key[u], 1, 64);
+            if (lane == 0) prev = carry;
+            carry = __shfl(key[u], 63, 64);
+            const bool head = i < end && (i == 0 || key[u] != prev);
+            const unsigned long long hb = __ballot(head);
+            const uint32_t rank = C + (uint32_t)__popcll(hb & below);
+            long long v = head ? (long long)bucket_slot(key[u], cap) - (long long)rank : BINS_NONE;
+            if (WRITE) {
+                for (int d = 1; d < 64; d <<= 1) { const long long o = __shfl_up(v, d, 64); if (lane >= d && o > v) v = o; }
+                if (M > v) v = M;
+                if (head) { binstart[rank] = (uint32_t)i; q[rank] = (uint64_t)(v + (long long)n); }
+                if (i < end && i + 1 == n) *nbins = rank + (head ? 1u : 0u);
+                M = __shfl(v, 63, 64);
+            } else if (v > M) M = v;
+            C += (uint32_t)__popcll(hb);
+        }
+    }
+    if (!WRITE) {
+        for (int o = 32; o > 0; o >>= 1) { const long long x = __shfl_xor(M, o, 64); if (x > M) M = x; }
+        if (lane == 0) part[w] = BinPart{ M, C, 0u };
+    }
+}
+// scratch: room for the segments' parts, twice; the more of it, the shorter the segments (at least BINS_SEG_MIN keys)
+int prim_bins_scan(harc_amd_ctx *c, const uint64_t *skeys, size_t n, uint64_t cap, uint32_t *binstart, uint64_t *q, uint32_t *nbins, void *scratch, size_t scratch_bytes)
 {
     if (n == 0) return HARC_AMD_OK;
-    PRIM_CALL(rocprim::inclusive_scan(tmp, bytes, in, out, n, rocprim::maximum<uint64_t>(), c->stream));
+    const size_t room = scratch_bytes / (2 * sizeof(BinPart));
+    if (room == 0 || n > 0xFFFFFFFFull || (n + room - 1) / room > (1u << 30) || room > 0x7FFFFFFFull) { harc_set_error("prim_bins_scan: %zu keys, scratch of %zu bytes", n, scratch_bytes); return HARC_AMD_EINVAL; }
+    size_t seg = (n + room - 1) / room;
+    if (seg < BINS_SEG_MIN) seg = BINS_SEG_MIN;
+    seg = (seg + 64 * BINS_UNROLL - 1) / (64 * BINS_UNROLL) * (64 * BINS_UNROLL);
+    const uint32_t nseg = (uint32_t)((n + seg - 1) / seg);       // <= room
+    BinPart *part = (BinPart *)scratch, *front = part + nseg;
+    const dim3 grid((nseg + 3) / 4);
+    hipLaunchKernelGGL(k_bins_pass<false>, grid, dim3(256), 0, c->stream, skeys, (uint32_t)n, cap, (uint32_t)seg, nseg, part, (uint32_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr);
+    PRIM_CALL(rocprim::exclusive_scan(tmp, bytes, part, front, BinPart{ BINS_NONE, 0u, 0u }, (size_t)nseg, BinPartOp(), c->stream));
+    hipLaunchKernelGGL(k_bins_pass<true>, grid, dim3(256), 0, c->stream, skeys, (uint32_t)n, cap, (uint32_t)seg, nseg, front, binstart, q, nbins);
+    HIP_TRY(hipGetLastError());
     return HARC_AMD_OK;
 }
 

@@ -237,28 +237,41 @@ int s1_partition_reads(harc_amd_ctx *c, const uint64_t *d_packed, uint32_t n, ui
 
 // ------------------------------------------------------------------------------------------------ index build
 // key_l(read) = bases [ds_l, de_l] of the read (reorder.cpp:295-299)
-// both dictionaries' keys in ONE pass over the reads (the second pass was 11 GB read again at configs[2]: 2.7 ms)
-template <int W> __global__ void k_keygen2(const uint64_t *reads, uint32_t n, int off0, int nbits0, int off1, int nbits1, uint64_t *keys0, uint64_t *keys1, uint32_t *ids)
+// both dictionaries' keys in ONE pass over the reads (the second pass was 11 GB read again at configs[2]: 2.7 ms) -- and, while a key sits in a
+// register, everything else that is a function of it alone: the SCRAMBLED key, rotated as the sort of harc_dict_build wants it (HARC_KEYS_SORTABLE),
+// stored instead of the key itself, and the key's place in the bitmap in front of the dictionary -- as an item of the tiled build
+// (harc_bitmap_from_items) or set right here with an atomic (small bitmaps).  The scramble is computed once and feeds both.  (Two passes of their
+// own did this before: k_scramble_keys in place and a second read of the keys for the items, 24 n bytes per dictionary.)
+// RAW: the keys as they are and nothing else (what the HARC_AMD_S1BLOOM_VERIFY reference bitmap is made from).
+__device__ __forceinline__ uint64_t rotl64(uint64_t x, unsigned r) { r &= 63u; return r ? (x << r) | (x >> (64u - r)) : x; }
+struct KeyOut { uint64_t *keys, *items; uint32_t *bloom; int off, nbits, nwin; };      // of one dictionary: at most one of items / bloom
+template <int W, bool RAW> __device__ __forceinline__ void keygen_one(const uint64_t (&r)[W], uint32_t i, const KeyOut &o, unsigned rot, uint32_t nlines, uint32_t mmask)
+{
+    const int wi = o.off >> 6, sh = o.off & 63;
+    const uint64_t lo = sel0<W>(r, wi), hi = sel0<W>(r, wi + 1);
+    uint64_t v = sh ? ((lo >> sh) | (hi << (64 - sh))) : lo;
+    if (o.nbits < 64) v &= ((uint64_t)1 << o.nbits) - 1;
+    if constexpr (RAW) o.keys[i] = v;
+    else {
+        const uint64_t hk = key_scramble(v);
+        o.keys[i] = rotl64(hk, rot);
+        if (o.items || o.bloom) {
+            uint32_t w, m;
+            bloom_pos(v, hk, nlines, o.nwin, mmask, &w, &m);
+            if (o.items) { const uint32_t b0 = (uint32_t)__ffs((int)m) - 1u, b1 = 31u - (uint32_t)__clz((int)m); o.items[i] = harc_bitmap_item(w, b0, b1); }
+            else if ((o.bloom[w] & m) != m) atomicOr(&o.bloom[w], m);
+        }
+    }
+}
+template <int W, bool RAW> __global__ void k_keygen2(const uint64_t *reads, uint32_t n, KeyOut o0, KeyOut o1, uint32_t *ids, unsigned rot, uint32_t nlines, uint32_t mmask)
 {
     const uint32_t i = harc_gid32();
     if (i >= n) return;
     uint64_t r[W];
 #pragma unroll
     for (int w = 0; w < W; w++) r[w] = reads[(size_t)i * W + w];
-    {
-        const int wi = off0 >> 6, sh = off0 & 63;
-        const uint64_t lo = sel0<W>(r, wi), hi = sel0<W>(r, wi + 1);
-        uint64_t v = sh ? ((lo >> sh) | (hi << (64 - sh))) : lo;
-        if (nbits0 < 64) v &= ((uint64_t)1 << nbits0) - 1;
-        keys0[i] = v;
-    }
-    {
-        const int wi = off1 >> 6, sh = off1 & 63;
-        const uint64_t lo = sel0<W>(r, wi), hi = sel0<W>(r, wi + 1);
-        uint64_t v = sh ? ((lo >> sh) | (hi << (64 - sh))) : lo;
-        if (nbits1 < 64) v &= ((uint64_t)1 << nbits1) - 1;
-        keys1[i] = v;
-    }
+    keygen_one<W, RAW>(r, i, o0, rot, nlines, mmask);
+    keygen_one<W, RAW>(r, i, o1, rot, nlines, mmask);
     ids[i] = i;
 }
 // Bins of more than HARC_LARGEBIN reads (repeats, low-complexity sequence) get their reads copied once more in bin order, so that the
@@ -291,20 +304,6 @@ template <int W> __global__ __launch_bounds__(64) void k_large_fill(const unsign
     }
     if (lane == 0) { largetab[b] = make_uint2(st, (uint32_t)m0); slot->start = b; }       // from now on the slot names its row of largetab
 }
-__global__ void k_mark_heads(const uint64_t *skeys, uint32_t n, uint32_t *head)
-{
-    const uint32_t i = harc_gid32();
-    if (i >= n) return;
-    head[i] = (i == 0 || skeys[i] != skeys[i - 1]) ? 1u : 0u;
-}
-// ... and, with the keys at hand, what the placement's max-scan starts from: 4 b_i - i of bin i (see below), biased by n to stay unsigned
-__global__ void k_bin_starts(const uint32_t *head, const uint32_t *binidx, uint32_t n, uint32_t *binstart, uint32_t *nbins, const uint64_t *skeys, uint64_t cap, uint64_t *v)
-{
-    const uint32_t i = harc_gid32();
-    if (i >= n) return;
-    if (head[i]) { const uint32_t b = binidx[i]; binstart[b] = i; v[b] = bucket_slot(skeys[i], cap) + (uint64_t)n - (uint64_t)b; }
-    if (i == n - 1) *nbins = binidx[i] + head[i];
-}
 #define HARC_LARGEBIN 16u    // stage-I bins with more reads than this are compacted between super-rounds (k_compact_bins)
 #define HARC_STEP_CAP 12    // schedule: a STEP that has made this many probes into such bins without a hit is put off -- the walk ends in front of it, and the next
                              // super-round takes the step up again behind the probes already made (they found nothing against fewer claims; ChainHdr.flags >> 16)
@@ -314,6 +313,8 @@ __global__ void k_bin_starts(const uint32_t *head, const uint32_t *binidx, uint3
 // The table is probed bucket by bucket (64 B = 4 slots); a search that finds a full bucket WITHOUT the overflow flag can stop.
 // The reads arrive sorted by scrambled key, so the bins arrive in bucket order (bucket_slot is monotone): the slot of bin i is
 // max(4 * bucket_i, slot_{i-1} + 1) -- the linear-probing invariant -- i.e. an inclusive max-scan of (4 * bucket_i - i), plus i.
+// prim_bins_scan (prims.hip) makes that scan's result q[], the bins' first places binstart[] and their number from the sorted keys alone, in two
+// walks over them (reduce, then scan: 28 n bytes; four passes -- heads, their ranks, bin starts with the scan's input, the max-scan -- took 64 n).
 // No atomics, and the stores walk the table front to back.  (A CAS insert ran at the random read-modify-write rate: 37 ms for 350 M bins.)
 // The sort of the scrambled keys looks at their TOP bits only (40 of 64 for up to 2^28 reads: five radix passes instead of eight -- the sort is
 // a sixth of the index build); two different keys that agree in those bits are rare (n^2 / 2^41 pairs: 55 000 among 350 M keys) and end up
@@ -325,7 +326,6 @@ __global__ void k_bin_starts(const uint32_t *head, const uint32_t *binidx, uint3
 #define MIXED_BUDGET 200000u
 // (the keys go through the sort ROTATED, their top bits at the bottom: rocprim sorts the low `sbits` bits, begin_bit = 0 -- with begin_bit > 0
 // its small-input path returned a wrong order here; this pass turns them back on the way)
-__device__ __forceinline__ uint64_t rotl64(uint64_t x, unsigned r) { r &= 63u; return r ? (x << r) | (x >> (64u - r)) : x; }
 __global__ void k_mixed_find(const uint64_t *rk, uint32_t n, unsigned sbits, uint64_t *sk, uint32_t *list, unsigned int *meta)
 {
     const uint32_t i = harc_gid32();
@@ -398,7 +398,7 @@ __global__ __launch_bounds__(256) void k_table_place(const uint64_t *skeys, cons
     if (blockIdx.x < first_block) return;                                          // pass 1: the bins beyond the end of the table are among the last
     const uint32_t i = harc_gid32();
     const bool have = i < nbins;
-    auto slot_of = [&](uint32_t k) -> uint64_t { return q[k] - (uint64_t)n + (uint64_t)k; };     // max-scan value (biased by n, k_bin_starts) + k
+    auto slot_of = [&](uint32_t k) -> uint64_t { return q[k] - (uint64_t)n + (uint64_t)k; };     // max-scan value (biased by n, prim_bins_scan) + k
     // fill (pass 0): the table has NOT been cleared (22 GB per dictionary at configs[2]): slots grow with the bin index, so the 256 bins of a
     // workgroup own one contiguous stretch of the table -- from behind the last slot of the workgroup before to their own last slot, to the end
     // of the table for the last bins inside it.  The stretch is put together in LDS (zeros, then the bins' slots) and written out as ONE
@@ -478,17 +478,8 @@ __global__ __launch_bounds__(256) void k_table_place(const uint64_t *skeys, cons
 
 // The same bitmap for a LARGE input, without the random atomics (configs[2]: 350 M of them into 700 MB, 13.6 ms per dictionary at the
 // random-access ceiling): every key becomes (tile of the bitmap, word inside the tile, its two bits) in one u64, the u64s are sorted by tile
-// (two radix passes over the tile bits), and one workgroup per tile ORs its keys into 64 KB of LDS and writes the tile out in one coalesced
+// (k_keygen2 makes them; two radix passes over the tile bits), and one workgroup per tile ORs its keys into 64 KB of LDS and writes the tile out in one coalesced
 // stream -- every byte of the bitmap is written exactly once, so it needs no clearing either.
-__global__ void k_s1_bloom_keys(const uint64_t *keys, uint32_t n, uint32_t nlines, int nwin, uint32_t mmask, uint64_t *pk)
-{
-    const uint32_t i = harc_gid32();
-    if (i >= n) return;
-    uint32_t w, m;
-    bloom_pos(keys[i], key_scramble(keys[i]), nlines, nwin, mmask, &w, &m);
-    const uint32_t b0 = (uint32_t)__ffs((int)m) - 1u, b1 = 31u - (uint32_t)__clz((int)m);
-    pk[i] = harc_bitmap_item(w, b0, b1);
-}
 __global__ __launch_bounds__(256) void k_s1_bloom_tile(const uint64_t *pk, uint32_t n, uint64_t nwords, uint32_t *bloom)
 {
     __shared__ uint32_t tile[BL_TILE_WORDS];
@@ -2782,23 +2773,29 @@ int harc_dict_alloc(harc_amd_ctx *c, DictDev *d, uint32_t n, uint64_t cap_like)
     RC_TRY(dalloc(c, &d->slots, d->cap)); RC_TRY(dalloc(c, &d->ids, n)); RC_TRY(dalloc(c, &d->d_nbins, 2));
     return HARC_AMD_OK;
 }
-int harc_dict_build(harc_amd_ctx *c, DictDev *d, uint64_t *keys, uint32_t *ids, uint32_t n, unsigned kbits)
+// top bits the index build's sort looks at: log2(n) + 8, in whole radix digits, all 64 from 2^36 keys on (HARC_AMD_SORT_BITS forces a count: tests use 8,
+// where nearly every stretch is mixed, and 64).  Who hands harc_dict_build HARC_KEYS_SORTABLE keys rotates them by this count (64: not at all).
+unsigned harc_dict_sort_bits(uint32_t n)
+{
+    unsigned lg = 1; while (((uint64_t)1 << lg) < n) lg++;
+    unsigned sbits = ((lg + 8 + 7) / 8) * 8; if (sbits > 64) sbits = 64;
+    if (const char *e = getenv("HARC_AMD_SORT_BITS")) { const int x = atoi(e); if (x >= 1 && x <= 64) sbits = (unsigned)x; }
+    return sbits;
+}
+// keys_are: HARC_KEYS_RAW -- the keys themselves, scrambled here, in place -- or HARC_KEYS_SORTABLE -- key_scramble(key) rotated left by
+// harc_dict_sort_bits(n) & 63 already (k_keygen2).  Either way keys[] is overwritten.
+int harc_dict_build(harc_amd_ctx *c, DictDev *d, uint64_t *keys, uint32_t *ids, uint32_t n, unsigned kbits, int keys_are)
 {
     (void)kbits;                                                  // the scrambled keys use all 64 bits
     if (n == 0) return HARC_AMD_OK;
     PoolScope scope(c);                                           // temporaries go on every way out
-    uint64_t *k1 = nullptr; uint32_t *h0 = nullptr, *b0 = nullptr, *bs = nullptr;
-    RC_TRY(dalloc(c, &k1, n)); RC_TRY(dalloc(c, &h0, n)); RC_TRY(dalloc(c, &b0, n)); RC_TRY(dalloc(c, &bs, n));
-    // top bits the sort looks at: log2(n) + 8, in whole radix digits, all 64 from 2^36 keys on (HARC_AMD_SORT_BITS forces a count: tests use 8,
-    // where nearly every stretch is mixed, and 64)
-    unsigned sbits = 64;
-    { unsigned lg = 1; while (((uint64_t)1 << lg) < n) lg++; sbits = ((lg + 8 + 7) / 8) * 8; if (sbits > 64) sbits = 64; }
-    if (const char *e = getenv("HARC_AMD_SORT_BITS")) { const int x = atoi(e); if (x >= 1 && x <= 64) sbits = (unsigned)x; }
+    uint64_t *k1 = nullptr; uint32_t *bs = nullptr;
+    RC_TRY(dalloc(c, &k1, n)); RC_TRY(dalloc(c, &bs, n));
+    unsigned sbits = harc_dict_sort_bits(n);
     uint32_t *mixed = nullptr; unsigned int *mmeta = nullptr; uint64_t *k2 = nullptr;
     RC_TRY(dalloc(c, &mixed, MIXED_MAX)); RC_TRY(dalloc(c, &mmeta, 4));
-    RC_TRY(dalloc(c, &k2, n));                                    // the sort's output on the top bits; then (k_bin_starts) what the placement's max-scan starts from
-    uint64_t *const k2v = k2;
-    hipLaunchKernelGGL(k_scramble_keys, harc_grid256(n), dim3(256), 0, c->stream, keys, n, sbits < 64 ? sbits : 0u);
+    RC_TRY(dalloc(c, &k2, n));                                    // the sort's output on the top bits; then (prim_bins_scan) q[]: what the placement makes its slots from
+    if (keys_are == HARC_KEYS_RAW) hipLaunchKernelGGL(k_scramble_keys, harc_grid256(n), dim3(256), 0, c->stream, keys, n, sbits);
     uint32_t nbins = 0;
     for (;;) {
         HIP_TRY(hipMemsetAsync(mmeta, 0, 16, c->stream));
@@ -2809,9 +2806,8 @@ int harc_dict_build(harc_amd_ctx *c, DictDev *d, uint64_t *keys, uint32_t *ids, 
             hipLaunchKernelGGL(k_mixed_own, dim3(MIXED_MAX / 256), dim3(256), 0, c->stream, (const uint64_t *)k1, (int)(64 - sbits), mixed, mmeta);
             hipLaunchKernelGGL(k_mixed_fix, dim3(MIXED_MAX / 256), dim3(256), 0, c->stream, k1, d->ids, n, (int)(64 - sbits), (const uint32_t *)mixed, mmeta);
         } else RC_TRY(prim_sort_pairs_u64_u32(c, keys, k1, ids, d->ids, n, 64));
-        hipLaunchKernelGGL(k_mark_heads, harc_grid256(n), dim3(256), 0, c->stream, k1, n, h0);
-        RC_TRY(prim_excl_scan_u32(c, h0, b0, n));
-        hipLaunchKernelGGL(k_bin_starts, harc_grid256(n), dim3(256), 0, c->stream, h0, b0, n, bs, d->d_nbins, (const uint64_t *)k1, d->cap, k2v);
+        // bin starts, the max-scan behind the slots and the number of bins.  (Its scratch is the list of mixed places: k_mixed_fix is through with it)
+        RC_TRY(prim_bins_scan(c, k1, n, d->cap, bs, k2, d->d_nbins, mixed, (size_t)MIXED_MAX * sizeof(uint32_t)));
         unsigned int mm[2] = { 0, 0 };
         HIP_TRY(hipMemcpyAsync(&nbins, d->d_nbins, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(mm, mmeta, 8, hipMemcpyDeviceToHost, c->stream));
@@ -2826,11 +2822,10 @@ int harc_dict_build(harc_amd_ctx *c, DictDev *d, uint64_t *keys, uint32_t *ids, 
     if (!fill) HIP_TRY(hipMemsetAsync(d->slots, 0, d->cap * sizeof(HashSlot), c->stream));
     d->nbins = nbins;
     {
-        uint64_t *v = k2v, *q = keys;                              // the unsorted keys are not needed any more
+        const uint64_t *q = k2;
         const unsigned gb = (nbins + 255) / 256;
-        RC_TRY(prim_incl_max_u64(c, v, q, nbins));
         for (int pass = 0; pass < 2; pass++)
-            hipLaunchKernelGGL(k_table_place, dim3(gb), dim3(256), 0, c->stream, (const uint64_t *)k1, (const uint32_t *)d->ids, (const uint32_t *)bs, nbins, n, (const uint64_t *)q,
+            hipLaunchKernelGGL(k_table_place, dim3(gb), dim3(256), 0, c->stream, (const uint64_t *)k1, (const uint32_t *)d->ids, (const uint32_t *)bs, nbins, n, q,
                                d->slots, d->cap, d->bigthresh, d->large_list, d->large_n, d->large_max, d->large_tag, d->d_nbins, pass, pass == 0 ? 0u : (gb > 64 ? gb - 64 : 0u), fill);
     }
     HIP_TRY(hipGetLastError());
@@ -2879,7 +2874,7 @@ static int selftest_index(harc_amd_ctx *c, const uint64_t *keys, uint32_t n, uin
     hipLaunchKernelGGL(k_selftest_ids, harc_grid256(n), dim3(256), 0, c->stream, i0, n);
     HIP_TRY(hipMemsetAsync(d.slots, 0xA5, d.cap * sizeof(HashSlot), c->stream));      // stale bytes: whatever the build leaves unwritten shows
     HIP_TRY(hipMemsetAsync(d.ids, 0xA5, (size_t)n * 4, c->stream));
-    RC_TRY(harc_dict_build(c, &d, k0, i0, n, 64));
+    RC_TRY(harc_dict_build(c, &d, k0, i0, n, 64, HARC_KEYS_RAW));
     *nbins = d.nbins;
     HIP_TRY(hipMemcpyAsync(slots, d.slots, d.cap * sizeof(HashSlot), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(ids, d.ids, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -3054,34 +3049,44 @@ template <int W> static int stage1_run_w(harc_amd_ctx *c)
                 bloom_nwin[l] = (same && bloom_m > 0 && nb > bloom_m && (size_t)bloom_lines * 64 >= bloom_mz_bytes) ? nb - bloom_m + 1 : 0;
             }
         }
+        // keys (scrambled, rotated for the sort), ids and the keys' places in the bitmaps, all in one pass over the reads.  The items of the second
+        // dictionary lie below those of the first, which go -- with the sort's second buffer -- before the first table is built
         PoolScope kscope(c);
-        uint64_t *kboth[2] = { nullptr, nullptr }; uint32_t *i0 = nullptr;
+        uint64_t *kboth[2] = { nullptr, nullptr }, *items[2] = { nullptr, nullptr }; uint32_t *i0 = nullptr;
         RC_TRY(dalloc(c, &kboth[0], N)); RC_TRY(dalloc(c, &kboth[1], N)); RC_TRY(dalloc(c, &i0, N));
-        hipLaunchKernelGGL((k_keygen2<W>), harc_grid256(N), dim3(256), 0, c->stream, c->d_reads, N, 2 * P.dict_start[0], 2 * (P.dict_end[0] - P.dict_start[0] + 1),
-                           2 * P.dict_start[1], 2 * (P.dict_end[1] - P.dict_start[1] + 1), kboth[0], kboth[1], i0);
+        const bool by_items = bloom_lines && bloom_tiled;
+        if (by_items) RC_TRY(dalloc(c, &items[1], N));
+        const harc_mark_t mark_items1 = harc_pool_mark(c);
+        if (by_items) RC_TRY(dalloc(c, &items[0], N));
+        KeyOut ko[2];
+        for (int l = 0; l < 2; l++)
+            ko[l] = KeyOut{ kboth[l], items[l], (bloom_lines && !by_items) ? d_bloom[l] : nullptr, 2 * P.dict_start[l], 2 * (P.dict_end[l] - P.dict_start[l] + 1), bloom_nwin[l] };
+        hipLaunchKernelGGL((k_keygen2<W, false>), harc_grid256(N), dim3(256), 0, c->stream, c->d_reads, N, ko[0], ko[1], i0, harc_dict_sort_bits(N), bloom_lines, bloom_mmask);
         ilap("bitmaps allocated, keys made");
         for (int l = 0; l < 2; l++) {
             const int kbits = 2 * (P.dict_end[l] - P.dict_start[l] + 1);
-            uint64_t *const k0 = kboth[l];
-            if (bloom_lines && bloom_tiled) {
+            if (by_items) {
                 PoolScope bscope(c);
-                uint64_t *pa = nullptr, *pb = nullptr; RC_TRY(dalloc(c, &pa, (size_t)N + 1)); RC_TRY(dalloc(c, &pb, (size_t)N + 1));
+                uint64_t *pb = nullptr; RC_TRY(dalloc(c, &pb, (size_t)N + 1));
                 const uint64_t nwords = (uint64_t)bloom_lines * 16;
-                hipLaunchKernelGGL(k_s1_bloom_keys, harc_grid256(N), dim3(256), 0, c->stream, (const uint64_t *)k0, N, bloom_lines, bloom_nwin[l], bloom_mmask, pa);
-                RC_TRY(harc_bitmap_from_items(c, pa, pb, N, nwords, d_bloom[l]));
-                if (getenv("HARC_AMD_S1BLOOM_VERIFY")) {            // tests: word for word what the atomics build
-                    uint32_t *ref = nullptr; unsigned long long *nd = nullptr, hnd = 0;
-                    RC_TRY(dalloc(c, &ref, (size_t)nwords)); RC_TRY(dalloc(c, &nd, 1));
+                RC_TRY(harc_bitmap_from_items(c, items[l], pb, N, nwords, d_bloom[l]));
+                if (getenv("HARC_AMD_S1BLOOM_VERIFY")) {            // tests: word for word what the atomics build, from RAW keys made over again
+                    uint32_t *ref = nullptr, *ri = nullptr; unsigned long long *nd = nullptr, hnd = 0; uint64_t *raw[2] = { nullptr, nullptr };
+                    RC_TRY(dalloc(c, &ref, (size_t)nwords)); RC_TRY(dalloc(c, &nd, 1)); RC_TRY(dalloc(c, &raw[0], N)); RC_TRY(dalloc(c, &raw[1], N)); RC_TRY(dalloc(c, &ri, N));
                     HIP_TRY(hipMemsetAsync(ref, 0, (size_t)nwords * 4, c->stream)); HIP_TRY(hipMemsetAsync(nd, 0, 8, c->stream));
-                    hipLaunchKernelGGL(k_s1_bloom_set, harc_grid256(N), dim3(256), 0, c->stream, (const uint64_t *)k0, N, ref, bloom_lines, bloom_nwin[l], bloom_mmask);
+                    KeyOut kr[2] = { ko[0], ko[1] };
+                    for (int x = 0; x < 2; x++) { kr[x].keys = raw[x]; kr[x].items = nullptr; kr[x].bloom = nullptr; }
+                    hipLaunchKernelGGL((k_keygen2<W, true>), harc_grid256(N), dim3(256), 0, c->stream, c->d_reads, N, kr[0], kr[1], ri, 0u, 0u, 0u);
+                    hipLaunchKernelGGL(k_s1_bloom_set, harc_grid256(N), dim3(256), 0, c->stream, (const uint64_t *)raw[l], N, ref, bloom_lines, bloom_nwin[l], bloom_mmask);
                     hipLaunchKernelGGL(k_s1_bloom_diff, harc_grid256(nwords), dim3(256), 0, c->stream, (const uint32_t *)ref, (const uint32_t *)d_bloom[l], nwords, nd);
                     HIP_TRY(hipMemcpyAsync(&hnd, nd, 8, hipMemcpyDeviceToHost, c->stream));
                     HIP_TRY(hipStreamSynchronize(c->stream));
                     if (hnd) { harc_set_error("stage I bitmap built by tiles differs from the one built with atomics in %llu words", hnd); return HARC_AMD_EINTERNAL; }
                 }
-            } else if (bloom_lines) hipLaunchKernelGGL(k_s1_bloom_set, harc_grid256(N), dim3(256), 0, c->stream, (const uint64_t *)k0, N, d_bloom[l], bloom_lines, bloom_nwin[l], bloom_mmask);
+            }
+            if (l == 0) harc_pool_release(c, mark_items1);        // (nothing allocated behind the mark is still in use: the stream runs in order)
             ilap("bitmap built");
-            RC_TRY(harc_dict_build(c, &dict[l], k0, i0, N, (unsigned)kbits));
+            RC_TRY(harc_dict_build(c, &dict[l], kboth[l], i0, N, (unsigned)kbits, HARC_KEYS_SORTABLE));
             ilap("table built");
         }
     }

@@ -1789,7 +1789,7 @@ int stage2_run(harc_amd_ctx *c)
             else if (bloom4) hipLaunchKernelGGL(k_bloom4_set, G256(T), (const uint64_t *)k0, T, bloom[0], a.bloom_lbits, a.bloom_nwin, l, a.kbits[l] / 3);
             else hipLaunchKernelGGL(k_bloom_set, G256(T), (const uint64_t *)k0, T, bloom[l], bloom_shift[l]);
             lap("  keys, bitmap items");
-            RC_TRY(harc_dict_build(c, &dict[l], k0, i0k, T, (unsigned)a.kbits[l]));
+            RC_TRY(harc_dict_build(c, &dict[l], k0, i0k, T, (unsigned)a.kbits[l], HARC_KEYS_RAW));
             hipLaunchKernelGGL(k_count_big_bins, G256(dict[l].cap), dict[l].slots, dict[l].cap, (uint32_t)P.maxsearch, d_big);
             lap("  dictionary built");
         }

@@ -41,6 +41,19 @@ STREAMS = dict(S1_ORDER=0, S1_FLAG=1, S1_POS=2, S1_RC=3, S1_ORDER_SINGLETON=4, S
 _lib = None
 
 
+class QMap(C.Structure):
+    """harc_amd_qmap: kind 1 a table over the byte values, kind 2 run smoothing with `radius`"""
+    _fields_ = [("kind", C.c_int32), ("radius", C.c_int32), ("table", C.c_uint8 * 256)]
+
+
+class QMapStats(C.Structure):
+    _fields_ = [("values", C.c_uint64), ("changed", C.c_uint64), ("sum_abs", C.c_uint64), ("sum_sq", C.c_uint64), ("max_abs", C.c_uint32),
+                ("distinct_in", C.c_uint32), ("distinct_out", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
 def lib_path():
     return os.environ.get("HARC_AMD_LIB") or os.path.join(HERE, "libharc_amd.so")      # override: experiment builds of the same sources
 
@@ -104,6 +117,12 @@ def lib():
     l.harc_amd_qunpack_host.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
     l.harc_amd_qpack_files.argtypes = [PP, C.c_char_p, C.c_char_p]
     l.harc_amd_qunpack_files.argtypes = [PP, C.c_char_p, C.c_char_p]
+    QM, QS = C.POINTER(QMap), C.POINTER(QMapStats)
+    l.harc_amd_qmap_parse.argtypes = [C.c_char_p, QM]
+    l.harc_amd_qmap_host.argtypes = [C.c_char_p, C.c_uint64, C.c_int32, QM, C.c_char_p, QS]
+    l.harc_amd_qmap_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_int32, QM, C.c_void_p, QS]
+    l.harc_amd_qmap_files.argtypes = [PP, C.c_char_p, C.c_char_p, QM, QS]
+    l.harc_amd_qpack_files_ex.argtypes = [PP, C.c_char_p, C.c_char_p, QM, QS]
     l.harc_amd_idpack_bound.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
     l.harc_amd_idpack_bound.restype = C.c_uint64
     l.harc_amd_idpack_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -295,10 +314,47 @@ def qunpack_host(packed):
     return out.raw[:size.value]
 
 
-def qpack_files(quality, out, device=0):
-    """the quality file `quality` (fixed-length lines) -> the packed quality file `out`, coded on the GPU (include/harc_amd.h: harc_amd_qpack_files)"""
+def qpack_files(quality, out, device=0, spec=None):
+    """the quality file `quality` (fixed-length lines) -> the packed quality file `out`, coded on the GPU (include/harc_amd.h: harc_amd_qpack_files).
+    spec (a spec string or a QMap): the values are mapped in device memory in front of the coder (harc_amd_qpack_files_ex) -> the statistics as a dict"""
     p = default_params(100, device=device)
-    _check(lib().harc_amd_qpack_files(C.byref(p), os.fsencode(quality), os.fsencode(out)))
+    if spec is None:
+        _check(lib().harc_amd_qpack_files(C.byref(p), os.fsencode(quality), os.fsencode(out)))
+        return None
+    m, st = _qmap(spec), QMapStats()
+    _check(lib().harc_amd_qpack_files_ex(C.byref(p), os.fsencode(quality), os.fsencode(out), C.byref(m), C.byref(st)))
+    return st.as_dict()
+
+
+def qmap_parse(spec):
+    """a spec string ("ill8", "bin:T:H:L", "cap:M", "pblock:R") -> its QMap; HarcAmdError(-1) naming the spec and the field for anything else; host only"""
+    m = QMap()
+    _check(lib().harc_amd_qmap_parse(spec.encode() if isinstance(spec, str) else spec, C.byref(m)))
+    return m
+
+
+def _qmap(spec):
+    return spec if isinstance(spec, QMap) else qmap_parse(spec)
+
+
+def qmap_host(text, readlen, spec, stats=True):
+    """the serial mapper of harc_amd/csrc/qm_block.h over lines of readlen quality values and a newline each: what the kernels are held to (no device).
+    -> (the mapped text, the statistics as a dict or None)"""
+    n, rem = divmod(len(text), readlen + 1)
+    if rem:
+        raise HarcAmdError(-1, f"{len(text)} bytes are no multiple of the {readlen + 1} bytes of a line")
+    m, st = _qmap(spec), QMapStats()
+    out = C.create_string_buffer(len(text) + 1)
+    _check(lib().harc_amd_qmap_host(text, n, readlen, C.byref(m), out, C.byref(st) if stats else None))
+    return out.raw[:len(text)], (st.as_dict() if stats else None)
+
+
+def qmap_files(quality, out, spec, device=0):
+    """the quality file `quality` -> the file `out` with its values mapped on the GPU (include/harc_amd.h: harc_amd_qmap_files) -> the statistics as a dict"""
+    p = default_params(100, device=device)
+    m, st = _qmap(spec), QMapStats()
+    _check(lib().harc_amd_qmap_files(C.byref(p), os.fsencode(quality), os.fsencode(out), C.byref(m), C.byref(st)))
+    return st.as_dict()
 
 
 def qunpack_files(packed, out, device=0):
@@ -465,6 +521,14 @@ class HarcAmd:
         _check(lib().harc_amd_qpack_device(self._ctx, C.c_void_p(d_text) if d_text else None, n_reads, readlen, reads_per_block, 1 if header else 0,
                                            C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
         return n.value
+
+    def qmap_device(self, d_text, n_reads, readlen, spec, out_ptr, stats=True):
+        """n_reads quality lines of readlen (and a newline each) at device address d_text -> the same text with its values mapped at device address out_ptr
+        (d_text itself: in place; else disjoint from it; any alignment).  spec: a spec string or a QMap.  -> the statistics as a dict, or None without them"""
+        m, st = _qmap(spec), QMapStats()
+        _check(lib().harc_amd_qmap_device(self._ctx, C.c_void_p(d_text) if d_text else None, n_reads, readlen, C.byref(m), C.c_void_p(out_ptr) if out_ptr else None,
+                                          C.byref(st) if stats else None))
+        return st.as_dict() if stats else None
 
     def qunpack_device(self, d_packed, nbytes, out_ptr=None, out_capacity=0):
         """a packed quality file in device memory -> its lines at out_ptr (device memory); without out_ptr only their size. -> bytes of text"""

@@ -186,6 +186,11 @@ struct PoolScope {
     void release_now() { if (armed) { harc_pool_release(c, mk); armed = false; } }
 };
 
+// ---- lossy quality values (qmap.hip), for qpack.hip: the map held to its rule, and n lines of L mapped from d_text to d_out (the same pointer, or disjoint)
+struct QmAcc;
+int harc_qmap_check(const char *who, const harc_amd_qmap *map);
+int harc_qmap_run(harc_amd_ctx *c, const char *d_text, uint64_t n, uint32_t L, const harc_amd_qmap *map, char *d_out, QmAcc *acc, double *seconds);
+
 // ---- primitives (prims.hip): thin wrappers over rocPRIM device-wide sort / scan
 int prim_sort_pairs_u64_u32(harc_amd_ctx *c, const uint64_t *kin, uint64_t *kout, const uint32_t *vin, uint32_t *vout, size_t n, unsigned end_bit);
 // a bitmap larger than the caches is built from sorted items instead of with random atomics (stage1.hip: harc_bitmap_from_items)

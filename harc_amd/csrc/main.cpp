@@ -13,7 +13,11 @@
 //   harc_amd_stage merge_shards <basedir> <world>                          the whole-job files of the archive from the rank parts
 //   harc_amd_stage fastq_out <dna> <ignored> <id> <quality> <out> [bgzf]     lines i of the three files -> record i of the FASTQ file <out> (./harc -d -q);
 //                                                                          bgzf: <out> is that text as BGZF, deflated on the GPU (./harc -d -q -z)
-//   harc_amd_stage quality_pack <quality> <device> <out>                   the fixed-length lines of <quality> -> the packed quality file <out> (./harc -c -q -Q)
+//   harc_amd_stage quality_pack <quality> <device> <out> [<spec>]          the fixed-length lines of <quality> -> the packed quality file <out> (./harc -c -q -Q);
+//                                                                          <spec>: their values are mapped first, in device memory (./harc -c -q -Q -b <spec>)
+//   harc_amd_stage quality_spec <spec>                                     0 when <spec> names a mapping of quality values (ill8, bin:T:H:L, cap:M, pblock:R), else 2
+//                                                                          and the reason; no device is touched
+//   harc_amd_stage quality_map <quality> <device> <out> <spec>             <quality> with its values mapped -> <out> (./harc -c -q -b <spec>)
 //   harc_amd_stage quality_unpack <packed> <device> <out>                  ... and back (./harc -d -q when only X.quality.hq is there)
 //   harc_amd_stage id_pack <id> <device> <out>                             the lines of <id> -> the packed id file <out> (./harc -c -q -I)
 //   harc_amd_stage id_unpack <packed> <device> <out>                       ... and back (./harc -d -q when only X.id.hi is there)
@@ -25,8 +29,21 @@
 #include <string.h>
 #include "../../include/harc_amd.h"
 
+// what a mapping of quality values did, one line on stdout
+static void print_qmap(const char *spec, const harc_amd_qmap_stats *st)
+{
+    printf("[qmap] %s: %llu values, %llu changed, mean absolute change %.3f, max change %u, distinct values %u -> %u\n", spec, (unsigned long long)st->values,
+           (unsigned long long)st->changed, st->values ? (double)st->sum_abs / (double)st->values : 0.0, st->max_abs, st->distinct_in, st->distinct_out);
+}
+
 int main(int argc, char **argv)
 {
+    if (argc >= 2 && !strcmp(argv[1], "quality_spec")) {
+        harc_amd_qmap M;
+        if (argc != 3) { fprintf(stderr, "quality_spec needs <spec>\n"); return 2; }
+        if (harc_amd_qmap_parse(argv[2], &M) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 2; }
+        return 0;
+    }
     if (argc < 4) { fprintf(stderr, "usage: %s reorder|encoder|compress|pack_order <basedir> <readlen> [num_thr] [num_chains]\n", argv[0]); return 2; }
     // RCCL between processes needs dmabuf IPC on this driver stack (hipIpcGetMemHandle fails otherwise): set before the first HIP call
     // of the process, which is inside the library.  An explicit setting of the caller wins.
@@ -50,8 +67,28 @@ int main(int argc, char **argv)
         harc_amd_params PQ;
         if (harc_amd_default_params(100, &PQ) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
         PQ.device = atoi(argv[3]);
+        if (!strcmp(argv[1], "quality_pack") && argc > 5) {         // the values mapped in front of the coder
+            harc_amd_qmap M; harc_amd_qmap_stats ST;
+            if (harc_amd_qmap_parse(argv[5], &M) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 2; }
+            const int rcm = harc_amd_qpack_files_ex(&PQ, argv[2], argv[4], &M, &ST);
+            if (rcm != 0) { fprintf(stderr, "harc_amd_stage %s failed (%d): %s\n", argv[1], rcm, harc_amd_last_error()); return 1; }
+            print_qmap(argv[5], &ST);
+            return 0;
+        }
         const int rcq = !strcmp(argv[1], "quality_pack") ? harc_amd_qpack_files(&PQ, argv[2], argv[4]) : harc_amd_qunpack_files(&PQ, argv[2], argv[4]);
         if (rcq != 0) { fprintf(stderr, "harc_amd_stage %s failed (%d): %s\n", argv[1], rcq, harc_amd_last_error()); return 1; }
+        return 0;
+    }
+    if (!strcmp(argv[1], "quality_map")) {
+        if (argc < 6) { fprintf(stderr, "quality_map needs <quality> <device> <out> <spec>\n"); return 2; }
+        harc_amd_qmap M; harc_amd_qmap_stats ST;
+        if (harc_amd_qmap_parse(argv[5], &M) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 2; }
+        harc_amd_params PM;
+        if (harc_amd_default_params(100, &PM) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
+        PM.device = atoi(argv[3]);
+        const int rcm = harc_amd_qmap_files(&PM, argv[2], argv[4], &M, &ST);
+        if (rcm != 0) { fprintf(stderr, "harc_amd_stage quality_map failed (%d): %s\n", rcm, harc_amd_last_error()); return 1; }
+        print_qmap(argv[5], &ST);
         return 0;
     }
     if (!strcmp(argv[1], "streams_pack") || !strcmp(argv[1], "streams_unpack")) {

@@ -18,6 +18,7 @@
 // device call and the file call -- are packfile.h's, shared with idpack.hip: this file hands them QV_FORMAT.
 #include "devutil.h"
 #include "qv_block.h"
+#include "qm_block.h"
 #include "packfile.h"
 
 #define QP_T 256
@@ -392,9 +393,11 @@ extern "C" int harc_amd_qunpack_host(const uint8_t *packed, uint64_t n_bytes, ch
 }
 
 // ------------------------------------------------------------------------------------------------ the files
-extern "C" int harc_amd_qpack_files(const harc_amd_params *params, const char *quality_path, const char *out_path)
+// map (may be null): every uploaded piece is mapped in place in device memory in front of the coder (qmap.hip); the mapped text never reaches a file
+extern "C" int harc_amd_qpack_files_ex(const harc_amd_params *params, const char *quality_path, const char *out_path, const harc_amd_qmap *map, harc_amd_qmap_stats *stats)
 {
     if (!params || !quality_path || !out_path) { harc_set_error("qpack_files: bad arguments"); return HARC_AMD_EINVAL; }
+    if (map) RC_TRY(harc_qmap_check("qpack_files", map));
     uint64_t qsz = 0;
     if (!file_size(quality_path, &qsz)) { harc_set_error("cannot open %s", quality_path); return HARC_AMD_EIO; }
     OutFileGuard outguard{ out_path };
@@ -416,6 +419,8 @@ extern "C" int harc_amd_qpack_files(const harc_amd_params *params, const char *q
     const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
     double t_read = 0, t_write = 0;
     QpStats st;
+    QmAcc acc; qm_acc_zero(&acc);
+    double t_map = 0;
     uint8_t h[QV_FILE_HEADER];
     if (n) qv_file_header(h, L, rb, n); else qv_file_header(h, 0, 0, 0);
     uint64_t at = QV_FILE_HEADER; int npieces = 0;
@@ -432,6 +437,7 @@ extern "C" int harc_amd_qpack_files(const harc_amd_params *params, const char *q
             RC_TRY(dev_reserve(&txt, (size_t)bytes));
             RC_TRY(dev_reserve(&out, (size_t)(qv_bound(m, L, rb) - QV_FILE_HEADER)));
             { const double t0 = mono_now(); RC_TRY(feed.upload_piece(p, txt.p, nullptr)); t_read += mono_now() - t0; }
+            if (map) RC_TRY(harc_qmap_run(c, txt.p, m, L, map, txt.p, stats ? &acc : nullptr, tlog ? &t_map : nullptr));
             uint64_t nblk = 0;
             RC_TRY(harc_qpack_run(c, txt.p, m, L, rb, (uint8_t *)out.p, out.cap, &nblk, &st));
             { const double t0 = mono_now(); RC_TRY(drain.put(out.p, (size_t)nblk, at)); t_write += mono_now() - t0; }
@@ -440,10 +446,20 @@ extern "C" int harc_amd_qpack_files(const harc_amd_params *params, const char *q
         drain.set_final_size(at);
         { const double t0 = mono_now(); RC_TRY(drain.finish()); t_write += mono_now() - t0; }
     }
-    if (tlog) fprintf(stderr, "[qpack] %llu bytes of text -> %llu bytes in %llu blocks (%llu stored), %d pieces: %.3f s in the kernels, %.3f s waiting for the readers, %.3f s waiting for the writers\n",
-                      (unsigned long long)qsz, (unsigned long long)at, (unsigned long long)nb, (unsigned long long)st.stored, npieces, st.seconds, t_read, t_write);
+    if (map && stats) qm_acc_stats(&acc, n * (uint64_t)L, stats);
+    if (tlog) {
+        char mapped[64] = "";
+        if (map) snprintf(mapped, sizeof mapped, ", %.3f s in the kernels of the map", t_map);
+        fprintf(stderr, "[qpack] %llu bytes of text -> %llu bytes in %llu blocks (%llu stored), %d pieces: %.3f s in the kernels, %.3f s waiting for the readers, %.3f s waiting for the writers%s\n",
+                (unsigned long long)qsz, (unsigned long long)at, (unsigned long long)nb, (unsigned long long)st.stored, npieces, st.seconds, t_read, t_write, mapped);
+    }
     outguard.ok = true;
     return HARC_AMD_OK;
+}
+
+extern "C" int harc_amd_qpack_files(const harc_amd_params *params, const char *quality_path, const char *out_path)
+{
+    return harc_amd_qpack_files_ex(params, quality_path, out_path, nullptr, nullptr);
 }
 
 extern "C" int harc_amd_qunpack_files(const harc_amd_params *params, const char *packed_path, const char *out_path)

@@ -261,7 +261,7 @@ int harc_amd_input_signature(harc_amd_ctx *ctx, uint64_t sig[3]);           /* o
 int harc_amd_stream_digest(harc_amd_ctx *ctx, uint64_t out[4]);
 /* sha256 (hex) of the kernel sources this library was built from: ties a committed profile (profiles/k_steps_traffic.json) to a build */
 const char *harc_amd_build_id(void);
-/* 1 when this library was built with the named optional part: "test_transport" (the file-mailbox transport of the one-GPU multi-rank tests), "experiments" (schedule constants from the environment); 0 otherwise */
+/* 1 when this library was built with the named optional part: "test_transport" (the file-mailbox transport of the one-GPU multi-rank tests), "experiments" (schedule constants from the environment), "spack" (the packed stream file), "qmap" (lossy quality values); 0 otherwise */
 int harc_amd_build_has(const char *feature);
 /* Self-test of the library's launch geometry (one thread per item over n items through harc_gid / harc_gid32, and four lanes per item in folded workgroups, n beyond 2^32 included: a one-dimensional grid of 2^32 and more
  * work-items is cut short without an error on this platform).  *visited == n and *index_sum == n (n - 1) / 2 mod 2^64 when every item was visited once. */
@@ -377,6 +377,50 @@ int harc_amd_qpack_files(const harc_amd_params *params, const char *quality_path
 /* packed_path -> the quality file at out_path, n * (readlen + 1) bytes known from the header before anything is decoded.  A short file, a wrong magic, a block
    prefix that leaves the file or any damaged block: HARC_AMD_EINVAL; a failed read: HARC_AMD_EIO.  On any failure out_path is removed. */
 int harc_amd_qunpack_files(const harc_amd_params *params, const char *packed_path, const char *out_path);
+
+/* ---- Lossy quality values (./harc -c -q -b SPEC; README.md, "-b and what it promises"): every quality value of a quality text -- n_reads lines of exactly
+   readlen bytes and a newline, readlen in 1..255, as above -- is replaced by a coarser one.  A value is a byte v in 33..126, its Phred score q = v - 33.
+   Newlines, and bytes outside 33..126, are never changed.  Every rule lives once in harc_amd/csrc/qm_block.h, for host and device.  The schemes:
+     kind 1, a table: v -> table[v].  Valid when table[v] == v for every v outside 33..126 and table[v] lies in 33..126 for every v inside.
+     kind 2, run smoothing with radius R (1..46): every line is cut, left to right, into blocks -- a block starts at the first byte not yet in one and takes the
+             next byte while max - min over the block stays <= 2 R -- and every byte of a block becomes floor((min + max) / 2): no value moves by more than R.
+   An invalid map is refused by every call with HARC_AMD_EINVAL, naming the first offending byte value. */
+typedef struct harc_amd_qmap {
+    int32_t kind;          /* 1: table, 2: run smoothing */
+    int32_t radius;        /* kind 2: R */
+    uint8_t table[256];    /* kind 1 */
+} harc_amd_qmap;
+/* What a mapping did, over the values 33..126 only.  A NULL pointer in a call: not computed (the kernels then do nothing for it). */
+typedef struct harc_amd_qmap_stats {
+    uint64_t values;       /* n_reads * readlen */
+    uint64_t changed;      /* values that are not what they were */
+    uint64_t sum_abs;      /* sum of |v' - v| */
+    uint64_t sum_sq;       /* sum of (v' - v)^2 */
+    uint32_t max_abs;
+    uint32_t distinct_in;  /* distinct values before ... */
+    uint32_t distinct_out; /* ... and after */
+    uint32_t reserved;
+} harc_amd_qmap_stats;
+/* Host only: a spec string -> its map.  "ill8" (the eight levels of README.md), "bin:T:H:L" (q' = H when q >= T, else L; 1 <= T <= 93, 0 <= L <= H <= 93),
+   "cap:M" (q' = min(q, M); 0 <= M <= 93), "pblock:R" (kind 2; 1 <= R <= 46).  Integers only.  Anything else -- an unknown name, a missing or surplus field, a
+   number out of range, trailing characters -- is HARC_AMD_EINVAL, and the message names the spec and the field. */
+int harc_amd_qmap_parse(const char *spec, harc_amd_qmap *out);
+/* The serial line-by-line mapper of qm_block.h on the host: what the kernels are held to, byte for byte (tests).  out == text (in place) or disjoint from it.
+   The (readlen + 1)-stride check of harc_amd_qpack_device applies, with the same message. */
+int harc_amd_qmap_host(const char *text, uint64_t n_reads, int32_t readlen, const harc_amd_qmap *map, char *out, harc_amd_qmap_stats *stats);
+/* The same on the GPU: d_text -> d_out, n_reads * (readlen + 1) bytes of device memory each, any alignment, and the two alignments may differ.  d_out == d_text
+   exactly (in place) or disjoint from it: any other overlap is HARC_AMD_EINVAL.  No byte outside d_out's bytes is written, and no load leaves the 16-byte-aligned
+   hull of d_text's.  A table runs as one streaming pass, run smoothing with a workgroup per 256 lines.  A text that fails the stride check is refused after the
+   pass: values of d_out may then have been mapped.  HARC_AMD_TRACE=1: one "[qmap] device call" line on stderr with the kernel's milliseconds. */
+int harc_amd_qmap_device(harc_amd_ctx *ctx, const char *d_text, uint64_t n_reads, int32_t readlen, const harc_amd_qmap *map, char *d_out, harc_amd_qmap_stats *stats);
+/* quality_path -> out_path (a different file), mapped on the GPU; only `device` is taken from params.  The file runs through the pinned ring in pieces of whole
+   lines (64 MiB; HARC_AMD_QMAP_PIECE=lines in tests), so it may be larger than device memory; the output is the same file whatever the piece, slice or thread
+   settings (HARC_AMD_FEED_SLICE, HARC_AMD_FEED_THREADS).  On any failure out_path is removed. */
+int harc_amd_qmap_files(const harc_amd_params *params, const char *quality_path, const char *out_path, const harc_amd_qmap *map, harc_amd_qmap_stats *stats);
+/* harc_amd_qpack_files over the mapped text: every uploaded piece is mapped in place in device memory in front of the coder, the mapped text never reaches a
+   file.  The packed file is that of harc_amd_qpack_files over the output of harc_amd_qmap_files.  map == NULL: harc_amd_qpack_files itself (stats is not touched).
+   HARC_AMD_TRACE=1: with a map the "[qpack]" line also names the seconds in the map's kernels. */
+int harc_amd_qpack_files_ex(const harc_amd_params *params, const char *quality_path, const char *out_path, const harc_amd_qmap *map, harc_amd_qmap_stats *stats);
 
 /* ---- The packed id file X.id.hi (./harc -c -q -I; the format is written down in README.md, "The packed id file"): an id text -- lines of any length, empty
    ones too, every one ended by a newline (a last line without one: HARC_AMD_EINVAL) -> a 32-byte header and blocks of lines_per_block lines, each stored or

@@ -10,7 +10,8 @@ from .api import (HarcAmd, HarcAmdError, Params, Counters, default_params, lib, 
                   fastq_assemble, bgzf_bound, bgzf_deflate_host, qpack_bound, qpack_host, qunpack_host, qpack_files, qunpack_files,
                   QMap, QMapStats, qmap_parse, qmap_host, qmap_files,
                   idpack_bound, idpack_host, idunpack_host, idpack_files, idunpack_files,
-                  spack_bound, spack_host, sunpack_host, spack_files, sunpack_files, spack_file_list, sunpack_file_list)
+                  spack_bound, spack_host, sunpack_host, spack_files, sunpack_files, spack_file_list, sunpack_file_list,
+                  text_digest_host, text_digest_file, reads_check_file)
 from ._build import build
 
 __all__ = ["HarcAmd", "HarcAmdError", "Params", "Counters", "default_params", "lib", "lib_path", "reorder", "encoder",
@@ -19,4 +20,5 @@ __all__ = ["HarcAmd", "HarcAmdError", "Params", "Counters", "default_params", "l
            "qpack_bound", "qpack_host", "qunpack_host", "qpack_files", "qunpack_files",
            "QMap", "QMapStats", "qmap_parse", "qmap_host", "qmap_files",
            "idpack_bound", "idpack_host", "idunpack_host", "idpack_files", "idunpack_files",
-           "spack_bound", "spack_host", "sunpack_host", "spack_files", "sunpack_files", "spack_file_list", "sunpack_file_list"]
+           "spack_bound", "spack_host", "sunpack_host", "spack_files", "sunpack_files", "spack_file_list", "sunpack_file_list",
+           "text_digest_host", "text_digest_file", "reads_check_file"]

@@ -158,6 +158,13 @@ def lib():
     l.harc_amd_selftest_launch.argtypes = [ctx, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     l.harc_amd_selftest_index.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    U3 = C.POINTER(C.c_uint64)
+    l.harc_amd_text_digest_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_uint64, U3]
+    l.harc_amd_text_digest_host.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, U3]
+    l.harc_amd_text_digest_files.argtypes = [PP, C.c_char_p, U3]
+    l.harc_amd_input_order_digest.argtypes = [ctx, U3]
+    l.harc_amd_reads_check_files.argtypes = [PP, C.c_char_p, U3, U3]
+    l.harc_amd_compress_fastq_files_checked.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32]
     l.harc_amd_build_id.restype = C.c_char_p
     _lib = l
     return l
@@ -207,11 +214,11 @@ def preprocess(fastq, basedir, readlen):
     _check(lib().harc_amd_preprocess_files(os.fsencode(fastq), os.fsencode(basedir), readlen))
 
 
-def compress_fastq(fastq, basedir, readlen, num_thr=1, num_chains=1, preserve_order=False, preserve_quality=False, **kw):
+def compress_fastq(fastq, basedir, readlen, num_thr=1, num_chains=1, preserve_order=False, preserve_quality=False, check=False, **kw):
     """harc:50-69 in one call, FASTQ parsed on the GPU; preserve_quality (-q) also writes output.quality / output.id
-    (preprocess.cpp:61-118, reorder_quality.cpp)"""
+    (preprocess.cpp:61-118, reorder_quality.cpp); check (-V): the streams are decoded once before they are written and output/read.check is written"""
     p = default_params(readlen, num_thr=num_thr, num_chains=num_chains, **kw)
-    _check(lib().harc_amd_compress_fastq_files_ex(C.byref(p), os.fsencode(fastq), os.fsencode(basedir), int(preserve_order), int(preserve_quality)))
+    _check(lib().harc_amd_compress_fastq_files_checked(C.byref(p), os.fsencode(fastq), os.fsencode(basedir), int(preserve_order), int(preserve_quality), int(check)))
 
 
 def build_has(feature):
@@ -449,6 +456,29 @@ def sunpack_file_list(pairs, device=0):
     _check(lib().harc_amd_sunpack_file_list(C.byref(p), len(pairs), _path_list([a for a, _ in pairs]), _path_list([b for _, b in pairs])))
 
 
+def text_digest_host(text, first_offset=0, acc=(0, 0, 0)):
+    """T = (bytes, newlines, D) of `text` at offset `first_offset` of a whole text, added to `acc`, on the host (include/harc_amd.h: harc_amd_text_digest_host)"""
+    a = (C.c_uint64 * 3)(*acc)
+    _check(lib().harc_amd_text_digest_host(bytes(text), len(text), first_offset, a))
+    return tuple(a)
+
+
+def text_digest_file(path, device=0):
+    """T = (bytes, newlines, D) of the file at `path`, digested on the GPU (include/harc_amd.h: harc_amd_text_digest_files)"""
+    p = default_params(100, device=device)
+    a = (C.c_uint64 * 3)()
+    _check(lib().harc_amd_text_digest_files(C.byref(p), os.fsencode(path), a))
+    return tuple(a)
+
+
+def reads_check_file(dna, device=0):
+    """the decoders' output read once on the GPU -> (multiset signature of its reads, T of its text) (include/harc_amd.h: harc_amd_reads_check_files)"""
+    p = default_params(100, device=device)
+    s, t = (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+    _check(lib().harc_amd_reads_check_files(C.byref(p), os.fsencode(dna), s, t))
+    return tuple(s), tuple(t)
+
+
 def pack_order(basedir, readlen=100, **kw):
     """== `pack_order.out <basedir>` (src/pack_order.cpp:11-77)"""
     p = default_params(readlen, **kw)
@@ -637,6 +667,18 @@ class HarcAmd:
         sig = (C.c_uint64 * 3)()
         _check(lib().harc_amd_input_signature(self._ctx, sig))
         return tuple(int(x) for x in sig)
+
+    def text_digest_device(self, ptr, nbytes, first_offset=0, acc=(0, 0, 0)):
+        """T = (bytes, newlines, D) of the nbytes bytes at `ptr` (device memory, any alignment), byte i at offset first_offset + i of the whole text, added to `acc`"""
+        a = (C.c_uint64 * 3)(*acc)
+        _check(lib().harc_amd_text_digest_device(self._ctx, C.c_void_p(ptr) if ptr else None, nbytes, first_offset, a))
+        return tuple(a)
+
+    def input_order_digest(self):
+        """T of the text "read_0\\nread_1\\n..." of the reads the context holds, in input record order"""
+        a = (C.c_uint64 * 3)()
+        _check(lib().harc_amd_input_order_digest(self._ctx, a))
+        return tuple(a)
 
     def reads_signature_device(self, d_ascii, n, stride):
         sig = (C.c_uint64 * 3)()

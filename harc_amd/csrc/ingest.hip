@@ -6,6 +6,7 @@
 #include "devutil.h"
 #include "inflate_member.h"
 #include "fileio.h"
+#include "check_block.h"
 
 // line index in two levels: newlines per 4096-byte tile -> scan of the tile counts -> positions written tile by tile
 #define NL_TILE 4096
@@ -768,6 +769,11 @@ static int gzip_kind(const char *path, double *ratio)
 // FASTQ file -> every stage-II file under <basedir>/output (+ read_order_N.bin, numreads.bin): harc:50-69 without input_clean.dna
 extern "C" int harc_amd_compress_fastq_files_ex(const harc_amd_params *params, const char *fastq, const char *basedir, int32_t preserve_order, int32_t preserve_quality)
 {
+    return harc_amd_compress_fastq_files_checked(params, fastq, basedir, preserve_order, preserve_quality, 0);
+}
+// check (./harc -c -V): the signature (and with -p the order digest) of the reads as ingested, the streams decoded once before they are written, read.check
+extern "C" int harc_amd_compress_fastq_files_checked(const harc_amd_params *params, const char *fastq, const char *basedir, int32_t preserve_order, int32_t preserve_quality, int32_t check)
+{
     if (!params || !fastq || !basedir) return HARC_AMD_EINVAL;
     for (double &x : g_fastq_timing) x = 0;
     const double t_begin = mono_now();
@@ -824,6 +830,12 @@ extern "C" int harc_amd_compress_fastq_files_ex(const harc_amd_params *params, c
     LapTimer tm{ "[compress_fastq]" };
     RC_TRY(spit_stream(c, HARC_AMD_IN_ORDER_N, 0, od + "read_order_N.bin"));
     { const uint32_t n32 = c->N; RC_TRY(spit_file(od + "numreads.bin", &n32, 4)); }
+    uint64_t sig_in[3] = { 0, 0, 0 }, t_order[3] = { 0, 0, 0 };
+    if (check) {                                                  // of the input as ingested, before a stage has touched it
+        RC_TRY(harc_amd_input_signature(c, sig_in));
+        if (preserve_order) RC_TRY(harc_amd_input_order_digest(c, t_order));
+        tm.lap("input signature");
+    }
     double t_ph = mono_now();
     RC_TRY(harc_amd_reorder(c));
     tm.lap("reorder");
@@ -834,6 +846,20 @@ extern "C" int harc_amd_compress_fastq_files_ex(const harc_amd_params *params, c
     harc_amd_counters C; harc_amd_get_counters(c, &C);
     printf("Reordering done, %llu were unmatched\n", (unsigned long long)C.unmatched);
     printf("Encoding done:\n%llu singleton reads were aligned\n%llu reads with N were aligned\n", (unsigned long long)C.aligned_singletons, (unsigned long long)C.aligned_N);
+    if (check) {                                                  // the streams are decoded once before a byte of them is written
+        uint64_t sig_out[3] = { 0, 0, 0 };
+        RC_TRY(harc_amd_decode_signature(c, sig_out));
+        tm.lap("streams decoded");
+        if (memcmp(sig_in, sig_out, sizeof sig_in)) {
+            harc_set_error("the streams do not decode to the reads that came in: the input's signature is (%016llx, %016llx, %016llx), the decoded streams' is (%016llx, %016llx, %016llx); nothing was written",
+                           (unsigned long long)sig_in[0], (unsigned long long)sig_in[1], (unsigned long long)sig_in[2], (unsigned long long)sig_out[0], (unsigned long long)sig_out[1], (unsigned long long)sig_out[2]);
+            return HARC_AMD_EINTERNAL;
+        }
+        char rec[256]; int k = snprintf(rec, sizeof rec, "%s\n", CK_MAGIC);
+        k += ck_format_reads(rec + k, sizeof rec - (size_t)k, sig_in);
+        if (preserve_order) k += ck_format_order(rec + k, sizeof rec - (size_t)k, t_order);
+        RC_TRY(spit_file(od + "read.check", rec, (size_t)k));
+    }
     RC_TRY(write_shard_family(c, od, 0));
     tm.lap("stream files");
     RC_TRY(write_whole_job_files(c, od));

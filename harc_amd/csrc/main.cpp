@@ -23,6 +23,10 @@
 //   harc_amd_stage id_unpack <packed> <device> <out>                       ... and back (./harc -d -q when only X.id.hi is there)
 //   harc_amd_stage streams_pack <device> <in> <out> [<in> <out> ...]       every <in> -> the packed stream file <out>, one after the other on one context (./harc -c -S)
 //   harc_amd_stage streams_unpack <device> <in> <out> [<in> <out> ...]     ... and back (./harc -d when the archive holds .hs files)
+//   harc_amd_stage text_digest <file> [<device>]                           "bytes lines D" of the file's text on stdout, 16 hex digits each (./harc -c -V, -d, -v)
+//   harc_amd_stage reads_check <dna> [<device>]                            "count sum xor bytes lines D" of the decoders' output, read once: the multiset signature
+//                                                                          of its reads and the digest of its text (./harc -d, -v on an archive made with -V)
+// compressfq takes one more trailing argument, "check" (./harc -c -V): the streams are decoded once before they are written, and output/read.check is written.
 // readlen / num_thr arrive as arguments instead of the compile-time macros of src/config.h (harc:52-63).
 #include <stdio.h>
 #include <stdlib.h>
@@ -42,6 +46,19 @@ int main(int argc, char **argv)
         harc_amd_qmap M;
         if (argc != 3) { fprintf(stderr, "quality_spec needs <spec>\n"); return 2; }
         if (harc_amd_qmap_parse(argv[2], &M) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 2; }
+        return 0;
+    }
+    if (argc >= 2 && (!strcmp(argv[1], "text_digest") || !strcmp(argv[1], "reads_check"))) {
+        if (argc < 3) { fprintf(stderr, "%s needs <file> [<device>]\n", argv[1]); return 2; }
+        harc_amd_params PC;
+        if (harc_amd_default_params(100, &PC) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
+        if (argc > 3) PC.device = atoi(argv[3]);
+        uint64_t sig[3] = { 0, 0, 0 }, t[3] = { 0, 0, 0 };
+        const bool reads = !strcmp(argv[1], "reads_check");
+        const int rcc = reads ? harc_amd_reads_check_files(&PC, argv[2], sig, t) : harc_amd_text_digest_files(&PC, argv[2], t);
+        if (rcc != 0) { fprintf(stderr, "harc_amd_stage %s failed (%d): %s\n", argv[1], rcc, harc_amd_last_error()); return 1; }
+        if (reads) printf("%016llx %016llx %016llx ", (unsigned long long)sig[0], (unsigned long long)sig[1], (unsigned long long)sig[2]);
+        printf("%016llx %016llx %016llx\n", (unsigned long long)t[0], (unsigned long long)t[1], (unsigned long long)t[2]);
         return 0;
     }
     if (argc < 4) { fprintf(stderr, "usage: %s reorder|encoder|compress|pack_order <basedir> <readlen> [num_thr] [num_chains]\n", argv[0]); return 2; }
@@ -131,7 +148,8 @@ int main(int argc, char **argv)
         if (argc > 6) P.num_chains = atoi(argv[6]);
         if (argc > 7) P.num_steps = atoi(argv[7]);
         const int po = argc > 8 && !strcmp(argv[8], "True"), pq = argc > 9 && !strcmp(argv[9], "True");     // preprocess.out's argv[3], argv[4] (harc:50)
-        rc = harc_amd_compress_fastq_files_ex(&P, argv[4], argv[2], po, pq);
+        if (argc > 10 && strcmp(argv[10], "check")) { fprintf(stderr, "compressfq: the argument behind <preserve_quality> can only be 'check' (got '%s')\n", argv[10]); return 2; }
+        rc = harc_amd_compress_fastq_files_checked(&P, argv[4], argv[2], po, pq, argc > 10);
     }
     else if (!strcmp(argv[1], "compressfq_shard")) {
         if (argc < 13) { fprintf(stderr, "compressfq_shard needs <fastq> <num_thr> <num_chains> <num_steps> <p> <q> <world> <rank> <comm_spec> [device]\n"); return 2; }

@@ -489,6 +489,30 @@ int harc_amd_sunpack_files(const harc_amd_params *params, const char *packed_pat
 int harc_amd_spack_file_list(const harc_amd_params *params, int32_t n_files, const char *const *in_paths, const char *const *out_paths);
 int harc_amd_sunpack_file_list(const harc_amd_params *params, int32_t n_files, const char *const *packed_paths, const char *const *out_paths);
 
+/* ---- Checked archives (./harc -c -V, -d, -v; README.md, "-V and what it promises").  The digest of a text of n bytes is T(text) = (n, newlines, D) with
+   D = sum over the offsets o of mix64(((o + 1) << 8) | byte_o) mod 2^64 (harc_amd/csrc/check_block.h): a changed byte always changes D, any other change goes
+   unnoticed with probability about 2^-64, and pieces that know their first offset add up to the digest of the whole.  Not cryptographic. */
+/* The nbytes bytes at d_text (device memory, any alignment; no load leaves the 16-byte-aligned hull of the text), byte i at offset first_offset + i of the whole
+   text: acc[0] += nbytes, acc[1] += newlines, acc[2] += their D terms.  nbytes may be 0.  HARC_AMD_TRACE=1: one "[check] device call" line on stderr. */
+int harc_amd_text_digest_device(harc_amd_ctx *ctx, const void *d_text, uint64_t nbytes, uint64_t first_offset, uint64_t acc[3]);
+/* The same sums over host memory, serially on the host: what the kernel is held to (tests).  Touches no device. */
+int harc_amd_text_digest_host(const void *text, uint64_t nbytes, uint64_t first_offset, uint64_t acc[3]);
+/* out = T of the file at path, sent through the pinned ring in pieces of 64 MiB; only `device` is taken from params.  The answer is the same whatever
+   HARC_AMD_FEED_THREADS and HARC_AMD_FEED_SLICE are; an empty file gives (0, 0, 0) and touches no device.  HARC_AMD_TRACE=1: one "[check]" line on stderr. */
+int harc_amd_text_digest_files(const harc_amd_params *params, const char *path, uint64_t out[3]);
+/* out = T of the text "read_0\nread_1\n..." of the reads the context holds, in input record order: after harc_amd_set_fastq_device (or the file ingest) from the
+   packed clean reads, the packed reads with N and the record numbers of the latter (HARC_AMD_IN_ORDER_N); after harc_amd_set_reads_* alone the clean reads in
+   their order.  out[0] = records * (readlen + 1), out[1] = records. */
+int harc_amd_input_order_digest(harc_amd_ctx *ctx, uint64_t out[3]);
+/* dna_path (what the decoders write: fixed-length reads, one per line; the read length is that of the first line) read once through the pinned ring:
+   sig = the multiset signature of its reads (harc_amd_reads_signature_device's definition), t = T of its text.  Only `device` is taken from params. */
+int harc_amd_reads_check_files(const harc_amd_params *params, const char *dna_path, uint64_t sig[3], uint64_t t[3]);
+/* harc_amd_compress_fastq_files_ex that also records and checks (check != 0; 0: that call itself): the multiset signature of the reads as ingested is taken before
+   stage I, and with preserve_order the order digest; after stage II the streams are decoded once on the GPU (harc_amd_decode_signature) and must give the same
+   signature -- otherwise HARC_AMD_EINTERNAL naming both triples, and no stream file is written.  <basedir>/output/read.check then holds "HARCV1", the line
+   "reads <count> <sum> <xor>" and, with preserve_order, "order <bytes> <D>", every value as 16 lowercase hex digits. */
+int harc_amd_compress_fastq_files_checked(const harc_amd_params *params, const char *fastq, const char *basedir, int32_t preserve_order, int32_t preserve_quality, int32_t check);
+
 #ifdef __cplusplus
 }
 #endif

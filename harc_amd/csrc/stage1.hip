@@ -62,7 +62,8 @@ struct S1Args {
     int budget;                      // HARC_SCAN_BUDGET (experiments may override it: HARC_AMD_BUDGET)
     int stepcap;                     // HARC_STEP_CAP (HARC_AMD_STEPCAP)
     int weedmin;                     // wave-uniform scan: single-read bins a batch must find before their claim bits are looked up ahead of the tests (HARC_AMD_WEEDMIN)
-    int lazy;                        // 1: steps that agree with the consensus everywhere take the rows from their read and leave the counts to cons_flush (HARC_AMD_LAZY=0: every step applies its counts; same bytes)
+    int lazy;                        // bit 0: steps that agree with the consensus everywhere take the rows from their read and leave the counts to cons_flush (HARC_AMD_LAZY=0: every step applies its counts; same bytes)
+                                     // bit 1 (with bit 0 only): such a step hands the bins its batch found behind the hit to the next step (k_steps' CARRY; HARC_AMD_CARRY=0: no; same bytes)
     uint4 *cstat_coop;               // ... the cooperative kernel's own (k_chain_counts adds both up and keeps its share apart: bench.py prices the two kernels against different ceilings)
     uint2 *csteps;                   // per chain: steps walked by the launches of the main kernel (x) and of the cooperative kernel (y), kept or not
     uint4 *cstat;                    // per chain statistics: x slots inspected, y candidates tested, z sequential-equivalent key lookups, w sequential-equivalent candidates
@@ -762,10 +763,12 @@ static inline size_t steps_lds_bytes_coop(int W, int maxmatch, int nprobe)
     const int NW = 2 * W, ROW = 3 * NW + 1, MROW = (NW + 3) & ~3;
     return ((size_t)2 * maxmatch * MROW + (size_t)((2 * ROW + 3) & ~3) + (size_t)MROW + (size_t)8 * NW + (size_t)32 + (size_t)2 * nprobe + 8) * 4 + HARC_WGCMD_BYTES + 16;
 }
-static inline size_t steps_lds_bytes(int W, int maxmatch, int nprobe, bool seq = false)
+// carry: the dense SPEC kernel's stash (HARC_CARRY_DW dwords, behind every wave's table of its own reads) and its (dir, dictionary, shift) -> probe map (16 bits each) behind the probes
+#define HARC_CARRY_DW (4 * (64 * 2 + 2))
+static inline size_t steps_lds_bytes(int W, int maxmatch, int nprobe, bool seq = false, bool carry = false)
 {
     const int NW = 2 * W, ROW = 3 * NW + 1, MROW = (NW + 3) & ~3;
-    return (size_t)4 * (64 * ((W + 1) / 2)) * 16 + ((size_t)2 * maxmatch * MROW + (size_t)4 * 2 * ROW + (size_t)4 * MROW + (size_t)4 * 8 * NW + (size_t)4 * 32 + (size_t)(seq ? 4 * HARC_OWN_SLOTS : 0) + (size_t)2 * nprobe + 8) * 4 + 32;      // (no command block: only the cooperative kernel scans by workgroup)
+    return (carry ? (size_t)(HARC_CARRY_DW + 2 * maxmatch) * 4 : 0) + (size_t)4 * (64 * ((W + 1) / 2)) * 16 + ((size_t)2 * maxmatch * MROW + (size_t)4 * 2 * ROW + (size_t)4 * MROW + (size_t)4 * 8 * NW + (size_t)4 * 32 + (size_t)(seq ? 4 * HARC_OWN_SLOTS : 0) + (size_t)2 * nprobe + 8) * 4 + 32;      // (no command block: only the cooperative kernel scans by workgroup)
 }
 // Hamming distance between a candidate read (registers) and the consensus shifted by the lane's own amount: `row` = ref or rref window
 // row in LDS, bitoff = 32 NW +- 2j, mrow = mask row of (direction, shift) (reorder.cpp:543,608 with mask[j] / revmask[j] of :706-718)
@@ -1266,6 +1269,20 @@ template <int W> __global__ void k_steps_tables(S1Args s, uint32_t *out)
         pinfo[i] = make_uint2((uint32_t)koff | ((uint32_t)dir << 13) | ((uint32_t)l << 14) | ((uint32_t)j << 16),
                               (uint32_t)hoff | ((uint32_t)((dir * s.maxmatch + j) * MROW) << 16));
     }
+    // ... then 16 bits per (dir | dict << 1, shift): the index of that probe, 0xFFFF where a step has no such probe -- what k_steps' CARRY asks to find
+    // the probe of the step before that looked at the same k-mer
+    uint32_t *const cmap = out + nm + 2 * s.nprobe;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < 2 * s.maxmatch; i += gridDim.x * blockDim.x) {
+        uint32_t w = 0;
+        for (int b = 0; b < 2; b++) {
+            const int e = 2 * i + b, g = e / s.maxmatch, j = e % s.maxmatch;
+            const uint32_t want = (uint32_t)j | ((uint32_t)(g & 1) << 8) | ((uint32_t)(g >> 1) << 9);
+            uint32_t q = 0xFFFFu;
+            for (int p = 0; p < s.nprobe && p < 0xFFFF; p++) if (s.probe_tab[p] == want) q = (uint32_t)p;
+            w |= q << (16 * b);
+        }
+        cmap[i] = w;
+    }
 }
 
 // ---- Exact mode (ONE chain: the reference at -t 1, byte for byte) and runs with a handful of chains leave the chip idle while a single wave
@@ -1405,6 +1422,17 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
     // (the cooperative kernel walks ONE chain per workgroup with its counts in registers: no counts area and one set of rows -- 16 KB per workgroup held
     // its one-wave form at 10 walks per compute unit where the registers allow 16)
     constexpr int NSL = COOP ? 1 : 4;                             // chains a workgroup walks
+    // CARRY (the dense SPEC kernel): a step that accepts a read with Hamming distance 0 makes that read the consensus, shifted by fj: probe (j, dir, l) of
+    // the next step reads the very bits probe (j + fj, dir, l) of this one read (k_steps_tables: forward keys at bit 2 (ds + j) of rowF, reverse keys at
+    // 2 (ds - j) of rowR, and the new rowR is the old one moved the other way).  Same key, same slot: what the lanes of the batch found BEHIND the hit
+    // -- eleven of twelve slots a step looks at -- is the next step's answer.  The step leaves {read or first id of the bin, count word} of every lane
+    // in LDS (the stash; count word 0 = looked up, nothing there; HARC_NONE = not known), the next one takes the probes it can map from there, in
+    // front of its first batch, and tests their candidates with the same loop; keys, scrambles, minimizers, bitmap and slot search are for the rest.
+    // Everything about it lives in LDS: 2 dwords x 64 lanes and one meta dword (base << 8 | fj; HARC_NONE = nothing carried) per wave, behind the
+    // wave's table of its own reads (one base address for both).
+    // (HARC_SEQ_OWNT: the stash lives behind the wave's table of its own reads and the carried pass asks that table -- a variant without the table has no carry)
+    constexpr bool CARRY = SEQ && SPEC && !COOP && !QUAD && W >= 4 && HARC_SEQ_OWNT;
+    constexpr int OWNSTRIDE = HARC_OWN_SLOTS + (CARRY ? HARC_CARRY_DW / 4 : 0);
     uint32_t *const s_mask = lds + (COOP ? (size_t)0 : (size_t)4 * ConsState<W, !QUAD>::LP * 4);
     uint32_t *const s_rows = s_mask + (size_t)2 * s.maxmatch * MROW;
     uint32_t *const s_rdl = s_rows + ((NSL * 2 * ROW + 3) & ~3);      // (the column bytes behind it are read 16 bytes at a time)
@@ -1415,7 +1443,7 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
     // chains (there LDS is no limit, and exact mode walks 64 steps per launch: comparing every candidate with up to 63 earlier reads by v_readlane was
     // what made long walks slower than short ones)
     constexpr bool OWNT = (SEQ && HARC_SEQ_OWNT) || (QUAD && !COOP);
-    uint2 *const s_pinfo = reinterpret_cast<uint2 *>(s_own + (OWNT ? 4 * HARC_OWN_SLOTS : 0));      // the table exists in the kernel that asks it only (2 KB more LDS cost the 150-bp kernel a workgroup per CU)
+    uint2 *const s_pinfo = reinterpret_cast<uint2 *>(s_own + (OWNT ? 4 * OWNSTRIDE : 0));      // the table exists in the kernel that asks it only (2 KB more LDS cost the 150-bp kernel a workgroup per CU)
     WgCmd *const cmd = reinterpret_cast<WgCmd *>(reinterpret_cast<char *>(s_pinfo + s.nprobe) + 8 - ((size_t)(s_pinfo + s.nprobe) & 7));
     // main kernel: 4 chains per workgroup, one wave each.  COOP: one chain per workgroup, wave 0 walks it (role 0), waves 1..3 help with the scans
     const int lane = threadIdx.x & 63, role = threadIdx.x >> 6, wv = COOP ? 0 : role;
@@ -1432,9 +1460,12 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
         for (int i = threadIdx.x; i < nm; i += 64 * NWV) s_mask[i] = s.lds_tab[i];
         const uint2 *const pt = reinterpret_cast<const uint2 *>(s.lds_tab + nm);
         for (int i = threadIdx.x; i < s.nprobe; i += 64 * NWV) s_pinfo[i] = pt[i];
+        if constexpr (CARRY) {                                    // the probe map behind the probes (nothing is carried into a launch: the meta words are HARC_NONE with the tables below)
+            for (int i = threadIdx.x; i < 2 * s.maxmatch; i += 64 * NWV) reinterpret_cast<uint32_t *>(s_pinfo + s.nprobe)[i] = s.lds_tab[nm + 2 * s.nprobe + i];
+        }
         for (int i = threadIdx.x; i < NSL * 2 * ROW; i += 64 * NWV) s_rows[i] = 0u;
         for (int i = threadIdx.x; i < NSL * 8 * NW; i += 64 * NWV) s_tmp[i] = 0u;
-        if constexpr (OWNT) for (int i = threadIdx.x; i < 4 * HARC_OWN_SLOTS; i += 64 * NWV) s_own[i] = HARC_NONE;
+        if constexpr (OWNT) for (int i = threadIdx.x; i < 4 * OWNSTRIDE; i += 64 * NWV) s_own[i] = HARC_NONE;
         __syncthreads();
     }
     if (COOP && role != 0) {                                      // helpers: wait for a scan, take part, until the walk is over
@@ -1478,9 +1509,14 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
         h.n_main = (uint32_t)__builtin_amdgcn_readfirstlane((int)h1.x); h.n_sing = (uint32_t)__builtin_amdgcn_readfirstlane((int)h1.y);
         h.nsteps = (uint32_t)__builtin_amdgcn_readfirstlane((int)h1.z); h.pad0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)h1.w);
     }
-    uint4 cst = s.cstat[c];
-    cst.x = (uint32_t)__builtin_amdgcn_readfirstlane((int)cst.x); cst.y = (uint32_t)__builtin_amdgcn_readfirstlane((int)cst.y);
-    cst.z = (uint32_t)__builtin_amdgcn_readfirstlane((int)cst.z); cst.w = (uint32_t)__builtin_amdgcn_readfirstlane((int)cst.w);
+    // (the dense SPEC kernel of reads of 100 bases and more has no register for four counters across the walk: it reads them where it adds to them)
+    constexpr bool CST_LATE = CARRY;
+    uint4 cst = make_uint4(0, 0, 0, 0);
+    if constexpr (!CST_LATE) {
+        cst = s.cstat[c];
+        cst.x = (uint32_t)__builtin_amdgcn_readfirstlane((int)cst.x); cst.y = (uint32_t)__builtin_amdgcn_readfirstlane((int)cst.y);
+        cst.z = (uint32_t)__builtin_amdgcn_readfirstlane((int)cst.z); cst.w = (uint32_t)__builtin_amdgcn_readfirstlane((int)cst.w);
+    }
     if (!(h.flags & CH_ACTIVE)) return;
     if (!COOP && s.bo && (s.bo[c] & 0xFFu)) return;             // sits this super-round out (back-off; resolve_body counts the rounds down)
     if (COOP && !(h.flags & CH_COOP)) return;
@@ -1492,7 +1528,8 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
             h.n_sing++;
         }
         if (r < assigned) {
-            const uint32_t id = s.seedbuf[r];
+            uint32_t id = s.seedbuf[r];
+            if constexpr (CARRY) id = (uint32_t)__builtin_amdgcn_readfirstlane((int)id);      // (there the header's copy of it is a scalar, not two vector registers held across the walk)
             h.cur = id; h.prev = id; h.flags = ((h.flags | CH_PREVUNM) & ~CH_NEEDSEED) & 0xFFFFu; h.mode = 2;
             const uint32_t first = r * (uint32_t)s.nsugg_per_seed;
             const uint32_t ng = first >= got ? 0u : (got - first < (uint32_t)s.nsugg_per_seed ? got - first : (uint32_t)s.nsugg_per_seed);
@@ -1548,11 +1585,17 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
 
     uint32_t *const rowF = s_rows + (size_t)wv * 2 * ROW, *const rowR = rowF + ROW, *const rdl = s_rdl + (size_t)wv * MROW;
     uint8_t *const coltmp = reinterpret_cast<uint8_t *>(s_tmp + (size_t)wv * 8 * NW);
-    uint32_t *const ownt = s_own + (size_t)wv * HARC_OWN_SLOTS;
+    uint32_t *const ownt = s_own + (size_t)wv * OWNSTRIDE;
+    uint2 *const stash = reinterpret_cast<uint2 *>(ownt + HARC_OWN_SLOTS); uint32_t *const cmeta = ownt + HARC_OWN_SLOTS + 128;      // CARRY only
     uint16_t *const pshift = reinterpret_cast<uint16_t *>(s_pend + (size_t)wv * 32);
     const uint64_t kmask0 = (SPEC || s.kbits[0] >= 64) ? ~(uint64_t)0 : (((uint64_t)1 << s.kbits[0]) - 1), kmask1 = (SPEC || s.kbits[1] >= 64) ? ~(uint64_t)0 : (((uint64_t)1 << s.kbits[1]) - 1);
     const uint64_t cap = s.cap[0];                               // both dictionaries have the same geometry (stage1_run_w)
     uint32_t dbg_bins = 0, dbg_iter = 0, dbg_miss = 0, dbg_surv = 0, dbg_batches = 0;   // coop scans / their 64-entry chunks / steps without a hit / (unused) / batches
+    // CARRY: nst | dbg_miss << 8 | dbg_batches << 16 while the walk lasts (at most 64 steps), and nuse: counted in two of the vector registers the kernel has
+    // left, not in four scalar ones that are spilled and reloaded in every step (the empty asm is what keeps the sums out of the scalar file)
+    uint32_t wk = 0;
+    // (every VACC sits where the whole wave is active and `inc` is wave-uniform: all lanes hold the same sum, and the readfirstlane behind the step loop is exact)
+#define VACC(x, inc) do { asm volatile("" : "+v"(x)); (x) += (inc); } while (0)
     uint32_t np = 0, nc = 0, nuse = 0, ncu = 0;                   // ncu: candidates a strictly sequential scan (reorder.cpp:517-649) would have tested too
     // the walk's own flags are ints, not bools: a bool that lives across the step loop is kept as a 64-bit lane mask (two scalar registers, and the
     // tests on it are mask arithmetic); as ints they are one register each -- 100 -> 66 reloads and stores of spilled scalars inside the loops of the
@@ -1569,7 +1612,7 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
     flag_t rows_ok = false; int pend = 0, ptot = 0;
     // (compiled into the wave-uniform kernels only: there the run of agreeing steps is the rule -- dense launches over error-free or nearly error-free
     // reads -- and the code fits; in the other kernels the second path cost registers: the 150-bp dense kernel lost 3.7 % to it)
-    const flag_t lazy = (SEQ || (QUAD && !COOP)) && s.lazy != 0;
+    const flag_t lazy = CARRY ? (flag_t)s.lazy : (flag_t)((SEQ || (QUAD && !COOP)) && s.lazy != 0);      // (CARRY: the whole word, bit 1 = carry; no second register)
     // FASTP (the kernel of runs with few chains; k_succ): while the consensus IS a read -- `lastrid`, taken in orientation `lastdir`: after a fresh
     // seed and after every step with Hamming distance 0 -- the step reads its candidates from that read's successor list instead of asking the
     // tables.  Such a step does not even fetch the read it takes: the window rows are made from it only when something asks for them
@@ -1657,7 +1700,10 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
         // every extra batch is a serial round trip to HBM.
         int base = (t == 0 && resume > 0) ? resume : 0;          // the probes before `resume` were made in an earlier super-round: nothing then, nothing now
         int stepbig = 0;                                         // COOP: probes into large live bins made by this STEP so far
-        for (int bi = 0; base < s.nprobe; bi++) {
+        int bi0 = 0;                                              // CARRY: -1 = the step before left its batch behind, the first turn of the loop is the carried pass
+        if constexpr (CARRY) { if (__builtin_amdgcn_readfirstlane((int)*cmeta) >= 0) bi0 = -1; }
+        int bi = bi0;
+        for (; base < s.nprobe; bi++) {
             // first batch: twice the running mean of the priority index of the chain's hits + 16 (high coverage -> hits at small shifts ->
             // narrow first batch; the mean, not the last hit: where reads start is Poisson, the last hit says little about the next),
             // at most firstmax probes; every later batch is a full wave.  A probe behind the winner is speculation: without the bitmap in
@@ -1665,10 +1711,10 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
             // 4-byte lookup (48: configs[2] chains 768 -> 728 ms); with the bitmap's lines chosen by minimizer it shares the lines of the
             // useful probes (64).  With few chains a round trip costs more than the probes (QUAD: 64).
             int bend;
-            { int w0 = bi == 0 ? ((HARC_W0_MUL * (lastp >> 4) + HARC_W0_ADD + 15) & ~15) : 64; const int wmax = (QUAD || SPEC) ? 64 : (bi <= 1 ? s.firstmax : 64); if (w0 > wmax) w0 = wmax; bend = base + w0; }
+            { int w0 = bi <= 0 ? ((HARC_W0_MUL * (lastp >> 4) + HARC_W0_ADD + 15) & ~15) : 64; const int wmax = (QUAD || SPEC) ? 64 : (bi <= 1 ? s.firstmax : 64); if (w0 > wmax) w0 = wmax; bend = base + w0; }
             if (bend > s.nprobe) bend = s.nprobe;
             if (bend <= base) bend = s.nprobe;
-            const int p = base + lane; dbg_batches++;
+            const int p = base + lane; if constexpr (!CARRY) dbg_batches++;
             uint32_t mine = HARC_NONE; int j = 0, dir = 0, l = 0, myhd = 0;
             uint32_t pix = 0;                                             // SEQ: the probe's descriptor word -- shift, direction and dictionary are taken from it again below (one register, not three, across the scans)
             uint32_t ncb = 0;                                             // candidates this lane tests in this batch
@@ -1676,6 +1722,31 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
             uint2 b_lt = make_uint2(0, 0);                               // COOP: its row of largetab, fetched by the lane that found it (all bins of the batch in ONE round trip)
             bool cand = false; uint32_t c_sst = 0, c_cw = 0, c_piy = 0; uint64_t c_slot = 0;     // SEQ (see "ONE AFTER THE OTHER" below): the small bin this lane's probe found
             uint32_t mrd[NW];                                             // !SEQ: only the lane that wins has loaded them, and only it reads them
+            if (CARRY && bi < 0) {
+                // the carried pass: lane p' asks the map for the probe q of the step before that had shift j' + fj in the same direction and dictionary;
+                // it is known when q was a lane of that batch whose lookup came to an end.  Only the probes in front of the first one that is not known
+                // take part (the sequential order: everything in front of a carried candidate has been looked up); the batches go on from there
+                const uint32_t cm = (uint32_t)__builtin_amdgcn_readfirstlane((int)*cmeta);
+                bool known = false;
+                int ln = lane; asm volatile("" : "+v"(ln));
+                if (ln < s.nprobe) {
+                    const uint2 pi = s_pinfo[ln];
+                    const uint32_t jn = (pi.x >> 16) + (cm & 0xFFu);
+                    if (jn < (uint32_t)s.maxmatch) {
+                        const uint32_t qb = reinterpret_cast<const uint16_t *>(s_pinfo + s.nprobe)[((pi.x >> 13) & 3u) * (uint32_t)s.maxmatch + jn], q = qb - (cm >> 8);
+                        if (qb != 0xFFFFu && q < 64u) {
+                            const uint2 e = stash[q];
+                            if (e.y != HARC_NONE) { known = true; pix = pi.x; c_piy = pi.y; c_sst = e.x; c_cw = e.y; cand = e.y != 0u; }
+                        }
+                    }
+                }
+                const unsigned long long unk = ~__ballot(known);
+                bend = unk ? __ffsll((long long)unk) - 1 : 64;
+                if (lane >= bend) cand = false;
+                // the chain's own reads: the one just taken sits in the shift-0 bins of both dictionaries
+                if (cand && (c_cw & SLOT_EMB) && own_has(ownt, c_sst)) { cand = false; c_cw = 0u; }
+                if (lane == 0) *cmeta = HARC_NONE;                        // consumed
+            } else
             if (p < bend && (SPEC || cap)) {                             // (SPEC: there is a bitmap, so there are reads and a table)
                 const uint2 pi = s_pinfo[p];
                 pix = pi.x;
@@ -1773,6 +1844,7 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                             // asks for the claim word anyway).  __ballot here counts the lanes that are in this branch.
                             if (__popcll(__ballot(true)) >= s.weedmin && ((reinterpret_cast<const uint32_t *>(s.claimed)[sst >> 5] >> (sst & 31u)) & 1u)) { cand = false; atomicOr(reinterpret_cast<uint32_t *>(&tab[sl + qhit]) + 3, SLOT_DEAD); }
                             else if (OWNT && own_has(ownt, sst)) cand = false;
+                            if constexpr (CARRY) c_cw = cand ? c_cw : 0u;     // (the stash says what the lane has: nothing, to the next step too)
                         }
                     }
                     else {
@@ -1812,6 +1884,7 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                 }
             }
             int winlane = 64;
+            if constexpr (CARRY) { if (p >= bend) c_cw = HARC_NONE; }       // what the stash says of a lane behind the end of the batch: not known
             if constexpr (SEQ) {
             // ---- the small bins the probes of this batch found, ONE AFTER THE OTHER in priority order (the sequential order of reorder.cpp:517-552),
             //      every candidate tested by the whole wave: NW lanes fetch one dword of the read each and take their share of the Hamming
@@ -1820,7 +1893,13 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
             //      vector instructions of a scan for the two or three lanes that had a bin, and cost 8 registers per lane for the read.
             {
                 unsigned long long mc = __ballot(cand);
-                if (!COOP) { const unsigned long long mb = __ballot(big); if (mb) mc &= (mb & (0ULL - mb)) - 1ULL; }      // behind a large bin the main kernel stops anyway
+                if (!COOP) {                                              // behind a large bin the main kernel stops anyway
+                    const unsigned long long mb = __ballot(big);
+                    if (mb) {
+                        mc &= (mb & (0ULL - mb)) - 1ULL;
+                        if constexpr (CARRY) { if (lane >= __ffsll((long long)mb) - 1) c_cw = HARC_NONE; }      // ... and nothing is known of these lanes
+                    }
+                }
                 const bool exactwin = !SPEC && s.maxsearch < (int)HARC_LARGEBIN;      // else the maxsearch window (reorder.cpp:540) cannot close inside a small bin
                 uint32_t ntest = 0;
                 while (mc) {
@@ -1841,6 +1920,9 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                     // the whole bin instead of one in front of every candidate
                     uint32_t idv = 0;
                     if (!emb && (uint32_t)lane < cntb) idv = ids[o_sst + lane];
+                    // (CARRY: the ids are waited for here, where the first candidate would wait for them anyway -- with the load still counted as in flight
+                    // inside the loop the compiler put a wait for it between the claim word's load and the read's in the 150-bp kernel)
+                    if constexpr (CARRY) asm volatile("" : "+v"(idv));
                     for (uint32_t i = cntb; i > 0 && seen < s.maxsearch; i--) {
                         const uint32_t rid = emb ? o_sst : (uint32_t)__builtin_amdgcn_readlane((int)idv, (int)(i - 1));
                         // taken by this chain earlier in this super-round? (not in the frozen bitmap: the read the consensus came from sits in the first bins of
@@ -1866,7 +1948,7 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                         if (hd <= s.thresh) { hit = rid; hit_hd = hd; break; }
                     }
                     // hints only (the claim bitmap stays the truth): claimed reads at the top of a bin are never looked at again
-                    if (lead && lane == 0) {
+                    if (lead && lane == 0 && !(CARRY && bi < 0)) {        // (a carried bin has no slot address: no hint from the carried pass)
                         uint32_t *cp = reinterpret_cast<uint32_t *>(&(o_l ? s.slots[1] : s.slots[0])[o_slot]) + 3;
                         if (lead == cntb) atomicOr(cp, SLOT_DEAD); else if (!emb) atomicMin(cp, (cntb - lead) | (o_cw & SLOT_OVF));
                     }
@@ -1903,7 +1985,7 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                 const unsigned long long bigall = __ballot(big);
                 unsigned long long bigm = bigall;
                 if (winlane < 64) bigm &= (1ULL << winlane) - 1ULL;
-                if (!COOP) { if (bigm) { defer = true; break; } }
+                if (!COOP) { if (bigm) { defer = true; if constexpr (CARRY) bi++; break; } }
                 // the probe at which the step reaches HARC_STEP_CAP probes into large live bins: if nothing is found up to and including
                 // it, the step is put off there (what lies behind it is not looked at: the oracle has not either)
                 int caplane = 64;
@@ -1957,18 +2039,30 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
             PH(3);
             if (lane <= winlane) ncu += ncb;                              // lanes behind the winner were speculation (winlane = 64: no hit, all count)
             if (found != HARC_NONE) {
-                nuse += (uint32_t)(base + winlane + 1);
+                if constexpr (CARRY) VACC(nuse, (uint32_t)(base + winlane + 1)); else nuse += (uint32_t)(base + winlane + 1);
                 lastp += 4 * (base + winlane) - (lastp >> 2);
+                if constexpr (CARRY) {
+                    // the read becomes the consensus (the step end below takes the same branch): every lane leaves what its lookup found.  Not known: the
+                    // lanes at and behind the first large bin, and those behind the end of the batch.  A bin weeded above is as empty to the next step
+                    // as to this one (the claim bitmap is frozen for the launch, the chain's own reads only get more)
+                    if ((lazy & 2) && fhd == 0) {
+                        int ln = lane; asm volatile("" : "+v"(ln));           // (the address is made here, not kept in a register across the loops)
+                        stash[ln] = make_uint2(c_sst, c_cw);                  // (c_cw: 0 in a lane that found nothing, HARC_NONE where nothing is known)
+                        if (lane == 0) *cmeta = ((uint32_t)base << 8) | (uint32_t)fj;
+                    }
+                    bi++;
+                }
                 break;
             }
             base = bend;
         }
+        if constexpr (CARRY) VACC(wk, (uint32_t)bi << 16);             // the batches of the step (the carried pass is turn -1: not one of them)
         }
         if (defer || stalled) break;
         if (found == HARC_NONE) {
             // no candidate: go on from the chain's look-ahead seeds (highest id first, skipping what was claimed meanwhile) -- the new
             // seed of reorder.cpp:652-668 without waiting for the next k_reseed
-            nuse += (uint32_t)s.nprobe; dbg_miss++;
+            if constexpr (CARRY) { VACC(nuse, (uint32_t)s.nprobe); VACC(wk, 1u << 8); } else { nuse += (uint32_t)s.nprobe; dbg_miss++; }
             if (ownlate && own_ins < t) own_sync(t);
             uint32_t sid = HARC_NONE;
             if (spos < nsugg) {
@@ -1981,7 +2075,7 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                     else for (int k = 0; k < t; k++) okc = okc && ((uint32_t)__builtin_amdgcn_readlane((int)ownreg, k) != id);
                 }
                 const unsigned long long sm = __ballot(okc);
-                if (sm) { const int f = __ffsll((long long)sm) - 1; sid = __shfl(id, f, 64); spos += f + 1; } else spos = nsugg;
+                if (sm) { const int f = __ffsll((long long)sm) - 1; if constexpr (CARRY) sid = (uint32_t)__builtin_amdgcn_readlane((int)id, f); else sid = __shfl(id, f, 64); spos += f + 1; } else spos = nsugg;
             }
             if (sid == HARC_NONE) { needseed = true; break; }
             if (lane == 0) s.steps[(size_t)c * 64 + t] = make_uint2(sid, (1u << 16) | ((uint32_t)spos << 24));     // (the bid: after the walk, below)
@@ -1992,10 +2086,12 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                 if (lane < NW) { const uint32_t *rp = reinterpret_cast<const uint32_t *>(s.reads + (size_t)sid * W); rdl[lane] = rp[lane]; }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
-                cons_reset_lds(st, rdl, L, lane);                  // every count is replaced: what was pending is gone with the old consensus
+                // (CARRY: the lane number is made anew for this rare path -- what the counts' addresses are made of is not kept in registers across the walk)
+                int ln = lane; if constexpr (CARRY) asm volatile("" : "+v"(ln));
+                cons_reset_lds(st, rdl, L, ln);                    // every count is replaced: what was pending is gone with the old consensus
             }
             rows_ok = false; pend = 0; ptot = 0;
-            nst++;
+            if constexpr (CARRY) VACC(wk, 1u); else nst++;
             if (COOP && bigprobes >= s.budget) break;
             continue;
         }
@@ -2029,10 +2125,12 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                 if (FASTP) { lastrid = HARC_NONE; rows_lazy = false; }
             }
         }
-        nst++;
+        if constexpr (CARRY) VACC(wk, 1u); else nst++;
         PH(4);
         if (COOP && bigprobes >= s.budget) break;
     }
+    if constexpr (CARRY) { wk = (uint32_t)__builtin_amdgcn_readfirstlane((int)wk); nst = (int)(wk & 0xFFu); dbg_miss = (wk >> 8) & 0xFFu; dbg_batches = wk >> 16; nuse = (uint32_t)__builtin_amdgcn_readfirstlane((int)nuse); }
+#undef VACC
     // the bids of the steps walked in this launch, all at once (lane t holds the read of step t): k_resolve is their only reader, and an atomic on a cold
     // line of bid[] in every step sat in front of the next step's first wait for memory (vmcnt counts loads and atomics alike)
     if (lane >= T0 && lane < T0 + nst) atomicMin(&s.bid[ownreg], ((uint32_t)lane << 20) | c);
@@ -2060,7 +2158,7 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
     if (lane == 0 && s.dbg) { atomicAdd(&s.dbg[0], (unsigned long long)dbg_bins); atomicAdd(&s.dbg[1], (unsigned long long)dbg_iter); atomicAdd(&s.dbg[2], (unsigned long long)dbg_miss); atomicAdd(&s.dbg[3], (unsigned long long)dbg_surv); atomicAdd(&s.dbg[4], (unsigned long long)nst); atomicAdd(&s.dbg[5], (unsigned long long)dbg_batches); atomicMax(&s.dbg[6], (unsigned long long)dbg_iter); atomicMax(&s.dbg[7], (unsigned long long)dbg_surv); atomicMax(&s.dbg[8], (unsigned long long)dbg_bins); }
     if (lane == 0) {
         if (COOP) { atomicAdd(&s.cstat_coop[c].x, np); atomicAdd(&s.cstat_coop[c].y, nc); atomicAdd(&s.cstat_coop[c].z, nuse); atomicAdd(&s.cstat_coop[c].w, ncu); s.csteps[c].y += (uint32_t)nst; }   // the helpers add to it too
-        else { cst.x += np; cst.y += nc; cst.z += nuse; cst.w += ncu; s.cstat[c] = cst; s.csteps[c].x += (uint32_t)nst; }
+        else { if constexpr (CST_LATE) cst = s.cstat[c]; cst.x += np; cst.y += nc; cst.z += nuse; cst.w += ncu; s.cstat[c] = cst; s.csteps[c].x += (uint32_t)nst; }
         h.mode = 0;
         h.nsteps = (h.nsteps & 0xFFFF0000u) | (uint32_t)(T0 + nst);
         h.pad0 = ((uint32_t)lastp & 0xFFFFu) | (((uint32_t)spos & 0xFFu) << 16) | (widebits << 24);
@@ -3187,7 +3285,7 @@ template <int W> static int stage1_run_w(harc_amd_ctx *c)
     {
         uint32_t *lt = nullptr;
         const size_t nm = (size_t)2 * P.maxmatch * StepsLds<W>::MROW;
-        RC_TRY(dalloc(c, &lt, nm + 2 * tab.size() + 2));
+        RC_TRY(dalloc(c, &lt, nm + 2 * tab.size() + 2 + 2 * (size_t)P.maxmatch));      // mask rows, probes, probe map
         hipLaunchKernelGGL((k_steps_tables<W>), dim3(4), dim3(256), 0, c->stream, a, lt);
         a.lds_tab = lt;
     }
@@ -3199,6 +3297,8 @@ template <int W> static int stage1_run_w(harc_amd_ctx *c)
     if (a.stepcap < 1) a.stepcap = 1;
     a.weedmin = getenv("HARC_AMD_WEEDMIN") ? atoi(getenv("HARC_AMD_WEEDMIN")) : 3;
     a.lazy = getenv("HARC_AMD_LAZY") ? (atoi(getenv("HARC_AMD_LAZY")) != 0 ? 1 : 0) : 1;
+    // the carry of the dense SPEC kernel (bit 1 of the same word): the shift travels in a byte, the probe map holds 16-bit indices
+    if (a.lazy && !(getenv("HARC_AMD_CARRY") && atoi(getenv("HARC_AMD_CARRY")) == 0) && a.nprobe < 0xFFFF && P.maxmatch <= 255) a.lazy |= 2;
     a.firstmax = (bloom_nwin[0] > 0 && bloom_nwin[1] > 0) ? 64 : 48;     // lines by minimizer: speculative probes share their lines
     if (const char *e = getenv("HARC_AMD_FIRSTMAX")) { const int x = atoi(e); a.firstmax = x < 1 ? 1 : x > 64 ? 64 : x; }
     // successor lists (k_succ): by default where the walk is ONE wave (exact mode, num_chains = 1) -- there the precomputation, twice the lookups of a
@@ -3248,7 +3348,7 @@ template <int W> static int stage1_run_w(harc_amd_ctx *c)
         for (uint32_t p = 0; p < a.own_mod; p++) x_ro[p] = (size_t)p * x_bytes;
         RC_TRY(dalloc(c, &x_dig, 8));
     }
-    const size_t lds_bytes = steps_lds_bytes(W, P.maxmatch, a.nprobe), lds_bytes_seq = steps_lds_bytes(W, P.maxmatch, a.nprobe, true), lds_bytes_coop = steps_lds_bytes_coop(W, P.maxmatch, a.nprobe);
+    const size_t lds_bytes = steps_lds_bytes(W, P.maxmatch, a.nprobe), lds_bytes_seq = steps_lds_bytes(W, P.maxmatch, a.nprobe, true), lds_bytes_carry = steps_lds_bytes(W, P.maxmatch, a.nprobe, true, true), lds_bytes_coop = steps_lds_bytes_coop(W, P.maxmatch, a.nprobe);
     const bool prof = P.profile != 0;
     // every launch that is not QUAD takes a dense kernel (7 / 8 waves per SIMD, see HARC_STEPS_WAVES; round 2: from 49 152 chains on; with the counts in
     // LDS they pay from 16 385 on: 24 k chains of configs[2] at 1/7 scale +5 %, the 21 k chains of c3sd +3.6 %)
@@ -3293,7 +3393,7 @@ template <int W> static int stage1_run_w(harc_amd_ctx *c)
             if (cm) hipLaunchKernelGGL(k_apply_seed, dim3(nblk), dim3(256), 0, c->stream, a);          // the seeds of the chains other ranks walk
             if (prof) { RC_TRY(R.dense.next_pair(&pair)); HIP_TRY(hipEventRecord(pair[0], c->stream)); }
             if (quad) hipLaunchKernelGGL((k_steps<W, true, false>), dim3((K + 3) / 4), dim3(256), lds_bytes_seq, c->stream, a);
-            else if (seq && spec) hipLaunchKernelGGL((k_steps<W, false, false, 4, true, true>), dim3((K + 3) / 4), dim3(256), lds_bytes_seq, c->stream, a);
+            else if (seq && spec) hipLaunchKernelGGL((k_steps<W, false, false, 4, true, true>), dim3((K + 3) / 4), dim3(256), lds_bytes_carry, c->stream, a);
             else if (seq) hipLaunchKernelGGL((k_steps<W, false, false, 4, true>), dim3((K + 3) / 4), dim3(256), lds_bytes_seq, c->stream, a);
             else hipLaunchKernelGGL((k_steps<W, false, false>), dim3((K + 3) / 4), dim3(256), lds_bytes, c->stream, a);
             if (prof) HIP_TRY(hipEventRecord(pair[1], c->stream));

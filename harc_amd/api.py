@@ -158,6 +158,9 @@ def lib():
     l.harc_amd_selftest_launch.argtypes = [ctx, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     l.harc_amd_selftest_index.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    if hasattr(l, "harc_amd_selftest_contigs"):          # (HARC_AMD_LIB may name a build from before it)
+        l.harc_amd_selftest_contigs.argtypes = [ctx, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
     U3 = C.POINTER(C.c_uint64)
     l.harc_amd_text_digest_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_uint64, U3]
     l.harc_amd_text_digest_host.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, U3]
@@ -712,6 +715,23 @@ class HarcAmd:
         if want_large and nl.value > large.size:
             raise HarcAmdError(-1, "harc_amd_selftest_index lists %d large bins among %d keys" % (nl.value, n))
         return int(cap.value), int(nbins.value), slots, ids, (large[:nl.value].copy() if want_large else None)
+
+    def selftest_contigs(self, flag, pos, L, q, cut=10000000):
+        """stage II's contig structure over flag[] (bytes, ord('0') = the read starts a contig) and pos[]: (head, cid, gstart, chead, ncontigs, total,
+        fellback) -- fellback says whether a read lay more than `cut` reads behind a contig start and the passes that cut contigs ran"""
+        import numpy as np
+        flag = np.ascontiguousarray(flag, dtype=np.uint8)
+        pos = np.ascontiguousarray(pos, dtype=np.uint8)
+        n = int(flag.size)
+        if int(pos.size) != n:
+            raise HarcAmdError(-1, "selftest_contigs: %d flags, %d positions" % (n, int(pos.size)))
+        head = np.zeros(n, dtype=np.uint8)
+        cid, chead = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        gstart = np.zeros(n, dtype=np.uint64)
+        nc, total, fb = C.c_uint32(0), C.c_uint64(0), C.c_int32(0)
+        _check(lib().harc_amd_selftest_contigs(self._ctx, flag.ctypes.data, pos.ctypes.data, n, L, q, cut, head.ctypes.data, cid.ctypes.data, gstart.ctypes.data,
+                                               chead.ctypes.data, C.byref(nc), C.byref(total), C.byref(fb)))
+        return head, cid, gstart, chead[:nc.value].copy(), int(nc.value), int(total.value), bool(fb.value)
 
     def stream_digest(self):
         """four 64-bit words over the stage-II streams of the last encode(), folded on the device (params.stream_digest = 1)"""

@@ -98,6 +98,15 @@ int harc_dev_alloc(harc_amd_ctx *c, void **p, size_t bytes)
     return HARC_AMD_OK;
 }
 void harc_dev_free(harc_amd_ctx *c, void *p) { (void)c; (void)p; }   // pool memory is released by mark, not by pointer
+void harc_dev_shrink(harc_amd_ctx *c, void *p, size_t bytes)
+{
+    if (c->pool_cur >= c->pool.size()) return;
+    harc_amd_ctx::PoolChunk &k = c->pool[c->pool_cur];
+    bytes = (bytes + 255) & ~(size_t)255;
+    if (bytes == 0) bytes = 256;
+    if ((char *)p < k.base || (char *)p + bytes > k.base + k.used) return;    // not of this chunk, or not smaller: stays as it is
+    k.used = (size_t)((char *)p - k.base) + bytes;
+}
 harc_mark_t harc_pool_mark(harc_amd_ctx *c)
 {
     if (c->pool.empty()) return 0;

@@ -169,6 +169,8 @@ void harc_drop_results(harc_amd_ctx *c);                                       /
 int harc_dev_alloc(harc_amd_ctx *c, void **p, size_t bytes);
 void harc_dev_free(harc_amd_ctx *c, void *p);
 template <class T> static inline int dalloc(harc_amd_ctx *c, T **p, size_t n) { return harc_dev_alloc(c, (void **)p, n * sizeof(T) + 16); }
+void harc_dev_shrink(harc_amd_ctx *c, void *p, size_t bytes);    // p = the pool's LAST allocation: it keeps its first `bytes` bytes, the rest is free again
+template <class T> static inline void dshrink(harc_amd_ctx *c, T *p, size_t n) { harc_dev_shrink(c, (void *)p, n * sizeof(T) + 16); }
 int harc_tmp_reserve(harc_amd_ctx *c, size_t bytes);
 int harc_raw_alloc(harc_amd_ctx *c, void **p, size_t bytes);     // plain hipMalloc, for buffers that outlive a run
 void harc_raw_free(harc_amd_ctx *c, void *p);
@@ -208,6 +210,10 @@ int prim_incl_scan_u64(harc_amd_ctx *c, const uint64_t *in, uint64_t *out, size_
 int prim_incl_max_u32(harc_amd_ctx *c, const uint32_t *in, uint32_t *out, size_t n);
 // sorted keys -> binstart[b], q[b] = max over the bins j <= b of (home_j + n - j), *nbins (prims.hip; k_table_place reads them)
 int prim_bins_scan(harc_amd_ctx *c, const uint64_t *skeys, size_t n, uint64_t cap, uint32_t *binstart, uint64_t *q, uint32_t *nbins, void *scratch, size_t scratch_bytes);
+// flag[], pos[] -> head, cid, gstart, chead (room for n) and the device words info[3 + (n - 1) / q + 1] = { contigs, columns, "a read lies more than cut
+// reads behind its last head1: nothing here holds", the column of read e * q ... } (prims.hip; stage2.hip: contig_structure reads them)
+int prim_contig_scan(harc_amd_ctx *c, const uint8_t *flag, const uint8_t *pos, size_t n, uint32_t L, uint32_t q, uint32_t cut, uint8_t *head, uint32_t *cid, uint64_t *gstart,
+                     uint32_t *chead, unsigned long long *info);
 
 // ---- stages
 int s1_pack_ascii(harc_amd_ctx *c, const char *d_ascii, uint32_t n, uint32_t stride, uint64_t *d_out);               // 2-bit

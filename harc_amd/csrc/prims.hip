@@ -159,6 +159,91 @@ int prim_bins_scan(harc_amd_ctx *c, const uint64_t *skeys, size_t n, uint64_t ca
     return HARC_AMD_OK;
 }
 
+// ---- stage II's contig structure from ONE scan of flag[] and pos[] (stage2.hip: contig_structure; the definitions stand there).  While no read lies more
+// than `cut` reads behind the last head1 (flag '0' or a shard start) before it, the heads ARE the head1, and a part of the reads sums up to c = its
+// heads, s = its column steps (L at a head, pos elsewhere; read 0: 0) and last = its last head -- read 0 is a head, so a plain maximum.  Reduce, then
+// scan, as k_bins_pass: a wave per segment, 64 reads a trip and CONTIG_UNROLL trips in flight; the library scans the segments' parts; the same walk
+// again writes head, cid, gstart and chead, 2 bytes read and 13 written per read.  The write pass also sees every read's distance to its last head1:
+// where one is above `cut` it raises info[2], and the caller runs the passes that know the cut instead (what this pass wrote is then wrong past that
+// read and is overwritten).  info: [0] contigs, [1] columns, [2] the flag, [3 + e] the column of read e * q.
+struct ContigPart { uint64_t s; uint32_t c, last; };
+struct ContigPartOp {
+    __host__ __device__ ContigPart operator()(const ContigPart &a, const ContigPart &b) const { return ContigPart{ a.s + b.s, a.c + b.c, a.last > b.last ? a.last : b.last }; }
+};
+#define CONTIG_SEG_MIN 2048u      // reads of a segment, at least; segments are whole multiples of 64 * CONTIG_UNROLL reads
+#define CONTIG_SEGS 16384u        // segments of a large input, about
+#define CONTIG_UNROLL 4
+template <bool WRITE> __global__ __launch_bounds__(256) void k_contig_pass(const uint8_t *flag, const uint8_t *pos, uint32_t n, uint32_t L, uint32_t q, uint32_t cut, uint32_t seg, uint32_t nseg,
+                                                                         ContigPart *part, uint8_t *head, uint32_t *cid, uint64_t *gstart, uint32_t *chead, unsigned long long *info)
+{
+    const uint32_t w = (blockIdx.x * 256u + threadIdx.x) >> 6;   // a wave per segment: everything below is wave-uniform but the lane's own read
+    if (w >= nseg) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const unsigned long long upto = ~0ull >> (63 - lane);        // this lane and the ones below
+    uint32_t C = 0, last = 0; uint64_t G = 0;                     // heads, last head and columns so far
+    if (WRITE) { C = part[w].c; last = part[w].last; G = part[w].s; }   // (the parts in front of the segment, scanned)
+    const uint64_t base = (uint64_t)w * seg, end = base + seg < n ? base + seg : (uint64_t)n;
+    uint32_t rem = (uint32_t)(base % q);                          // index of the trip's first read modulo q
+    for (uint64_t at = base; at < end; at += 64u * CONTIG_UNROLL) {
+        uint8_t f[CONTIG_UNROLL], p[CONTIG_UNROLL];
+#pragma unroll
+        for (int u = 0; u < CONTIG_UNROLL; u++) { const uint64_t i = at + 64u * u + lane; f[u] = i < end ? flag[i] : (uint8_t)0; p[u] = i < end ? pos[i] : (uint8_t)0; }
+#pragma unroll
+        for (int u = 0; u < CONTIG_UNROLL; u++) {
+            const uint64_t i0 = at + 64u * u, i = i0 + lane;
+            const uint32_t m = rem + lane;                        // < q + 64: a shard starts where it is a multiple of q
+            const bool sh = q >= 128u ? (m == 0 || m == q) : (m % q) == 0;
+            if (q >= 128u) { rem += 64u; if (rem >= q) rem -= q; } else rem = (rem + 64u) % q;
+            const bool h = i < end && (f[u] == '0' || sh);
+            const unsigned long long hb = __ballot(h);
+            uint32_t v = i >= end ? 0u : h ? (i == 0 ? 0u : L) : (uint32_t)p[u];   // a trip's steps sum to 64 * 255 at most
+            if (WRITE) {
+                const uint32_t rank = C + (uint32_t)__popcll(hb & upto) - (h ? 1u : 0u);
+                for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(v, d, 64); if (lane >= (uint32_t)d) v += o; }
+                const uint64_t g = G + v;
+                const unsigned long long mine = hb & upto;
+                const uint32_t l1 = mine ? (uint32_t)i0 + 63u - (uint32_t)__clzll(mine) : last;    // the last head1 at or before the read
+                if (i < end) {
+                    head[i] = h ? 1 : 0; cid[i] = rank; gstart[i] = g;
+                    if (h) chead[rank] = (uint32_t)i;
+                    if (sh) info[3 + (uint32_t)i / q] = g;
+                    if ((uint32_t)i - l1 > cut) info[2] = 1;
+                    if (i + 1 == n) { info[0] = rank + (h ? 1u : 0u); info[1] = g + L; }
+                }
+                G += __shfl(v, 63, 64);
+            } else {
+                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+                G += v;
+            }
+            if (hb) last = (uint32_t)i0 + 63u - (uint32_t)__clzll(hb);
+            C += (uint32_t)__popcll(hb);
+        }
+    }
+    if (!WRITE && lane == 0) part[w] = ContigPart{ G, C, last };
+}
+// head, cid, gstart: n entries; chead: room for n; info (device): 3 + (n - 1) / q + 1 words, the caller reads them behind the stream
+int prim_contig_scan(harc_amd_ctx *c, const uint8_t *flag, const uint8_t *pos, size_t n, uint32_t L, uint32_t q, uint32_t cut, uint8_t *head, uint32_t *cid, uint64_t *gstart,
+                     uint32_t *chead, unsigned long long *info)
+{
+    if (n == 0) return HARC_AMD_OK;
+    if (n > 0xFFFFFFFFull || q == 0) { harc_set_error("prim_contig_scan: %zu reads, shards of %u", n, q); return HARC_AMD_EINVAL; }
+    size_t seg = (n + CONTIG_SEGS - 1) / CONTIG_SEGS;
+    if (seg < CONTIG_SEG_MIN) seg = CONTIG_SEG_MIN;
+    seg = (seg + 64 * CONTIG_UNROLL - 1) / (64 * CONTIG_UNROLL) * (64 * CONTIG_UNROLL);
+    const uint32_t nseg = (uint32_t)((n + seg - 1) / seg);
+    PoolScope scope(c);
+    ContigPart *part = nullptr; RC_TRY(dalloc(c, &part, (size_t)2 * nseg));
+    ContigPart *front = part + nseg;
+    const dim3 grid((nseg + 3) / 4);
+    HIP_TRY(hipMemsetAsync(info + 2, 0, 8, c->stream));
+    hipLaunchKernelGGL(k_contig_pass<false>, grid, dim3(256), 0, c->stream, flag, pos, (uint32_t)n, L, q, cut, (uint32_t)seg, nseg, part, (uint8_t *)nullptr, (uint32_t *)nullptr, (uint64_t *)nullptr,
+                       (uint32_t *)nullptr, (unsigned long long *)nullptr);
+    PRIM_CALL(rocprim::exclusive_scan(tmp, bytes, part, front, ContigPart{ 0, 0u, 0u }, (size_t)nseg, ContigPartOp(), c->stream));
+    hipLaunchKernelGGL(k_contig_pass<true>, grid, dim3(256), 0, c->stream, flag, pos, (uint32_t)n, L, q, cut, (uint32_t)seg, nseg, front, head, cid, gstart, chead, info);
+    HIP_TRY(hipGetLastError());
+    return HARC_AMD_OK;
+}
+
 // ---- self-test of the launch geometry (devutil.h: harc_grid256 / harc_gid): n items, a thread each; returns how many were visited and the sum of their
 // indices -- n and n (n - 1) / 2 (mod 2^64) when every item was visited exactly once.  tests/test_gpu_parity.py runs it beyond 2^32 items, where a plain
 // one-dimensional grid is cut short without an error on this platform.

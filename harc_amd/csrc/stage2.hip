@@ -9,7 +9,7 @@
 //                             first-come claim of the reference at num_thr=1 is exactly the minimum tuple
 //   list.insert  :310-313  -> a merge by rank (two binary searches) of the reads with the accepted candidates
 //   writecontig  :654-717  -> k_noise<W, false/true> (sizes, then noise, noisepos, pos, order routing, rc) on packed words
-//   packbits     :512-616  -> k_pack2_bytes / k_pack1_bytes
+//   packbits     :512-616  -> k_pack_seq (read_seq, from the packed consensus) / k_pack2_bytes / k_pack1_bytes
 // Shard e of num_thr owns reordered reads [e*q, (e+1)*q) (:171-180); its streams are slices of the global arrays.
 #include "devutil.h"
 #include <time.h>
@@ -37,7 +37,7 @@ struct S2Args {
     unsigned long long *bestbin[2];    // k_realign_big: best[] once more in the order of ids[l] (refreshed before every window pass): a look reads 64 claims in one line instead of 64 lines
     const uint32_t *bloom[2]; int bloom_shift[2];   // one-hash bitmap over the keys of each dictionary (16 bits per key): most windows match nothing
     int bloom_lbits, bloom_nwin;                    // combined bitmap (k_bloom4_set): log2 of its 64-byte lines; minimizer windows per key (0: lines hashed from the key)
-    const uint64_t *cons2;             // consensus, 2-bit code A0 G1 C2 T3, 32 columns per word (k_pack_cons2)
+    uint64_t *cons2;                   // consensus, 2-bit code A0 G1 C2 T3, 32 columns per word (k_consensus writes it beside cons)
     const uint64_t *cand2, *candN;     // T x W: the candidates in the same 2-bit code (N -> 0) and their N masks (both bits of the field set)
     uint4 *events;                     // probes that hit a bin larger than maxsearch: {tuple lo, tuple hi, dict, slot index lo} (+ slot hi in w>>?)
     unsigned int *nevents; uint32_t maxevents;
@@ -132,13 +132,13 @@ __global__ void k_heads1(const uint8_t *flag, uint32_t M, uint32_t q, uint8_t *h
     const uint8_t h = (flag[i] == '0' || (i % q) == 0) ? 1 : 0;
     head[i] = h; hidx[i] = h ? i : 0;
 }
-// step 2: a contig is cut once it holds 10,000,001 reads (encoder.cpp:226 `list_size>10000000`)
-__global__ void k_heads2(uint32_t M, uint8_t *head, const uint32_t *hmax, uint32_t *hidx)
+// step 2: a contig is cut once it holds cut + 1 = 10,000,001 reads (encoder.cpp:226 `list_size>10000000`)
+__global__ void k_heads2(uint32_t M, uint32_t cut, uint8_t *head, const uint32_t *hmax, uint32_t *hidx)
 {
     const uint32_t i = harc_gid32();
     if (i >= M) return;
     const uint32_t r = i - hmax[i];
-    if (r > 0 && (r % 10000001u) == 0) head[i] = 1;
+    if (r > 0 && (r % (cut + 1u)) == 0) head[i] = 1;
     hidx[i] = head[i] ? 1u : 0u;                                  // reused as the flag array for the contig-id scan
 }
 __global__ void k_col_steps(const uint8_t *head, const uint8_t *pos, uint32_t M, int L, uint64_t *d)
@@ -207,17 +207,17 @@ __global__ void k_consensus_tiles(S2Args s, uint32_t ntiles, uint32_t *tlo, uint
     thi[t] = (uint32_t)ub_le(s.gstart, (long long)s.M, X1 - 1);             // last read starting inside or before the tile (every column is covered: >= 0)
     tlo[t] = X0 >= (uint64_t)s.L ? (uint32_t)(ub_le(s.gstart, (long long)s.M, X0 - (uint64_t)s.L) + 1) : 0u;   // first read that reaches column X0
 }
-// NPL = CSHALLOW: the kernel every tile goes through, its counts good for 2^CSHALLOW - 1 reads on a column; a tile where a carry leaves the top plane
-// says so in tovf[tile] and is counted again by NPL = CPLANES, launched behind it, whose other workgroups leave at once.
-template <int NPL> __global__ __launch_bounds__(CTHREADS, NPL == CPLANES ? 4 : 6) void k_consensus(S2Args s, const uint32_t *cid, const unsigned long long *cinfo, int want_windows, const uint32_t *tlo, const uint32_t *thi, uint32_t *tovf)
+// One tile (the `tile`-th of the rank), counted in NPL main planes by the whole workgroup; true in the lanes where a carry left the top plane.
+// Beside the bytes of cons the strip's 16 columns go into cons2 as they stand in the lane, one 32-bit half of a word (A0 G1 C2 T3: the two bits of a
+// row index swapped; zero from the end of the consensus to the end of its last word).
+template <int NPL> __device__ __forceinline__ bool consensus_tile(const S2Args &s, const uint32_t tile, const uint32_t *cid, const unsigned long long *cinfo, int want_windows, const uint32_t *tlo, const uint32_t *thi)
 {
-    if (NPL == CPLANES && !tovf[blockIdx.x]) return;
     extern __shared__ uint64_t cl_words[];                        // [CCHUNK][W] read words, then CCHUNK tile-relative starts
     int *const cl_g = reinterpret_cast<int *>(cl_words + (size_t)CCHUNK * s.W);
     const uint32_t *const cl_w32 = reinterpret_cast<const uint32_t *>(cl_words);   // the same words, 16 bases each
-    const uint64_t X0 = (uint64_t)(blockIdx.x + s.tile_base) * CTILE;
+    const uint64_t X0 = (uint64_t)(tile + s.tile_base) * CTILE;
     const int L = s.L, W = s.W;
-    const long long ilo = tlo[blockIdx.x], ihi = thi[blockIdx.x];
+    const long long ilo = tlo[tile], ihi = thi[tile];
     const int x0r = (int)threadIdx.x * CSTRIP;                   // tile-relative first column of the strip
     const uint64_t x0 = X0 + (uint64_t)x0r;
     const bool mine = x0 < s.total;
@@ -323,8 +323,11 @@ template <int NPL> __global__ __launch_bounds__(CTHREADS, NPL == CPLANES ? 4 : 6
         }
     }
     flush();
-    if (NPL < CPLANES && ovf) tovf[blockIdx.x] = 1;
-    if (!mine) return;
+    uint32_t *const cons2h = reinterpret_cast<uint32_t *>(s.cons2);
+    if (!mine) {
+        if (x0 < ((s.total + 31) & ~31ull)) cons2h[x0 / CSTRIP] = 0;     // the other half of the consensus' last word
+        return ovf;
+    }
     // first strict maximum over the rows A C G T = the earliest row that holds the largest count.  lt: C > A (even bits), T > G (odd bits);
     // w = the planes of the two winners; lt2 (even bits): the winner of (G, T) > the winner of (A, C).  A tie keeps the earlier row every time.
     depth = __builtin_amdgcn_readfirstlane(depth);
@@ -339,6 +342,7 @@ template <int NPL> __global__ __launch_bounds__(CTHREADS, NPL == CPLANES ? 4 : 6
             lt2 |= d & ~dec2 & (w >> 1); dec2 |= d;
         }
     const uint32_t indw = (lt2 & (lt >> 1)) | (~lt2 & lt & EVEN) | (lt2 << 1);     // two bits a column: row A0 C1 G2 T3
+    cons2h[x0 / CSTRIP] = (((indw & EVEN) << 1) | ((indw >> 1) & EVEN)) & (ncol == CSTRIP ? 0xFFFFFFFFu : (1u << (2 * ncol)) - 1u);
     // may a realignment window start at x: the contig of the last read that starts at or before x says.  The reads that start inside the strip
     // are ilast + 1 .. ilast + nstart: where the last of them lies in the contig of read ilast (nearly everywhere) the whole strip has one
     // answer behind two trips to memory; else the reads are walked column by column.
@@ -376,6 +380,20 @@ template <int NPL> __global__ __launch_bounds__(CTHREADS, NPL == CPLANES ? 4 : 6
         *reinterpret_cast<uint4 *>(s.cons + x0) = make_uint4(outw[0], outw[1], outw[2], outw[3]);
     } else {
         for (int c = 0; c < ncol; c++) s.cons[x0 + c] = (uint8_t)(outw[c >> 2] >> (8 * (c & 3)));
+    }
+    return ovf;
+}
+// NPL = CSHALLOW: the kernel every tile goes through, a workgroup a tile, its counts good for 2^CSHALLOW - 1 reads on a column; a tile where a carry
+// leaves the top plane is appended to the list tovf (tovf[0] tiles, their numbers behind it) and counted again by NPL = CPLANES, launched behind it
+// on a small grid that strides over the list.
+template <int NPL> __global__ __launch_bounds__(CTHREADS, NPL == CPLANES ? 4 : 6) void k_consensus(S2Args s, const uint32_t *cid, const unsigned long long *cinfo, int want_windows, const uint32_t *tlo, const uint32_t *thi, uint32_t *tovf)
+{
+    if (NPL == CPLANES) {
+        const uint32_t n = tovf[0];
+        for (uint32_t k = blockIdx.x; k < n; k += gridDim.x) consensus_tile<NPL>(s, tovf[1 + k], cid, cinfo, want_windows, tlo, thi);
+    } else {
+        const bool ovf = consensus_tile<NPL>(s, blockIdx.x, cid, cinfo, want_windows, tlo, thi);
+        if (__syncthreads_or(ovf) && threadIdx.x == 0) tovf[1 + atomicAdd(&tovf[0], 1u)] = blockIdx.x;
     }
 }
 
@@ -1366,22 +1384,6 @@ __global__ void k_shard_bounds(const uint64_t *gstart, uint32_t M, uint32_t q, u
 // The noise pass works on packed words: `cons2` is the consensus on the global column axis in the reads' own 2-bit code (A0 G1 C2 T3,
 // 32 columns per word), so a read is compared with W funnel-shifted words and the mismatching columns are the set bits of
 // ((x | x>>1) & 0x55..) with x = read ^ consensus; an N of a candidate read is a mismatch wherever it stands.
-__global__ void k_pack_cons2(const uint8_t *cons, uint64_t total, uint64_t w0, uint64_t nwords, uint64_t *cons2)
-{
-    const uint64_t w = w0 + harc_gid();      // the words [w0, w0 + nwords)
-    if (w >= w0 + nwords) return;
-    uint64_t v = 0;
-    const uint64_t c0 = w * 32;
-    if (c0 + 32 <= total) {
-        const uint4 q0 = *(const uint4 *)(cons + c0), q1 = *(const uint4 *)(cons + c0 + 16);
-        const uint32_t qq[8] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w };
-#pragma unroll
-        for (int k = 0; k < 32; k++) { const uint32_t idx = (qq[k >> 2] >> (8 * (k & 3))) & 3; v |= (uint64_t)(((idx & 1) << 1) | (idx >> 1)) << (2 * k); }
-    } else {
-        for (int k = 0; k < 32 && c0 + k < total; k++) { const uint32_t idx = cons[c0 + k] & 3; v |= (uint64_t)(((idx & 1) << 1) | (idx >> 1)) << (2 * k); }
-    }
-    cons2[w] = v;
-}
 // final element -> W words of 2-bit code as written to the contig (candidates reverse-complemented when kind 2) + N mask (both bits of
 // the field set); 3-bit code A0 N1 G2 C4 T6 -> 2-bit code = c3 >> 1, N = c3 & 1
 template <int W> __device__ __forceinline__ void final_words(const S2Args &s, uint32_t ref, int kind, uint64_t (&rd)[W], uint64_t (&nmk)[W])
@@ -1444,6 +1446,7 @@ template <int W, bool EMIT> __global__ void k_noise(S2Args s, FinalArrays f, con
     if (!EMIT) {                                                  // writecontig's sizes first (encoder.cpp:654-717)
         nm[i] = cnt;
         nonN[i] = (kind != 0 && ref >= s.S) ? 0u : 1u;            // N reads are exactly the candidates with index >= S
+        if (i + 1 == F) nm[F] = nonN[F] = 0;                      // the entry behind the group's end, which its scans read
         return;
     }
     uint64_t np = nmoff[i], nz = nmoff[i] + i;                    // one '\n' per earlier read
@@ -1550,6 +1553,25 @@ __global__ __launch_bounds__(256) void k_left_emit_w(S2Args s, uint32_t t0, cons
     if (!single && lane == 0) ot[s.L] = '\n';
 }
 
+// read_seq of all shards of the rank at once, from the packed consensus: a shard's stream is the consensus from its first column on, four columns a
+// byte, in the row code A0 C1 G2 T3 -- cons2's words shifted to the shard's first column, the two bits of every column swapped back.  A thread
+// makes 8 bytes (the shard's last ones singly: its tail bases stand right behind them); blockIdx.y is the shard.
+struct SeqShard { uint64_t col0, nbytes, off; };                 // first column; whole bytes; where its stream starts in the buffer (16-byte aligned)
+__global__ __launch_bounds__(256) void k_pack_seq(const uint64_t *cons2, const SeqShard *shards, uint8_t *out)
+{
+    const SeqShard sh = shards[blockIdx.y];
+    const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;  // word of the shard's stream
+    if (8 * j >= sh.nbytes) return;
+    const uint64_t x = sh.col0 + 32 * j;
+    const uint64_t *w = cons2 + (x >> 5);
+    const int b = 2 * (int)(x & 31);
+    uint64_t v = w[0] >> b;
+    if (b) v |= w[1] << (64 - b);
+    v = ((v & 0x5555555555555555ULL) << 1) | ((v >> 1) & 0x5555555555555555ULL);
+    uint8_t *o = out + sh.off + 8 * j;
+    if (8 * j + 8 <= sh.nbytes) *reinterpret_cast<uint64_t *>(o) = v;
+    else for (uint64_t k = 0; 8 * j + k < sh.nbytes; k++) o[k] = (uint8_t)(v >> (8 * k));
+}
 // packbits (encoder.cpp:527-548, :560-578)
 __global__ void k_pack2_bytes(const uint8_t *bases, uint64_t nbytes_out, uint8_t *out)
 {
@@ -1627,6 +1649,94 @@ static int digest_range(harc_amd_ctx *c, const void *base, uint64_t nbytes, uint
     return HARC_AMD_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- contig structure (host)
+// For the reads in reordered order, flag[] and pos[] as stage I left them, shards of q reads (encoder.cpp:171-180):
+//   head1[i] = flag[i] == '0' || i % q == 0;  head[i] = head1[i], or i lies a positive multiple of cut + 1 reads behind the last head1 at or before it;
+//   cid = exclusive count of the heads;  gstart = inclusive sum of (head ? (i ? L : 0) : pos);  chead[cid[i]] = i at the heads;
+//   *nC = heads, *total = gstart[M - 1] + L, sh_col[e] = gstart[e * q] (total from the first shard on that starts behind the reads), e = 0 .. E.
+// One scan (prim_contig_scan), its few words read in one copy behind one synchronise, while no read lies more than `cut` reads behind its head1 -- no
+// workload we know of has a contig of ten million reads.  Where one does, the seven passes below run, which carry every read's distance to its head1
+// through memory.  chead has room for M entries.
+#define CONTIG_CUT 10000000u
+static int contig_structure(harc_amd_ctx *c, const uint8_t *flag, const uint8_t *pos, uint32_t M, int L, uint32_t q, uint32_t cut, uint32_t E, uint8_t *head, uint32_t *cid,
+                            uint64_t *gstart, uint32_t *chead, uint32_t *nC, uint64_t *total, uint64_t *sh_col, int *fellback)
+{
+    *nC = 0; *total = 0;
+    if (fellback) *fellback = 0;
+    for (uint32_t e = 0; e <= E; e++) sh_col[e] = 0;
+    if (!M) return HARC_AMD_OK;
+    PoolScope scope(c);
+    const uint32_t nsh = (M - 1u) / q + 1u;                       // shards that hold a read
+    std::vector<unsigned long long> hinfo((size_t)3 + nsh, 0);
+    unsigned long long *info = nullptr; RC_TRY(dalloc(c, &info, hinfo.size()));
+    RC_TRY(prim_contig_scan(c, flag, pos, M, (uint32_t)L, q, cut, head, cid, gstart, chead, info));
+    HIP_TRY(hipMemcpyAsync(hinfo.data(), info, hinfo.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!hinfo[2]) {
+        *nC = (uint32_t)hinfo[0]; *total = hinfo[1];
+        for (uint32_t e = 0; e <= E; e++) sh_col[e] = e < nsh && e < E ? hinfo[3 + e] : *total;
+        return HARC_AMD_OK;
+    }
+    if (fellback) *fellback = 1;
+    uint32_t *u0 = nullptr; uint64_t *d64 = nullptr;
+    RC_TRY(dalloc(c, &u0, (size_t)M + 1)); RC_TRY(dalloc(c, &d64, (size_t)M + 1));
+    hipLaunchKernelGGL(k_heads1, G256(M), flag, M, q, head, u0);
+    RC_TRY(prim_incl_max_u32(c, u0, cid, M));
+    hipLaunchKernelGGL(k_heads2, G256(M), M, cut, head, cid, u0);                 // u0 := head flags as u32
+    RC_TRY(prim_excl_scan_u32(c, u0, cid, M));                                    // contig id
+    hipLaunchKernelGGL(k_col_steps, G256(M), head, pos, M, L, d64);
+    RC_TRY(prim_incl_scan_u64(c, d64, gstart, M));
+    hipLaunchKernelGGL(k_contig_heads, G256(M), head, cid, M, chead);
+    uint32_t lastcid = 0, lasthead = 0; uint64_t lastg = 0;
+    HIP_TRY(hipMemcpyAsync(&lastcid, cid + (M - 1), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&lasthead, u0 + (M - 1), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&lastg, gstart + (M - 1), 8, hipMemcpyDeviceToHost, c->stream));
+    for (uint32_t e = 0; e < E && e < nsh; e++) HIP_TRY(hipMemcpyAsync(&sh_col[e], gstart + (size_t)e * q, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *nC = lastcid + lasthead; *total = lastg + (uint64_t)L;
+    for (uint32_t e = 0; e <= E; e++) if (e >= nsh || e >= E) sh_col[e] = *total;
+    return HARC_AMD_OK;
+}
+
+// ---- self-test of the contig structure (include/harc_amd.h; tests/test_gpu_contig_scan.py holds it to the definitions above): contig_structure as
+// stage2_run calls it, over flag[] and pos[] from the host, with the cut a parameter
+static int selftest_contigs(harc_amd_ctx *c, const uint8_t *flag, const uint8_t *pos, uint32_t M, int L, uint32_t q, uint32_t cut, uint8_t *head, uint32_t *cid, uint64_t *gstart,
+                            uint32_t *chead, uint32_t *nC, uint64_t *total, int32_t *fellback)
+{
+    PoolScope scope(c);                                           // everything goes on every way out
+    uint8_t *d_flag = nullptr, *d_pos = nullptr, *d_head = nullptr; uint32_t *d_cid = nullptr, *d_chead = nullptr; uint64_t *d_gstart = nullptr;
+    RC_TRY(dalloc(c, &d_flag, M)); RC_TRY(dalloc(c, &d_pos, M)); RC_TRY(dalloc(c, &d_head, (size_t)M + 1)); RC_TRY(dalloc(c, &d_cid, (size_t)M + 1));
+    RC_TRY(dalloc(c, &d_gstart, (size_t)M + 1)); RC_TRY(dalloc(c, &d_chead, (size_t)M + 1));
+    HIP_TRY(hipMemcpyAsync(d_flag, flag, M, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_pos, pos, M, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(d_head, 0xA5, M, c->stream)); HIP_TRY(hipMemsetAsync(d_cid, 0xA5, (size_t)M * 4, c->stream));      // stale bytes: whatever stays unwritten shows
+    HIP_TRY(hipMemsetAsync(d_gstart, 0xA5, (size_t)M * 8, c->stream)); HIP_TRY(hipMemsetAsync(d_chead, 0xA5, (size_t)M * 4, c->stream));
+    const uint32_t E = (M - 1u) / q + 1u;
+    std::vector<uint64_t> sh_col((size_t)E + 1, 0);
+    int fb = 0;
+    RC_TRY(contig_structure(c, d_flag, d_pos, M, L, q, cut, E, d_head, d_cid, d_gstart, d_chead, nC, total, sh_col.data(), &fb));
+    *fellback = fb;
+    HIP_TRY(hipMemcpyAsync(head, d_head, M, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(cid, d_cid, (size_t)M * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(gstart, d_gstart, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(chead, d_chead, (size_t)M * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t e = 0; e < E; e++)                              // the shard columns the stage reads are the reads' own
+        if (sh_col[e] != gstart[(size_t)e * q]) { harc_set_error("harc_amd_selftest_contigs: shard %u starts at column %llu, its first read at %llu", e, (unsigned long long)sh_col[e], (unsigned long long)gstart[(size_t)e * q]); return HARC_AMD_EINTERNAL; }
+    if (sh_col[E] != *total) { harc_set_error("harc_amd_selftest_contigs: the column behind the last shard is not the total"); return HARC_AMD_EINTERNAL; }
+    return HARC_AMD_OK;
+}
+extern "C" int harc_amd_selftest_contigs(harc_amd_ctx *c, const uint8_t *flag, const uint8_t *pos, uint64_t n, int32_t readlen, uint32_t q, uint32_t cut, uint8_t *head, uint32_t *cid,
+                                         uint64_t *gstart, uint32_t *chead, uint32_t *ncontigs, uint64_t *total, int32_t *fellback)
+{
+    if (!c || !flag || !pos || n == 0 || n > 0xFFFFFFF0ull || readlen < 1 || readlen > 255 || q == 0 || cut == 0xFFFFFFFFu) { harc_set_error("harc_amd_selftest_contigs: bad arguments"); return HARC_AMD_EINVAL; }
+    if (!head || !cid || !gstart || !chead || !ncontigs || !total || !fellback) { harc_set_error("harc_amd_selftest_contigs: a NULL output"); return HARC_AMD_EINVAL; }
+    HIP_TRY(hipSetDevice(c->P.device));
+    const int rc = selftest_contigs(c, flag, pos, (uint32_t)n, readlen, q, cut, head, cid, gstart, chead, ncontigs, total, fellback);
+    if (rc != HARC_AMD_OK) (void)hipStreamSynchronize(c->stream);                     // nothing of a failed run is still running when its memory is reused
+    return rc;
+}
+
 // The host side of stage II.  On one GPU (and on every rank of a bucket-sharded run) the function covers all encoder shards.  In a design-(R)
 // run (harc_amd_replicate_exchange: every rank holds the stage-I result of the WHOLE job) the work is partitioned over the ranks by encoder
 // shard -- contigs never cross a shard start (encoder.cpp:171-180), so a rank's shards are a self-contained piece of the global column axis:
@@ -1694,35 +1804,13 @@ int stage2_run(harc_amd_ctx *c)
     //      (configs[3]: 185 -> 140 GB peak)
     uint8_t *head = nullptr; uint32_t *u1 = nullptr; uint64_t *gstart = nullptr; uint32_t *chead = nullptr;
     RC_TRY(dalloc(c, &head, (size_t)M + 1)); RC_TRY(dalloc(c, &u1, (size_t)M + 1)); RC_TRY(dalloc(c, &gstart, (size_t)M + 1));
+    RC_TRY(dalloc(c, &chead, (size_t)M + 1));                     // room for a contig a read until their number is known
     uint32_t nC = 0; uint64_t total = 0;
-    if (M) {
-        PoolScope cscope(c);
-        uint32_t *u0 = nullptr; uint64_t *d64 = nullptr;
-        RC_TRY(dalloc(c, &u0, (size_t)M + 1)); RC_TRY(dalloc(c, &d64, (size_t)M + 1));
-        hipLaunchKernelGGL(k_heads1, G256(M), c->d_flag, M, a.q, head, u0);
-        RC_TRY(prim_incl_max_u32(c, u0, u1, M));
-        hipLaunchKernelGGL(k_heads2, G256(M), M, head, u1, u0);                  // u0 := head flags as u32
-        RC_TRY(prim_excl_scan_u32(c, u0, u1, M));                                // u1 := contig id
-        hipLaunchKernelGGL(k_col_steps, G256(M), head, c->d_pos, M, L, d64);
-        RC_TRY(prim_incl_scan_u64(c, d64, gstart, M));
-        uint32_t lastcid = 0, lasthead = 0; uint64_t lastg = 0;
-        HIP_TRY(hipMemcpyAsync(&lastcid, u1 + (M - 1), 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(&lasthead, u0 + (M - 1), 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(&lastg, gstart + (M - 1), 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        nC = lastcid + lasthead; total = lastg + (uint64_t)L;
-    }
-    RC_TRY(dalloc(c, &chead, (size_t)nC + 1));
-    if (M) hipLaunchKernelGGL(k_contig_heads, G256(M), head, u1, M, chead);
+    std::vector<uint64_t> sh_col(E + 1, 0), seq_off(E, 0), seq_nb(E, 0), seq_tl(E, 0);
+    RC_TRY(contig_structure(c, c->d_flag, c->d_pos, M, L, a.q, CONTIG_CUT, E, head, u1, gstart, chead, &nC, &total, sh_col.data(), nullptr));
+    dshrink(c, chead, (size_t)nC + 1);
     a.head = head; a.gstart = gstart; a.chead = chead; a.nC = nC; a.total = total;
     c->C.contigs = nC; c->C.seq_bases = total;
-    std::vector<uint64_t> sh_col(E + 1, total), seq_off(E, 0), seq_nb(E, 0), seq_tl(E, 0);
-    for (uint32_t e = 0; e <= E; e++) {
-        const uint64_t st = (uint64_t)e * a.q; const uint32_t i = e == E ? M : (uint32_t)(st > M ? M : st);
-        if (i >= M) { sh_col[e] = total; continue; }
-        HIP_TRY(hipMemcpyAsync(&sh_col[e], gstart + i, 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
     const uint64_t col0 = sh_col[e0], col1 = sh_col[e1];
     a.col0 = col0; a.col1 = col1; a.tile_base = (uint32_t)(col0 / CTILE);
     if (part) c->C.seq_bases = col1 - col0;                       // this rank's share (the merge adds the ranks up)
@@ -1736,6 +1824,7 @@ int stage2_run(harc_amd_ctx *c)
     uint64_t seq_total = 0;
     for (uint32_t e = e0; e < e1; e++) { const uint64_t cc = sh_col[e + 1] - sh_col[e]; seq_nb[e] = cc / 4; seq_tl[e] = cc % 4; seq_off[e] = seq_total; seq_total += (seq_nb[e] + seq_tl[e] + 15) & ~15ull; }
     uint8_t *seqpk = nullptr; RC_TRY(dalloc(c, &seqpk, (size_t)seq_total + 64));
+    std::vector<SeqShard> seq_shards(e1 - e0);                    // (read by a copy on the stream: lives to the end)
     PoolScope ascope(c);                                          // ---- from here to the end of the realignment: released before the merge
     uint64_t *cand2 = nullptr, *candN = nullptr;
     RC_TRY(dalloc(c, &cand2, (size_t)T * W + 1)); RC_TRY(dalloc(c, &candN, (size_t)T * W + 1));
@@ -1827,22 +1916,28 @@ int stage2_run(harc_amd_ctx *c)
         const uint32_t ntiles = (uint32_t)((col1 + CTILE - 1) / CTILE) - a.tile_base;      // the tiles that hold a column of [col0, col1)
         uint32_t *tlo = nullptr, *thi = nullptr; RC_TRY(dalloc(c, &tlo, (size_t)ntiles + 1)); RC_TRY(dalloc(c, &thi, (size_t)ntiles + 1));
         hipLaunchKernelGGL(k_consensus_tiles, G256(ntiles), a, ntiles, tlo, thi);
-        uint32_t *tovf = nullptr; RC_TRY(dalloc(c, &tovf, (size_t)ntiles + 1));
-        HIP_TRY(hipMemsetAsync(tovf, 0, (size_t)ntiles * 4, c->stream));
+        uint32_t *tovf = nullptr; RC_TRY(dalloc(c, &tovf, (size_t)ntiles + 1));      // the tiles to count again: how many, then which
+        HIP_TRY(hipMemsetAsync(tovf, 0, 4, c->stream));
         hipLaunchKernelGGL(k_consensus<CSHALLOW>, dim3(ntiles), dim3(CTHREADS), (size_t)CCHUNK * (W * 8 + 4), c->stream, a, (const uint32_t *)u1, (const unsigned long long *)cinfo, T ? 1 : 0,
                            (const uint32_t *)tlo, (const uint32_t *)thi, tovf);
-        hipLaunchKernelGGL(k_consensus<CPLANES>, dim3(ntiles), dim3(CTHREADS), (size_t)CCHUNK * (W * 8 + 4), c->stream, a, (const uint32_t *)u1, (const unsigned long long *)cinfo, T ? 1 : 0,
+        hipLaunchKernelGGL(k_consensus<CPLANES>, dim3(ntiles < 1024u ? ntiles : 1024u), dim3(CTHREADS), (size_t)CCHUNK * (W * 8 + 4), c->stream, a, (const uint32_t *)u1, (const unsigned long long *)cinfo, T ? 1 : 0,
                            (const uint32_t *)tlo, (const uint32_t *)thi, tovf);
-        { const uint64_t w0 = col0 / 32, w1 = (col1 + 31) / 32; hipLaunchKernelGGL(k_pack_cons2, G256(w1 - w0), (const uint8_t *)a.cons, total, w0, w1 - w0, cons2); }
         {   // read_seq (packbits, encoder.cpp:527-548) is final here -- the realignment below does not touch the consensus -- and the shard
-            // boundaries on the column axis follow from gstart alone: it is packed now and goes to the host on the copy stream while the
-            // realignment, the merge and the noise kernels run (the largest stream: a quarter of a byte per consensus base)
+            // boundaries on the column axis follow from gstart alone: it is packed now, all shards in one launch from the packed consensus, and
+            // goes to the host on the copy stream while the realignment, the merge and the noise kernels run (the largest stream: a quarter of
+            // a byte per consensus base)
             const uint64_t soff = seq_total;
-            for (uint32_t e = e0; e < e1; e++) {
-                const uint64_t cc0 = sh_col[e];
-                if (seq_nb[e]) hipLaunchKernelGGL(k_pack2_bytes, G256(seq_nb[e]), cons + cc0, seq_nb[e], seqpk + seq_off[e]);
-                if (seq_tl[e]) hipLaunchKernelGGL(k_bases_to_ascii, G256(seq_tl[e]), cons + cc0 + 4 * seq_nb[e], seq_tl[e], seqpk + seq_off[e] + seq_nb[e]);
+            uint64_t maxnb = 0;
+            for (uint32_t e = e0; e < e1; e++) { seq_shards[e - e0] = SeqShard{ sh_col[e], seq_nb[e], seq_off[e] }; if (seq_nb[e] > maxnb) maxnb = seq_nb[e]; }
+            if (maxnb) {
+                SeqShard *d_shards = nullptr; RC_TRY(dalloc(c, &d_shards, (size_t)(e1 - e0)));
+                HIP_TRY(hipMemcpyAsync(d_shards, seq_shards.data(), (size_t)(e1 - e0) * sizeof(SeqShard), hipMemcpyHostToDevice, c->stream));
+                for (uint32_t y = 0; y < e1 - e0; y += 65535u)   // (a grid's second dimension ends there)
+                    hipLaunchKernelGGL(k_pack_seq, dim3((unsigned)((maxnb + 8 * 256 - 1) / (8 * 256)), e1 - e0 - y < 65535u ? e1 - e0 - y : 65535u), dim3(256), 0, c->stream, (const uint64_t *)cons2,
+                                       (const SeqShard *)d_shards + y, seqpk);
             }
+            for (uint32_t e = e0; e < e1; e++)
+                if (seq_tl[e]) hipLaunchKernelGGL(k_bases_to_ascii, G256(seq_tl[e]), cons + sh_col[e] + 4 * seq_nb[e], seq_tl[e], seqpk + seq_off[e] + seq_nb[e]);
             HIP_TRY(hipGetLastError());
             if (want_digest) for (uint32_t e = e0; e < e1; e++) RC_TRY(digest_range(c, seqpk + seq_off[e], seq_nb[e] + seq_tl[e], 0x100 + e, d_digest + 0));
             RC_TRY(harc_host_alloc(c, (void **)&h_seq, (size_t)soff));
@@ -2127,7 +2222,6 @@ int stage2_run(harc_amd_ctx *c)
     RC_TRY(dalloc(c, &f.ref, (size_t)F + 1)); RC_TRY(dalloc(c, &f.kind, (size_t)F + 1)); RC_TRY(dalloc(c, &f.g, (size_t)F + 1));
     uint32_t *nm = nullptr, *nonN = nullptr, *nonNrank = nullptr; uint64_t *nmoff = nullptr;
     RC_TRY(dalloc(c, &nm, (size_t)F + 1)); RC_TRY(dalloc(c, &nonN, (size_t)F + 1)); RC_TRY(dalloc(c, &nonNrank, (size_t)F + 1)); RC_TRY(dalloc(c, &nmoff, (size_t)F + 1));
-    HIP_TRY(hipMemsetAsync(nm, 0, ((size_t)F + 1) * 4, c->stream)); HIP_TRY(hipMemsetAsync(nonN, 0, ((size_t)F + 1) * 4, c->stream));
     uint8_t *posb = nullptr, *rcb = nullptr;
     RC_TRY(dalloc(c, &posb, (size_t)F + 1)); RC_TRY(dalloc(c, &rcb, (size_t)F + 8));
     uint8_t *h_packed = nullptr, *h_pos = nullptr, *h_meta = nullptr;
@@ -2153,7 +2247,7 @@ int stage2_run(harc_amd_ctx *c)
         }
         if (sh_a[eb] > sh_a[ea]) hipLaunchKernelGGL(k_merge_acc, G256(sh_a[eb] - sh_a[ea]), gstart, M, tup, rid, sh_a[ea], sh_a[eb] - sh_a[ea], f, fbase);
         launch_noise<false>(c, a, f, cons2, fa, fb, nm, nonN, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-        // exclusive scans over the group (nm[fb] = nonN[fb] = 0 still: the next group writes them after this)
+        // exclusive scans over the group (nm[fb] = nonN[fb] = 0: the sizing pass cleared them, the next group writes them after this)
         RC_TRY(prim_excl_scan_u32_to_u64(c, nm + fa, nmoff + fa, (size_t)(fb - fa) + 1));
         RC_TRY(prim_excl_scan_u32(c, nonN + fa, nonNrank + fa, (size_t)(fb - fa) + 1));
         HIP_TRY(hipMemcpyAsync(&h_tot[0], nmoff + fb, 8, hipMemcpyDeviceToHost, c->stream));

@@ -275,6 +275,13 @@ int harc_amd_selftest_launch(harc_amd_ctx *ctx, uint64_t n, uint64_t *visited, u
  * *n_large.  Nothing stays allocated, and after an error return the context is as usable as before. */
 int harc_amd_selftest_index(harc_amd_ctx *ctx, const uint64_t *keys, uint64_t n, int32_t slots_per_read, uint32_t bigthresh, int32_t want_large,
                             uint64_t *cap, uint32_t *nbins, void *slots, uint32_t *ids, uint64_t *large, uint64_t large_capacity, uint64_t *n_large);
+/* Self-test of stage II's contig structure: the very code the encoder runs, over flag[n] ('0' = the read starts a contig) and pos[n] (the read's shift
+ * against the read before it) in host memory, for reads of `readlen` bases, encoder shards of q reads and contigs cut every cut + 1 reads (the encoder:
+ * 10 000 000).  Out come head[n], cid[n] (heads before the read), gstart[n] (first column), chead[*ncontigs] (the caller's buffer has room for n),
+ * *ncontigs, *total (columns) and *fellback: 0 when the single scan did it, 1 when a read lay more than `cut` reads behind the last flag-'0' read or
+ * shard start and the passes that cut contigs ran.  Nothing stays allocated. */
+int harc_amd_selftest_contigs(harc_amd_ctx *ctx, const uint8_t *flag, const uint8_t *pos, uint64_t n, int32_t readlen, uint32_t q, uint32_t cut, uint8_t *head, uint32_t *cid,
+                              uint64_t *gstart, uint32_t *chead, uint32_t *ncontigs, uint64_t *total, int32_t *fellback);
 
 /* Where the wall time of this process's last harc_amd_compress_fastq_files_ex went, in seconds (the end-to-end leg of bench.py; preprocess.cpp:81-121 + harc:50-69):
  * out[0] context + device pool, [1] ingest (file -> HBM -> packed stores; reads, uploads and kernels overlapped), [2] of it the calling thread waiting for

@@ -7,7 +7,7 @@ There is no CPU fallback: importing works anywhere, every compute call needs a g
 """
 from .api import (HarcAmd, HarcAmdError, Params, Counters, default_params, lib, lib_path, reorder, encoder, compress,
                   pack_order, preprocess, decoder, compress_fastq, STREAMS, comm_get_id, compress_fastq_shard, merge_shards, build_id, last_fastq_timing, build_has,
-                  fastq_assemble, bgzf_bound, bgzf_deflate_host, qpack_bound, qpack_host, qunpack_host, qpack_files, qunpack_files,
+                  fastq_assemble, bgzf_bound, bgzf_deflate_host, GunzipStats, gunzip_host, gunzip_files, qpack_bound, qpack_host, qunpack_host, qpack_files, qunpack_files,
                   QMap, QMapStats, qmap_parse, qmap_host, qmap_files,
                   idpack_bound, idpack_host, idunpack_host, idpack_files, idunpack_files,
                   spack_bound, spack_host, sunpack_host, spack_files, sunpack_files, spack_file_list, sunpack_file_list,
@@ -17,6 +17,7 @@ from ._build import build
 __all__ = ["HarcAmd", "HarcAmdError", "Params", "Counters", "default_params", "lib", "lib_path", "reorder", "encoder",
            "compress", "pack_order", "preprocess", "decoder", "compress_fastq", "build", "STREAMS", "comm_get_id", "compress_fastq_shard",
            "merge_shards", "build_id", "last_fastq_timing", "build_has", "fastq_assemble", "bgzf_bound", "bgzf_deflate_host",
+           "GunzipStats", "gunzip_host", "gunzip_files",
            "qpack_bound", "qpack_host", "qunpack_host", "qpack_files", "qunpack_files",
            "QMap", "QMapStats", "qmap_parse", "qmap_host", "qmap_files",
            "idpack_bound", "idpack_host", "idunpack_host", "idpack_files", "idunpack_files",

@@ -54,6 +54,15 @@ class QMapStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
 
+class GunzipStats(C.Structure):
+    """harc_amd_gunzip_stats: what the parallel inflate of a gzip stream did"""
+    _fields_ = [("members", C.c_uint64), ("chunks", C.c_uint64), ("starts_found", C.c_uint64), ("starts_dropped", C.c_uint64), ("repair_walks", C.c_uint64),
+                ("text_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 def lib_path():
     return os.environ.get("HARC_AMD_LIB") or os.path.join(HERE, "libharc_amd.so")      # override: experiment builds of the same sources
 
@@ -105,6 +114,10 @@ def lib():
                                                  C.POINTER(C.c_uint64)]
     l.harc_amd_fastq_assemble_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]
     l.harc_amd_fastq_assemble_files_ex.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32]
+    GS = C.POINTER(GunzipStats)
+    l.harc_amd_gunzip_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), GS]
+    l.harc_amd_gunzip_host.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), GS]
+    l.harc_amd_gunzip_files.argtypes = [PP, C.c_char_p, C.c_char_p, GS]
     l.harc_amd_bgzf_bound.argtypes = [C.c_uint64]
     l.harc_amd_bgzf_bound.restype = C.c_uint64
     l.harc_amd_bgzf_deflate_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -295,6 +308,23 @@ def bgzf_deflate_host(text, eof=True):
     n = C.c_uint64(0)
     _check(lib().harc_amd_bgzf_deflate_host(text, len(text), 1 if eof else 0, out, cap, C.byref(n)))
     return out.raw[:n.value]
+
+
+def gunzip_host(blob, chunk_bytes=0):
+    """any gzip byte string -> (its text, the statistics as a dict): the chunked inflate of HarcAmd.gunzip_device run in a row on the host (tests; no device).
+    chunk_bytes: compressed bytes per chunk, 0 = the default (include/harc_amd.h: harc_amd_gunzip_host)"""
+    n, st = C.c_uint64(0), GunzipStats()
+    _check(lib().harc_amd_gunzip_host(blob, len(blob), chunk_bytes, None, 0, C.byref(n), None))
+    out = C.create_string_buffer(n.value + 1)
+    _check(lib().harc_amd_gunzip_host(blob, len(blob), chunk_bytes, out, n.value, C.byref(n), C.byref(st)))
+    return out.raw[:n.value], st.as_dict()
+
+
+def gunzip_files(gz, out, device=0):
+    """the gzip file `gz` (any gzip, not only BGZF) -> the file `out` holding its text, inflated on the GPU -> the statistics as a dict"""
+    p, st = default_params(100, device=device), GunzipStats()
+    _check(lib().harc_amd_gunzip_files(C.byref(p), os.fsencode(gz), os.fsencode(out), C.byref(st)))
+    return st.as_dict()
 
 
 def qpack_bound(n_reads, readlen, reads_per_block=0):
@@ -529,6 +559,13 @@ class HarcAmd:
         n = C.c_uint64(0)
         _check(lib().harc_amd_bgzf_inflate_device(self._ctx, C.c_void_p(dptr), nbytes, C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
         return n.value
+
+    def gunzip_device(self, dptr, nbytes, out_ptr=None, out_capacity=0, chunk_bytes=0):
+        """any gzip bytes in device memory -> their text at out_ptr (device memory); without out_ptr only the text size. -> (text bytes, statistics as a dict)"""
+        n, st = C.c_uint64(0), GunzipStats()
+        _check(lib().harc_amd_gunzip_device(self._ctx, C.c_void_p(dptr), nbytes, chunk_bytes, C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n),
+                                            C.byref(st)))
+        return n.value, st.as_dict()
 
     def bgzf_deflate_device(self, d_text, nbytes, out_ptr=None, out_capacity=0, eof=True):
         """text in device memory -> BGZF at out_ptr (device memory), members of 65 280 bytes of text deflated on the GPU, the end-of-file marker behind them

@@ -28,6 +28,9 @@ enum {
     IM_E_CRC = 9,          // CRC-32 of the text differs from the trailer
     IM_E_HEADER = 10,      // no BGZF header at the member's offset
     IM_E_ISIZE = 11,       // ISIZE > 65536
+    IM_E_GZHEADER = 12,    // inflate_stream.h: no RFC 1952 member header (magic, CM other than 8, a reserved flag bit)
+    IM_E_TRAILING = 13,    // inflate_stream.h: bytes behind a member's trailer that are no member header
+    IM_E_LENGTH = 14,      // inflate_stream.h: the text's length mod 2^32 differs from the trailer's ISIZE
 };
 
 #define IM_MAXBITS 15

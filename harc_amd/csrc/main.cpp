@@ -23,7 +23,9 @@
 //   harc_amd_stage id_unpack <packed> <device> <out>                       ... and back (./harc -d -q when only X.id.hi is there)
 //   harc_amd_stage streams_pack <device> <in> <out> [<in> <out> ...]       every <in> -> the packed stream file <out>, one after the other on one context (./harc -c -S)
 //   harc_amd_stage streams_unpack <device> <in> <out> [<in> <out> ...]     ... and back (./harc -d when the archive holds .hs files)
-//   harc_amd_stage text_digest <file> [<device>]                           "bytes lines D" of the file's text on stdout, 16 hex digits each (./harc -c -V, -d, -v)
+//   harc_amd_stage gunzip <gz> <device> <out>                              any gzip file -> its text, inflated on the GPU (HARC_AMD_GUNZIP=1 ./harc -c on a .fastq.gz that is not BGZF);
+//                                                                          one line on stdout: members, chunks, starts found / dropped / repaired, bytes of text
+//   harc_amd_stage text_digest <file> [<device>]                          "bytes lines D" of the file's text on stdout, 16 hex digits each (./harc -c -V, -d, -v)
 //   harc_amd_stage reads_check <dna> [<device>]                            "count sum xor bytes lines D" of the decoders' output, read once: the multiset signature
 //                                                                          of its reads and the digest of its text (./harc -d, -v on an archive made with -V)
 // compressfq takes one more trailing argument, "check" (./harc -c -V): the streams are decoded once before they are written, and output/read.check is written.
@@ -108,7 +110,18 @@ int main(int argc, char **argv)
         print_qmap(argv[5], &ST);
         return 0;
     }
-    if (!strcmp(argv[1], "streams_pack") || !strcmp(argv[1], "streams_unpack")) {
+    if (!strcmp(argv[1], "gunzip")) {
+        if (argc < 5) { fprintf(stderr, "gunzip needs <gz> <device> <out>\n"); return 2; }
+        harc_amd_params PG; harc_amd_gunzip_stats GS;
+        if (harc_amd_default_params(100, &PG) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
+        PG.device = atoi(argv[3]);
+        const int rcg = harc_amd_gunzip_files(&PG, argv[2], argv[4], &GS);
+        if (rcg != 0) { fprintf(stderr, "harc_amd_stage gunzip failed (%d): %s\n", rcg, harc_amd_last_error()); return 1; }
+        printf("[gunzip] %llu members, %llu chunks, %llu starts found, %llu dropped, %llu repaired, %llu bytes of text\n", (unsigned long long)GS.members, (unsigned long long)GS.chunks,
+               (unsigned long long)GS.starts_found, (unsigned long long)GS.starts_dropped, (unsigned long long)GS.repair_walks, (unsigned long long)GS.text_bytes);
+        return 0;
+    }
+    if (!strcmp(argv[1], "streams_pack") ||!strcmp(argv[1], "streams_unpack")) {
         if (argc < 5 || (argc - 3) % 2) { fprintf(stderr, "%s needs <device> <in> <out> [<in> <out> ...]\n", argv[1]); return 2; }
         harc_amd_params PS;
         if (harc_amd_default_params(100, &PS) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }

@@ -167,7 +167,34 @@ int harc_amd_set_fastq_device(harc_amd_ctx *ctx, const char *d_fastq, uint64_t n
    leaves the buffer, a position where a member must start but none parses, ISIZE > 65536, a wrong length or CRC-32 or malformed DEFLATE
    data: HARC_AMD_EINVAL naming the compressed byte offset of the member. */
 int harc_amd_bgzf_inflate_device(harc_amd_ctx *ctx, const uint8_t *d_bgzf, uint64_t n_bytes, char *d_out, uint64_t out_capacity, uint64_t *n_out);
-/* The other way: text in device memory -> BGZF in device memory, deflated on the GPU.  The text is cut every 65 280 bytes (bgzip's size) into members that are
+/* ---- Any gzip file (RFC 1952: one DEFLATE stream per member, what gzip, sequencer software and fastq-dump --gzip write) inflated on the GPU.  A stream has no
+   member table to cut it by: the compressed bytes are cut into chunks (256 KiB; HARC_AMD_GUNZIP_CHUNK=bytes, at least 64, or chunk_bytes where a call takes
+   it; 0 = the default), a kernel finds in every chunk the first bit offset at which a non-final dynamic block header parses, every such start is decoded to the
+   end of its chunk with the 32 KiB window in front of it kept symbolic, the host chains the walks (a walk whose start the chain does not land on is dropped;
+   where the chain lands on no start, one walk is counted from there: a repair), the windows are resolved in file order and the symbols translated, CRC-32 and
+   ISIZE of every member checked.  harc_amd/csrc/inflate_stream.h holds the rules, NOTES.md (Plain gzip input) what it measures. */
+typedef struct harc_amd_gunzip_stats {
+    uint64_t members;          /* gzip members */
+    uint64_t chunks;           /* chunks looked at, summed over members (and over pieces of a file) */
+    uint64_t starts_found;     /* chunks behind a first one in which the finder found a start */
+    uint64_t starts_dropped;   /* of them: never reached by the chain, or not decodable */
+    uint64_t repair_walks;     /* walks counted one at a time because the chain landed on no start */
+    uint64_t text_bytes;
+} harc_amd_gunzip_stats;
+/* gzip bytes in device memory -> their text in device memory.  d_out == NULL: *n_out = size of the text, nothing written (the members are walked to learn
+   it, their CRC-32 is not checked); else out_capacity must be at least that, and no byte outside [d_out, d_out + *n_out) is written.  Damaged input --
+   no gzip header, malformed DEFLATE data, input that ends inside a block or a trailer, a wrong CRC-32 or ISIZE, anything behind a trailer that is no member
+   header (zero padding included) -- is HARC_AMD_EINVAL naming the compressed byte.  stats may be NULL. */
+int harc_amd_gunzip_device(harc_amd_ctx *ctx, const uint8_t *d_gz, uint64_t n_bytes, uint64_t chunk_bytes, char *d_out, uint64_t out_capacity, uint64_t *n_out,
+                           harc_amd_gunzip_stats *stats);
+/* the same chunked algorithm run in a row on the host (host memory, no device): the same text, the same stats, the same refusals (tests) */
+int harc_amd_gunzip_host(const uint8_t *gz, uint64_t n_bytes, uint64_t chunk_bytes, char *out, uint64_t out_capacity, uint64_t *n_out, harc_amd_gunzip_stats *stats);
+/* gz_path -> out_path, inflated on the GPU; only `device` is taken from params.  The compressed file runs through the pinned ring in pieces (64 MiB;
+   HARC_AMD_GUNZIP_PIECE=bytes in tests); what lies behind the last block boundary reached in a piece is carried into the next with the boundary's bit offset and
+   the resolved window, so the file may be larger than device memory, and the text of one piece that would not fit HARC_AMD_GUNZIP_BUDGET bytes (1 GiB) is
+   produced in several turns.  On any failure out_path is removed.  HARC_AMD_TRACE=1 laps the stages on stderr. */
+int harc_amd_gunzip_files(const harc_amd_params *params, const char *gz_path, const char *out_path, harc_amd_gunzip_stats *stats);
+/* The other way: text in device memory -> BGZF in device memory, deflated on the GPU. The text is cut every 65 280 bytes (bgzip's size) into members that are
    deflated independently, a workgroup each: matches only against the line four lines up at the same column (what repeats in FASTQ; no search), one dynamic
    Huffman block per member, a stored block where that is not smaller (harc_amd/csrc/deflate_member.h holds the rules).  The bytes depend on the text alone.
    flags bit 0: the 28-byte end-of-file marker follows the last member; n_bytes == 0 gives the marker alone, or nothing.  *n_out = bytes of the members (and the

@@ -11,7 +11,8 @@ from .api import (HarcAmd, HarcAmdError, Params, Counters, default_params, lib, 
                   QMap, QMapStats, qmap_parse, qmap_host, qmap_files,
                   idpack_bound, idpack_host, idunpack_host, idpack_files, idunpack_files,
                   spack_bound, spack_host, sunpack_host, spack_files, sunpack_files, spack_file_list, sunpack_file_list,
-                  text_digest_host, text_digest_file, reads_check_file)
+                  text_digest_host, text_digest_file, reads_check_file,
+                  compress_fastq_pair, IDMATE_RULES, idmate_rule_host, idmate_apply_host, idmate_rule_files, fastq_assemble_pair)
 from ._build import build
 
 __all__ = ["HarcAmd", "HarcAmdError", "Params", "Counters", "default_params", "lib", "lib_path", "reorder", "encoder",
@@ -22,4 +23,5 @@ __all__ = ["HarcAmd", "HarcAmdError", "Params", "Counters", "default_params", "l
            "QMap", "QMapStats", "qmap_parse", "qmap_host", "qmap_files",
            "idpack_bound", "idpack_host", "idunpack_host", "idpack_files", "idunpack_files",
            "spack_bound", "spack_host", "sunpack_host", "spack_files", "sunpack_files", "spack_file_list", "sunpack_file_list",
-           "text_digest_host", "text_digest_file", "reads_check_file"]
+           "text_digest_host", "text_digest_file", "reads_check_file",
+           "compress_fastq_pair", "IDMATE_RULES", "idmate_rule_host", "idmate_apply_host", "idmate_rule_files", "fastq_assemble_pair"]

@@ -181,6 +181,21 @@ def lib():
     l.harc_amd_input_order_digest.argtypes = [ctx, U3]
     l.harc_amd_reads_check_files.argtypes = [PP, C.c_char_p, U3, U3]
     l.harc_amd_compress_fastq_files_checked.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32]
+    U64P, U32P = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    if hasattr(l, "harc_amd_idmate_rule_device"):        # (HARC_AMD_LIB may name a build from before paired-end input)
+        l.harc_amd_idmate_rule_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, U64P, U32P]
+        l.harc_amd_idmate_rule_host.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, U64P, U32P]
+        l.harc_amd_idmate_rule_of.argtypes = [C.c_uint32, C.c_uint64]
+        l.harc_amd_idmate_rule_of.restype = C.c_int32
+        l.harc_amd_idmate_rule_name.argtypes = [C.c_int32]
+        l.harc_amd_idmate_rule_name.restype = C.c_char_p
+        l.harc_amd_idmate_rule_parse.argtypes = [C.c_char_p]
+        l.harc_amd_idmate_rule_parse.restype = C.c_int32
+        l.harc_amd_idmate_rule_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.POINTER(C.c_int32), U64P]
+        l.harc_amd_idmate_apply_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_int32, U64P]
+        l.harc_amd_idmate_apply_host.argtypes = [C.c_char_p, C.c_uint64, C.c_int32, U64P]
+        l.harc_amd_compress_fastq_pair_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, U64P]
+        l.harc_amd_fastq_assemble_pair_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32]
     l.harc_amd_build_id.restype = C.c_char_p
     _lib = l
     return l
@@ -235,6 +250,60 @@ def compress_fastq(fastq, basedir, readlen, num_thr=1, num_chains=1, preserve_or
     (preprocess.cpp:61-118, reorder_quality.cpp); check (-V): the streams are decoded once before they are written and output/read.check is written"""
     p = default_params(readlen, num_thr=num_thr, num_chains=num_chains, **kw)
     _check(lib().harc_amd_compress_fastq_files_checked(C.byref(p), os.fsencode(fastq), os.fsencode(basedir), int(preserve_order), int(preserve_quality), int(check)))
+
+
+def compress_fastq_pair(fastq1, fastq2, basedir, readlen, num_thr=1, num_chains=1, preserve_quality=False, check=False, **kw):
+    """compress_fastq over two files as one job, the order kept (./harc -c R1 -2 R2 -p): the records of fastq1, then those of fastq2 -- the archive of their
+    `cat` without the copy, plus output/read.pair; with preserve_quality output.id holds the ids of fastq1 and output.id2 those of fastq2
+    (include/harc_amd.h: harc_amd_compress_fastq_pair_files) -> the records in each file"""
+    p = default_params(readlen, num_thr=num_thr, num_chains=num_chains, **kw)
+    n = C.c_uint64(0)
+    _check(lib().harc_amd_compress_fastq_pair_files(C.byref(p), os.fsencode(fastq1), os.fsencode(fastq2), os.fsencode(basedir), int(preserve_quality), int(check), C.byref(n)))
+    return n.value
+
+
+IDMATE_RULES = ("none", "same", "slash", "space")      # HARC_AMD_IDMATE_NONE .. HARC_AMD_IDMATE_SPACE
+
+
+def _rule_number(rule):
+    return IDMATE_RULES.index(rule) if isinstance(rule, str) else int(rule)
+
+
+def _rule_from_flags(flags, pairs):
+    return IDMATE_RULES[lib().harc_amd_idmate_rule_of(flags, pairs)]
+
+
+def idmate_rule_host(a, b):
+    """the mate rule of the id texts a and b (bytes: id lines, a newline behind each) on the host (include/harc_amd.h: harc_amd_idmate_rule_host)
+    -> (rule name, pairs, the AND of the pairs' flags: bit 0 same, 1 slash, 2 space); no device"""
+    n, f = C.c_uint64(0), C.c_uint32(0)
+    _check(lib().harc_amd_idmate_rule_host(a, len(a), b, len(b), C.byref(n), C.byref(f)))
+    return _rule_from_flags(f.value, n.value), n.value, f.value
+
+
+def idmate_apply_host(ids, rule):
+    """file 2's ids from file 1's on the host: the whole lines of `ids` patched by `rule` (a name or a number) -> (the patched text, lines that did not carry
+    the '1' to replace); no device"""
+    buf = C.create_string_buffer(bytes(ids), len(ids) + 1)
+    bad = C.c_uint64(0)
+    _check(lib().harc_amd_idmate_apply_host(buf, len(ids), _rule_number(rule), C.byref(bad)))
+    return buf.raw[:len(ids)], bad.value
+
+
+def idmate_rule_files(path_a, path_b, device=0):
+    """the mate rule of two id files, walked in lockstep on the GPU (include/harc_amd.h: harc_amd_idmate_rule_files) -> (rule name, pairs)"""
+    p = default_params(100, device=device)
+    r, n = C.c_int32(0), C.c_uint64(0)
+    _check(lib().harc_amd_idmate_rule_files(C.byref(p), os.fsencode(path_a), os.fsencode(path_b), C.byref(r), C.byref(n)))
+    return IDMATE_RULES[r.value], n.value
+
+
+def fastq_assemble_pair(dna, ids, quality, out1, out2, records, rule, device=0, bgzf=False):
+    """fastq_assemble for a paired archive: records [0, records) -> out1, [records, 2 records) -> out2; rule none: `ids` holds the lines of both files, any other
+    rule: the first file's, and the second file's are made from them on the GPU (include/harc_amd.h: harc_amd_fastq_assemble_pair_files)"""
+    p = default_params(100, device=device)
+    _check(lib().harc_amd_fastq_assemble_pair_files(C.byref(p), os.fsencode(dna), os.fsencode(ids), os.fsencode(quality), os.fsencode(out1), os.fsencode(out2),
+                                                    records, _rule_number(rule), 1 if bgzf else 0))
 
 
 def build_has(feature):
@@ -713,6 +782,18 @@ class HarcAmd:
         a = (C.c_uint64 * 3)(*acc)
         _check(lib().harc_amd_text_digest_device(self._ctx, C.c_void_p(ptr) if ptr else None, nbytes, first_offset, a))
         return tuple(a)
+
+    def idmate_rule_device(self, d_a, a_bytes, d_b, b_bytes):
+        """the mate rule of two id texts in device memory (any alignment) -> (rule name, pairs, the AND of the pairs' flags)"""
+        n, f = C.c_uint64(0), C.c_uint32(0)
+        _check(lib().harc_amd_idmate_rule_device(self._ctx, C.c_void_p(d_a) if d_a else None, a_bytes, C.c_void_p(d_b) if d_b else None, b_bytes, C.byref(n), C.byref(f)))
+        return _rule_from_flags(f.value, n.value), n.value, f.value
+
+    def idmate_apply_device(self, d_ids, id_bytes, rule):
+        """the whole lines of the id text at d_ids (device memory, any alignment) patched in place by `rule` -> lines that did not carry the '1' to replace"""
+        bad = C.c_uint64(0)
+        _check(lib().harc_amd_idmate_apply_device(self._ctx, C.c_void_p(d_ids) if d_ids else None, id_bytes, _rule_number(rule), C.byref(bad)))
+        return bad.value
 
     def input_order_digest(self):
         """T of the text "read_0\\nread_1\\n..." of the reads the context holds, in input record order"""

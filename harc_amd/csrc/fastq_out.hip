@@ -16,6 +16,7 @@
 #include "devutil.h"
 #include "fileio.h"
 #include "deflate_member.h"
+#include "idmate.h"
 
 #define FQ_TILE 16384
 #define FQ_WAVES 4
@@ -139,7 +140,7 @@ __global__ void k_fq_stride_check(const char *txt, uint64_t nbytes, int L, unsig
 }
 
 // the line index of an id text and whether its last line lacks the newline.  Pool memory: the caller brackets it
-static int fq_index(harc_amd_ctx *c, const char *d_ids, uint64_t id_bytes, const uint64_t **nls, uint64_t *lines, bool *open_tail)
+int fq_index(harc_amd_ctx *c, const char *d_ids, uint64_t id_bytes, const uint64_t **nls, uint64_t *lines, bool *open_tail)
 {
     *lines = 0; *open_tail = false;
     if (id_bytes == 0) {                                          // no text, no line; the kernel still reads nls[-1]
@@ -224,80 +225,96 @@ extern "C" int harc_amd_fastq_assemble_files(const harc_amd_params *params, cons
     return harc_amd_fastq_assemble_files_ex(params, dna_path, id_path, quality_path, out_path, 0);
 }
 
-// bgzf: every assembled piece is deflated where it sits (bgzf_out.hip).  Members are cut at multiples of DM_TEXT of the whole text: what a piece leaves behind its
-// last full member stays at the front of the text buffer and the next piece is assembled behind it, so the file does not depend on how the job was cut into pieces
-extern "C" int harc_amd_fastq_assemble_files_ex(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out_path,
-                                                int32_t bgzf)
+// what a file call knows about its three inputs before a device is touched: the read length is the length of the first read, everything else about the sizes follows from it
+struct FqInputs { const char *dna_path, *id_path, *quality_path; uint64_t isz = 0, n = 0; int L = 1; bool id_open_tail = false; };
+static int fq_probe(const char *who, const char *dna_path, const char *id_path, const char *quality_path, FqInputs *in)
 {
-    if (!params || !dna_path || !id_path || !quality_path || !out_path) { harc_set_error("fastq_assemble_files: bad arguments"); return HARC_AMD_EINVAL; }
     uint64_t dsz = 0, isz = 0, qsz = 0;
     if (!file_size(dna_path, &dsz)) { harc_set_error("cannot open %s", dna_path); return HARC_AMD_EIO; }
     if (!file_size(id_path, &isz)) { harc_set_error("cannot open %s", id_path); return HARC_AMD_EIO; }
     if (!file_size(quality_path, &qsz)) { harc_set_error("cannot open %s", quality_path); return HARC_AMD_EIO; }
-    // the read length is the length of the first read; everything else about the sizes follows from it, before a device is touched
     uint32_t L1 = 1; bool id_closed = true;
-    if (dsz) RC_TRY(first_line_length(dna_path, "fastq_assemble_files", &L1));
+    if (dsz) RC_TRY(first_line_length(dna_path, who, &L1));
     if (isz) RC_TRY(last_byte_is_newline(id_path, &id_closed));
-    const int L = (int)L1; const bool id_open_tail = !id_closed;
+    const int L = (int)L1;
+    const uint64_t LL = (uint64_t)L + 1;
+    if (dsz % LL) { harc_set_error("%s: %s holds %llu bytes, no multiple of the %llu bytes of a read of %d characters and its newline", who, dna_path, (unsigned long long)dsz, (unsigned long long)LL, L); return HARC_AMD_EINVAL; }
+    if (qsz != dsz) { harc_set_error("%s: %s holds %llu bytes and %s %llu: not a quality line per read", who, quality_path, (unsigned long long)qsz, dna_path, (unsigned long long)dsz); return HARC_AMD_EINVAL; }
+    if (dsz / LL > 4294967290ull) { harc_set_error("Too many reads. HARC supports at most 4294967290 reads"); return HARC_AMD_EINVAL; }
+    in->dna_path = dna_path; in->id_path = id_path; in->quality_path = quality_path;
+    in->isz = isz; in->n = dsz / LL; in->L = L; in->id_open_tail = !id_closed;
+    return HARC_AMD_OK;
+}
+
+// One output file: records [rec_base, rec_base + nrec) of the two fixed-stride files, with the id lines that start at byte id_begin of the id file.  The id lines
+// run to the end of the id file and must be nrec -- or, with stop_at_nrec, end after exactly nrec of them: a piece is cut at that line, not only at its last
+// newline, and the size of the output is only bounded beforehand.  rule (idmate.h): IDM_SLASH and IDM_SPACE patch the whole lines of every piece in front of
+// the tile kernel (what is carried stays unpatched until it is a whole line); a line without the '1' to patch fails the call.  *id_end: the byte of the id file
+// behind the last line taken.  on_mismatch(id lines seen) sets the error of a line count that is not nrec.
+// bgzf: every assembled piece is deflated where it sits (bgzf_out.hip).  Members are cut at multiples of DM_TEXT of the whole text: what a piece leaves behind its
+// last full member stays at the front of the text buffer and the next piece is assembled behind it, so the file does not depend on how the job was cut into pieces.
+// Three feeders (ids, reads, quality values) and the drain are alive at the same time and the context has ONE pinned ring: gq[0 .. 4) are its four quarters --
+// 0: the id feeder, 1: the read feeder, 2: the quality feeder, 3: the drain.  The caller guards the output file (OutFileGuard) and owns the context.
+template <class M> static int fq_assemble_part(harc_amd_ctx *c, const RingGeom *gq, const FqInputs &in, uint64_t id_begin, uint64_t rec_base, uint64_t nrec, bool stop_at_nrec,
+                                               int32_t rule, const char *out_path, int32_t bgzf, uint64_t *id_end, M &&on_mismatch)
+{
+    const int L = in.L; const uint64_t isz = in.isz;
     const uint64_t LL = (uint64_t)L + 1, K = 2ull * (uint64_t)L + 4;
-    if (dsz % LL) { harc_set_error("fastq_assemble_files: %s holds %llu bytes, no multiple of the %llu bytes of a read of %d characters and its newline", dna_path, (unsigned long long)dsz, (unsigned long long)LL, L); return HARC_AMD_EINVAL; }
-    if (qsz != dsz) { harc_set_error("fastq_assemble_files: %s holds %llu bytes and %s %llu: not a quality line per read", quality_path, (unsigned long long)qsz, dna_path, (unsigned long long)dsz); return HARC_AMD_EINVAL; }
-    const uint64_t n = dsz / LL;
-    if (n > 4294967290ull) { harc_set_error("Too many reads. HARC supports at most 4294967290 reads"); return HARC_AMD_EINVAL; }
-    const uint64_t out_size = isz + (id_open_tail ? 1 : 0) + n * K;    // known before a byte is read: the output is sized and mapped up front
-    CtxGuard guard;
-    RC_TRY(side_context(params, L, &guard.c));
-    harc_amd_ctx *c = guard.c;
-    // Three feeders (ids, reads, quality values) and the drain are alive at the same time and the context has ONE pinned ring: it is split into four quarters of four
-    // slices each -- quarter 0: the id feeder, 1: the read feeder, 2: the quality feeder, 3: the drain -- and reserved whole before any of them starts.  With the default
-    // slice of 64 MB that is the 1 GiB the ring always had.  HARC_AMD_FEED_SLICE sets the slice, HARC_AMD_FEED_THREADS the host threads of all four together.
-    RingGeom gq[4];
-    RC_TRY(ring_split(c, 4, 4, "FASTQ output", gq));
-    OutFileGuard outguard{ out_path };
+    const bool id_open_tail = in.id_open_tail && isz > id_begin;
+    const uint64_t out_size = (isz - id_begin) + (id_open_tail ? 1 : 0) + nrec * K;    // known before a byte is read: the output is sized and mapped up front (stop_at_nrec: a bound)
     CarriedText ids(c); DevBuf dna{ c }, qual{ c }, out{ c }, gz{ c };
     const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
     double t_kernel = 0, t_read = 0, t_write = 0;
     KernelTimer timer(&t_kernel);
     PoolScope scope(c);
     unsigned int *d_err = nullptr; RC_TRY(dalloc(c, &d_err, 4));
-    HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
+    unsigned long long *d_bad = nullptr; RC_TRY(dalloc(c, &d_bad, 2));
+    HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream)); HIP_TRY(hipMemsetAsync(d_bad, 0, 16, c->stream));
     FileDrain drain(c);
-    RC_TRY(drain.start(out_path, bgzf ? (size_t)dm_bound(out_size) : (size_t)out_size, &gq[3], bgzf != 0));
+    RC_TRY(drain.start(out_path, bgzf ? (size_t)dm_bound(out_size) : (size_t)out_size, &gq[3], bgzf != 0 || stop_at_nrec));
     BgzfOutStats gst; uint64_t gz_at = 0, tcarry = 0;                  // bgzf: bytes of the file so far; text in front of `out` that no member holds yet
     // the job is driven by the id file: a piece is a byte range of it; what follows the piece's last newline is carried into the next piece
     const uint64_t piece = env_u64("HARC_AMD_FQOUT_PIECE", (uint64_t)256 << 20);
     std::vector<std::pair<uint64_t, uint64_t>> pieces;
-    for (uint64_t a = 0; a < isz; a += piece) pieces.emplace_back(a, isz - a < piece ? isz : a + piece);
-    FileFeeder idf(c, id_path);
+    if (!(stop_at_nrec && nrec == 0)) for (uint64_t a = id_begin; a < isz; a += piece) pieces.emplace_back(a, isz - a < piece ? isz : a + piece);
+    FileFeeder idf(c, in.id_path);
     if (!pieces.empty()) RC_TRY(idf.start(pieces, gq[0]));
     uint64_t r0 = 0, lines_seen = 0, out_at = 0; int npieces = 0; bool over = false;
+    *id_end = id_begin;
     for (size_t p = 0; p < pieces.size(); p++) {
-        const uint64_t len = pieces[p].second - pieces[p].first, total = ids.carry + len; const bool lastp = p + 1 == pieces.size();
+        const uint64_t len = pieces[p].second - pieces[p].first, total = ids.carry + len, origin = pieces[p].first - ids.carry; const bool lastp = p + 1 == pieces.size();
         RC_TRY(ids.take(idf, p, len, &t_read));                                              // the carried bytes sit at its front
-        const char *d_ids = ids.text();
+        char *d_ids = ids.text();
         PoolScope piece_scope(c);
         const uint64_t *nls = nullptr; uint64_t lines = 0; bool open_tail = false;
         RC_TRY(fq_index(c, d_ids, total, &nls, &lines, &open_tail));
-        const uint64_t m = lines - ((open_tail && !lastp) ? 1 : 0);                        // whole lines; a last line of the FILE without its newline is one
+        uint64_t m = lines - ((open_tail && !lastp) ? 1 : 0);                              // whole lines; a last line of the FILE without its newline is one
         if (m == 0 && !lastp) { ids.carry = total; continue; }                               // not one whole line yet: the piece grows by the next one
+        const bool clip = stop_at_nrec && r0 + m > nrec;                                     // the lines of this output end inside the piece
+        if (clip) m = nrec - r0;
         uint64_t cut = total;
-        if (open_tail && !lastp) {
-            HIP_TRY(hipMemcpyAsync(&cut, nls + (m - 1), 8, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            cut += 1;
+        if ((open_tail && !lastp) || clip) {
+            cut = 0;
+            if (m) {
+                HIP_TRY(hipMemcpyAsync(&cut, nls + (m - 1), 8, hipMemcpyDeviceToHost, c->stream));
+                HIP_TRY(hipStreamSynchronize(c->stream));
+                cut += 1;
+            }
         }
         lines_seen += m;
-        if (r0 + m > n) over = true;                                                         // more ids than reads: the lines are still counted, for the message
+        if (r0 + m > nrec) over = true;                                                      // more ids than reads: the lines are still counted, for the message
         if (!over && m) {
-            const uint64_t nb = m * LL, out_bytes = cut + ((lastp && open_tail) ? 1 : 0) + m * K;
+            const uint64_t nb = m * LL, out_bytes = cut + ((lastp && open_tail && !clip) ? 1 : 0) + m * K;
             RC_TRY(dev_reserve(&dna, (size_t)nb)); RC_TRY(dev_reserve(&qual, (size_t)nb)); RC_TRY(dev_reserve(&out, (size_t)(tcarry + out_bytes), (size_t)tcarry));
-            {   // lines [r0, r0 + m) of the two fixed-width files, by offset
-                FileFeeder fd(c, dna_path), fq(c, quality_path);
-                RC_TRY(fd.start({ { r0 * LL, (r0 + m) * LL } }, gq[1])); RC_TRY(fq.start({ { r0 * LL, (r0 + m) * LL } }, gq[2]));
+            {   // lines [rec_base + r0, rec_base + r0 + m) of the two fixed-width files, by offset
+                const uint64_t f0 = (rec_base + r0) * LL, f1 = (rec_base + r0 + m) * LL;
+                FileFeeder fd(c, in.dna_path), fq(c, in.quality_path);
+                RC_TRY(fd.start({ { f0, f1 } }, gq[1])); RC_TRY(fq.start({ { f0, f1 } }, gq[2]));
                 const double t0 = mono_now();
                 RC_TRY(fd.upload_piece(0, dna.p, nullptr)); RC_TRY(fq.upload_piece(0, qual.p, nullptr));
                 t_read += mono_now() - t0;
                 RC_TRY(timer.begin(c->stream));
+                RC_TRY(harc_idmate_apply_lines(c, d_ids, nls, m, rule, d_bad));              // (nothing for the rules that patch nothing)
                 RC_TRY(fq_run(c, d_ids, nls, dna.p, qual.p, (uint32_t)m, L, out.p + tcarry, out_bytes, d_err));
                 RC_TRY(timer.end_mark(c->stream));
                 if (!bgzf) { const double t0w = mono_now(); RC_TRY(drain.put(out.p, (size_t)out_bytes, out_at)); t_write += mono_now() - t0w; }
@@ -318,16 +335,25 @@ extern "C" int harc_amd_fastq_assemble_files_ex(const harc_amd_params *params, c
             }                                                                                // (the feeders wait for the stream when they go)
         }
         if (!over) r0 += m;
+        *id_end = origin + cut;
+        if (stop_at_nrec && r0 == nrec) break;                                               // what follows belongs to the next output
         const uint64_t rest = total - cut;
         if (rest) RC_TRY(ids.carry_from(cut, rest));
         else ids.carry = 0;
     }
-    if (over || r0 != n) {
-        harc_set_error("fastq_assemble_files: %s holds %llu lines, %s %llu reads", id_path, (unsigned long long)lines_seen, dna_path, (unsigned long long)n);
-        return HARC_AMD_EINVAL;
-    }
-    if (out_at != out_size) { harc_set_error("fastq_assemble_files: %llu bytes assembled, the file sizes announce %llu", (unsigned long long)out_at, (unsigned long long)out_size); return HARC_AMD_EINTERNAL; }
+    if (over || r0 != nrec) { on_mismatch(lines_seen); return HARC_AMD_EINVAL; }
+    if (!stop_at_nrec && out_at != out_size) { harc_set_error("fastq_assemble_files: %llu bytes assembled, the file sizes announce %llu", (unsigned long long)out_at, (unsigned long long)out_size); return HARC_AMD_EINTERNAL; }
     RC_TRY(fq_check_errors(c, d_err, L));
+    {
+        unsigned long long bad = 0;
+        HIP_TRY(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (bad) {
+            harc_set_error("fastq_assemble_pair_files: %llu id lines of %s do not carry the '1' that the mate rule '%s' turns into '2': the id file is damaged or another rule was recorded than the one that holds",
+                           bad, in.id_path, idm_rule_name(rule));
+            return HARC_AMD_EINVAL;
+        }
+    }
     if (bgzf) {                                                       // the last member and the end-of-file marker
         uint64_t ngz = 0;
         RC_TRY(dev_reserve(&gz, (size_t)dm_bound(tcarry)));
@@ -335,13 +361,74 @@ extern "C" int harc_amd_fastq_assemble_files_ex(const harc_amd_params *params, c
         { const double t0w = mono_now(); RC_TRY(drain.put(gz.p, (size_t)ngz, gz_at)); t_write += mono_now() - t0w; }
         gz_at += ngz;
         drain.set_final_size(gz_at);
-    }
+    } else if (stop_at_nrec) drain.set_final_size(out_at);
     { const double t0 = mono_now(); RC_TRY(drain.finish()); t_write += mono_now() - t0; }
     if (tlog && bgzf) fprintf(stderr, "[fastq_out] %llu bytes in %d pieces: %.3f s in the kernel, %.3f s waiting for the readers, %.3f s waiting for the writers; BGZF: %llu bytes of text -> %llu bytes in %llu members (%llu stored), %.3f s in the deflate kernels\n",
-                              (unsigned long long)out_size, npieces, t_kernel, t_read, t_write, (unsigned long long)gst.text, (unsigned long long)gz_at, (unsigned long long)gst.members,
+                              (unsigned long long)out_at, npieces, t_kernel, t_read, t_write, (unsigned long long)gst.text, (unsigned long long)gz_at, (unsigned long long)gst.members,
                               (unsigned long long)gst.stored, gst.seconds);
     else if (tlog) fprintf(stderr, "[fastq_out] %llu bytes in %d pieces: %.3f s in the kernel, %.3f s waiting for the readers, %.3f s waiting for the writers\n",
-                      (unsigned long long)out_size, npieces, t_kernel, t_read, t_write);
+                      (unsigned long long)out_at, npieces, t_kernel, t_read, t_write);
+    return HARC_AMD_OK;
+}
+
+extern "C" int harc_amd_fastq_assemble_files_ex(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out_path,
+                                                int32_t bgzf)
+{
+    if (!params || !dna_path || !id_path || !quality_path || !out_path) { harc_set_error("fastq_assemble_files: bad arguments"); return HARC_AMD_EINVAL; }
+    FqInputs in;
+    RC_TRY(fq_probe("fastq_assemble_files", dna_path, id_path, quality_path, &in));
+    CtxGuard guard;
+    RC_TRY(side_context(params, in.L, &guard.c));
+    harc_amd_ctx *c = guard.c;
+    // the ring is split into four quarters of four slices each and reserved whole before any mover starts.  With the default slice of 64 MB that is the 1 GiB the
+    // ring always had.  HARC_AMD_FEED_SLICE sets the slice, HARC_AMD_FEED_THREADS the host threads of all four together.
+    RingGeom gq[4];
+    RC_TRY(ring_split(c, 4, 4, "FASTQ output", gq));
+    OutFileGuard outguard{ out_path };
+    uint64_t id_end = 0;
+    RC_TRY(fq_assemble_part(c, gq, in, 0, 0, in.n, false, IDM_NONE, out_path, bgzf, &id_end, [&](uint64_t seen) {
+        harc_set_error("fastq_assemble_files: %s holds %llu lines, %s %llu reads", id_path, (unsigned long long)seen, dna_path, (unsigned long long)in.n);
+    }));
     outguard.ok = true;
+    return HARC_AMD_OK;
+}
+
+// The two FASTQ files of a paired archive (./harc -d -p -q): the reads and quality values of file 1 are records [0, n), those of file 2 records [n, 2 n) of the
+// fixed-stride files.  rule none: the id file holds 2 n lines, file 2 continues where file 1 stopped.  Any other rule: it holds file 1's n lines, and file 2's
+// are made from them on the GPU, a piece at a time, in front of the tile kernel.  On any failure neither output file is left.
+extern "C" int harc_amd_fastq_assemble_pair_files(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out1_path,
+                                                  const char *out2_path, uint64_t records_per_file, int32_t rule, int32_t bgzf)
+{
+    if (!params || !dna_path || !id_path || !quality_path || !out1_path || !out2_path) { harc_set_error("fastq_assemble_pair_files: bad arguments"); return HARC_AMD_EINVAL; }
+    if (rule < IDM_NONE || rule > IDM_SPACE) { harc_set_error("fastq_assemble_pair_files: %d is no mate rule (0 none, 1 same, 2 slash, 3 space)", (int)rule); return HARC_AMD_EINVAL; }
+    FqInputs in;
+    RC_TRY(fq_probe("fastq_assemble_pair_files", dna_path, id_path, quality_path, &in));
+    const uint64_t n = records_per_file;
+    if (in.n != 2 * n) {
+        harc_set_error("fastq_assemble_pair_files: %s holds %llu reads, the pair record announces 2 x %llu", dna_path, (unsigned long long)in.n, (unsigned long long)n);
+        return HARC_AMD_EINVAL;
+    }
+    CtxGuard guard;
+    RC_TRY(side_context(params, in.L, &guard.c));
+    harc_amd_ctx *c = guard.c;
+    RingGeom gq[4];
+    RC_TRY(ring_split(c, 4, 4, "FASTQ output", gq));
+    OutFileGuard guard1{ out1_path }, guard2{ out2_path };
+    const uint64_t want = rule == IDM_NONE ? 2 * n : n;
+    uint64_t id_end = 0, taken = 0;
+    auto refuse = [&](uint64_t seen) {
+        harc_set_error("fastq_assemble_pair_files: %s holds %s%llu lines, %llu are needed (%llu records in each file, ids %s)", id_path, (rule == IDM_NONE && !taken) ? "only " : "",
+                       (unsigned long long)(taken + seen), (unsigned long long)want, (unsigned long long)n, idm_rule_name(rule));
+    };
+    if (rule == IDM_NONE) {
+        RC_TRY(fq_assemble_part(c, gq, in, 0, 0, n, true, IDM_NONE, out1_path, bgzf, &id_end, refuse));
+        taken = n;
+        const uint64_t from = id_end;
+        RC_TRY(fq_assemble_part(c, gq, in, from, n, n, false, IDM_NONE, out2_path, bgzf, &id_end, refuse));
+    } else {
+        RC_TRY(fq_assemble_part(c, gq, in, 0, 0, n, false, IDM_SAME, out1_path, bgzf, &id_end, refuse));
+        RC_TRY(fq_assemble_part(c, gq, in, 0, n, n, false, rule, out2_path, bgzf, &id_end, refuse));
+    }
+    guard1.ok = guard2.ok = true;
     return HARC_AMD_OK;
 }

@@ -146,14 +146,19 @@ static int in_grow(harc_amd_ctx *c, harc_amd_ctx::InBuf *b, size_t need, size_t 
     return HARC_AMD_OK;
 }
 // one chunk of whole 4-line records (the last chunk of the file may end inside a record).  expect_*: the caller's estimate of the final
-// counts (0 = unknown), so that the stores are sized once
-static int ingest_append(harc_amd_ctx *c, IngestState &st, const char *d_txt, uint64_t nbytes, bool last, uint64_t expect_clean, uint64_t expect_N)
+// counts (0 = unknown), so that the stores are sized once.  whole_records_of (a pair run): the file the chunk comes from; no chunk of it, the last included, may end
+// inside a record -- the next file's first line must never be glued to it
+static int ingest_append(harc_amd_ctx *c, IngestState &st, const char *d_txt, uint64_t nbytes, bool last, uint64_t expect_clean, uint64_t expect_N, const char *whole_records_of = nullptr)
 {
     if (nbytes == 0) return HARC_AMD_OK;
     const int L = c->P.readlen;
     PoolScope scope(c);                                           // scratch goes on every way out
     const uint64_t *nls = nullptr; uint64_t total_lines = 0;
     RC_TRY(build_line_index(c, d_txt, nbytes, &nls, &total_lines));
+    if (whole_records_of && (total_lines % 4)) {
+        harc_set_error("FASTQ: %s does not hold whole 4-line records (a piece of it ends after line %llu of a record); a pair run does not tolerate a truncated last record", whole_records_of, (unsigned long long)(total_lines % 4));
+        return HARC_AMD_EINVAL;
+    }
     if (!last && (total_lines % 4)) { harc_set_error("FASTQ: a piece of the file does not hold whole 4-line records (%llu lines)", (unsigned long long)total_lines); return HARC_AMD_EINVAL; }
     // a truncated last record still counts as a read when its sequence line is there: the getline loop handles line 2 before it meets
     // the end of the file (preprocess.cpp:90-111); only `readnum` (case 3, :118) misses it
@@ -390,13 +395,20 @@ static int q_routes(harc_amd_ctx *c, const uint32_t *isN, const uint32_t *isC, u
 
 // output.quality and output.id of an archive, or the quality / id parts of a rank: both are there or the call fails, both are closed on every way out
 struct QIdFiles {
-    FILE *fq = nullptr, *fi = nullptr;
-    ~QIdFiles() { if (fq) fclose(fq); if (fi) fclose(fi); }
+    FILE *fq = nullptr, *fi = nullptr, *fi2 = nullptr;             // fi2: output.id2, the ids of the second file of a pair run
+    ~QIdFiles() { if (fq) fclose(fq); if (fi) fclose(fi); if (fi2) fclose(fi2); }
     bool open2(const std::string &q, const std::string &i) { fq = fopen(q.c_str(), "wb"); fi = fopen(i.c_str(), "wb"); return fq && fi; }
     int open(const std::string &od)
     {
         if (open2(od + "output.quality", od + "output.id")) return HARC_AMD_OK;
         harc_set_error("cannot create %soutput.quality / output.id", od.c_str()); return HARC_AMD_EIO;
+    }
+    int open_pair(const std::string &od)
+    {
+        RC_TRY(open(od));
+        fi2 = fopen((od + "output.id2").c_str(), "wb");
+        if (fi2) return HARC_AMD_OK;
+        harc_set_error("cannot create %soutput.id2", od.c_str()); return HARC_AMD_EIO;
     }
     int open_parts(const std::string &sd, const std::string &r)
     {
@@ -745,6 +757,40 @@ static int ingest_file_range(harc_amd_ctx *c, FILE *f, const char *name, uint64_
     }));
     return ingest_finish(c, st);
 }
+// The records of two files as ONE job (./harc -c R1 -2 R2 -p): the pieces of file 1, then the pieces of file 2, into the same IngestState, so that read_order_N.bin,
+// the record numbers and the packed stores continue across the boundary; each file is plain or BGZF on its own.  Neither file may end inside a record or without
+// its last newline.  With fq (-q): output.quality takes the lines of both files in order, fi the ids of file 1 and fi2 those of file 2.  nrec[k]: records of file k
+static int ingest_file_pair(harc_amd_ctx *c, FILE *const f[2], const char *const name[2], const uint64_t fsz[2], const bool bgzf[2], IngestState &st, FILE *fq, FILE *fi, FILE *fi2,
+                            uint64_t nrec[2])
+{
+    RC_TRY(ingest_begin(c, st));
+    for (int k = 0; k < 2; k++) {
+        const uint64_t before = st.nfull;
+        RC_TRY(text_pieces(c, f[k], name[k], 0, fsz[k], fsz[k], bgzf[k], &g_fastq_timing[2], &g_fastq_timing[8], [&](const char *d_txt, uint64_t n, bool last, uint64_t a) -> int {
+            const double ta = mono_now();
+            // the two files hold the same number of records: file k is done to the fraction a / fsz[k], the job to (k + that) / 2; the stores are sized once
+            uint64_t expC = 0, expN = 0;
+            const double frac = 0.5 * ((double)k + (double)a / (double)fsz[k]);
+            if (frac > 0) { expC = (uint64_t)(1.03 * (double)st.nC / frac); expN = (uint64_t)(1.03 * (double)st.nN / frac); }
+            if (last && n) {
+                char lastch = 0;
+                HIP_TRY(hipMemcpyAsync(&lastch, d_txt + n - 1, 1, hipMemcpyDeviceToHost, c->stream));
+                HIP_TRY(hipStreamSynchronize(c->stream));
+                if (lastch != '\n') { harc_set_error("FASTQ: %s does not end in a newline; a pair run does not tolerate a last line that is cut short", name[k]); return HARC_AMD_EINVAL; }
+            }
+            RC_TRY(ingest_append(c, st, d_txt, n, false, expC, expN, name[k]));
+            g_fastq_timing[3] += mono_now() - ta;
+            if (fq) RC_TRY(emit_q_fileorder(c, d_txt, n, fq, k ? fi2 : fi));
+            return HARC_AMD_OK;
+        }));
+        nrec[k] = st.nfull - before;
+    }
+    if (nrec[0] != nrec[1]) {
+        harc_set_error("the two files of the pair hold different numbers of records: %s %llu, %s %llu; mates are paired by their place", name[0], (unsigned long long)nrec[0], name[1], (unsigned long long)nrec[1]);
+        return HARC_AMD_EINVAL;
+    }
+    return ingest_finish(c, st);
+}
 
 // What the first bytes of a file say: 0 = not gzip, 1 = BGZF (the first member carries a BC subfield), -1 = another gzip.  *ratio (may be null):
 // text bytes per compressed byte over the members that start in the first MB (the -q mode is chosen by the size of the text).
@@ -771,8 +817,10 @@ extern "C" int harc_amd_compress_fastq_files_ex(const harc_amd_params *params, c
 {
     return harc_amd_compress_fastq_files_checked(params, fastq, basedir, preserve_order, preserve_quality, 0);
 }
-// check (./harc -c -V): the signature (and with -p the order digest) of the reads as ingested, the streams decoded once before they are written, read.check
-extern "C" int harc_amd_compress_fastq_files_checked(const harc_amd_params *params, const char *fastq, const char *basedir, int32_t preserve_order, int32_t preserve_quality, int32_t check)
+// check (./harc -c -V): the signature (and with -p the order digest) of the reads as ingested, the streams decoded once before they are written, read.check.
+// fastq2 (a pair run, harc_amd_compress_fastq_pair_files): the records of fastq followed by those of fastq2 are the job, in that order; read.pair is written
+static int compress_fastq_job(const harc_amd_params *params, const char *fastq, const char *fastq2, const char *basedir, int32_t preserve_order, int32_t preserve_quality, int32_t check,
+                              uint64_t *records_per_file)
 {
     if (!params || !fastq || !basedir) return HARC_AMD_EINVAL;
     for (double &x : g_fastq_timing) x = 0;
@@ -782,6 +830,8 @@ extern "C" int harc_amd_compress_fastq_files_checked(const harc_amd_params *para
     const int gz = gzip_kind(fastq, &ratio);
     if (gz < 0) { harc_set_error("%s is gzip but not BGZF: recompress it with bgzip or decompress it first", fastq); return HARC_AMD_EINVAL; }
     const bool bgzf = gz > 0;
+    const int gz2 = fastq2 ? gzip_kind(fastq2, nullptr) : 0;       // each file of a pair is sniffed on its own
+    if (gz2 < 0) { harc_set_error("%s is gzip but not BGZF: recompress it with bgzip or decompress it first", fastq2); return HARC_AMD_EINVAL; }
     CtxGuard guard; RC_TRY(harc_amd_create(params, &guard.c));
     harc_amd_ctx *const c = guard.c;
     g_fastq_timing[0] = mono_now() - t_begin;
@@ -802,7 +852,15 @@ extern "C" int harc_amd_compress_fastq_files_checked(const harc_amd_params *para
         stream_q = (hipMemGetInfo(&fr, &tot) == hipSuccess && text_est > 0.45 * (double)fr);
         if (const char *e = getenv("HARC_AMD_Q_STREAM")) stream_q = atoi(e) != 0;       // tests: either way on a small file
     }
-    if (preserve_quality && !preserve_order && !stream_q) {
+    uint64_t pair_records[2] = { 0, 0 };
+    if (fastq2) {                                                 // (always with the order kept: quality values and ids in file order, written while the pieces pass through)
+        InFile in2; RC_TRY(in2.open(fastq2));
+        QIdFiles out;
+        if (preserve_quality) RC_TRY(out.open_pair(od));
+        FILE *const ff[2] = { f, in2.f }; const char *const nn[2] = { fastq, fastq2 }; const uint64_t zz[2] = { fsz, in2.size }; const bool bb[2] = { bgzf, gz2 > 0 };
+        RC_TRY(ingest_file_pair(c, ff, nn, zz, bb, st, out.fq, out.fi, out.fi2, pair_records));
+        if (records_per_file) *records_per_file = pair_records[0];
+    } else if (preserve_quality && !preserve_order && !stream_q) {
         if (bgzf) {                                               // the text pieces appended into one buffer
             tsz = 0;
             // sized once from the estimate; grown (with a copy) only where the estimate was short
@@ -860,6 +918,10 @@ extern "C" int harc_amd_compress_fastq_files_checked(const harc_amd_params *para
         if (preserve_order) k += ck_format_order(rec + k, sizeof rec - (size_t)k, t_order);
         RC_TRY(spit_file(od + "read.check", rec, (size_t)k));
     }
+    if (fastq2) {                                                 // the record of a pair run; ./harc appends the line "ids <rule>" with -q
+        char rec[64]; const int k = snprintf(rec, sizeof rec, "HARCP1\nrecords %llu\n", (unsigned long long)pair_records[0]);
+        RC_TRY(spit_file(od + "read.pair", rec, (size_t)k));
+    }
     RC_TRY(write_shard_family(c, od, 0));
     tm.lap("stream files");
     RC_TRY(write_whole_job_files(c, od));
@@ -872,6 +934,16 @@ extern "C" int harc_amd_compress_fastq_files_checked(const harc_amd_params *para
         tm.lap("quality values and ids");
     }
     return HARC_AMD_OK;
+}
+extern "C" int harc_amd_compress_fastq_files_checked(const harc_amd_params *params, const char *fastq, const char *basedir, int32_t preserve_order, int32_t preserve_quality, int32_t check)
+{
+    return compress_fastq_job(params, fastq, nullptr, basedir, preserve_order, preserve_quality, check, nullptr);
+}
+extern "C" int harc_amd_compress_fastq_pair_files(const harc_amd_params *params, const char *fastq1, const char *fastq2, const char *basedir, int32_t preserve_quality, int32_t check,
+                                                  uint64_t *records_per_file)
+{
+    if (!fastq2) { harc_set_error("compress_fastq_pair_files: bad arguments"); return HARC_AMD_EINVAL; }
+    return compress_fastq_job(params, fastq1, fastq2, basedir, 1, preserve_quality, check, records_per_file);
 }
 extern "C" int harc_amd_compress_fastq_files(const harc_amd_params *params, const char *fastq, const char *basedir)
 {

@@ -28,6 +28,14 @@
 //   harc_amd_stage text_digest <file> [<device>]                          "bytes lines D" of the file's text on stdout, 16 hex digits each (./harc -c -V, -d, -v)
 //   harc_amd_stage reads_check <dna> [<device>]                            "count sum xor bytes lines D" of the decoders' output, read once: the multiset signature
 //                                                                          of its reads and the digest of its text (./harc -d, -v on an archive made with -V)
+//   harc_amd_stage compressfq_pair <basedir> <readlen> <fastq1> <fastq2> <num_thr> <num_chains> <num_steps> <preserve_quality> [check]
+//                                                                          compressfq over two files as one job, the order kept (./harc -c R1 -2 R2 -p): the records of
+//                                                                          <fastq1>, then those of <fastq2>; output/read.pair records their number
+//   harc_amd_stage id_mates <a> <b> [<device>]                             "<rule> <pairs>" on stdout and nothing else: the mate rule (none, same, slash, space) that every
+//                                                                          pair of lines of the two id files follows
+//   harc_amd_stage fastq_out_pair <dna> <ignored> <id> <quality> <out1> <out2> <records> <rule> [bgzf]
+//                                                                          fastq_out for a paired archive: records [0, n) -> <out1>, [n, 2 n) -> <out2>, the second file's ids
+//                                                                          made from the first's by <rule> on the GPU (./harc -d -p -q)
 // compressfq takes one more trailing argument, "check" (./harc -c -V): the streams are decoded once before they are written, and output/read.check is written.
 // readlen / num_thr arrive as arguments instead of the compile-time macros of src/config.h (harc:52-63).
 #include <stdio.h>
@@ -63,6 +71,17 @@ int main(int argc, char **argv)
         printf("%016llx %016llx %016llx\n", (unsigned long long)t[0], (unsigned long long)t[1], (unsigned long long)t[2]);
         return 0;
     }
+    if (argc >= 2 && !strcmp(argv[1], "id_mates")) {
+        if (argc < 4) { fprintf(stderr, "id_mates needs <a> <b> [<device>]\n"); return 2; }
+        harc_amd_params PM;
+        if (harc_amd_default_params(100, &PM) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
+        if (argc > 4) PM.device = atoi(argv[4]);
+        int32_t rule = 0; uint64_t pairs = 0;
+        const int rcm = harc_amd_idmate_rule_files(&PM, argv[2], argv[3], &rule, &pairs);
+        if (rcm != 0) { fprintf(stderr, "harc_amd_stage id_mates failed (%d): %s\n", rcm, harc_amd_last_error()); return 1; }
+        printf("%s %llu\n", harc_amd_idmate_rule_name(rule), (unsigned long long)pairs);
+        return 0;
+    }
     if (argc < 4) { fprintf(stderr, "usage: %s reorder|encoder|compress|pack_order <basedir> <readlen> [num_thr] [num_chains]\n", argv[0]); return 2; }
     // RCCL between processes needs dmabuf IPC on this driver stack (hipIpcGetMemHandle fails otherwise): set before the first HIP call
     // of the process, which is inside the library.  An explicit setting of the caller wins.
@@ -79,6 +98,20 @@ int main(int argc, char **argv)
         if (harc_amd_default_params(100, &PF) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
         const int rcf = argc > 7 ? harc_amd_fastq_assemble_files_ex(&PF, argv[2], argv[4], argv[5], argv[6], 1) : harc_amd_fastq_assemble_files(&PF, argv[2], argv[4], argv[5], argv[6]);
         if (rcf != 0) { fprintf(stderr, "harc_amd_stage fastq_out failed (%d): %s\n", rcf, harc_amd_last_error()); return 1; }
+        return 0;
+    }
+    if (!strcmp(argv[1], "fastq_out_pair")) {
+        if (argc < 10) { fprintf(stderr, "fastq_out_pair needs <dna> <ignored> <id> <quality> <out1> <out2> <records> <rule> [bgzf]\n"); return 2; }
+        if (argc > 10 && strcmp(argv[10], "bgzf")) { fprintf(stderr, "fastq_out_pair: the ninth argument can only be 'bgzf' (got '%s')\n", argv[10]); return 2; }
+        char *end = nullptr;
+        const unsigned long long records = strtoull(argv[8], &end, 10);
+        if (!*argv[8] || *end) { fprintf(stderr, "fastq_out_pair: <records> must be a decimal number (got '%s')\n", argv[8]); return 2; }
+        const int32_t rule = harc_amd_idmate_rule_parse(argv[9]);
+        if (rule < 0) { fprintf(stderr, "fastq_out_pair: <rule> must be none, same, slash or space (got '%s')\n", argv[9]); return 2; }
+        harc_amd_params PF;
+        if (harc_amd_default_params(100, &PF) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
+        const int rcf = harc_amd_fastq_assemble_pair_files(&PF, argv[2], argv[4], argv[5], argv[6], argv[7], records, rule, argc > 10);
+        if (rcf != 0) { fprintf(stderr, "harc_amd_stage fastq_out_pair failed (%d): %s\n", rcf, harc_amd_last_error()); return 1; }
         return 0;
     }
     if (!strcmp(argv[1], "quality_pack") || !strcmp(argv[1], "quality_unpack")) {     // the read length is in the file
@@ -163,6 +196,12 @@ int main(int argc, char **argv)
         const int po = argc > 8 && !strcmp(argv[8], "True"), pq = argc > 9 && !strcmp(argv[9], "True");     // preprocess.out's argv[3], argv[4] (harc:50)
         if (argc > 10 && strcmp(argv[10], "check")) { fprintf(stderr, "compressfq: the argument behind <preserve_quality> can only be 'check' (got '%s')\n", argv[10]); return 2; }
         rc = harc_amd_compress_fastq_files_checked(&P, argv[4], argv[2], po, pq, argc > 10);
+    }
+    else if (!strcmp(argv[1], "compressfq_pair")) {
+        if (argc < 10) { fprintf(stderr, "compressfq_pair needs <fastq1> <fastq2> <num_thr> <num_chains> <num_steps> <preserve_quality> [check]\n"); return 2; }
+        P.num_thr = atoi(argv[6]); P.num_chains = atoi(argv[7]); P.num_steps = atoi(argv[8]);
+        if (argc > 10 && strcmp(argv[10], "check")) { fprintf(stderr, "compressfq_pair: the argument behind <preserve_quality> can only be 'check' (got '%s')\n", argv[10]); return 2; }
+        rc = harc_amd_compress_fastq_pair_files(&P, argv[4], argv[5], argv[2], !strcmp(argv[9], "True"), argc > 10, nullptr);
     }
     else if (!strcmp(argv[1], "compressfq_shard")) {
         if (argc < 13) { fprintf(stderr, "compressfq_shard needs <fastq> <num_thr> <num_chains> <num_steps> <p> <q> <world> <rank> <comm_spec> [device]\n"); return 2; }

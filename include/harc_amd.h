@@ -547,6 +547,50 @@ int harc_amd_reads_check_files(const harc_amd_params *params, const char *dna_pa
    "reads <count> <sum> <xor>" and, with preserve_order, "order <bytes> <D>", every value as 16 lowercase hex digits. */
 int harc_amd_compress_fastq_files_checked(const harc_amd_params *params, const char *fastq, const char *basedir, int32_t preserve_order, int32_t preserve_quality, int32_t check);
 
+/* ---- Paired-end input (./harc -c R1 -2 R2 -p, ./harc -d -p -q; README.md, "-2 and what it promises").
+   The mate rule.  Let a be id line i of file 1 and b id line i of file 2, without their newlines, the '@' included, any bytes.  A pair satisfies at most one of
+     same    b == a
+     slash   |a| = |b| >= 2, a ends in "/1", b is a with its last byte '2'
+     space   |a| = |b|, a has a first space at s with s + 1 < |a|, a[s + 1] = '1', b is a with byte s + 1 set to '2'
+   The rule of two files is the one that EVERY pair satisfies; no pair at all gives same; otherwise the rule is none.  By construction apply(A, rule) == B.
+   A pair's flags: bit 0 same, bit 1 slash, bit 2 space; a rule as a number: */
+#define HARC_AMD_IDMATE_NONE 0
+#define HARC_AMD_IDMATE_SAME 1
+#define HARC_AMD_IDMATE_SLASH 2
+#define HARC_AMD_IDMATE_SPACE 3
+/* *flags_and = the AND of the flags of all pairs of lines of the two id texts in device memory (any alignment; no load leaves the 8-byte-aligned hull of a text),
+   7 when they hold no line; *n_pairs = the pairs.  Texts with different line counts or a last line without its newline: HARC_AMD_EINVAL naming both counts.
+   HARC_AMD_TRACE=1: one "[idmate] device call" line on stderr with the rule kernel's time. */
+int harc_amd_idmate_rule_device(harc_amd_ctx *ctx, const char *d_a, uint64_t a_bytes, const char *d_b, uint64_t b_bytes, uint64_t *n_pairs, uint32_t *flags_and);
+/* The same over host memory, serially: what the kernel is held to (tests).  Touches no device. */
+int harc_amd_idmate_rule_host(const char *a, uint64_t a_bytes, const char *b, uint64_t b_bytes, uint64_t *n_pairs, uint32_t *flags_and);
+/* The rule that a flag word over n_pairs pairs stands for; its name ("none", "same", "slash", "space"; "?" for anything else); a name -> its number, or -1. */
+int32_t harc_amd_idmate_rule_of(uint32_t flags_and, uint64_t n_pairs);
+const char *harc_amd_idmate_rule_name(int32_t rule);
+int32_t harc_amd_idmate_rule_parse(const char *name);
+/* The rule of two id files, walked in lockstep through the pinned ring: a byte range of A and the next of B per turn, min(lines of A, lines of B) whole lines are
+   compared, the rest of both is carried into the next turn.  HARC_AMD_IDMATE_PIECE: bytes per range (default 256 MiB; tests: pieces of a few lines); the answer
+   does not depend on it.  Different line counts or a last line without its newline: HARC_AMD_EINVAL.  Only `device` is taken from params. */
+int harc_amd_idmate_rule_files(const harc_amd_params *params, const char *path_a, const char *path_b, int32_t *rule, uint64_t *n_pairs);
+/* File 2's ids from file 1's: the whole lines of the id text at d_ids (device memory, any alignment) are patched in place -- slash: the byte in front of each
+   newline, space: the byte behind each line's first space, '1' -> '2'; same and none patch nothing.  *bad = the lines where the byte to replace is not '1' or
+   does not exist (they stay as they are): a damaged id file, or another rule than the one recorded, is counted instead of assembled. */
+int harc_amd_idmate_apply_device(harc_amd_ctx *ctx, char *d_ids, uint64_t id_bytes, int32_t rule, uint64_t *bad);
+int harc_amd_idmate_apply_host(char *ids, uint64_t id_bytes, int32_t rule, uint64_t *bad);
+/* harc_amd_compress_fastq_files_checked over TWO files as one job, the order always kept: the records of fastq1 followed by those of fastq2 -- the archive of
+   `cat fastq1 fastq2` without the copy.  Each file is plain FASTQ or BGZF on its own.  Neither may end inside a 4-line record or without its last newline (the file
+   is named), and both must hold the same number of records (both counts are named); *records_per_file (may be null) = that number.  With preserve_quality
+   <basedir>/output/output.quality holds the quality lines of both files in order, output.id the ids of fastq1 and output.id2 those of fastq2.
+   <basedir>/output/read.pair holds "HARCP1" and "records <n>" (decimal). */
+int harc_amd_compress_fastq_pair_files(const harc_amd_params *params, const char *fastq1, const char *fastq2, const char *basedir, int32_t preserve_quality, int32_t check,
+                                       uint64_t *records_per_file);
+/* harc_amd_fastq_assemble_files_ex for a paired archive: records [0, n) of dna_path / quality_path -> out1_path, records [n, 2 n) -> out2_path, n = records_per_file.
+   rule none: id_path holds 2 n lines, the second file continues where the first stopped.  Any other rule: id_path holds n lines, the first file's; the second
+   file's are made from them on the GPU in front of the assembly (harc_amd_idmate_apply_device's patch and count).  Another line count: HARC_AMD_EINVAL naming the
+   counts.  bgzf: each output is the BGZF file of its own text.  On any failure neither output file is left. */
+int harc_amd_fastq_assemble_pair_files(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out1_path,
+                                       const char *out2_path, uint64_t records_per_file, int32_t rule, int32_t bgzf);
+
 #ifdef __cplusplus
 }
 #endif

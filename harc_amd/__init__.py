@@ -12,7 +12,8 @@ from .api import (HarcAmd, HarcAmdError, Params, Counters, default_params, lib, 
                   idpack_bound, idpack_host, idunpack_host, idpack_files, idunpack_files,
                   spack_bound, spack_host, sunpack_host, spack_files, sunpack_files, spack_file_list, sunpack_file_list,
                   text_digest_host, text_digest_file, reads_check_file,
-                  compress_fastq_pair, IDMATE_RULES, idmate_rule_host, idmate_apply_host, idmate_rule_files, fastq_assemble_pair)
+                  compress_fastq_pair, IDMATE_RULES, idmate_rule_host, idmate_apply_host, idmate_rule_files, fastq_assemble_pair,
+                  LINE_NONE, line_offset_host, line_range_file, qunpack_range_files, idunpack_range_files)
 from ._build import build
 
 __all__ = ["HarcAmd", "HarcAmdError", "Params", "Counters", "default_params", "lib", "lib_path", "reorder", "encoder",
@@ -24,4 +25,5 @@ __all__ = ["HarcAmd", "HarcAmdError", "Params", "Counters", "default_params", "l
            "idpack_bound", "idpack_host", "idunpack_host", "idpack_files", "idunpack_files",
            "spack_bound", "spack_host", "sunpack_host", "spack_files", "sunpack_files", "spack_file_list", "sunpack_file_list",
            "text_digest_host", "text_digest_file", "reads_check_file",
-           "compress_fastq_pair", "IDMATE_RULES", "idmate_rule_host", "idmate_apply_host", "idmate_rule_files", "fastq_assemble_pair"]
+           "compress_fastq_pair", "IDMATE_RULES", "idmate_rule_host", "idmate_apply_host", "idmate_rule_files", "fastq_assemble_pair",
+           "LINE_NONE", "line_offset_host", "line_range_file", "qunpack_range_files", "idunpack_range_files"]

@@ -196,6 +196,14 @@ def lib():
         l.harc_amd_idmate_apply_host.argtypes = [C.c_char_p, C.c_uint64, C.c_int32, U64P]
         l.harc_amd_compress_fastq_pair_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, U64P]
         l.harc_amd_fastq_assemble_pair_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32]
+    if hasattr(l, "harc_amd_line_offset_device"):        # (HARC_AMD_LIB may name a build from before range restore)
+        l.harc_amd_line_offset_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_uint64, U64P]
+        l.harc_amd_line_offset_host.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, U64P]
+        l.harc_amd_line_range_files.argtypes = [PP, C.c_char_p, C.c_uint64, C.c_uint64, U64P]
+        l.harc_amd_qunpack_range_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64]
+        l.harc_amd_idunpack_range_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64]
+        l.harc_amd_decoder_range_files.argtypes = [PP, C.c_char_p, C.c_int32, C.c_int32, U64P, U64P]
+        l.harc_amd_decoder_preserve_range_files.argtypes = [PP, C.c_char_p, C.c_int32, C.c_int32, U64P, U64P]
     l.harc_amd_build_id.restype = C.c_char_p
     _lib = l
     return l
@@ -345,13 +353,51 @@ def merge_shards(basedir, world):
     _check(lib().harc_amd_merge_shard_files(os.fsencode(basedir), world))
 
 
-def decoder(basedir, num_thr_e, device=0, preserve_order=False, memory_gb=0):
+def decoder(basedir, num_thr_e, device=0, preserve_order=False, memory_gb=0, ranges=None):
     """== `decoder.out <basedir> <num_thr> <num_thr_e>` (src/decoder.cpp:44-172): output/output.dna;
-    preserve_order: the -p chain unpack_order + decoder_preserve + merge_N (harc:183-185)"""
+    preserve_order: the -p chain unpack_order + decoder_preserve + merge_N (harc:183-185).  ranges: one or two (first, count) of output lines, first counted
+    from 0 -- output.dna then holds those lines alone, one range after the other (include/harc_amd.h: harc_amd_decoder_range_files)"""
     p = default_params(100, device=device)
     p.decode_memory_gb = memory_gb
-    f = lib().harc_amd_decoder_preserve_files if preserve_order else lib().harc_amd_decoder_files
-    _check(f(C.byref(p), os.fsencode(basedir), num_thr_e))
+    if ranges is None:
+        f = lib().harc_amd_decoder_preserve_files if preserve_order else lib().harc_amd_decoder_files
+        _check(f(C.byref(p), os.fsencode(basedir), num_thr_e))
+        return
+    first, count = (C.c_uint64 * len(ranges))(*[a for a, _ in ranges]), (C.c_uint64 * len(ranges))(*[b for _, b in ranges])
+    f = lib().harc_amd_decoder_preserve_range_files if preserve_order else lib().harc_amd_decoder_range_files
+    _check(f(C.byref(p), os.fsencode(basedir), num_thr_e, len(ranges), first, count))
+
+
+LINE_NONE = 2 ** 64 - 1      # line_offset_*: the text holds fewer than k newlines
+
+
+def line_offset_host(text, k):
+    """(newlines of `text`, the byte offset at which line k starts: 0 for k = 0, else one past the k-th newline, LINE_NONE when there are fewer) on the host:
+    what HarcAmd.line_offset_device is held to (include/harc_amd.h: harc_amd_line_offset_host); no device"""
+    out = (C.c_uint64 * 2)()
+    _check(lib().harc_amd_line_offset_host(bytes(text), len(text), k, out))
+    return int(out[0]), int(out[1])
+
+
+def line_range_file(path, first_line, n_lines, device=0):
+    """the byte range (begin, end) of lines first_line .. first_line + n_lines - 1 (counted from 0) of the text file at `path`, the newlines counted on the GPU
+    piece by piece (include/harc_amd.h: harc_amd_line_range_files)"""
+    p = default_params(100, device=device)
+    out = (C.c_uint64 * 2)()
+    _check(lib().harc_amd_line_range_files(C.byref(p), os.fsencode(path), first_line, n_lines, out))
+    return int(out[0]), int(out[1])
+
+
+def qunpack_range_files(packed, out, first_line, n_lines, device=0):
+    """qunpack_files for lines first_line .. first_line + n_lines - 1 (counted from 0) alone: only the blocks that hold them are read, decoded and checked"""
+    p = default_params(100, device=device)
+    _check(lib().harc_amd_qunpack_range_files(C.byref(p), os.fsencode(packed), os.fsencode(out), first_line, n_lines))
+
+
+def idunpack_range_files(packed, out, first_line, n_lines, device=0):
+    """idunpack_files for lines first_line .. first_line + n_lines - 1 (counted from 0) alone: only the blocks that hold them are read, decoded and checked"""
+    p = default_params(100, device=device)
+    _check(lib().harc_amd_idunpack_range_files(C.byref(p), os.fsencode(packed), os.fsencode(out), first_line, n_lines))
 
 
 def fastq_assemble(dna, ids, quality, out, device=0, bgzf=False):
@@ -782,6 +828,12 @@ class HarcAmd:
         a = (C.c_uint64 * 3)(*acc)
         _check(lib().harc_amd_text_digest_device(self._ctx, C.c_void_p(ptr) if ptr else None, nbytes, first_offset, a))
         return tuple(a)
+
+    def line_offset_device(self, ptr, nbytes, k):
+        """(newlines of the nbytes bytes at `ptr` (device memory, any alignment), the byte offset at which line k starts or LINE_NONE): line_offset_host on the GPU"""
+        out = (C.c_uint64 * 2)()
+        _check(lib().harc_amd_line_offset_device(self._ctx, C.c_void_p(ptr) if ptr else None, nbytes, k, out))
+        return int(out[0]), int(out[1])
 
     def idmate_rule_device(self, d_a, a_bytes, d_b, b_bytes):
         """the mate rule of two id texts in device memory (any alignment) -> (rule name, pairs, the AND of the pairs' flags)"""

@@ -500,6 +500,7 @@ extern "C" int harc_amd_build_has(const char *feature)
     if (!strcmp(feature, "spack")) return 1;                      // the packed stream file (spack.hip): ./harc -c -S
     if (!strcmp(feature, "qmap")) return 1;                       // lossy quality values (qmap.hip): ./harc -c -q -b
     if (!strcmp(feature, "pair")) return 1;                       // paired-end input (ingest.hip, idmate.hip, fastq_out.hip): ./harc -c R1 -2 R2 -p
+    if (!strcmp(feature, "range")) return 1;                      // range restore (linesel.hip, packfile.h, verify.hip): ./harc -d -r FIRST:LAST
 #ifdef HARC_AMD_TEST_TRANSPORT
     if (!strcmp(feature, "test_transport")) return 1;
 #endif

@@ -489,3 +489,9 @@ extern "C" int harc_amd_idunpack_files(const harc_amd_params *params, const char
 {
     return pack_unpack_files(ID_FORMAT, params, packed_path, out_path);
 }
+
+extern "C" int harc_amd_idunpack_range_files(const harc_amd_params *params, const char *packed_path, const char *out_path, uint64_t first_line, uint64_t n_lines)
+{
+    const uint64_t range[2] = { first_line, n_lines };
+    return pack_unpack_files(ID_FORMAT, params, packed_path, out_path, nullptr, 0, range);
+}

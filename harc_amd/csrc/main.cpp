@@ -36,6 +36,14 @@
 //   harc_amd_stage fastq_out_pair <dna> <ignored> <id> <quality> <out1> <out2> <records> <rule> [bgzf]
 //                                                                          fastq_out for a paired archive: records [0, n) -> <out1>, [n, 2 n) -> <out2>, the second file's ids
 //                                                                          made from the first's by <rule> on the GPU (./harc -d -p -q)
+//   harc_amd_stage line_range <file> <first> <count> [<device>]            "begin end" on stdout and nothing else: the byte range of lines <first> .. <first> + <count> - 1 of the
+//                                                                          text file, the newlines counted on the GPU (./harc -d -q -r on a plain X.id)
+//   harc_amd_stage quality_unpack_range <packed> <device> <out> <first> <count>   quality_unpack for those lines alone: only the blocks that hold them are read (./harc -d -q -r)
+//   harc_amd_stage id_unpack_range <packed> <device> <out> <first> <count>        ... and id_unpack
+//   harc_amd_stage decoder_range <basedir> <ignored> <num_thr_e> <first> <count> [<first> <count>]
+//                                                                          decoder that writes only those lines of its output, one range after the other (./harc -d -r)
+//   harc_amd_stage decoder_preserve_range <basedir> <ignored> <num_thr_e> <memory_gb> <first> <count> [<first> <count>]     ... and decoder_preserve (./harc -d -p -r)
+// (every <first> above counts lines from 0; ./harc -r counts from 1)
 // compressfq takes one more trailing argument, "check" (./harc -c -V): the streams are decoded once before they are written, and output/read.check is written.
 // readlen / num_thr arrive as arguments instead of the compile-time macros of src/config.h (harc:52-63).
 #include <stdio.h>
@@ -175,6 +183,44 @@ int main(int argc, char **argv)
         PI.device = atoi(argv[3]);
         const int rci = !strcmp(argv[1], "id_pack") ? harc_amd_idpack_files(&PI, argv[2], argv[4]) : harc_amd_idunpack_files(&PI, argv[2], argv[4]);
         if (rci != 0) { fprintf(stderr, "harc_amd_stage %s failed (%d): %s\n", argv[1], rci, harc_amd_last_error()); return 1; }
+        return 0;
+    }
+    // a decimal number that fits 64 bits and nothing else
+    auto number = [](const char *s, uint64_t *v) { char *end = nullptr; if (!*s || *s == '-' || *s == '+') return false; *v = strtoull(s, &end, 10); return *end == 0; };
+    if (!strcmp(argv[1], "line_range")) {
+        uint64_t first = 0, count = 0, r[2] = { 0, 0 };
+        if (argc < 5 || !number(argv[3], &first) || !number(argv[4], &count)) { fprintf(stderr, "line_range needs <file> <first> <count> [<device>], lines counted from 0\n"); return 2; }
+        harc_amd_params PL;
+        if (harc_amd_default_params(100, &PL) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
+        if (argc > 5) PL.device = atoi(argv[5]);
+        const int rcl = harc_amd_line_range_files(&PL, argv[2], first, count, r);
+        if (rcl != 0) { fprintf(stderr, "harc_amd_stage line_range failed (%d): %s\n", rcl, harc_amd_last_error()); return 1; }
+        printf("%llu %llu\n", (unsigned long long)r[0], (unsigned long long)r[1]);
+        return 0;
+    }
+    if (!strcmp(argv[1], "quality_unpack_range") || !strcmp(argv[1], "id_unpack_range")) {
+        uint64_t first = 0, count = 0;
+        if (argc < 7 || !number(argv[5], &first) || !number(argv[6], &count)) { fprintf(stderr, "%s needs <packed> <device> <out> <first> <count>, lines counted from 0\n", argv[1]); return 2; }
+        harc_amd_params PR;
+        if (harc_amd_default_params(100, &PR) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
+        PR.device = atoi(argv[3]);
+        const int rcr = !strcmp(argv[1], "quality_unpack_range") ? harc_amd_qunpack_range_files(&PR, argv[2], argv[4], first, count) : harc_amd_idunpack_range_files(&PR, argv[2], argv[4], first, count);
+        if (rcr != 0) { fprintf(stderr, "harc_amd_stage %s failed (%d): %s\n", argv[1], rcr, harc_amd_last_error()); return 1; }
+        return 0;
+    }
+    if (!strcmp(argv[1], "decoder_range") || !strcmp(argv[1], "decoder_preserve_range")) {
+        // decoder_range <basedir> <ignored> <num_thr_e> <first> <count> [<first> <count>]; decoder_preserve_range has <memory_gb> in front of the first <first>
+        const bool keep = !strcmp(argv[1], "decoder_preserve_range");
+        const int at = keep ? 6 : 5, left = argc - at;
+        uint64_t first[2] = { 0, 0 }, count[2] = { 0, 0 };
+        bool ok = left == 2 || left == 4;
+        for (int k = 0; ok && k < left / 2; k++) ok = number(argv[at + 2 * k], &first[k]) && number(argv[at + 2 * k + 1], &count[k]);
+        if (!ok) { fprintf(stderr, "%s needs <basedir> <ignored> <num_thr_e> %s<first> <count> [<first> <count>], lines counted from 0\n", argv[1], keep ? "<memory_gb> " : ""); return 2; }
+        harc_amd_params PD;
+        if (harc_amd_default_params(100, &PD) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
+        if (keep) PD.decode_memory_gb = atoi(argv[5]);
+        const int rcd = keep ? harc_amd_decoder_preserve_range_files(&PD, argv[2], atoi(argv[4]), left / 2, first, count) : harc_amd_decoder_range_files(&PD, argv[2], atoi(argv[4]), left / 2, first, count);
+        if (rcd != 0) { fprintf(stderr, "harc_amd_stage %s failed (%d): %s\n", argv[1], rcd, harc_amd_last_error()); return 1; }
         return 0;
     }
     harc_amd_params P;

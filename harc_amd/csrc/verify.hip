@@ -326,8 +326,27 @@ extern "C" int harc_amd_decode_signature(harc_amd_ctx *c, uint64_t *sig3)
     return HARC_AMD_OK;
 }
 
-// decoder.out <basedir> <num_thr> <num_thr_e>  (src/decoder.cpp:44-172, harc:188): writes output/output.dna
-extern "C" int harc_amd_decoder_files(const harc_amd_params *params, const char *basedir, int32_t num_thr_e)
+// The ranges of output lines a decoder writes, one after the other (./harc -d -r): [lo, hi) in lines of the whole output, `out`: the lines written in front of it.
+// No range asked for: the whole output as one range
+struct LineRange { uint64_t lo, hi, out; };
+static int line_ranges(const char *who, int32_t n_ranges, const uint64_t *first, const uint64_t *count, uint64_t total, std::vector<LineRange> *R, uint64_t *lines_out)
+{
+    R->clear(); *lines_out = 0;
+    if (n_ranges == 0) { R->push_back(LineRange{ 0, total, 0 }); *lines_out = total; return HARC_AMD_OK; }
+    if (n_ranges < 0 || n_ranges > 2 || !first || !count) { harc_set_error("%s: one or two ranges, not %d", who, n_ranges); return HARC_AMD_EINVAL; }
+    for (int r = 0; r < n_ranges; r++) {
+        if (count[r] == 0 || first[r] >= total || count[r] > total - first[r]) {
+            harc_set_error("%s: lines %llu .. %llu are wanted, the archive holds %llu", who, (unsigned long long)first[r] + 1, (unsigned long long)(first[r] + count[r]), (unsigned long long)total);
+            return HARC_AMD_EINVAL;
+        }
+        R->push_back(LineRange{ first[r], first[r] + count[r], *lines_out });
+        *lines_out += count[r];
+    }
+    return HARC_AMD_OK;
+}
+
+// decoder.out <basedir> <num_thr> <num_thr_e>  (src/decoder.cpp:44-172, harc:188): writes output/output.dna, or the lines of the ranges alone
+extern "C" int harc_amd_decoder_range_files(const harc_amd_params *params, const char *basedir, int32_t num_thr_e, int32_t n_ranges, const uint64_t *first, const uint64_t *count)
 {
     std::string od; int L = 0; CtxGuard guard;
     RC_TRY(open_archive(params, basedir, num_thr_e, &od, &L, &guard.c));
@@ -342,11 +361,25 @@ extern "C" int harc_amd_decoder_files(const harc_amd_params *params, const char 
     // the N reads of every shard come behind the singletons (decoder.cpp:159-165): they wait in device memory of their own (declared in front of the
     // drain: it goes after the drain has written what it still holds)
     struct NParts { harc_amd_ctx *c; std::vector<std::pair<char *, size_t>> v; ~NParts() { for (auto &x : v) if (x.first) harc_raw_free(c, x.first); } } nparts{ c, {} };
+    std::vector<LineRange> R; uint64_t lines_out = 0;
+    RC_TRY(line_ranges("decoder", n_ranges, first, count, total_out / LL, &R, &lines_out));
     const double td0 = mono_now(); double t_slurp = 0, t_put = 0;
     FileDrain drain(c);
-    RC_TRY(drain.start(od + "output.dna", total_out));
+    RC_TRY(drain.start(od + "output.dna", n_ranges ? (size_t)lines_out * LL : total_out));
     const double td1 = mono_now();
     uint64_t out_at = 0;
+    // the segment of `len` bytes that continues the whole output at byte out_at, in device memory (d) or on the host (h): the parts of it inside a range are written
+    auto emit = [&](const char *d, const uint8_t *h, size_t len) -> int {
+        for (const LineRange &r : R) {
+            const uint64_t rlo = r.lo * LL, rhi = n_ranges ? r.hi * LL : (uint64_t)total_out;     // (the whole decode: an input_N.dna that is not whole lines is written as it is)
+            const uint64_t lo = out_at > rlo ? out_at : rlo, hi = out_at + len < rhi ? out_at + len : rhi;
+            if (lo >= hi) continue;
+            if (d) RC_TRY(drain.put(d + (lo - out_at), (size_t)(hi - lo), r.out * LL + (lo - rlo)));
+            else RC_TRY(drain.put_host(h + (lo - out_at), (size_t)(hi - lo), r.out * LL + (lo - rlo)));
+        }
+        out_at += len;
+        return HARC_AMD_OK;
+    };
     unsigned int *d_err = nullptr; RC_TRY(dalloc(c, &d_err, 4));
     HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
     for (int e = 0; e < num_thr_e; e++) {
@@ -363,7 +396,7 @@ extern "C" int harc_amd_decoder_files(const harc_amd_params *params, const char 
             nparts.v.emplace_back(keep, bytesN);
             HIP_TRY(hipMemcpyAsync(keep, ln.outN, bytesN, hipMemcpyDeviceToDevice, c->stream));
         }
-        { const double tp0 = mono_now(); if (bytesA) { RC_TRY(drain.put(ln.outA, bytesA, out_at)); out_at += bytesA; } t_put += mono_now() - tp0; }
+        { const double tp0 = mono_now(); RC_TRY(emit(ln.outA, nullptr, bytesA)); t_put += mono_now() - tp0; }
     }
     {   // singletons (decoder.cpp:148-158), then the N reads of every shard (:159-165), then input_N.dna (:166-168)
         std::vector<uint8_t> sg, sgt, nt;
@@ -372,9 +405,9 @@ extern "C" int harc_amd_decoder_files(const harc_amd_params *params, const char 
         PoolScope scope(c);
         uint32_t ns = 0; uint8_t *codes = nullptr; char *lines = nullptr;
         RC_TRY(singletons_unpack(c, view_of(sg), view_of(sgt), L, &ns, &codes, &lines));
-        if (ns) { RC_TRY(drain.put(lines, (size_t)ns * LL, out_at)); out_at += (size_t)ns * LL; }
-        for (auto &p : nparts.v) { RC_TRY(drain.put(p.first, p.second, out_at)); out_at += p.second; }
-        RC_TRY(drain.put_host(nt.data(), nt.size(), out_at)); out_at += nt.size();
+        if (ns) RC_TRY(emit(lines, nullptr, (size_t)ns * LL));
+        for (auto &p : nparts.v) RC_TRY(emit(p.first, nullptr, p.second));
+        RC_TRY(emit(nullptr, nt.data(), nt.size()));
     }
     if (out_at != total_out) { harc_set_error("decoder: %llu bytes decoded, the stream files announce %zu", (unsigned long long)out_at, total_out); return HARC_AMD_EIO; }
     unsigned int err = 0;
@@ -386,6 +419,10 @@ extern "C" int harc_amd_decoder_files(const harc_amd_params *params, const char 
     if (err) { harc_set_error("decoder: %u reads with inconsistent pos/noise streams", err); return HARC_AMD_EIO; }
     printf("Decoding done\n");                                                 // decoder.cpp:170
     return HARC_AMD_OK;
+}
+extern "C" int harc_amd_decoder_files(const harc_amd_params *params, const char *basedir, int32_t num_thr_e)
+{
+    return harc_amd_decoder_range_files(params, basedir, num_thr_e, 0, nullptr, nullptr);
 }
 
 // signature of the reads the context currently holds (2-bit clean reads + 3-bit N reads): the other side of the round-trip check
@@ -479,7 +516,7 @@ __global__ void k_merge_lines(const char *clean, const char *withN, const uint32
     out[gid] = flag[p] ? withN[(uint64_t)(rankN[p] - nlo) * LL + j] : clean[(uint64_t)(p - rankN[p] - clo) * LL + j];
 }
 
-extern "C" int harc_amd_decoder_preserve_files(const harc_amd_params *params, const char *basedir, int32_t num_thr_e)
+extern "C" int harc_amd_decoder_preserve_range_files(const harc_amd_params *params, const char *basedir, int32_t num_thr_e, int32_t n_ranges, const uint64_t *first, const uint64_t *count)
 {
     std::string od; int L = 0; CtxGuard guard;
     RC_TRY(open_archive(params, basedir, num_thr_e, &od, &L, &guard.c));
@@ -498,6 +535,8 @@ extern "C" int harc_amd_decoder_preserve_files(const harc_amd_params *params, co
     const uint64_t total64 = (uint64_t)nC + nN;
     if (total64 > 4294967290ull) { harc_set_error("more than 4294967290 reads"); return HARC_AMD_EINVAL; }
     const uint32_t total = (uint32_t)total64;
+    std::vector<LineRange> R; uint64_t lines_out = 0;
+    RC_TRY(line_ranges("decoder -p", n_ranges, first, count, total64, &R, &lines_out));
     uint32_t *d_order = nullptr, *d_ordNpe = nullptr, *d_ordN = nullptr, *flag = nullptr, *rankN = nullptr; unsigned int *d_err = nullptr;
     RC_TRY(dalloc(c, &d_order, (size_t)nC + 32)); RC_TRY(dalloc(c, &d_ordNpe, (size_t)nN + 1)); RC_TRY(dalloc(c, &d_ordN, (size_t)nN + 1)); RC_TRY(dalloc(c, &d_err, 4));
     RC_TRY(dalloc(c, &flag, (size_t)total + 1)); RC_TRY(dalloc(c, &rankN, (size_t)total + 1));
@@ -561,9 +600,10 @@ extern "C" int harc_amd_decoder_preserve_files(const harc_amd_params *params, co
         if (err) { harc_set_error("decoder -p: %u inconsistent order / stream entries", err); return HARC_AMD_EIO; }
         return HARC_AMD_OK;
     };
-    for (uint64_t p0 = 0; p0 < total || (total == 0 && p0 == 0); p0 += bin_lines) {
+    // a bin is [p0, p0 + pn) inside one range (an archive without reads: one bin without lines, for the checks)
+    for (const LineRange &rg : R) for (uint64_t p0 = rg.lo; p0 < rg.hi || (rg.hi == 0 && p0 == 0); p0 += bin_lines) {
         PoolScope bin(c);                                         // what a bin allocates goes with it
-        const uint32_t pn = (uint32_t)(total - p0 < bin_lines ? total - p0 : bin_lines);
+        const uint32_t pn = (uint32_t)(rg.hi - p0 < bin_lines ? rg.hi - p0 : bin_lines);
         uint32_t r0 = 0, r1 = 0;
         HIP_TRY(hipMemcpyAsync(&r0, rankN + p0, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(&r1, rankN + p0 + pn, 4, hipMemcpyDeviceToHost, c->stream));
@@ -613,8 +653,11 @@ extern "C" int harc_amd_decoder_preserve_files(const harc_amd_params *params, co
             HIP_TRY(hipStreamSynchronize(c->stream));
             if (fwrite(host.data(), 1, host.size(), fo) != host.size()) { harc_set_error("short write on output.dna"); return HARC_AMD_EIO; }
         }
-        if (total == 0) break;
     }
     printf("Decoding done\n");
     return HARC_AMD_OK;
+}
+extern "C" int harc_amd_decoder_preserve_files(const harc_amd_params *params, const char *basedir, int32_t num_thr_e)
+{
+    return harc_amd_decoder_preserve_range_files(params, basedir, num_thr_e, 0, nullptr, nullptr);
 }

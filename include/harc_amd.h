@@ -591,6 +591,36 @@ int harc_amd_compress_fastq_pair_files(const harc_amd_params *params, const char
 int harc_amd_fastq_assemble_pair_files(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out1_path,
                                        const char *out2_path, uint64_t records_per_file, int32_t rule, int32_t bgzf);
 
+/* ---- Range restore (./harc -d -r FIRST:LAST; README.md, "-r and what it promises").  Lines are counted from 0 in every call below.
+   A text of nbytes bytes holds as many lines as newlines.  out[0] = the newlines of the nbytes bytes at d_text (device memory, any alignment; no load leaves
+   the 16-byte-aligned hull of the text), out[1] = the byte offset at which line k starts: 0 for k = 0, else one past the k-th newline (nbytes itself when that
+   newline is the last byte), UINT64_MAX when the text holds fewer than k newlines.  One streaming read that leaves a count per workgroup, the library's scan over
+   the counts, and a second launch in which only the workgroup whose span holds the k-th newline looks for it; no atomics.  nbytes may be 0, and is at most
+   2^32 - 1 (HARC_AMD_EINVAL beyond: harc_amd_line_range_files walks a longer text in pieces).  HARC_AMD_TRACE=1: one "[linesel] device call" line on stderr. */
+int harc_amd_line_offset_device(harc_amd_ctx *ctx, const void *d_text, uint64_t nbytes, uint64_t k, uint64_t out[2]);
+/* The same over host memory, serially: what the kernels are held to (tests).  Touches no device. */
+int harc_amd_line_offset_host(const void *text, uint64_t nbytes, uint64_t k, uint64_t out[2]);
+/* out = the byte range [begin, end) of lines first_line .. first_line + n_lines - 1 of the file at path.  The file goes through the pinned ring in pieces of
+   HARC_AMD_LINESEL_PIECE bytes (default 256 MiB; tests: a few bytes), the newline count is carried from piece to piece, and nothing behind the piece that holds the
+   end of the last line is looked at.  A file with fewer lines: HARC_AMD_EINVAL naming the lines wanted and the lines found.  Only `device` is taken from params;
+   first_line = 0 and n_lines = 0 touch no device. */
+int harc_amd_line_range_files(const harc_amd_params *params, const char *path, uint64_t first_line, uint64_t n_lines, uint64_t out[2]);
+/* harc_amd_qunpack_files / harc_amd_idunpack_files for lines first_line .. first_line + n_lines - 1 alone (n_lines >= 1): the 32-byte header is read, the block
+   prefixes are walked with pread up to the last block that holds one of the lines (a prefix that leaves the file: HARC_AMD_EINVAL naming the block), only the
+   blocks that hold one of the lines are read and decoded -- every check of the block decoders stays in force for them --, the first and the last of them are
+   cut in device memory (quality: by the stride readlen + 1; ids: where harc_amd_line_offset_device finds the line), and out_path holds exactly the wanted
+   lines.  Blocks outside the range are NEITHER READ NOR CHECKED.  A range that passes the header's line count: HARC_AMD_EINVAL naming both.  One status line on
+   stdout: the blocks decoded and the bytes of packed_path that were read.  On any failure out_path is removed. */
+int harc_amd_qunpack_range_files(const harc_amd_params *params, const char *packed_path, const char *out_path, uint64_t first_line, uint64_t n_lines);
+int harc_amd_idunpack_range_files(const harc_amd_params *params, const char *packed_path, const char *out_path, uint64_t first_line, uint64_t n_lines);
+/* harc_amd_decoder_files / harc_amd_decoder_preserve_files that write only the lines of n_ranges (1 or 2) ranges [first[r], first[r] + count[r]) of what those
+   calls write, one range after the other, into output/output.dna; every count is at least 1.  With the order restored the bins of output lines run over the
+   ranges alone.  Without it every shard is still decoded (where the lines with N of a shard start is only known after decoding it) and only the parts of each
+   segment inside a range are written.  Every consistency check of the whole decode stays in force.  A range past the total: HARC_AMD_EINVAL naming the total.
+   n_ranges = 0 is the whole decode. */
+int harc_amd_decoder_range_files(const harc_amd_params *params, const char *basedir, int32_t num_thr_e, int32_t n_ranges, const uint64_t *first, const uint64_t *count);
+int harc_amd_decoder_preserve_range_files(const harc_amd_params *params, const char *basedir, int32_t num_thr_e, int32_t n_ranges, const uint64_t *first, const uint64_t *count);
+
 #ifdef __cplusplus
 }
 #endif

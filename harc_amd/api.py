@@ -204,6 +204,17 @@ def lib():
         l.harc_amd_idunpack_range_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64]
         l.harc_amd_decoder_range_files.argtypes = [PP, C.c_char_p, C.c_int32, C.c_int32, U64P, U64P]
         l.harc_amd_decoder_preserve_range_files.argtypes = [PP, C.c_char_p, C.c_int32, C.c_int32, U64P, U64P]
+    if hasattr(l, "harc_amd_recovery_make_files"):       # (HARC_AMD_LIB may name a build from before the recovery record)
+        CPP, VPP, I32P = C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)
+        l.harc_amd_block_digests_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, U64P]
+        l.harc_amd_block_digests_host.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, U64P]
+        l.harc_amd_gf_combine_device.argtypes = [ctx, C.c_uint32, C.c_int32, VPP, C.c_int32, VPP, C.c_char_p]
+        l.harc_amd_gf_combine_host.argtypes = [C.c_uint32, C.c_int32, VPP, C.c_int32, VPP, C.c_char_p]
+        l.harc_amd_recovery_make_files.argtypes = [PP, C.c_int32, CPP, C.c_uint32, C.c_char_p, U64P]
+        l.harc_amd_recovery_check_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_uint64, I32P]
+        l.harc_amd_recovery_repair_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_uint64, I32P]
+        l.harc_amd_recovery_make_host.argtypes = [C.c_int32, CPP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, U64P]
+        l.harc_amd_recovery_repair_host.argtypes = [C.c_char_p, C.c_int32, C.c_char_p, C.c_uint64, I32P]
     l.harc_amd_build_id.restype = C.c_char_p
     _lib = l
     return l
@@ -627,6 +638,73 @@ def reads_check_file(dna, device=0):
     return tuple(s), tuple(t)
 
 
+_RECOVERY_STATS = ("files", "bytes", "record_bytes", "blocks", "groups")
+
+
+def recovery_make_host(files, pct, block_bytes=0, span_blocks=0, group_blocks=0, out=None):
+    """the recovery record over the files at `files` -> `out` (default: the first file's name with .hr for its last suffix), in plain C++ on the host; 0: the
+    environment's or the default geometry.  -> the stats as a dict (include/harc_amd.h: harc_amd_recovery_make_host)"""
+    out = out or os.path.splitext(files[0])[0] + ".hr"
+    st = (C.c_uint64 * 5)()
+    _check(lib().harc_amd_recovery_make_host(len(files), _path_list(files), pct, block_bytes, span_blocks, group_blocks, os.fsencode(out), st))
+    return dict(zip(_RECOVERY_STATS, st), out=out)
+
+
+def recovery_make_files(files, pct, out=None, device=0):
+    """the same record made on the GPU, every file through the pinned ring a span at a time (include/harc_amd.h: harc_amd_recovery_make_files)"""
+    out = out or os.path.splitext(files[0])[0] + ".hr"
+    p = default_params(100, device=device)
+    st = (C.c_uint64 * 5)()
+    _check(lib().harc_amd_recovery_make_files(C.byref(p), len(files), _path_list(files), pct, os.fsencode(out), st))
+    return dict(zip(_RECOVERY_STATS, st), out=out)
+
+
+def _recovery_run(call):
+    rep, status = C.create_string_buffer(1 << 16), C.c_int32(1)
+    rc = call(rep, len(rep), C.byref(status))
+    if rc != 0:
+        raise HarcAmdError(rc, lib().harc_amd_last_error().decode(errors="replace"))
+    return status.value, rep.value.decode(errors="replace").splitlines()
+
+
+def recovery_repair_host(record, files=None, write=True):
+    """the files the record names, next to it, held against it and (write) repaired in place, on the host -> (status, report lines); status 0: every file verifies
+    in the end (write=False: nothing at all is damaged).  `files` is not needed: the record names them (include/harc_amd.h: harc_amd_recovery_repair_host)"""
+    return _recovery_run(lambda rep, cap, st: lib().harc_amd_recovery_repair_host(os.fsencode(record), 1 if write else 0, rep, cap, st))
+
+
+def recovery_check_files(record, device=0):
+    """-> (status, report lines), every digest taken on the GPU, nothing written (include/harc_amd.h: harc_amd_recovery_check_files)"""
+    p = default_params(100, device=device)
+    return _recovery_run(lambda rep, cap, st: lib().harc_amd_recovery_check_files(C.byref(p), os.fsencode(record), rep, cap, st))
+
+
+def recovery_repair_files(record, device=0):
+    """-> (status, report lines), the lost blocks rebuilt on the GPU and written in place (include/harc_amd.h: harc_amd_recovery_repair_files)"""
+    p = default_params(100, device=device)
+    return _recovery_run(lambda rep, cap, st: lib().harc_amd_recovery_repair_files(C.byref(p), os.fsencode(record), rep, cap, st))
+
+
+def block_digests_host(data, block_bytes):
+    """the digests of the blocks of `data`, the last one as short as it is (include/harc_amd.h: harc_amd_block_digests_host)"""
+    nb = (len(data) + block_bytes - 1) // block_bytes
+    out = (C.c_uint64 * max(nb, 1))()
+    if nb:
+        _check(lib().harc_amd_block_digests_host(bytes(data), nb, block_bytes, len(data) - (nb - 1) * block_bytes, out))
+    return list(out)[:nb]
+
+
+def gf_combine_host(sources, coef):
+    """out[q] = XOR_s coef[q][s] * sources[s] over GF(2^8), on the host's packed words -> list of bytes (include/harc_amd.h: harc_amd_gf_combine_host)"""
+    B, ns, e = len(sources[0]), len(sources), len(coef)
+    src = [C.create_string_buffer(bytes(s), B) for s in sources]
+    out = [C.create_string_buffer(B) for _ in range(e)]
+    sp = (C.c_void_p * ns)(*[C.addressof(b) for b in src])
+    op = (C.c_void_p * e)(*[C.addressof(b) for b in out])
+    _check(lib().harc_amd_gf_combine_host(B, ns, sp, e, op, bytes(bytearray(v for row in coef for v in row))))
+    return [b.raw for b in out]
+
+
 def pack_order(basedir, readlen=100, **kw):
     """== `pack_order.out <basedir>` (src/pack_order.cpp:11-77)"""
     p = default_params(readlen, **kw)
@@ -828,6 +906,18 @@ class HarcAmd:
         a = (C.c_uint64 * 3)(*acc)
         _check(lib().harc_amd_text_digest_device(self._ctx, C.c_void_p(ptr) if ptr else None, nbytes, first_offset, a))
         return tuple(a)
+
+    def block_digests_device(self, ptr, n_blocks, block_bytes, last_bytes=None):
+        """the digests of n_blocks blocks of block_bytes bytes at `ptr` (16-byte aligned), the last of last_bytes (include/harc_amd.h: harc_amd_block_digests_device)"""
+        out = (C.c_uint64 * max(n_blocks, 1))()
+        _check(lib().harc_amd_block_digests_device(self._ctx, C.c_void_p(ptr) if ptr else None, n_blocks, block_bytes, block_bytes if last_bytes is None else last_bytes, out))
+        return list(out)[:n_blocks]
+
+    def gf_combine_device(self, block_bytes, src_ptrs, out_ptrs, coef):
+        """out[q] = XOR_s coef[q][s] * src[s] over block_bytes bytes, blocks given as device pointers, coef as rows (include/harc_amd.h: harc_amd_gf_combine_device)"""
+        ns, e = len(src_ptrs), len(out_ptrs)
+        sp, op = (C.c_void_p * ns)(*src_ptrs), (C.c_void_p * e)(*out_ptrs)
+        _check(lib().harc_amd_gf_combine_device(self._ctx, block_bytes, ns, sp, e, op, bytes(bytearray(v for row in coef for v in row))))
 
     def line_offset_device(self, ptr, nbytes, k):
         """(newlines of the nbytes bytes at `ptr` (device memory, any alignment), the byte offset at which line k starts or LINE_NONE): line_offset_host on the GPU"""

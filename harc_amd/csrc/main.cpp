@@ -43,6 +43,11 @@
 //   harc_amd_stage decoder_range <basedir> <ignored> <num_thr_e> <first> <count> [<first> <count>]
 //                                                                          decoder that writes only those lines of its output, one range after the other (./harc -d -r)
 //   harc_amd_stage decoder_preserve_range <basedir> <ignored> <num_thr_e> <memory_gb> <first> <count> [<first> <count>]     ... and decoder_preserve (./harc -d -p -r)
+//   harc_amd_stage recovery_make <pct> <device> <out> <file> [<file> ...]  the recovery record <out> over the files, erasure-coded on the GPU (./harc -c -P <pct>); one "[recovery]" line
+//                                                                          on stdout: files, bytes protected, bytes of <out>, blocks, groups
+//   harc_amd_stage recovery_check <record> [<device>]                      the files the record names, next to it, held against it; one "[recovery]" line per file; 0 when nothing
+//                                                                          is damaged (./harc -R -n)
+//   harc_amd_stage recovery_repair <record> [<device>]                     ... and the damaged blocks rebuilt in place; 0 when every file verifies in the end (./harc -R)
 // (every <first> above counts lines from 0; ./harc -r counts from 1)
 // compressfq takes one more trailing argument, "check" (./harc -c -V): the streams are decoded once before they are written, and output/read.check is written.
 // readlen / num_thr arrive as arguments instead of the compile-time macros of src/config.h (harc:52-63).
@@ -89,6 +94,34 @@ int main(int argc, char **argv)
         if (rcm != 0) { fprintf(stderr, "harc_amd_stage id_mates failed (%d): %s\n", rcm, harc_amd_last_error()); return 1; }
         printf("%s %llu\n", harc_amd_idmate_rule_name(rule), (unsigned long long)pairs);
         return 0;
+    }
+    if (argc >= 2 && !strcmp(argv[1], "recovery_make")) {
+        char *end = nullptr;
+        const long pct = argc > 2 ? strtol(argv[2], &end, 10) : 0;
+        if (argc < 6 || !*argv[2] || *end || pct < 1 || pct > 100) { fprintf(stderr, "recovery_make needs <pct 1..100> <device> <out> <file> [<file> ...]\n"); return 2; }
+        harc_amd_params PR;
+        if (harc_amd_default_params(100, &PR) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
+        PR.device = atoi(argv[3]);
+        uint64_t st[5] = { 0, 0, 0, 0, 0 };
+        const int rcr = harc_amd_recovery_make_files(&PR, argc - 5, (const char *const *)(argv + 5), (uint32_t)pct, argv[4], st);
+        if (rcr != 0) { fprintf(stderr, "harc_amd_stage recovery_make failed (%d): %s\n", rcr, harc_amd_last_error()); return 1; }
+        printf("[recovery] %llu files, %llu bytes protected, %llu bytes of %s, %llu blocks, %llu groups\n", (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[2],
+               argv[4], (unsigned long long)st[3], (unsigned long long)st[4]);
+        return 0;
+    }
+    if (argc >= 2 && (!strcmp(argv[1], "recovery_check") || !strcmp(argv[1], "recovery_repair"))) {
+        if (argc < 3) { fprintf(stderr, "%s needs <record> [<device>]\n", argv[1]); return 2; }
+        harc_amd_params PR;
+        if (harc_amd_default_params(100, &PR) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
+        if (argc > 3) PR.device = atoi(argv[3]);
+        static char report[1 << 16];
+        int32_t status = 1;
+        report[0] = 0;
+        const int rcr = !strcmp(argv[1], "recovery_check") ? harc_amd_recovery_check_files(&PR, argv[2], report, sizeof report, &status)
+                                                           : harc_amd_recovery_repair_files(&PR, argv[2], report, sizeof report, &status);
+        fputs(report, stdout);
+        if (rcr != 0) { fprintf(stderr, "harc_amd_stage %s failed (%d): %s\n", argv[1], rcr, harc_amd_last_error()); return 1; }
+        return status ? 1 : 0;
     }
     if (argc < 4) { fprintf(stderr, "usage: %s reorder|encoder|compress|pack_order <basedir> <readlen> [num_thr] [num_chains]\n", argv[0]); return 2; }
     // RCCL between processes needs dmabuf IPC on this driver stack (hipIpcGetMemHandle fails otherwise): set before the first HIP call

@@ -621,6 +621,44 @@ int harc_amd_idunpack_range_files(const harc_amd_params *params, const char *pac
 int harc_amd_decoder_range_files(const harc_amd_params *params, const char *basedir, int32_t num_thr_e, int32_t n_ranges, const uint64_t *first, const uint64_t *count);
 int harc_amd_decoder_preserve_range_files(const harc_amd_params *params, const char *basedir, int32_t num_thr_e, int32_t n_ranges, const uint64_t *first, const uint64_t *count);
 
+/* ---- The recovery record (./harc -c -P PCT writes X.hr, ./harc -R repairs from it; README: "-P and what it promises", "The recovery record (X.hr)").  Files are cut
+   into blocks of B bytes, blocks into spans, spans into interleaved groups of at most 128 members; a group of k members gets m = min(128, max(1, ceil(k PCT / 100)))
+   recovery blocks, recovery block i = XOR_j inverse(i ^ (128 + j)) * member_j over GF(2^8) with the polynomial 0x11D (a Cauchy matrix: any e <= m lost members of a
+   group are rebuilt from any e intact recovery blocks).  harc_amd/csrc/gf_block.h holds the arithmetic, the geometry and the head of the record, once for host and device. */
+/* out[b] = the digest of block b of n_blocks blocks of block_bytes bytes that lie one behind the other at d_data (device memory, 16-byte aligned): D of the text
+   digest above with offsets counted from 0 inside the block, over block_bytes bytes, of the last block over last_bytes (1 .. block_bytes).  block_bytes: a multiple
+   of 16 from 16 to 2^24.  One launch, a workgroup per block, no atomics; out is host memory.  No load leaves the 16-byte hull of the bytes digested. */
+int harc_amd_block_digests_device(harc_amd_ctx *ctx, const void *d_data, uint64_t n_blocks, uint32_t block_bytes, uint32_t last_bytes, uint64_t *out);
+int harc_amd_block_digests_host(const void *data, uint64_t n_blocks, uint32_t block_bytes, uint32_t last_bytes, uint64_t *out);
+/* out[q] = XOR over s of coef[q * ns + s] * src[s], byte by byte over block_bytes bytes, for q < e (1 .. 128) outputs and s < ns (1 .. 256) sources.  d_src and
+   d_out are host arrays of device pointers, each 16-byte aligned and naming block_bytes bytes; an output may not overlap a source.  coef is host memory.  The one
+   kernel serves both directions: making the record (sources a group's members, coef the Cauchy rows) and repairing (sources the intact members and recovery
+   blocks, coef the solved matrix).  HARC_AMD_TRACE=1: one "[recovery] device call" line on stderr. */
+int harc_amd_gf_combine_device(harc_amd_ctx *ctx, uint32_t block_bytes, int32_t ns, const void *const *d_src, int32_t e, void *const *d_out, const uint8_t *coef);
+/* The same over host memory (any alignment), on the packed words of gf_block.h: what the kernel is held to (tests).  Touches no device. */
+int harc_amd_gf_combine_host(uint32_t block_bytes, int32_t ns, const void *const *src, int32_t e, void *const *out, const uint8_t *coef);
+/* out_path = the recovery record over the n_files files at paths (their base names are recorded and must differ), pct 1 .. 100.  Every file goes through the pinned
+   ring a span at a time: block digests, the file's D, one combine launch for the groups of the span, the recovery blocks written into the record.  The geometry is
+   HARC_AMD_RECOVERY_BLOCK (bytes, default 65536), HARC_AMD_RECOVERY_SPAN (blocks, default 8192) and HARC_AMD_RECOVERY_GROUP (blocks, default and maximum 128); it is
+   recorded in the file.  The record's bytes do not depend on HARC_AMD_FEED_SLICE or HARC_AMD_FEED_THREADS.  stats (may be NULL): files, bytes protected, bytes of
+   the record, data blocks, groups.  On any failure out_path is removed.  Only `device` is taken from params. */
+int harc_amd_recovery_make_files(const harc_amd_params *params, int32_t n_files, const char *const *paths, uint32_t pct, const char *out_path, uint64_t *stats);
+/* The files that the record at record_path names, looked for in the record's own directory, held against it: every block of every file and every recovery block
+   is digested on the GPU and compared on the host.  check writes nothing; repair rebuilds the lost blocks of every group that holds at least as many intact recovery
+   blocks (each rebuilt block is digested and compared with its recorded digest before a byte is written; then the file is synced and its D compared), extends a
+   file that is shorter than recorded and creates one that is missing.  A file with a group that cannot be solved is not touched; the other files still are.
+   report (may be NULL) receives the lines "[recovery] <name> ok | repaired: x of nb blocks | damaged: x of nb blocks, recoverable | NOT recoverable: span s group g
+   has lost e of k blocks and holds x recovery blocks", one per file, in front of them what is wrong with the record itself, cut to report_capacity.
+   *status = 0 when every file verifies in the end (check: when nothing at all is damaged, the record included), else 1.  A record whose two head copies both fail,
+   a head whose counts do not give the record's size, a name with a '/', a file longer than recorded: HARC_AMD_EINVAL, and nothing is written.  No record:
+   HARC_AMD_EIO. */
+int harc_amd_recovery_check_files(const harc_amd_params *params, const char *record_path, char *report, uint64_t report_capacity, int32_t *status);
+int harc_amd_recovery_repair_files(const harc_amd_params *params, const char *record_path, char *report, uint64_t report_capacity, int32_t *status);
+/* The same two jobs in plain C++ on the host, through the functions of gf_block.h: they touch no device, and they are what the kernels and the file calls are held
+   to (tests).  block_bytes, span_blocks, group_blocks: 0 = the environment's or the default.  write = 0: check, else repair. */
+int harc_amd_recovery_make_host(int32_t n_files, const char *const *paths, uint32_t pct, uint32_t block_bytes, uint32_t span_blocks, uint32_t group_blocks, const char *out_path, uint64_t *stats);
+int harc_amd_recovery_repair_host(const char *record_path, int32_t write, char *report, uint64_t report_capacity, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

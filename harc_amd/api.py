@@ -174,6 +174,8 @@ def lib():
     if hasattr(l, "harc_amd_selftest_contigs"):          # (HARC_AMD_LIB may name a build from before it)
         l.harc_amd_selftest_contigs.argtypes = [ctx, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
+    if hasattr(l, "harc_amd_selftest_probe_prefix"):     # (as above)
+        l.harc_amd_selftest_probe_prefix.argtypes = [PP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     U3 = C.POINTER(C.c_uint64)
     l.harc_amd_text_digest_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_uint64, U3]
     l.harc_amd_text_digest_host.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, U3]
@@ -233,6 +235,14 @@ def default_params(readlen, num_thr=8, num_chains=0, device=0, profile=0, num_st
     p.stream_digest = stream_digest
     p.table_slots_per_read = table_slots_per_read      # 0: the library chooses (4, 3 or 2 by free memory); include/harc_amd.h
     return p
+
+
+def probe_prefix(params):
+    """(nprobe, nreg) of the probe table these parameters make: the probes of one chain step, and how many leading shifts hold all four of
+    them in the canonical order (host code: harc_amd_selftest_probe_prefix)"""
+    n, r = C.c_int32(0), C.c_int32(0)
+    _check(lib().harc_amd_selftest_probe_prefix(C.byref(params), C.byref(n), C.byref(r)))
+    return n.value, r.value
 
 
 def build_id():

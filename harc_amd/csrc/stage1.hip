@@ -64,6 +64,7 @@ struct S1Args {
     int weedmin;                     // wave-uniform scan: single-read bins a batch must find before their claim bits are looked up ahead of the tests (HARC_AMD_WEEDMIN)
     int lazy;                        // bit 0: steps that agree with the consensus everywhere take the rows from their read and leave the counts to cons_flush (HARC_AMD_LAZY=0: every step applies its counts; same bytes)
                                      // bit 1 (with bit 0 only): such a step hands the bins its batch found behind the hit to the next step (k_steps' CARRY; HARC_AMD_CARRY=0: no; same bytes)
+                                     // bits 8..15 (with bit 1 only): nreg = probe_prefix(), the leading shifts j whose four probes are probes 4 j + 2 dir + dict of a step (in this word: the kernel holds it in a register anyway)
     uint4 *cstat_coop;               // ... the cooperative kernel's own (k_chain_counts adds both up and keeps its share apart: bench.py prices the two kernels against different ceilings)
     uint2 *csteps;                   // per chain: steps walked by the launches of the main kernel (x) and of the cooperative kernel (y), kept or not
     uint4 *cstat;                    // per chain statistics: x slots inspected, y candidates tested, z sequential-equivalent key lookups, w sequential-equivalent candidates
@@ -1428,7 +1429,11 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
     // -- eleven of twelve slots a step looks at -- is the next step's answer.  The step leaves {read or first id of the bin, count word} of every lane
     // in LDS (the stash; count word 0 = looked up, nothing there; HARC_NONE = not known), the next one takes the probes it can map from there, in
     // front of its first batch, and tests their candidates with the same loop; keys, scrambles, minimizers, bitmap and slot search are for the rest.
-    // Everything about it lives in LDS: 2 dwords x 64 lanes and one meta dword (base << 8 | fj; HARC_NONE = nothing carried) per wave, behind the
+    // The stash is written in the NEXT step's numbering: the lane that holds old probe `po` (shift j) stores its pair at entry pn, the index of the probe
+    // with shift j - fj, same direction and dictionary -- po - 4 fj while j lies in the regular prefix of the probe table (probe_prefix(): nearly always),
+    // the (dir, dictionary, shift) -> probe map otherwise -- when 0 <= pn < 64; the 64 entries are cleared to "not known" first.  The reader is one LDS
+    // read of its own entry: no map, no base, no fj on its side.
+    // Everything about it lives in LDS: 2 dwords x 64 lanes and one meta dword (0 = a stash was left; HARC_NONE = nothing carried) per wave, behind the
     // wave's table of its own reads (one base address for both).
     // (HARC_SEQ_OWNT: the stash lives behind the wave's table of its own reads and the carried pass asks that table -- a variant without the table has no carry)
     constexpr bool CARRY = SEQ && SPEC && !COOP && !QUAD && W >= 4 && HARC_SEQ_OWNT;
@@ -1714,7 +1719,7 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
             { int w0 = bi <= 0 ? ((HARC_W0_MUL * (lastp >> 4) + HARC_W0_ADD + 15) & ~15) : 64; const int wmax = (QUAD || SPEC) ? 64 : (bi <= 1 ? s.firstmax : 64); if (w0 > wmax) w0 = wmax; bend = base + w0; }
             if (bend > s.nprobe) bend = s.nprobe;
             if (bend <= base) bend = s.nprobe;
-            const int p = base + lane; if constexpr (!CARRY) dbg_batches++;
+            int p = base + lane; if constexpr (!CARRY) dbg_batches++;
             uint32_t mine = HARC_NONE; int j = 0, dir = 0, l = 0, myhd = 0;
             uint32_t pix = 0;                                             // SEQ: the probe's descriptor word -- shift, direction and dictionary are taken from it again below (one register, not three, across the scans)
             uint32_t ncb = 0;                                             // candidates this lane tests in this batch
@@ -1722,23 +1727,17 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
             uint2 b_lt = make_uint2(0, 0);                               // COOP: its row of largetab, fetched by the lane that found it (all bins of the batch in ONE round trip)
             bool cand = false; uint32_t c_sst = 0, c_cw = 0, c_piy = 0; uint64_t c_slot = 0;     // SEQ (see "ONE AFTER THE OTHER" below): the small bin this lane's probe found
             uint32_t mrd[NW];                                             // !SEQ: only the lane that wins has loaded them, and only it reads them
+            bool look = true;                                             // CARRY: a turn that looks probes up (all but a carried pass with something to test)
             if (CARRY && bi < 0) {
-                // the carried pass: lane p' asks the map for the probe q of the step before that had shift j' + fj in the same direction and dictionary;
-                // it is known when q was a lane of that batch whose lookup came to an end.  Only the probes in front of the first one that is not known
-                // take part (the sequential order: everything in front of a carried candidate has been looked up); the batches go on from there
-                const uint32_t cm = (uint32_t)__builtin_amdgcn_readfirstlane((int)*cmeta);
+                // the carried pass: lane p' reads entry p' of the stash, which the step before wrote in this step's numbering (the lane that held the probe
+                // with shift j' + fj in the same direction and dictionary); it is known when that lane's lookup came to an end.  Only the probes in front
+                // of the first one that is not known take part (the sequential order: everything in front of a carried candidate has been looked up); the
+                // batches go on from there
                 bool known = false;
                 int ln = lane; asm volatile("" : "+v"(ln));
-                if (ln < s.nprobe) {
-                    const uint2 pi = s_pinfo[ln];
-                    const uint32_t jn = (pi.x >> 16) + (cm & 0xFFu);
-                    if (jn < (uint32_t)s.maxmatch) {
-                        const uint32_t qb = reinterpret_cast<const uint16_t *>(s_pinfo + s.nprobe)[((pi.x >> 13) & 3u) * (uint32_t)s.maxmatch + jn], q = qb - (cm >> 8);
-                        if (qb != 0xFFFFu && q < 64u) {
-                            const uint2 e = stash[q];
-                            if (e.y != HARC_NONE) { known = true; pix = pi.x; c_piy = pi.y; c_sst = e.x; c_cw = e.y; cand = e.y != 0u; }
-                        }
-                    }
+                if (ln < s.nprobe) {                                      // (descriptor and entry: two reads by lane number, one trip)
+                    const uint2 pi = s_pinfo[ln], e = stash[ln];
+                    if (e.y != HARC_NONE) { known = true; pix = pi.x; c_piy = pi.y; c_sst = e.x; c_cw = e.y; cand = e.y != 0u; }
                 }
                 const unsigned long long unk = ~__ballot(known);
                 bend = unk ? __ffsll((long long)unk) - 1 : 64;
@@ -1746,8 +1745,19 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                 // the chain's own reads: the one just taken sits in the shift-0 bins of both dictionaries
                 if (cand && (c_cw & SLOT_EMB) && own_has(ownt, c_sst)) { cand = false; c_cw = 0u; }
                 if (lane == 0) *cmeta = HARC_NONE;                        // consumed
-            } else
-            if (p < bend && (SPEC || cap)) {                             // (SPEC: there is a bitmap, so there are reads and a table)
+                // Nothing carried is left to test (the rule: what sits in front of the winner is the chain's own reads, weeded just now) and probes are left:
+                // the step's first batch starts at P* in THIS turn -- the same probes, width and counts as the turn of its own it used to get, without a
+                // second round through the candidate loop's set-up, the large-bin block and the exit tests.  (What the carried lanes knew is "nothing
+                // there"; a batch from P* never stashed it either.)  With a carried candidate the order stays: test it first (one trip), look up on a miss
+                look = false;
+                if (bend < s.nprobe && !__ballot(cand)) {
+                    int w0 = (HARC_W0_MUL * (lastp >> 4) + HARC_W0_ADD + 15) & ~15;
+                    base = bend; bend = base + (w0 > 64 ? 64 : w0);
+                    if (bend > s.nprobe) bend = s.nprobe;
+                    p = base + lane; c_cw = 0u; bi = 0; look = true;
+                }
+            }
+            if ((!CARRY || look) && p < bend && (SPEC || cap)) {         // (SPEC: there is a bitmap, so there are reads and a table)
                 const uint2 pi = s_pinfo[p];
                 pix = pi.x;
                 j = (int)(pi.x >> 16); dir = (int)((pi.x >> 13) & 1);
@@ -2046,9 +2056,19 @@ template <int W, bool QUAD, bool COOP, int NWV = 4, bool SEQ = false, bool SPEC 
                     // lanes at and behind the first large bin, and those behind the end of the batch.  A bin weeded above is as empty to the next step
                     // as to this one (the claim bitmap is frozen for the launch, the chain's own reads only get more)
                     if ((lazy & 2) && fhd == 0) {
+                        // ... at the entry of the probe that looks at the same k-mer in the next step: shift j - fj, same direction and dictionary
                         int ln = lane; asm volatile("" : "+v"(ln));           // (the address is made here, not kept in a register across the loops)
-                        stash[ln] = make_uint2(c_sst, c_cw);                  // (c_cw: 0 in a lane that found nothing, HARC_NONE where nothing is known)
-                        if (lane == 0) *cmeta = ((uint32_t)base << 8) | (uint32_t)fj;
+                        stash[ln].y = HARC_NONE;                              // what nobody writes is not known (one wave: LDS takes its stores in order)
+                        if (c_cw != HARC_NONE) {                              // (c_cw: 0 in a lane that found nothing; a lane with HARC_NONE has no descriptor either)
+                            const uint32_t jo = pix >> 16;
+                            uint32_t pn = (uint32_t)(base + ln - 4 * fj);     // inside the regular prefix (a negative one is no entry)
+                            if (jo >= ((uint32_t)lazy >> 8)) {                // behind it: ask the map (0xFFFF = the next step has no such probe)
+                                pn = 0xFFFFu;
+                                if (jo >= (uint32_t)fj) pn = reinterpret_cast<const uint16_t *>(s_pinfo + s.nprobe)[((pix >> 13) & 3u) * (uint32_t)s.maxmatch + jo - (uint32_t)fj];
+                            }
+                            if (pn < 64u) stash[pn] = make_uint2(c_sst, c_cw);
+                        }
+                        if (lane == 0) *cmeta = 0u;
                     }
                     bi++;
                 }
@@ -3012,6 +3032,25 @@ static std::vector<uint16_t> make_probe_table(const harc_amd_params &P)
     return t;
 }
 
+// The regular prefix of a probe table: how many leading shifts j have all four probes, in the canonical order -- probe 4 j + 2 dir + dict is
+// (shift j, dir, dict) for every j below the result.  There the probe that looks at the same k-mer one step later (shift j - fj) is probe p - 4 fj:
+// what k_steps' CARRY writes its stash by without asking the map.  Computed from the table itself, not from the parameters that made it.
+static int probe_prefix(const std::vector<uint16_t> &t)
+{
+    int n = 0;
+    for (; (size_t)4 * n + 3 < t.size(); n++)
+        for (int k = 0; k < 4; k++) if (t[(size_t)4 * n + k] != (uint16_t)(n | ((k >> 1) << 8) | ((k & 1) << 9))) return n;
+    return n;
+}
+
+extern "C" int harc_amd_selftest_probe_prefix(const harc_amd_params *p, int32_t *nprobe, int32_t *nreg)
+{
+    if (!p || !nprobe || !nreg || p->maxmatch < 0 || p->maxmatch > 255) { harc_set_error("harc_amd_selftest_probe_prefix: bad arguments"); return HARC_AMD_EINVAL; }
+    const std::vector<uint16_t> t = make_probe_table(*p);
+    *nprobe = (int32_t)t.size(); *nreg = probe_prefix(t);
+    return HARC_AMD_OK;
+}
+
 static uint32_t auto_chains(uint32_t N, int reads_per_chain)
 {
     // one chain per ~2048 reads keeps chains sparse on the genome (every chain costs about one extra contig);
@@ -3298,7 +3337,7 @@ template <int W> static int stage1_run_w(harc_amd_ctx *c)
     a.weedmin = getenv("HARC_AMD_WEEDMIN") ? atoi(getenv("HARC_AMD_WEEDMIN")) : 3;
     a.lazy = getenv("HARC_AMD_LAZY") ? (atoi(getenv("HARC_AMD_LAZY")) != 0 ? 1 : 0) : 1;
     // the carry of the dense SPEC kernel (bit 1 of the same word): the shift travels in a byte, the probe map holds 16-bit indices
-    if (a.lazy && !(getenv("HARC_AMD_CARRY") && atoi(getenv("HARC_AMD_CARRY")) == 0) && a.nprobe < 0xFFFF && P.maxmatch <= 255) a.lazy |= 2;
+    if (a.lazy && !(getenv("HARC_AMD_CARRY") && atoi(getenv("HARC_AMD_CARRY")) == 0) && a.nprobe < 0xFFFF && P.maxmatch <= 255) a.lazy |= 2 | (probe_prefix(tab) << 8);      // (at most maxmatch shifts: a byte)
     a.firstmax = (bloom_nwin[0] > 0 && bloom_nwin[1] > 0) ? 64 : 48;     // lines by minimizer: speculative probes share their lines
     if (const char *e = getenv("HARC_AMD_FIRSTMAX")) { const int x = atoi(e); a.firstmax = x < 1 ? 1 : x > 64 ? 64 : x; }
     // successor lists (k_succ): by default where the walk is ONE wave (exact mode, num_chains = 1) -- there the precomputation, twice the lookups of a

@@ -309,6 +309,10 @@ int harc_amd_selftest_index(harc_amd_ctx *ctx, const uint64_t *keys, uint64_t n,
  * shard start and the passes that cut contigs ran.  Nothing stays allocated. */
 int harc_amd_selftest_contigs(harc_amd_ctx *ctx, const uint8_t *flag, const uint8_t *pos, uint64_t n, int32_t readlen, uint32_t q, uint32_t cut, uint8_t *head, uint32_t *cid,
                               uint64_t *gstart, uint32_t *chead, uint32_t *ncontigs, uint64_t *total, int32_t *fellback);
+/* Self-test of the probe table's regular prefix (host code, no device): *nprobe = the probes of one chain step for these parameters (reorder.cpp:517-649:
+ * shift by shift, forward then reverse, dictionary 0 then 1, a probe left out where its k-mer leaves the read), *nreg = how many leading shifts hold all
+ * four of them in that order -- below it probe 4 j + 2 dir + dict is (shift j, dir, dict), which the dense chain kernel's carry relies on.  maxmatch <= 255. */
+int harc_amd_selftest_probe_prefix(const harc_amd_params *p, int32_t *nprobe, int32_t *nreg);
 
 /* Where the wall time of this process's last harc_amd_compress_fastq_files_ex went, in seconds (the end-to-end leg of bench.py; preprocess.cpp:81-121 + harc:50-69):
  * out[0] context + device pool, [1] ingest (file -> HBM -> packed stores; reads, uploads and kernels overlapped), [2] of it the calling thread waiting for

@@ -894,6 +894,11 @@ class HarcAmd:
     def reorder(self):
         _check(lib().harc_amd_reorder(self._ctx))
 
+    def set_stage1_streams(self, temp_dna, flag, pos, order, rc, temp_dna_singleton, order_singleton):
+        """a stage-I result from outside (the seven files of reorder.cpp:722-830 as bytes): encode() then runs on it"""
+        n_main, n_sing = len(order) // 4, len(order_singleton) // 4
+        _check(lib().harc_amd_set_stage1_streams(self._ctx, temp_dna, flag, pos, order, rc, n_main, temp_dna_singleton, order_singleton, n_sing))
+
     def encode(self):
         _check(lib().harc_amd_encode(self._ctx))
 

@@ -161,11 +161,16 @@ static int check_params(const harc_amd_params *p)
     if (p->num_thr < 1 || p->num_thr > 4096) { harc_set_error("num_thr %d out of range", p->num_thr); return HARC_AMD_EINVAL; }
     if (p->num_chains < 0) { harc_set_error("num_chains < 0"); return HARC_AMD_EINVAL; }
     if (p->num_steps < 0 || p->num_steps > 64) { harc_set_error("num_steps %d out of range 0..64", p->num_steps); return HARC_AMD_EINVAL; }
-    if (p->maxmatch < 0 || p->maxmatch > 128 || p->maxmatch > L) { harc_set_error("maxmatch out of range"); return HARC_AMD_EINVAL; }
-    if (p->maxsearch < 1 || p->thresh < 0 || p->thresh_s < 0) { harc_set_error("thresholds out of range"); return HARC_AMD_EINVAL; }
+    if (p->maxmatch < 0 || p->maxmatch > 128 || p->maxmatch > L) { harc_set_error("maxmatch %d out of range 0..min(128, readlen = %d)", p->maxmatch, L); return HARC_AMD_EINVAL; }
+    if (p->maxsearch < 1) { harc_set_error("maxsearch %d out of range (at least 1)", p->maxsearch); return HARC_AMD_EINVAL; }
+    if (p->thresh < 0) { harc_set_error("thresh %d out of range (at least 0)", p->thresh); return HARC_AMD_EINVAL; }
+    if (p->thresh_s < 0) { harc_set_error("thresh_s %d out of range (at least 0)", p->thresh_s); return HARC_AMD_EINVAL; }
     for (int l = 0; l < 2; l++) {
         const int n = p->dict_end[l] - p->dict_start[l] + 1;
-        if (p->dict_start[l] < 0 || p->dict_end[l] >= L || n < 0 || n > 32) { harc_set_error("dictionary window %d out of range", l); return HARC_AMD_EINVAL; }
+        if (p->dict_start[l] < 0) { harc_set_error("dict_start[%d] = %d out of range 0..readlen - 1", l, p->dict_start[l]); return HARC_AMD_EINVAL; }
+        if (p->dict_end[l] >= L) { harc_set_error("dict_end[%d] = %d out of range 0..readlen - 1 = %d", l, p->dict_end[l], L - 1); return HARC_AMD_EINVAL; }
+        // (a window of no bases has no meaning in the reference: its key would be the same for every read)
+        if (n < 1 || n > 32) { harc_set_error("dictionary window %d (dict_start .. dict_end = %d .. %d) holds %d bases: 1..32", l, p->dict_start[l], p->dict_end[l], n); return HARC_AMD_EINVAL; }
     }
     return HARC_AMD_OK;
 }

@@ -110,6 +110,8 @@ static inline int side_context(const harc_amd_params *params, int L, harc_amd_ct
     if (harc_amd_default_params(L, &P) != HARC_AMD_OK) return HARC_AMD_EINVAL;
     P.device = params->device;
     if (num_thr) P.num_thr = num_thr;
+    // side files of fewer than 4 bases a line: harc:57-60 gives windows of no bases there, which harc_amd_create refuses.  No stage runs on this context
+    for (int l = 0; l < 2; l++) if (P.dict_end[l] < P.dict_start[l]) P.dict_end[l] = P.dict_start[l];
     return harc_amd_create(&P, c);
 }
 // The context's ONE pinned ring in `parts` disjoint parts of `slices_each` slices, out[0 .. parts), for movers that are alive at the same time; the host threads are

@@ -50,12 +50,14 @@ typedef struct harc_amd_params {
     int32_t num_chains;       /* K concurrent chains of stage I.  1 reproduces the reference at num_thr=1 byte for byte.
                                  0 = auto (throughput mode).  The reference's own num_thr>1 is a race (reorder.cpp:545-552);
                                  K>1 here is the deterministic round-synchronous schedule documented in DESIGN.md. */
-    int32_t maxmatch;         /* `maxmatch` = readlen/2 */
-    int32_t thresh;           /* `thresh` = 4 */
-    int32_t thresh_s;         /* `thresh_s` = 24 */
-    int32_t maxsearch;        /* `maxsearch` = 1000 */
+    int32_t maxmatch;         /* `maxmatch` = readlen/2; accepted: 0 .. min(128, readlen) */
+    int32_t thresh;           /* `thresh` = 4; accepted: >= 0 */
+    int32_t thresh_s;         /* `thresh_s` = 24; accepted: >= 0 */
+    int32_t maxsearch;        /* `maxsearch` = 1000; accepted: >= 1 */
     int32_t dict_start[2];    /* `dict1_start`,`dict2_start` */
-    int32_t dict_end[2];      /* `dict1_end`,`dict2_end` */
+    int32_t dict_end[2];      /* `dict1_end`,`dict2_end`: each window 1 .. 32 bases inside the read, anywhere, in any order, overlapping or not.  A window of no
+                                 bases (dict_end = dict_start - 1) is refused with HARC_AMD_EINVAL: it has no meaning in the reference.  (harc:57-60 gives such
+                                 windows below 4 bases: harc_amd_default_params fills them in, harc_amd_create refuses them.) */
     int32_t device;           /* HIP device ordinal */
     int32_t profile;          /* 1: time every launch of the dominant kernel with HIP events on the context's stream */
     int32_t num_steps;        /* S: speculative chain steps per launch of the chain kernel (1..64; 0 = auto: 16; 64 for one chain; 32 from

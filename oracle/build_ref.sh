@@ -9,6 +9,8 @@
 #   oracle/build_ref.sh L T        -> reorder_L<L>_t<T>.out, encoder_L<L>_t<T>.out
 #   oracle/build_ref.sh quality L     -> reorder_quality_L<L>.out (-q without -p, harc:121-124)
 #   oracle/build_ref.sh preserve L E  -> decoder_preserve_L<L>_e<E>.out (the -p decoder, harc:173-178; num_thr 1)
+#   oracle/build_ref.sh params TAG L MAXMATCH THRESH THRESH_S MAXSEARCH D1S D1E D2S D2E
+#                                  -> reorder_<TAG>.out, encoder_<TAG>.out with these macros in config.h, num_thr 1
 set -e
 REF=${HARC_REFERENCE:-/root/reference}
 HERE="$(cd "$(dirname "$0")" && pwd)"
@@ -39,6 +41,23 @@ if [ "$1" = preserve ]; then
   mkdir -p "$CFG"
   { echo "#define readlen $L"; echo "#define MAX_BIN_SIZE 7"; echo "#define num_thr 1"; echo "#define num_thr_e $E"; } > "$CFG/config.h"   # harc:174-177
   [ -x "$OUT/decoder_preserve_L${L}_e${E}.out" ] || g++ "$REF/src/decoder_preserve.cpp" -I"$CFG" $CXXFLAGS -o "$OUT/decoder_preserve_L${L}_e${E}.out"
+  exit 0
+fi
+if [ "$1" = params ]; then
+  # the ten macros of harc:52-63 from arguments (numdict stays 2), num_thr 1: the reference under another config.h than the driver writes
+  [ $# -eq 11 ] || { echo "usage: $0 params TAG L MAXMATCH THRESH THRESH_S MAXSEARCH DICT1_START DICT1_END DICT2_START DICT2_END"; exit 2; }
+  TAG=$2
+  CFG="$OUT/cfgx_${TAG}"
+  mkdir -p "$CFG"
+  { echo "#define maxmatch $4"; echo "#define thresh $5"; echo "#define thresh_s $6"; echo "#define numdict 2"
+    echo "#define maxsearch $7"
+    echo "#define dict1_start $8"; echo "#define dict1_end $9"
+    echo "#define dict2_start ${10}"; echo "#define dict2_end ${11}"
+    echo "#define readlen $3"; echo "#define num_thr 1"; } > "$CFG/config.h.new"
+  # another parameter set under an old tag: the binaries are stale
+  if ! cmp -s "$CFG/config.h.new" "$CFG/config.h"; then mv "$CFG/config.h.new" "$CFG/config.h"; rm -f "$OUT/reorder_${TAG}.out" "$OUT/encoder_${TAG}.out"; else rm -f "$CFG/config.h.new"; fi
+  [ -x "$OUT/reorder_${TAG}.out" ] || g++ "$REF/src/reorder.cpp" -I"$CFG" $CXXFLAGS -lpthread -o "$OUT/reorder_${TAG}.out"
+  [ -x "$OUT/encoder_${TAG}.out" ] || g++ "$REF/src/encoder.cpp" -I"$CFG" $CXXFLAGS -lpthread -o "$OUT/encoder_${TAG}.out"
   exit 0
 fi
 L=$1; T=$2

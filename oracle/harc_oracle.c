@@ -6,7 +6,8 @@
  *
  * PARITY PIN: harc_oracle_reorder / harc_oracle_encoder / harc_oracle_pack_order with K=1, E=1 are checked
  * byte-for-byte against tests/golden/*.tar.xz, which were produced by the real reference compiled from
- * /root/reference by oracle/build_ref.sh and run at num_thr=1 (oracle/make_goldens.py).
+ * /root/reference by oracle/build_ref.sh and run at num_thr=1 (oracle/make_goldens.py).  The _ex entry points take the macros of the reference's
+ * config.h (harc:52-63) as a struct; tests/golden/p_*.tar.xz pin them to the reference compiled with the same values (make_goldens.py PCASES).
  *
  * What is restated (file:line are into /root/reference):
  *   stage I   src/reorder.cpp: 2-bit read store :184-209, dictionary :277-432 (BBHash src/BooPHF.h replaced by an
@@ -60,6 +61,29 @@ static void params_init(params_t *p, int L)
     if (L > 100) { p->ds[0] = h - 32; p->de[0] = h - 1; p->ds[1] = h; p->de[1] = h - 1 + 32; }
     else { p->ds[0] = h - L * 32 / 100; p->de[0] = h - 1; p->ds[1] = h; p->de[1] = h - 1 + L * 32 / 100; }
     for (int l = 0; l < 2; l++) p->kbits[l] = 2 * (p->de[l] - p->ds[l] + 1);
+}
+
+/* the same quantities from outside: what the reference takes from the config.h it regenerates for every run (harc:52-63), here as arguments of the
+ * _ex entry points.  Stage II reads thresh_s and maxsearch only; its two windows are fixed by encoder.cpp:132-145. */
+typedef struct { int32_t L, maxmatch, thresh, thresh_s, maxsearch, ds[2], de[2]; } harc_oracle_params;
+
+static int params_from(params_t *p, const harc_oracle_params *x)
+{
+    if (!x || x->L < 1 || x->L > MAXL) return -2;
+    if (x->maxmatch < 0 || x->maxmatch > x->L || x->maxsearch < 1 || x->thresh < 0 || x->thresh_s < 0) return -2;
+    p->L = x->L; p->W = (2 * x->L + 63) / 64;
+    p->maxmatch = x->maxmatch; p->thresh = x->thresh; p->thresh_s = x->thresh_s; p->maxsearch = x->maxsearch;
+    for (int l = 0; l < 2; l++) {
+        const int n = x->de[l] - x->ds[l] + 1;
+        if (x->ds[l] < 0 || x->de[l] >= x->L || n < 0 || n > 32) return -2;      /* n = 0: what params_init gives below 4 bases */
+        p->ds[l] = x->ds[l]; p->de[l] = x->de[l]; p->kbits[l] = 2 * n;
+    }
+    return 0;
+}
+static void params_to(harc_oracle_params *x, const params_t *p)
+{
+    x->L = p->L; x->maxmatch = p->maxmatch; x->thresh = p->thresh; x->thresh_s = p->thresh_s; x->maxsearch = p->maxsearch;
+    for (int l = 0; l < 2; l++) { x->ds[l] = p->ds[l]; x->de[l] = p->de[l]; }
 }
 
 /* ------------------------------------------------------------------ 2-bit read store (reorder.cpp:184-209) */
@@ -517,10 +541,10 @@ static void bput(bytes *b, const void *src, size_t n)
 static void bputc(bytes *b, char c) { bput(b, &c, 1); }
 
 /* ------------------------------------------------------------------ stage I, file contract of reorder.out <basedir> */
-int harc_oracle_reorder(const char *basedir, int L, uint32_t K, uint32_t S, uint32_t *unmatched_out, uint64_t *stats4)
+int harc_oracle_reorder_ex(const char *basedir, const harc_oracle_params *px, uint32_t K, uint32_t S, uint32_t *unmatched_out, uint64_t *stats4)
 {
-    if (L < 1 || L > MAXL) return -2;
-    params_t p; params_init(&p, L);
+    params_t p; if (params_from(&p, px)) return -2;
+    const int L = p.L;
     size_t n; uint8_t *nb = slurp(basedir, "numreads.bin", &n);
     if (n < 4) { free(nb); return -1; }
     uint32_t N; memcpy(&N, nb, 4); free(nb);
@@ -545,11 +569,20 @@ int harc_oracle_reorder(const char *basedir, int L, uint32_t K, uint32_t S, uint
     return 0;
 }
 
-/* in-memory stage I for timing (cpu_baseline "port"): reads = N*L ASCII, no separators */
-int harc_oracle_stage1_mem(const char *ascii, uint32_t N, int L, uint32_t K, uint32_t nsteps, uint32_t *order, uint8_t *flag, uint8_t *pos,
-                           uint8_t *rc, uint32_t *M, uint32_t *order_s, uint32_t *S, uint32_t *unmatched, uint64_t *stats4)
+int harc_oracle_reorder(const char *basedir, int L, uint32_t K, uint32_t S, uint32_t *unmatched_out, uint64_t *stats4)
 {
+    if (L < 1 || L > MAXL) return -2;
     params_t p; params_init(&p, L);
+    harc_oracle_params x; params_to(&x, &p);
+    return harc_oracle_reorder_ex(basedir, &x, K, S, unmatched_out, stats4);
+}
+
+/* in-memory stage I for timing (cpu_baseline "port"): reads = N*L ASCII, no separators */
+int harc_oracle_stage1_mem_ex(const char *ascii, uint32_t N, const harc_oracle_params *px, uint32_t K, uint32_t nsteps, uint32_t *order, uint8_t *flag, uint8_t *pos,
+                              uint8_t *rc, uint32_t *M, uint32_t *order_s, uint32_t *S, uint32_t *unmatched, uint64_t *stats4)
+{
+    params_t p; if (params_from(&p, px)) return -2;
+    const int L = p.L;
     uint64_t *reads = calloc((size_t)N * p.W + 1, 8);
     for (uint32_t i = 0; i < N; i++) pack_read(ascii + (size_t)i * L, L, p.W, reads + (size_t)i * p.W);
     stage1_out_t o; stage1_run(reads, N, &p, K, nsteps, &o);
@@ -562,6 +595,15 @@ int harc_oracle_stage1_mem(const char *ascii, uint32_t N, int L, uint32_t K, uin
     if (stats4) { stats4[0] = o.rounds; stats4[1] = o.probes; stats4[2] = o.cands; stats4[3] = o.conflicts; }
     free(reads); stage1_free(&o);
     return 0;
+}
+
+int harc_oracle_stage1_mem(const char *ascii, uint32_t N, int L, uint32_t K, uint32_t nsteps, uint32_t *order, uint8_t *flag, uint8_t *pos,
+                           uint8_t *rc, uint32_t *M, uint32_t *order_s, uint32_t *S, uint32_t *unmatched, uint64_t *stats4)
+{
+    if (L < 1 || L > MAXL) return -2;
+    params_t p; params_init(&p, L);
+    harc_oracle_params x; params_to(&x, &p);
+    return harc_oracle_stage1_mem_ex(ascii, N, &x, K, nsteps, order, flag, pos, rc, M, order_s, S, unmatched, stats4);
 }
 
 /* ------------------------------------------------------------------ stage II (encoder.cpp) */
@@ -712,9 +754,10 @@ static void packbits_rev(const bytes *txt, bytes *bin, bytes *tail)       /* enc
 }
 
 /* file contract of encoder.out <basedir>; E = num_thr */
-int harc_oracle_encoder(const char *basedir, int L, uint32_t E, uint32_t *matched_s_out, uint32_t *matched_N_out)
+int harc_oracle_encoder_ex(const char *basedir, const harc_oracle_params *px, uint32_t E, uint32_t *matched_s_out, uint32_t *matched_N_out)
 {
-    if (L < 1 || L > MAXL || E == 0) return -2;
+    params_t p; if (params_from(&p, px) || E == 0) return -2;
+    const int L = p.L;
     size_t n_dna, n_flag, n_pos, n_order, n_rc, n_sing, n_os, n_N;
     uint8_t *dna = slurp(basedir, "temp.dna", &n_dna), *flag = slurp(basedir, "tempflag.txt", &n_flag),
             *pos = slurp(basedir, "temppos.txt", &n_pos), *ord = slurp(basedir, "read_order.bin", &n_order),
@@ -750,7 +793,7 @@ int harc_oracle_encoder(const char *basedir, int L, uint32_t E, uint32_t *matche
             if (flag[i] == '0' || c.n > 10000000) {                   /* encoder.cpp:226 */
                 if (c.n) {
                     size_t reflen; char *ref = buildcontig(&c, L, &reflen);
-                    if (T) realign(&c, ref, reflen, L, dict, ds, de, rd, order_s, claimed, 24, 1000);
+                    if (T) realign(&c, ref, reflen, L, dict, ds, de, rd, order_s, claimed, p.thresh_s, p.maxsearch);
                     writecontig(ref, &c, L, &so);
                     for (size_t k = 0; k < c.n; k++) if (c.v[k].owned) free((void *)c.v[k].read);
                     free(ref); c.n = 0;
@@ -795,6 +838,14 @@ int harc_oracle_encoder(const char *basedir, int L, uint32_t E, uint32_t *matche
     free(claimed); dict_free(&dict[0]); dict_free(&dict[1]); free(rd); free(order_s);
     free(dna); free(flag); free(pos); free(ord); free(rc); free(sing); free(os); free(Ntxt);
     return 0;
+}
+
+int harc_oracle_encoder(const char *basedir, int L, uint32_t E, uint32_t *matched_s_out, uint32_t *matched_N_out)
+{
+    if (L < 1 || L > MAXL || E == 0) return -2;
+    params_t p; params_init(&p, L);
+    harc_oracle_params x; params_to(&x, &p);
+    return harc_oracle_encoder_ex(basedir, &x, E, matched_s_out, matched_N_out);
 }
 
 /* ------------------------------------------------------------------ pack_order.cpp:20-77 */

@@ -27,7 +27,7 @@ def revcomp(s):
     return "".join(COMP[c] for c in reversed(s))
 
 
-def gen_reads(seed, n, L, genome_len, err=0.0, rc=True, repeat=0, dup=0, n_frac=0.25):
+def gen_reads(seed, n, L, genome_len, err=0.0, rc=True, repeat=0, dup=0, n_frac=0.25, noisy=0):
     """i.i.d. genome (optionally with one `repeat`-bp segment copied elsewhere), uniform read starts,
     per-base substitution probability `err` of which n_frac become 'N' (gen_fastq_noRC.cpp:67-71 spirit),
     odd reads reverse-complemented, `dup` extra identical copies of read 0."""
@@ -53,6 +53,16 @@ def gen_reads(seed, n, L, genome_len, err=0.0, rc=True, repeat=0, dup=0, n_frac=
         reads.append(r)
     for _ in range(dup):
         reads.insert(rs.randint(0, len(reads)), reads[0])
+    # `noisy` more reads with one N and 30 substitutions behind base 42 (stage II's windows are bases 0..41, encoder.cpp:132-145): about 40 bits of the
+    # 3-bit store from their place in the genome -- refused by thresh_s = 24, taken by 60
+    for _ in range(noisy):
+        p = rs.randint(0, genome_len - L)
+        r = list(genome[p:p + L])
+        cols = 42 + rs.permutation(L - 42)[:31]
+        for j in cols[:30]:
+            r[j] = "ACGT"[("ACGT".index(r[j]) + rs.randint(1, 4)) % 4]
+        r[cols[30]] = "N"
+        reads.insert(rs.randint(0, len(reads)), "".join(r))
     return reads
 
 
@@ -140,6 +150,24 @@ CASES = {
 }
 
 
+# The reference built with ANOTHER config.h than its driver writes (build_ref.sh params): (generator kwargs, overridden fields).  Every input has
+# substitutions, reads with N and reverse complements; each is chosen so that the overridden value decides bytes (tests/test_oracle_golden.py checks
+# that the oracle with default parameters gives other files).
+_PER_START = dict(custom="per_start", L=100, n_start=150, per=(4, 5, 6, 7, 8, 9, 10), big=(60, 50, 40, 40), err=0.006)
+PCASES = {
+    "p_L100_ms3": (dict(_PER_START, seed=101), dict(maxsearch=3)),
+    "p_L100_ms16": (dict(_PER_START, seed=101), dict(maxsearch=16)),
+    "p_L100_t0_ts1": (dict(seed=103, n=1500, L=100, genome_len=8000, err=0.01), dict(thresh=0, thresh_s=1)),
+    "p_L150_t130_ts60": (dict(seed=104, n=1000, L=150, genome_len=9000, err=0.02, n_frac=0.5, noisy=200), dict(thresh=130, thresh_s=60)),
+    "p_L100_mm0": (dict(seed=105, n=300, L=100, genome_len=1500, err=0.01), dict(maxmatch=0)),
+    # (low coverage: with the driver's windows maxmatch = 100 adds one shift to the 50 of L / 2, the first window's forward probe at shift 50 -- reorder.cpp:520)
+    "p_L100_mm100": (dict(seed=106, n=1500, L=100, genome_len=60000, err=0.01), dict(maxmatch=100)),
+    "p_L100_mm100_dict_ends": (dict(seed=109, n=1500, L=100, genome_len=60000, err=0.01), dict(maxmatch=100, dict_start=[0, 68], dict_end=[31, 99])),
+    "p_L150_dict_narrow_apart": (dict(seed=107, n=1000, L=150, genome_len=9000, err=0.01), dict(dict_start=[17, 90], dict_end=[32, 109])),
+    "p_L100_dict_swapped_ends": (dict(seed=108, n=1500, L=100, genome_len=8000, err=0.01), dict(dict_start=[68, 0], dict_end=[99, 31])),
+}
+
+
 def run(cmd, cwd):
     r = subprocess.run(cmd, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode not in (0,):
@@ -157,11 +185,26 @@ def snapshot(outdir):
     return d
 
 
-def make_case(name, kw):
+def make_case(name, kw, overrides=None):
+    """overrides (PCASES): the parameter fields that differ from what harc:52-60 derives from L; the reference is then built with that config.h"""
     L = kw["L"]
     subprocess.check_call([os.path.join(HERE, "build_ref.sh")])
-    subprocess.check_call([os.path.join(HERE, "build_ref.sh"), str(L), "1"])
-    if kw.get("custom") == "bigbin_stage2":
+    params = None
+    if overrides is None:
+        subprocess.check_call([os.path.join(HERE, "build_ref.sh"), str(L), "1"])
+        tag = f"L{L}_t1"
+    else:
+        sys.path.insert(0, os.path.dirname(HERE))
+        from tests import oracle_lib as ol
+        params = ol.params_dict(L, overrides)
+        tag = name
+        subprocess.check_call([os.path.join(HERE, "build_ref.sh"), "params", tag, str(L)] + [str(params[k]) for k in ("maxmatch", "thresh", "thresh_s", "maxsearch")]
+                              + [str(params["dict_start"][0]), str(params["dict_end"][0]), str(params["dict_start"][1]), str(params["dict_end"][1])])
+    if kw.get("custom") == "per_start":
+        sys.path.insert(0, os.path.dirname(HERE))
+        from tests import gen as tgen
+        reads = tgen.lines_of(tgen.reads_array_per_start(**{k: v for k, v in kw.items() if k != "custom"})).decode().split()
+    elif kw.get("custom") == "bigbin_stage2":
         sys.path.insert(0, os.path.dirname(HERE))
         from tests import gen as tgen
         reads = tgen.reads_text_bigbin_stage2(kw["seed"]).decode().split()
@@ -179,9 +222,9 @@ def make_case(name, kw):
             for i, r in enumerate(reads):
                 f.write(f"@T.{i}\n{r}\n+\n{'H' * L}\n")
         log = run([os.path.join(REF, "preprocess.out"), fq, wd, "False", "False", str(L)], wd)
-        log += run([os.path.join(REF, f"reorder_L{L}_t1.out"), wd], wd)   # cwd=wd: BBHash temp files land in CWD
+        log += run([os.path.join(REF, f"reorder_{tag}.out"), wd], wd)   # cwd=wd: BBHash temp files land in CWD
         stage1 = snapshot(os.path.join(wd, "output"))
-        log += run([os.path.join(REF, f"encoder_L{L}_t1.out"), wd], wd)
+        log += run([os.path.join(REF, f"encoder_{tag}.out"), wd], wd)
         stage2 = snapshot(os.path.join(wd, "output"))
         # -p path: pack_order on a copy of read_order.bin (harc:112)
         pd = tempfile.mkdtemp(prefix="harc_gold_p_")
@@ -198,6 +241,9 @@ def make_case(name, kw):
             decoded = fh.read()
         assert sorted(decoded.decode().split()) == sorted(reads), "reference round trip failed?!"
         meta = dict(name=name, L=L, n_reads=len(reads), gen=kw, log=log.splitlines())
+        if params is not None:
+            meta["params"] = params
+            meta["overrides"] = overrides
         os.makedirs(GOLD, exist_ok=True)
         tarpath = os.path.join(GOLD, name + ".tar.xz")
         with tarfile.open(tarpath, "w:xz", preset=9) as tf:
@@ -334,9 +380,11 @@ def make_md5case(name, kw):
 
 
 if __name__ == "__main__":
-    names = sys.argv[1:] or (list(CASES) + list(QCASES) + list(MD5CASES))
+    names = sys.argv[1:] or (list(CASES) + list(PCASES) + list(QCASES) + list(MD5CASES))
     for n in names:
-        if n in MD5CASES:
+        if n in PCASES:
+            make_case(n, *PCASES[n])
+        elif n in MD5CASES:
             make_md5case(n, MD5CASES[n])
         elif n in QCASES:
             make_qcase(n, QCASES[n])

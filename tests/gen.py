@@ -188,6 +188,44 @@ def reads_text_hugebin_families(seed, L, n_core=10400, n_norm=6000, genome_len=6
     return lines_of(r)
 
 
+def reads_array_per_start(seed, L, n_start, per=(4, 5, 6, 7, 8, 9, 10), big=(), windows=None, heavy=0.5, nheavy=8, step=9, err=0.01, n_frac=0.25, rc_share=0.3):
+    """several reads per start position, for scans that must stop inside a bin: n_start starts `step` bases apart on an i.i.d. genome, the i-th with
+    per[rs] reads (big[i] for the first len(big) starts).  A `heavy` share of the reads carries nheavy substitutions in columns outside the dictionary
+    windows (`windows`: [(first, last), ...] in read coordinates, and outside their mirror images, so that this also holds for the reads that are
+    reverse-complemented): they sit in their start's bin in both dictionaries and fail every Hamming test of a small threshold, so how far a scan
+    goes into the bin decides what it finds.  Then substitutions at rate err (a share n_frac of them N), an rc_share of the reads reverse-complemented,
+    all of it permuted.  -> [n, L] uint8"""
+    rs = np.random.RandomState(seed)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    genome = acgt[rs.randint(0, 4, size=n_start * step + L)]
+    cnt = rs.choice(np.asarray(per), size=n_start)
+    cnt[:len(big)] = big
+    starts = np.repeat(np.arange(n_start) * step, cnt)
+    n = starts.shape[0]
+    r = genome[starts[:, None] + np.arange(L)[None, :]].copy()
+    if windows is None:
+        w = 32 if L > 100 else L * 32 // 100                          # harc:57-60
+        windows = [(L // 2 - w, L // 2 - 1), (L // 2, L // 2 - 1 + w)]
+    free = np.ones(L, dtype=bool)
+    for a, b in windows:
+        free[a:b + 1] = False
+        free[L - 1 - b:L - a] = False
+    free = np.nonzero(free)[0]
+    k = min(nheavy, free.size)
+    for i in np.nonzero(rs.random_sample(n) < heavy)[0]:
+        cols = rs.choice(free, size=k, replace=False)
+        r[i, cols] = acgt[(np.searchsorted(acgt, r[i, cols]) + rs.randint(1, 4, size=k)) % 4]
+    if err > 0:
+        e = rs.random_sample((n, L)) < err
+        isN = e & (rs.random_sample((n, L)) < n_frac)
+        sub = e & ~isN
+        r[sub] = acgt[(np.searchsorted(acgt, r[sub]) + rs.randint(1, 4, size=int(sub.sum()))) % 4]
+        r[isN] = ord("N")
+    rev = rs.random_sample(n) < rc_share
+    r[rev] = _COMP[r[rev][:, ::-1]]
+    return r[rs.permutation(n)]
+
+
 def auto_chains(n_clean, reads_per_chain=2048, clean=None):
     """auto_chains() of harc_amd/csrc/stage1.hip: K when harc_amd_params.num_chains = 0.  clean: the clean reads ([n, L] uint8 array or
     the lines of input_clean.dna) for the low-coverage rule of stage1_run_w -- more than 98 % distinct first-dictionary k-mers: up to

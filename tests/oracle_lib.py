@@ -12,6 +12,46 @@ GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 _lib = None
 
 
+class OracleParams(C.Structure):
+    """harc_oracle_params of oracle/harc_oracle.c: the macros of the reference's config.h (harc:52-63) as arguments of the _ex entry points"""
+    _fields_ = [("L", C.c_int32), ("maxmatch", C.c_int32), ("thresh", C.c_int32), ("thresh_s", C.c_int32), ("maxsearch", C.c_int32),
+                ("ds", C.c_int32 * 2), ("de", C.c_int32 * 2)]
+
+
+PARAM_FIELDS = ("maxmatch", "thresh", "thresh_s", "maxsearch", "dict_start", "dict_end")
+
+
+def params_dict(L, overrides=None):
+    """the six parameter fields as harc:52-60 derives them from the read length, then `overrides` ({field: value}; dict_start / dict_end: a pair)"""
+    h = L // 2
+    w = 32 if L > 100 else L * 32 // 100
+    d = dict(maxmatch=L // 2, thresh=4, thresh_s=24, maxsearch=1000, dict_start=[h - w, h], dict_end=[h - 1, h - 1 + w])
+    for k, v in (overrides or {}).items():
+        if k not in PARAM_FIELDS:
+            raise KeyError(f"{k} is not a parameter field ({PARAM_FIELDS})")
+        d[k] = [int(x) for x in v] if k.startswith("dict_") else int(v)
+    return d
+
+
+def oracle_params(L, overrides=None):
+    d = params_dict(L, overrides)
+    return OracleParams(L, d["maxmatch"], d["thresh"], d["thresh_s"], d["maxsearch"], (C.c_int32 * 2)(*d["dict_start"]), (C.c_int32 * 2)(*d["dict_end"]))
+
+
+def both_params(L, overrides=None, **kw):
+    """-> (OracleParams, harc_amd.Params) from ONE dict of overrides: the two sides of a comparison cannot disagree about the case.
+    kw: the schedule fields of harc_amd.default_params (num_thr, num_chains, num_steps, ...)"""
+    import harc_amd
+    d = params_dict(L, overrides)
+    p = harc_amd.default_params(L, **kw)
+    for k in PARAM_FIELDS:
+        if k.startswith("dict_"):
+            getattr(p, k)[0], getattr(p, k)[1] = d[k]
+        else:
+            setattr(p, k, d[k])
+    return oracle_params(L, overrides), p
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -29,12 +69,21 @@ def load():
     lib.harc_oracle_preprocess.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_char_p]
     lib.harc_oracle_quality.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_char_p]
     lib.harc_oracle_stage1_mem.argtypes = [C.c_char_p, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u32p, u32p, u32p, u64p]
+    pp = C.POINTER(OracleParams)
+    lib.harc_oracle_reorder_ex.argtypes = [C.c_char_p, pp, C.c_uint32, C.c_uint32, u32p, u64p]
+    lib.harc_oracle_encoder_ex.argtypes = [C.c_char_p, pp, C.c_uint32, u32p, u32p]
+    lib.harc_oracle_stage1_mem_ex.argtypes = [C.c_char_p, C.c_uint32, pp, C.c_uint32, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u32p, u32p, u32p, u64p]
     _lib = lib
     return lib
 
 
 def golden_cases():
-    return sorted(f[:-7] for f in os.listdir(GOLDEN_DIR) if f.endswith(".tar.xz") and not f.startswith("q_"))
+    return sorted(f[:-7] for f in os.listdir(GOLDEN_DIR) if f.endswith(".tar.xz") and not f.startswith(("q_", "p_")))
+
+
+def param_cases():
+    """fixtures of the reference built with another config.h than the driver writes (oracle/make_goldens.py PCASES): meta.json carries `params`"""
+    return sorted(f[:-7] for f in os.listdir(GOLDEN_DIR) if f.endswith(".tar.xz") and f.startswith("p_"))
 
 
 def quality_cases():

@@ -86,3 +86,66 @@ def test_harc_driver_usage_without_gpu(tmp_path):
     fq.write_bytes(b"@a\n" + b"A" * 300 + b"\n+\n" + b"H" * 300 + b"\n")
     r = subprocess.run([os.path.join(root, "harc"), "-c", str(fq)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 1 and "Maximum read length exceeded" in r.stdout
+
+
+def _refused(p):
+    """harc_amd_create's answer to a parameter set it must refuse: the message.  check_params runs before the device is asked for, so the refusal is
+    HARC_AMD_EINVAL (-1) with or without a GPU (where it accepts, a machine without one answers HARC_AMD_ENODEVICE, -2)"""
+    import harc_amd
+    with pytest.raises(harc_amd.HarcAmdError) as e:
+        harc_amd.HarcAmd(p).close()
+    assert e.value.code == -1, str(e.value)
+    return str(e.value)
+
+
+@pytest.mark.parametrize("L,field,value", [(100, "maxmatch", -1), (100, "maxmatch", 129), (150, "maxmatch", 129), (100, "maxmatch", 101), (40, "maxmatch", 41),
+                                           (100, "maxsearch", 0), (100, "maxsearch", -5), (100, "thresh", -1), (100, "thresh_s", -1)])
+def test_create_refuses_scalar_parameters_out_of_range(L, field, value):
+    import harc_amd
+    p = harc_amd.default_params(L)
+    setattr(p, field, value)
+    msg = _refused(p)
+    assert field + " " in msg and str(value) in msg
+    if field == "thresh":
+        assert "thresh_s" not in msg
+
+
+@pytest.mark.parametrize("l", [0, 1])
+@pytest.mark.parametrize("what,start,end", [("dict_end", 70, 100), ("dict_start", -1, 20), ("window", 10, 42), ("window", 50, 49), ("window", 50, 30)])
+def test_create_refuses_dictionary_windows_out_of_range(l, what, start, end):
+    """dict_end = L, dict_start = -1, a window of 33 bases, and a window of no bases (dict_end = dict_start - 1: no meaning in the reference) or fewer"""
+    import harc_amd
+    L = 100
+    p = harc_amd.default_params(L)
+    p.dict_start[l], p.dict_end[l] = start, end
+    msg = _refused(p)
+    assert (f"{what}[{l}]" if what != "window" else f"dictionary window {l}") in msg
+
+
+@pytest.mark.parametrize("L,field,value", [(100, "maxmatch", 0), (100, "maxmatch", 100), (150, "maxmatch", 128), (100, "maxsearch", 1), (255, "thresh", 300),
+                                           (100, "thresh", 0), (100, "thresh_s", 0)])
+def test_create_accepts_the_edges_of_the_ranges(L, field, value):
+    """the other side of every edge: not refused as a parameter (without a device the answer is 'no device', never 'invalid')"""
+    import torch
+    import harc_amd
+    p = harc_amd.default_params(L)
+    setattr(p, field, value)
+    if torch.cuda.is_available():
+        harc_amd.HarcAmd(p).close()
+    else:
+        with pytest.raises(harc_amd.HarcAmdError) as e:
+            harc_amd.HarcAmd(p)
+        assert e.value.code == -2
+
+
+def test_windows_of_one_base_at_both_ends_are_accepted():
+    import torch
+    import harc_amd
+    p = harc_amd.default_params(100)
+    p.dict_start[0], p.dict_end[0], p.dict_start[1], p.dict_end[1] = 0, 0, 99, 99
+    if torch.cuda.is_available():
+        harc_amd.HarcAmd(p).close()
+    else:
+        with pytest.raises(harc_amd.HarcAmdError) as e:
+            harc_amd.HarcAmd(p)
+        assert e.value.code == -2

@@ -69,6 +69,83 @@ def test_pack_order_and_decoder(case, oracle, tmp_path):
         assert oracle.harc_oracle_pack_order(base.encode()) == -3
 
 
+# ------------------------------------------------------------------------------------------------ other parameters than the driver's
+# tests/golden/p_*.tar.xz: the reference compiled with another config.h (oracle/build_ref.sh params, oracle/make_goldens.py PCASES), run at -t 1.
+# The oracle takes the same values through its _ex entry points; K = 1, E = 1 as above.
+PCASES = ol.param_cases()
+
+
+def _pcase(case):
+    import json
+    g = ol.load_golden(case)
+    meta = json.loads(g["meta.json"])
+    return g, meta, meta["L"], ol.oracle_params(meta["L"], meta["overrides"])
+
+
+def test_param_fixtures_are_those_of_make_goldens():
+    assert len(PCASES) == 9 and not set(PCASES) & set(CASES)
+    for case in PCASES:
+        g, meta, L, op = _pcase(case)
+        assert meta["params"] == ol.params_dict(L, meta["overrides"]) and meta["params"] != ol.params_dict(L)
+        reads = g["reads.txt"].split()
+        assert any(b"N" in r for r in reads)
+        if meta["params"]["maxmatch"] > 0:                              # (with maxmatch = 0 no read is ever placed behind another one)
+            assert b"r" in g["stage1/read_rev.txt"] and b"1" in g["stage1/tempflag.txt"]     # reads matched as reverse complements
+
+
+@pytest.mark.parametrize("S", [1, 16])
+@pytest.mark.parametrize("case", PCASES)
+def test_param_stage1_K1_bit_exact(case, S, oracle, tmp_path):
+    g, meta, L, op = _pcase(case)
+    base = ol.stage_dir(tmp_path, {k: g["stage1/" + k] for k in ["input_clean.dna", "numreads.bin"]})
+    unmatched = C.c_uint32(0)
+    assert oracle.harc_oracle_reorder_ex(base.encode(), C.byref(op), 1, S, C.byref(unmatched), None) == 0
+    got = ol.read_dir(base)
+    for f in ol.STAGE1_FILES:
+        assert got[f] == g["stage1/" + f], f"{case}: {f} differs from reference"
+    assert unmatched.value == [int(l.split()[2]) for l in meta["log"] if l.startswith("Reordering done")][0]
+
+
+@pytest.mark.parametrize("case", PCASES)
+def test_param_stage2_E1_bit_exact(case, oracle, tmp_path):
+    g, meta, L, op = _pcase(case)
+    base = ol.stage_dir(tmp_path, {k[len("stage1/"):]: v for k, v in g.items() if k.startswith("stage1/")})
+    ms, mn = C.c_uint32(0), C.c_uint32(0)
+    assert oracle.harc_oracle_encoder_ex(base.encode(), C.byref(op), 1, C.byref(ms), C.byref(mn)) == 0
+    got = ol.read_dir(base)
+    for f in ol.stage2_files(1):
+        assert got[f] == g["stage2/" + f], f"{case}: {f} differs from reference"
+    assert ms.value == [int(l.split()[0]) for l in meta["log"] if "singleton reads were aligned" in l][0]
+    assert mn.value == [int(l.split()[0]) for l in meta["log"] if "reads with N were aligned" in l][0]
+
+
+@pytest.mark.parametrize("case", PCASES)
+def test_param_values_decide_bytes(case, oracle, tmp_path):
+    """the fixture pins something: with the driver's own parameters the oracle writes OTHER stage-I files on the same input (other stage-II files too
+    where thresh_s is overridden, on the fixture's own stage-I files)"""
+    g, meta, L, op = _pcase(case)
+    base = ol.stage_dir(tmp_path, {k[len("stage1/"):]: v for k, v in g.items() if k.startswith("stage1/")})
+    if "thresh_s" in meta["overrides"]:
+        assert oracle.harc_oracle_encoder(base.encode(), L, 1, None, None) == 0
+        got = ol.read_dir(base)
+        assert any(got[f] != g["stage2/" + f] for f in ol.stage2_files(1))
+    assert oracle.harc_oracle_reorder(base.encode(), L, 1, 16, None, None) == 0
+    got = ol.read_dir(base)
+    assert any(got[f] != g["stage1/" + f] for f in ol.STAGE1_FILES)
+
+
+@pytest.mark.parametrize("case", PCASES)
+def test_param_pack_order_and_decoder(case, oracle, tmp_path):
+    g, meta, L, op = _pcase(case)
+    base = ol.stage_dir(tmp_path, {k[len("stage2/"):]: v for k, v in g.items() if k.startswith("stage2/")})
+    assert oracle.harc_oracle_decoder(base.encode(), 1) == 0
+    assert ol.read_dir(base)["output.dna"] == g["decoded.txt"]
+    assert oracle.harc_oracle_pack_order(base.encode()) == 0
+    got = ol.read_dir(base)
+    assert got["read_order.bin"] == g["packed/read_order.bin"]
+    assert got["read_order.bin.tail"] == g["packed/read_order.bin.tail"]
+
+
 @pytest.mark.parametrize("case", ol.quality_cases())
 def test_quality_and_ids_match_reference(case, oracle, tmp_path):
     """-q: oracle restatement of preprocess.cpp:61-118 + reorder_quality.cpp == the reference's output.quality / output.id,

@@ -223,7 +223,7 @@ void harc_drop_results(harc_amd_ctx *c)
 {
     harc_pool_release(c, 0);                                     // every per-run buffer lives in the pool
     c->d_order = nullptr; c->d_flag = c->d_pos = c->d_rc = nullptr; c->d_order_s = nullptr; c->d_oreads = nullptr; c->d_sreads = nullptr;
-    c->have_s1 = c->have_s2 = c->s1_from_files = false; c->M = c->S = 0;
+    c->have_s1 = c->have_s2 = c->s1_from_files = c->oreads_whole = c->s2_gather = false; c->M = c->S = 0;
     c->d_s2_order = c->d_s2_orderN = nullptr; c->n_s2_order = c->n_s2_orderN = 0;
     // results go; what came with the inputs (HARC_AMD_IN_ORDER_N, owned bytes) stays until the inputs are replaced
     for (auto it = c->out.begin(); it != c->out.end();) { if (it->first.first < HARC_AMD_IN_ORDER_N) it = c->out.erase(it); else ++it; }
@@ -344,7 +344,7 @@ extern "C" int harc_amd_set_stage1_streams(harc_amd_ctx *c, const char *temp_dna
         HIP_TRY(hipStreamSynchronize(c->stream)); harc_raw_free(c, d);
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->have_s1 = true; c->s1_from_files = true;
+    c->have_s1 = true; c->s1_from_files = true; c->oreads_whole = true;
     c->C.n_main = M; c->C.n_singleton = S;
     return HARC_AMD_OK;
 }
@@ -416,7 +416,20 @@ extern "C" int harc_amd_encode(harc_amd_ctx *c)
         const uint64_t a0 = (uint64_t)c->s2_e0 * q, a1 = (uint64_t)c->s2_e1 * q;
         oi0 = (uint32_t)(a0 > c->M ? c->M : a0); oi1 = (uint32_t)((uint32_t)c->s2_e1 >= E || a1 > c->M ? c->M : a1);
     }
-    if (!c->s1_from_files) RC_TRY(stage1_make_oriented(c, oi0, oi1));
+    // the oriented reads (temp.dna in HBM).  Where they are not there yet (they are after stage I from files, after HARC_AMD_S1_DNA and after an
+    // earlier encode) the tiles of k_consensus gather them from d_reads and leave them in d_oreads on the way; HARC_AMD_S2_GATHER=0: a pass of
+    // k_orient in front of stage II, which then streams them back in (tests; A/B inside one build)
+    const bool gather_on = getenv("HARC_AMD_S2_GATHER") ? atoi(getenv("HARC_AMD_S2_GATHER")) != 0 : true;
+    c->s2_gather = false;
+    if (!c->oreads_whole) {
+        if (gather_on) {
+            if (!c->d_oreads) RC_TRY(dalloc(c, &c->d_oreads, (size_t)c->M * c->W + 1));      // where stage1_make_oriented allocates it: the peak does not move
+            c->s2_gather = true;
+        } else {
+            RC_TRY(stage1_make_oriented(c, oi0, oi1));
+            if (oi0 == 0 && oi1 >= c->M) c->oreads_whole = true;
+        }
+    }
     RC_TRY(stage2_run(c));
     c->C.encode_ms = now_ms() - t0;
     c->C.total_ms += c->C.encode_ms;
@@ -453,7 +466,8 @@ extern "C" int harc_amd_get_stream(harc_amd_ctx *c, int32_t id, int32_t shard, c
             case HARC_AMD_S1_RC: RC_TRY(harc_d2h(c, b, c->d_rc, c->M)); break;
             case HARC_AMD_S1_ORDER_SINGLETON: RC_TRY(harc_d2h(c, b, c->d_order_s, (size_t)c->S * 4)); break;
             case HARC_AMD_S1_DNA: {
-                if (!c->d_oreads) { RC_TRY(stage1_make_oriented(c)); made_oriented = true; }
+                // (an encode partitioned over the ranks, or one that launched no tile, leaves d_oreads allocated and not whole)
+                if (!c->oreads_whole) { RC_TRY(stage1_make_oriented(c)); c->oreads_whole = true; made_oriented = true; }
                 const harc_mark_t mk = harc_pool_mark(c);
                 char *d = nullptr; RC_TRY(dalloc(c, &d, (size_t)c->M * (L + 1) + 1));
                 RC_TRY(s1_unpack_to_ascii(c, c->d_oreads, c->M, d));

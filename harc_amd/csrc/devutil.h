@@ -178,6 +178,16 @@ template <int W> __device__ __forceinline__ void rc_words(const uint64_t (&a)[W]
         o[w] = (~v) & lowmask_word(2 * L, w);
     }
 }
+// word w of rc_words' result for a read whose W words lie in memory (LDS): the same reversal, shift and mask, from the two words it draws on -- for
+// a lane that wants one word and has no registers for the 3 W words rc_words holds
+template <int W> __device__ __forceinline__ uint64_t rc_word_at(const uint64_t *a, int L, int w)
+{
+    const int s = 64 * W - 2 * L;
+    const int ws = s >> 6, bs = s & 63, j = w + ws;               // r[j] = rev2(a[W - 1 - j]), 0 from W on (sel0)
+    const uint64_t lo = j < W ? rev2(a[W - 1 - j]) : 0, hi = j + 1 < W ? rev2(a[W - 2 - j]) : 0;
+    const uint64_t v = bs ? ((lo >> bs) | (hi << (64 - bs))) : lo;
+    return (~v) & lowmask_word(2 * L, w);
+}
 // spread the low 32 bits of a to the even bit positions
 __device__ __forceinline__ uint64_t spread32(uint64_t a)
 {

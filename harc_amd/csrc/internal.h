@@ -122,6 +122,8 @@ struct harc_amd_ctx {
     uint32_t *d_order = nullptr; uint8_t *d_flag = nullptr, *d_pos = nullptr, *d_rc = nullptr; uint32_t *d_order_s = nullptr;
     // stage-II inputs, device
     uint64_t *d_oreads = nullptr;          // M x W oriented reads (= temp.dna)
+    bool oreads_whole = false;             // d_oreads holds all M reads (stage I from files, stage1_make_oriented over all reads, or a stage II whose tiles gathered every read)
+    bool s2_gather = false;                // this encode: k_consensus stages its reads from d_reads through order / rc and writes d_oreads (harc_amd_encode decides)
     uint64_t *d_sreads = nullptr;          // S x W singleton reads (= temp.dna.singleton), only when set from files
     bool s1_from_files = false;
     bool have_s2 = false;

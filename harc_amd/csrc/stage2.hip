@@ -24,6 +24,8 @@ struct S2Args {
     uint32_t M, S, T, q, nC;
     uint64_t total;                    // total consensus columns
     const uint64_t *oreads;            // M x W oriented reads
+    const uint64_t *reads;             // the clean reads as stage I holds them, and d_oreads to write: k_consensus<NPL, W> gathers read order[i], reverse-
+    uint64_t *oreads_out;              // complemented where rc[i] == 'r', and the tile a read starts in leaves its words in oreads_out (else: null)
     const uint8_t *flag, *pos, *rc;
     const uint32_t *order;
     const uint64_t *cand3;             // T x W3 : singletons then N reads, 3-bit
@@ -207,16 +209,84 @@ __global__ void k_consensus_tiles(S2Args s, uint32_t ntiles, uint32_t *tlo, uint
     thi[t] = (uint32_t)ub_le(s.gstart, (long long)s.M, X1 - 1);             // last read starting inside or before the tile (every column is covered: >= 0)
     tlo[t] = X0 >= (uint64_t)s.L ? (uint32_t)(ub_le(s.gstart, (long long)s.M, X0 - (uint64_t)s.L) + 1) : 0u;   // first read that reaches column X0
 }
+// The gathering form of a piece's staging (round 14): reads base .. base + nch - 1 of the reordered list are fetched from the clean reads as stage I
+// holds them -- read order[i], reverse-complemented where rc[i] == 'r', exactly what k_orient (stage1.hip) writes -- instead of being streamed back in
+// from d_oreads behind a k_orient launch that does nothing but wait for its gather.  The request has k_orient's shape: the W words of a read are loaded
+// by W neighbouring lanes, one request to one sector (48.5 G/s against 26.3 for a lane that loads its read alone), 64 / W reads a wave, the spare lanes
+// of W = 3, 5, 6, 7 idle.  gstart, order and rc of the piece do not depend on each other and are asked for together, B passes of the workgroup at a time
+// (CGBATCH = 4 at W = 1, 2, 4: half a piece of 256 reads at W = 4; 2 elsewhere, where more would spill), the reads behind them: two dependent trips a
+// batch.  The words go to LDS as they arrive.  Behind a barrier a lane of a reversed read takes the two words its own word draws on from there
+// (rc_word_at, one word of rc_words: k_orient shuffles all W words to every lane, and beside the counter planes there are no registers for that) and
+// turns the read in place; the tile a read STARTS in (start >= X0; it is <= the tile's last column by thi) leaves the read's words in d_oreads, 64 / W
+// reads a wave in one contiguous store.  Every read has one writer, a read across a tile's edge is gathered by both tiles, and no tile reads d_oreads
+// (k_noise and HARC_AMD_S1_DNA do, behind this kernel).
+#ifndef CGBATCH
+#define CGBATCH 4
+#endif
+template <int W, int B> __device__ __forceinline__ void consensus_gather(const S2Args &s, const long long base, const int nch, const uint64_t X0, uint64_t *cl_words, int *cl_g)
+{
+    constexpr int RPW = 64 / W, RPP = (CTHREADS / 64) * RPW;      // reads a wave, reads a pass of the workgroup
+    constexpr int NPASS = (CCHUNK + RPP - 1) / RPP;
+    static_assert(NPASS <= 32 && CCHUNK <= 2 * CTHREADS, "a bit a pass in revmask; two starts a thread");
+    int tid = (int)threadIdx.x;
+    asm volatile("" : "+v"(tid));                                 // what hangs on the lane is worked out here, piece by piece: hoisted out of the tile's loop over
+                                                                  // its pieces (nearly always one) it sat in registers through the counting, and the kernel spilled
+    const int lane = tid & 63, rl = lane / W, w = lane % W;
+    const int kk0 = (tid >> 6) * RPW + rl;
+    const bool lane_on = rl < RPW;
+    const int k0 = tid, k1 = k0 + CTHREADS;
+    unsigned long long g0 = 0, g1 = 0;
+    if (k0 < nch) g0 = s.gstart[base + k0];
+    if (k1 < nch) g1 = s.gstart[base + k1];
+    uint32_t revmask = 0;                                         // bit p: the lane's read of pass p is reverse-complemented
+    for (int p0 = 0; p0 < NPASS && p0 * RPP < nch; p0 += B) {
+        uint32_t rid[B]; uint8_t rv[B]; uint64_t mine[B];
+#pragma unroll
+        for (int p = 0; p < B; p++) {
+            const int kk = kk0 + (p0 + p) * RPP;
+            rid[p] = 0; rv[p] = 0;
+            if (lane_on && kk < nch) { rid[p] = s.order[base + kk]; rv[p] = s.rc[base + kk]; }
+        }
+        if (p0 == 0) {                                            // (the starts are here with the first batch's order and rc)
+            if (k0 < nch) cl_g[k0] = (int)((long long)g0 - (long long)X0);
+            if (k1 < nch) cl_g[k1] = (int)((long long)g1 - (long long)X0);
+        }
+#pragma unroll
+        for (int p = 0; p < B; p++) revmask |= (rv[p] == 'r' ? 1u : 0u) << (p0 + p);
+#pragma unroll
+        for (int p = 0; p < B; p++) {
+            const int kk = kk0 + (p0 + p) * RPP;
+            mine[p] = 0;
+            if (lane_on && kk < nch) mine[p] = s.reads[(size_t)rid[p] * W + w];
+        }
+#pragma unroll
+        for (int p = 0; p < B; p++) {
+            const int kk = kk0 + (p0 + p) * RPP;
+            if (lane_on && kk < nch) cl_words[kk * W + w] = mine[p];
+        }
+    }
+    __syncthreads();
+    for (int p = 0; p * RPP < nch; p++) {
+        const int kk = kk0 + p * RPP;
+        if (!(lane_on && kk < nch)) continue;
+        uint64_t ow = cl_words[kk * W + w];
+        if ((revmask >> p) & 1u) {                                // the W lanes of a read are neighbours in one wave: all have read before one writes
+            ow = rc_word_at<W>(cl_words + kk * W, s.L, w);
+            cl_words[kk * W + w] = ow;
+        }
+        if (cl_g[kk] >= 0) s.oreads_out[(size_t)(base + kk) * W + w] = ow;
+    }
+}
 // One tile (the `tile`-th of the rank), counted in NPL main planes by the whole workgroup; true in the lanes where a carry left the top plane.
 // Beside the bytes of cons the strip's 16 columns go into cons2 as they stand in the lane, one 32-bit half of a word (A0 G1 C2 T3: the two bits of a
-// row index swapped; zero from the end of the consensus to the end of its last word).
-template <int NPL> __device__ __forceinline__ bool consensus_tile(const S2Args &s, const uint32_t tile, const uint32_t *cid, const unsigned long long *cinfo, int want_windows, const uint32_t *tlo, const uint32_t *thi)
+// row index swapped; zero from the end of the consensus to the end of its last word).  GW = 0: the reads are staged from d_oreads; GW = W: gathered.
+template <int NPL, int GW> __device__ __forceinline__ bool consensus_tile(const S2Args &s, const uint32_t tile, const uint32_t *cid, const unsigned long long *cinfo, int want_windows, const uint32_t *tlo, const uint32_t *thi)
 {
     extern __shared__ uint64_t cl_words[];                        // [CCHUNK][W] read words, then CCHUNK tile-relative starts
-    int *const cl_g = reinterpret_cast<int *>(cl_words + (size_t)CCHUNK * s.W);
+    const int L = s.L, W = GW ? GW : s.W;
+    int *const cl_g = reinterpret_cast<int *>(cl_words + (size_t)CCHUNK * W);
     const uint32_t *const cl_w32 = reinterpret_cast<const uint32_t *>(cl_words);   // the same words, 16 bases each
     const uint64_t X0 = (uint64_t)(tile + s.tile_base) * CTILE;
-    const int L = s.L, W = s.W;
     const long long ilo = tlo[tile], ihi = thi[tile];
     const int x0r = (int)threadIdx.x * CSTRIP;                   // tile-relative first column of the strip
     const uint64_t x0 = X0 + (uint64_t)x0r;
@@ -270,8 +340,11 @@ template <int NPL> __device__ __forceinline__ bool consensus_tile(const S2Args &
     for (long long base = ilo; base <= ihi; base += CCHUNK) {
         const int nch = (int)(ihi + 1 - base < CCHUNK ? ihi + 1 - base : CCHUNK);
         __syncthreads();
-        for (int k = threadIdx.x; k < nch * W; k += CTHREADS) cl_words[k] = s.oreads[(size_t)base * W + k];
-        for (int k = threadIdx.x; k < nch; k += CTHREADS) cl_g[k] = (int)((long long)s.gstart[base + k] - (long long)X0);
+        if constexpr (GW != 0) consensus_gather<(GW ? GW : 1), (NPL == CPLANES || GW > 4 || GW == 3 ? 2 : CGBATCH)>(s, base, nch, X0, cl_words, cl_g);
+        else {
+            for (int k = threadIdx.x; k < nch * W; k += CTHREADS) cl_words[k] = s.oreads[(size_t)base * W + k];
+            for (int k = threadIdx.x; k < nch; k += CTHREADS) cl_g[k] = (int)((long long)s.gstart[base + k] - (long long)X0);
+        }
         __syncthreads();
         // reads of the piece that cover a column of the strip: start in (x0r - L, xlr].  The first one by binary search; the run ends at the first
         // start past xlr, which the loop meets by itself (a strip past the end of the consensus: none)
@@ -386,13 +459,17 @@ template <int NPL> __device__ __forceinline__ bool consensus_tile(const S2Args &
 // NPL = CSHALLOW: the kernel every tile goes through, a workgroup a tile, its counts good for 2^CSHALLOW - 1 reads on a column; a tile where a carry
 // leaves the top plane is appended to the list tovf (tovf[0] tiles, their numbers behind it) and counted again by NPL = CPLANES, launched behind it
 // on a small grid that strides over the list.
-template <int NPL> __global__ __launch_bounds__(CTHREADS, NPL == CPLANES ? 4 : 6) void k_consensus(S2Args s, const uint32_t *cid, const unsigned long long *cinfo, int want_windows, const uint32_t *tlo, const uint32_t *thi, uint32_t *tovf)
+// GW = W: the tiles gather their reads themselves (consensus_gather).
+#ifndef CGWAVES
+#define CGWAVES 6
+#endif
+template <int NPL, int GW> __global__ __launch_bounds__(CTHREADS, NPL == CPLANES ? 4 : GW ? CGWAVES : 6) void k_consensus(S2Args s, const uint32_t *cid, const unsigned long long *cinfo, int want_windows, const uint32_t *tlo, const uint32_t *thi, uint32_t *tovf)
 {
     if (NPL == CPLANES) {
         const uint32_t n = tovf[0];
-        for (uint32_t k = blockIdx.x; k < n; k += gridDim.x) consensus_tile<NPL>(s, tovf[1 + k], cid, cinfo, want_windows, tlo, thi);
+        for (uint32_t k = blockIdx.x; k < n; k += gridDim.x) consensus_tile<NPL, GW>(s, tovf[1 + k], cid, cinfo, want_windows, tlo, thi);
     } else {
-        const bool ovf = consensus_tile<NPL>(s, blockIdx.x, cid, cinfo, want_windows, tlo, thi);
+        const bool ovf = consensus_tile<NPL, GW>(s, blockIdx.x, cid, cinfo, want_windows, tlo, thi);
         if (__syncthreads_or(ovf) && threadIdx.x == 0) tovf[1 + atomicAdd(&tovf[0], 1u)] = blockIdx.x;
     }
 }
@@ -1772,7 +1849,7 @@ int stage2_run(harc_amd_ctx *c)
     a.M = M; a.S = S; a.T = T;
     a.q = 1u + (uint32_t)((M - 1u) / E);                          // uint32 arithmetic as encoder.cpp:171
     if (a.q == 0) a.q = 1;
-    a.oreads = c->d_oreads; a.flag = c->d_flag; a.pos = c->d_pos; a.rc = c->d_rc; a.order = c->d_order;
+    a.oreads = c->d_oreads; a.reads = c->s2_gather ? c->d_reads : nullptr; a.oreads_out = c->s2_gather ? c->d_oreads : nullptr; a.flag = c->d_flag; a.pos = c->d_pos; a.rc = c->d_rc; a.order = c->d_order;
     const uint32_t i0 = (uint32_t)((uint64_t)e0 * a.q > M ? M : (uint64_t)e0 * a.q), i1 = e1 >= E ? M : (uint32_t)((uint64_t)e1 * a.q > M ? M : (uint64_t)e1 * a.q);   // this rank's reordered reads
 
     // the two order streams outlive the scratch: worst-case sized, copied to the host only when asked for (harc_amd_get_stream)
@@ -1918,10 +1995,20 @@ int stage2_run(harc_amd_ctx *c)
         hipLaunchKernelGGL(k_consensus_tiles, G256(ntiles), a, ntiles, tlo, thi);
         uint32_t *tovf = nullptr; RC_TRY(dalloc(c, &tovf, (size_t)ntiles + 1));      // the tiles to count again: how many, then which
         HIP_TRY(hipMemsetAsync(tovf, 0, 4, c->stream));
-        hipLaunchKernelGGL(k_consensus<CSHALLOW>, dim3(ntiles), dim3(CTHREADS), (size_t)CCHUNK * (W * 8 + 4), c->stream, a, (const uint32_t *)u1, (const unsigned long long *)cinfo, T ? 1 : 0,
-                           (const uint32_t *)tlo, (const uint32_t *)thi, tovf);
-        hipLaunchKernelGGL(k_consensus<CPLANES>, dim3(ntiles < 1024u ? ntiles : 1024u), dim3(CTHREADS), (size_t)CCHUNK * (W * 8 + 4), c->stream, a, (const uint32_t *)u1, (const unsigned long long *)cinfo, T ? 1 : 0,
-                           (const uint32_t *)tlo, (const uint32_t *)thi, tovf);
+        // both kernels in one form: staged from d_oreads (GW = 0), or gathered from d_reads by the tiles, which then write d_oreads (GW = W; the
+        // re-count of an overflowed tile gathers and writes the same words again)
+#define CONSENSUS_LAUNCH(GW) { \
+        hipLaunchKernelGGL((k_consensus<CSHALLOW, GW>), dim3(ntiles), dim3(CTHREADS), (size_t)CCHUNK * (W * 8 + 4), c->stream, a, (const uint32_t *)u1, (const unsigned long long *)cinfo, T ? 1 : 0, \
+                           (const uint32_t *)tlo, (const uint32_t *)thi, tovf); \
+        hipLaunchKernelGGL((k_consensus<CPLANES, GW>), dim3(ntiles < 1024u ? ntiles : 1024u), dim3(CTHREADS), (size_t)CCHUNK * (W * 8 + 4), c->stream, a, (const uint32_t *)u1, (const unsigned long long *)cinfo, T ? 1 : 0, \
+                           (const uint32_t *)tlo, (const uint32_t *)thi, tovf); }
+        if (!c->s2_gather) CONSENSUS_LAUNCH(0)
+        else switch (W) {
+            case 1: CONSENSUS_LAUNCH(1) break; case 2: CONSENSUS_LAUNCH(2) break; case 3: CONSENSUS_LAUNCH(3) break; case 4: CONSENSUS_LAUNCH(4) break;
+            case 5: CONSENSUS_LAUNCH(5) break; case 6: CONSENSUS_LAUNCH(6) break; case 7: CONSENSUS_LAUNCH(7) break; default: CONSENSUS_LAUNCH(8) break;
+        }
+#undef CONSENSUS_LAUNCH
+        if (c->s2_gather && !part) c->oreads_whole = true;       // every read starts in one of the tiles of [0, total)
         {   // read_seq (packbits, encoder.cpp:527-548) is final here -- the realignment below does not touch the consensus -- and the shard
             // boundaries on the column axis follow from gstart alone: it is packed now, all shards in one launch from the packed consensus, and
             // goes to the host on the copy stream while the realignment, the merge and the noise kernels run (the largest stream: a quarter of
@@ -1988,7 +2075,7 @@ int stage2_run(harc_amd_ctx *c)
         return HARC_AMD_OK;
     };
     RC_TRY(best_digest("after the proposals"));
-    lap("consensus + read_seq + proposals (this rank's columns)");
+    lap(c->s2_gather ? "consensus (reads gathered by the tiles) + read_seq + proposals (this rank's columns)" : "consensus (reads staged from the oriented copy) + read_seq + proposals (this rank's columns)");
     // ---- the window words of the events (k_realign_big reads them instead of the consensus: with the columns partitioned the consensus under an
     //      event of another rank is not here)
     uint64_t *evwin = nullptr;

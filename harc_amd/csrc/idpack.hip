@@ -9,17 +9,18 @@
 //                 Pass 2: the lane walks its events backwards through the coder into its slab (id_strand_encode).  The strand lengths are scanned over the
 //                 workgroup, the head of the payload is written in front of the table, and the block's size, stored or coded, is decided.
 //   (scan of the block sizes, prims.hip)
-//   k_ip_gather   a workgroup per block copies u32 payload_bytes, head, table and strands -- or the stored text -- to their byte-granular place: whole dwords
-//                 of the destination inside the block, the bytes in front of and behind them one by one.  Nothing outside the blocks is written.
+//   k_ip_gather   a workgroup per block writes u32 payload_bytes and the stored text behind its length -- or has head, table and strands copied to their
+//                 byte-granular place by pack_gather_coded (packfile.h).  Nothing outside the blocks is written.
 // A lane's walk over its own lines is byte-serial and not coalesced: neighbouring lanes read text q lines apart.  That is accepted here (NOTES.md has the rate).
 //
-// Unpacking.  The block offsets follow from the payload_bytes prefixes and the places in the text from the block_text_bytes behind them (id_prefix: k_ip_walk,
-// one lane; on the host the walk of packfile.h).
+// Unpacking.  The block offsets follow from the payload_bytes prefixes and the places in the text from the block_text_bytes behind them (IdRule over id_prefix,
+// for the walks of packfile.h on the host and in one lane of the device).
 //   k_ip_decode   a workgroup per block validates head, bitmap, rows and strand sizes into LDS (id_check_head, id_load_row, id_check_strand), then a lane per
 //                 strand decodes forward (id_strand_decode) and writes its text at its prefix-summed offset.  Any violation raises the error word:
 //                 block number << 8 | ID_E_*.
-// The plumbing of the file calls (probes, guards, ring split, device buffers, kernel timer, the carried tail of the text) is fileio.h's; the drivers of the way back
-// -- the run of k_ip_decode, the device call and the file call -- are packfile.h's, shared with qpack.hip: this file hands them ID_FORMAT.
+// The plumbing of the file calls (probes, guards, ring split, device buffers, kernel timer, the carried tail of the text) is fileio.h's.  The drivers are packfile.h's,
+// shared with qpack.hip and spack.hip: pack_run and pack_device on the way in, which harc_idpack_run and harc_amd_idpack_device hand their scratch, launches, error
+// words and messages (and the line index, built first); the host call, the run of k_ip_decode, the device call and the file call on the way back, which get ID_FORMAT.
 #include "devutil.h"
 #include "id_block.h"
 #include "packfile.h"
@@ -34,8 +35,6 @@ struct IpShared {
     uint32_t scan[IP_T / 64 + 1];
     unsigned long long tsum, lsum;
 };
-struct IpGather { uint32_t scan[IP_T / 64 + 1], soff[ID_STRANDS], slen[ID_STRANDS]; };
-struct IpStats { uint64_t text = 0, bytes = 0, blocks = 0, stored = 0; double seconds = 0; };
 
 // The blocks of the lines [0, n_lines) whose line index is nls (nls[-1]: the newline in front of the first of them, absolute like the others; t0: where the
 // first line starts).  events: u16 (text bytes + 2 lines of the call); slabs: 2 bytes per event and 32 per strand; heads: IP_HDR per block.
@@ -107,7 +106,7 @@ __global__ __launch_bounds__(IP_T) void k_ip_encode(const uint8_t *text, const u
 __global__ __launch_bounds__(IP_T) void k_ip_gather(const uint8_t *text, uint32_t nb, const uint8_t *slabs, const uint8_t *heads, const uint64_t *sat, const uint64_t *btext,
                                                     const uint32_t *bsize, const uint32_t *bmode, const uint64_t *boff, uint8_t *out)
 {
-    __shared__ IpGather S;
+    __shared__ PackGather S;
     const uint64_t b = harc_bid();
     if (b >= nb) return;
     const uint32_t t = threadIdx.x;
@@ -122,37 +121,9 @@ __global__ __launch_bounds__(IP_T) void k_ip_gather(const uint8_t *text, uint32_
         for (uint32_t j = t; j < T; j += IP_T) dst[4u + ID_HEAD0 + j] = tx[j];
         return;
     }
-    const uint8_t *hdr = heads + b * (uint64_t)IP_HDR;
-    const uint32_t len = qv_le32(hdr + ID_HEAD0 + 4u * ID_STRANDS + 4u * t);
-    uint32_t total;
-    const uint32_t off = block_excl_scan_u32<IP_T>(len, S.scan, &total);
-    const uint32_t h = payload - total;
-    S.soff[t] = off; S.slen[t] = len;
-    group_copy_bytes(dst + 4, hdr, h, t, IP_T);
-    __syncthreads();
-    const uint32_t wv = t >> 6, lane = t & 63u;
-    for (uint32_t s = wv; s < ID_STRANDS; s += IP_T / 64) {
-        const uint32_t n = S.slen[s];
-        if (n) group_copy_bytes(dst + 4 + h + S.soff[s], slabs + sat[(uint64_t)ID_STRANDS * b + s], n, lane, 64);
-    }
-}
-
-// The offsets of the nb blocks behind the 32-byte header of p[0 .. n_bytes), relative to p + 32, and of their text; off[nb] / toff[nb] = their ends.
-// bad[0]: 1 + the first block whose prefix, head or payload leaves the bytes or whose text is longer than 2^30 bytes (nb + 1: bytes are left behind the last block,
-// nb + 2: the text bytes of the blocks are not those of the header), bad[1]: its offset
-__global__ void k_ip_walk(const uint8_t *p, uint64_t n_bytes, uint64_t nb, uint64_t text_bytes, uint64_t *off, uint64_t *toff, unsigned long long *bad)
-{
-    if (threadIdx.x || blockIdx.x) return;
-    uint64_t at = ID_FILE_HEADER, tat = 0;
-    for (uint64_t b = 0; b < nb; b++) {
-        off[b] = at - ID_FILE_HEADER; toff[b] = tat;
-        uint64_t pb = 0, tb = 0;
-        if (!id_prefix(p + at, n_bytes - at, text_bytes - tat, &pb, &tb)) { bad[0] = b + 1; bad[1] = at; return; }
-        at += 4 + pb; tat += tb;
-    }
-    off[nb] = at - ID_FILE_HEADER; toff[nb] = tat;
-    if (at != n_bytes) { bad[0] = nb + 1; bad[1] = at; }
-    else if (tat != text_bytes) { bad[0] = nb + 2; bad[1] = tat; }
+    const uint8_t *hdr = heads + b * (uint64_t)IP_HDR;                                       // the lengths follow the strand text bytes; sat says where a strand starts
+    const uint64_t *at = sat + (uint64_t)ID_STRANDS * b;
+    pack_gather_coded(S, dst, payload, hdr, hdr + ID_HEAD0 + 4u * ID_STRANDS, [=](uint32_t s, uint32_t) { return slabs + at[s]; });
 }
 
 // blocks: block b of this call at blocks + off[b], off[b + 1] - off[b] bytes with its u32; its text at text + toff[b], toff[b + 1] - toff[b] bytes (the walk has
@@ -230,45 +201,33 @@ static const char *id_error_text(uint32_t e)
 // the blocks alone (no file header) of the n lines that start at d_text + t0 and end at d_text + t1, nls their line index (nls[-1] + 1 == t0) -> d_out[0 .. *n_out);
 // d_out == nullptr: the size alone.  block0: the number of the first of them, for the message
 static int harc_idpack_run(harc_amd_ctx *c, const char *d_text, const uint64_t *nls, uint64_t t0, uint64_t t1, uint64_t n, uint32_t RB, uint8_t *d_out, uint64_t out_capacity,
-                           uint64_t *n_out, uint64_t block0, IpStats *st)
+                           uint64_t *n_out, uint64_t block0, PackStats *st)
 {
-    *n_out = 0;
-    const uint64_t nb64 = id_blocks(n, RB);
-    if (nb64 > 0x7FFFFFF0ull / ID_STRANDS) { harc_set_error("idpack: too many blocks for one call"); return HARC_AMD_EINVAL; }
-    const uint32_t nb = (uint32_t)nb64;
-    if (!nb) return HARC_AMD_OK;
-    PoolScope scope(c);
+    const uint8_t *text = (const uint8_t *)d_text;
     const uint64_t nev = (t1 - t0) + 2ull * n;
-    uint16_t *events = nullptr; uint8_t *slabs = nullptr, *heads = nullptr; uint64_t *sat = nullptr, *btext = nullptr, *boff = nullptr; uint32_t *bsize = nullptr, *bmode = nullptr;
-    unsigned int *d_err = nullptr;
-    RC_TRY(dalloc(c, &events, (size_t)nev)); RC_TRY(dalloc(c, &slabs, (size_t)(2ull * nev + 32ull * ID_STRANDS * nb))); RC_TRY(dalloc(c, &heads, (size_t)IP_HDR * nb));
-    RC_TRY(dalloc(c, &sat, (size_t)ID_STRANDS * nb)); RC_TRY(dalloc(c, &btext, (size_t)nb)); RC_TRY(dalloc(c, &boff, (size_t)nb + 1));
-    RC_TRY(dalloc(c, &bsize, (size_t)nb + 1)); RC_TRY(dalloc(c, &bmode, (size_t)nb)); RC_TRY(dalloc(c, &d_err, 4));
-    HIP_TRY(hipMemsetAsync(bsize + nb, 0, 4, c->stream));
-    HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
-    HIP_TRY(hipMemsetAsync(d_err, 0xFF, 4, c->stream));
-    KernelTimer timer(st ? &st->seconds : nullptr);
-    RC_TRY(timer.begin(c->stream));
-    hipLaunchKernelGGL(k_ip_encode, harc_fold256(nb), dim3(IP_T), 0, c->stream, (const uint8_t *)d_text, nls, t0, n, RB, nb, events, slabs, heads, sat, btext, bsize, bmode, d_err);
-    HIP_TRY(hipGetLastError());
-    RC_TRY(prim_excl_scan_u32_to_u64(c, bsize, boff, (size_t)nb + 1));
-    uint64_t total = 0; unsigned int err[4] = { 0, 0, 0, 0 };
-    HIP_TRY(hipMemcpyAsync(&total, boff + nb, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(err, d_err, 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (err[0] != 0xFFFFFFFFu) { harc_set_error("idpack: the text of block %llu is longer than %u bytes", (unsigned long long)(block0 + err[0] - 1), ID_MAX_BLOCK_TEXT); return HARC_AMD_EINVAL; }
-    if (err[1]) { harc_set_error("idpack: %u strands did not fit their scratch", err[1]); return HARC_AMD_EINTERNAL; }
-    *n_out = total;
-    if (st) { st->text += t1 - t0; st->bytes += total; st->blocks += nb; st->stored += err[2]; }
-    if (d_out) {
-        if (out_capacity < total) { harc_set_error("idpack_device: the blocks take %llu bytes, the buffer holds %llu", (unsigned long long)total, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
-        hipLaunchKernelGGL(k_ip_gather, harc_fold256(nb), dim3(IP_T), 0, c->stream, (const uint8_t *)d_text, nb, (const uint8_t *)slabs, (const uint8_t *)heads, (const uint64_t *)sat,
-                           (const uint64_t *)btext, (const uint32_t *)bsize, (const uint32_t *)bmode, (const uint64_t *)boff, d_out);
-        HIP_TRY(hipGetLastError());
-    }
-    RC_TRY(timer.end(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));                     // the scratch goes back to the pool
-    return HARC_AMD_OK;
+    uint16_t *events = nullptr; uint8_t *slabs = nullptr, *heads = nullptr; uint64_t *sat = nullptr, *btext = nullptr;
+    // (sat holds ID_STRANDS entries a block: that many fewer blocks a call.  err[0] is lowered by atomicMin: all ones says that no block is too long)
+    return pack_run(c, "idpack", id_blocks(n, RB), 0x7FFFFFF0ull / ID_STRANDS, t1 - t0, d_out, out_capacity, n_out, st,
+        [&](const PackBlocks &B) -> int {
+            const size_t nb = B.nb;
+            RC_TRY(dalloc(c, &events, (size_t)nev)); RC_TRY(dalloc(c, &slabs, (size_t)(2ull * nev + 32ull * ID_STRANDS * nb))); RC_TRY(dalloc(c, &heads, (size_t)IP_HDR * nb));
+            RC_TRY(dalloc(c, &sat, (size_t)ID_STRANDS * nb)); RC_TRY(dalloc(c, &btext, nb));
+            HIP_TRY(hipMemsetAsync(B.err, 0xFF, 4, c->stream));
+            return HARC_AMD_OK;
+        },
+        [&](const PackBlocks &B) {
+            hipLaunchKernelGGL(k_ip_encode, harc_fold256(B.nb), dim3(IP_T), 0, c->stream, text, nls, t0, n, RB, B.nb, events, slabs, heads, sat, btext, B.bsize, B.bmode, B.err);
+        },
+        [&](const unsigned int *err, PackStats *stats) {
+            if (err[0] != 0xFFFFFFFFu) { harc_set_error("idpack: the text of block %llu is longer than %u bytes", (unsigned long long)(block0 + err[0] - 1), ID_MAX_BLOCK_TEXT); return HARC_AMD_EINVAL; }
+            if (err[1]) { harc_set_error("idpack: %u strands did not fit their scratch", err[1]); return HARC_AMD_EINTERNAL; }
+            if (stats) stats->mode[0] += err[2];
+            return HARC_AMD_OK;
+        },
+        [&](const PackBlocks &B, uint8_t *out) {
+            hipLaunchKernelGGL(k_ip_gather, harc_fold256(B.nb), dim3(IP_T), 0, c->stream, text, B.nb, (const uint8_t *)slabs, (const uint8_t *)heads, (const uint64_t *)sat,
+                               (const uint64_t *)btext, (const uint32_t *)B.bsize, (const uint32_t *)B.bmode, (const uint64_t *)B.boff, out);
+        });
 }
 // the line index of text_bytes > 0 bytes that end in a newline.  Pool memory: the caller brackets it
 static int ip_index(harc_amd_ctx *c, const char *who, const char *d_text, uint64_t text_bytes, const uint64_t **nls, uint64_t *lines)
@@ -286,35 +245,22 @@ extern "C" uint64_t harc_amd_idpack_bound(uint64_t text_bytes, uint64_t n_lines,
 extern "C" int harc_amd_idpack_device(harc_amd_ctx *c, const char *d_text, uint64_t text_bytes, uint32_t lines_per_block, int32_t flags, uint8_t *d_out, uint64_t out_capacity,
                                       uint64_t *n_out)
 {
-    if (!c || (text_bytes && !d_text) || !n_out) { harc_set_error("idpack_device: bad arguments"); return HARC_AMD_EINVAL; }
     const uint32_t rb = ip_rb(lines_per_block);
-    HIP_TRY(hipSetDevice(c->P.device));
-    const uint64_t head = (flags & HARC_AMD_IDPACK_NO_HEADER) ? 0 : ID_FILE_HEADER;
-    const bool trace = getenv("HARC_AMD_TRACE") != nullptr;
-    IpStats st; uint64_t nblk = 0, n = 0;
-    *n_out = head;
-    // the size first: a buffer that is too small is refused with both numbers before a byte of it is written
-    if (d_out && out_capacity < head) { harc_set_error("idpack_device: the blocks take at least %llu bytes, the buffer holds %llu", (unsigned long long)head, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
-    PoolScope scope(c);
-    if (text_bytes) {
-        const uint64_t *nls = nullptr;
-        RC_TRY(ip_index(c, "idpack_device", d_text, text_bytes, &nls, &n));
-        const int rc = harc_idpack_run(c, d_text, nls, 0, text_bytes, n, rb, d_out ? d_out + head : nullptr, d_out ? out_capacity - head : 0, &nblk, 0, trace ? &st : nullptr);
-        *n_out = head + nblk;
-        if (rc != HARC_AMD_OK) {
-            if (d_out && nblk && out_capacity - head < nblk) harc_set_error("idpack_device: the packed form takes %llu bytes, the buffer holds %llu", (unsigned long long)(head + nblk), (unsigned long long)out_capacity);
-            return rc;
-        }
-    }
-    if (d_out && head) {
-        uint8_t h[ID_FILE_HEADER];
-        id_file_header(h, rb, n, text_bytes);
-        HIP_TRY(hipMemcpyAsync(d_out, h, ID_FILE_HEADER, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    if (trace) fprintf(stderr, "[idpack] device call: %llu bytes of text -> %llu bytes in %llu blocks (%llu stored), kernels %.3f ms (%.2f GB/s of text)\n", (unsigned long long)text_bytes,
-                       (unsigned long long)*n_out, (unsigned long long)st.blocks, (unsigned long long)st.stored, 1e3 * st.seconds, st.seconds > 0 ? 1e-9 * (double)st.text / st.seconds : 0.0);
-    return HARC_AMD_OK;
+    uint64_t n = 0;
+    return pack_device("idpack", c, !text_bytes || d_text, (flags & HARC_AMD_IDPACK_NO_HEADER) ? 0 : ID_FILE_HEADER, d_out, out_capacity, n_out,
+        [] { return HARC_AMD_OK; },                                // (every number of lines per block is a geometry)
+        [&](uint8_t *o, uint64_t cap, uint64_t *nblk, PackStats *st) -> int {
+            if (!text_bytes) return HARC_AMD_OK;
+            PoolScope scope(c);                                    // the line index
+            const uint64_t *nls = nullptr;
+            RC_TRY(ip_index(c, "idpack_device", d_text, text_bytes, &nls, &n));
+            return harc_idpack_run(c, d_text, nls, 0, text_bytes, n, rb, o, cap, nblk, 0, st);
+        },
+        [&](uint8_t *h) { id_file_header(h, rb, n, text_bytes); },
+        [&](const PackStats &st, uint64_t bytes) {
+            fprintf(stderr, "[idpack] device call: %llu bytes of text -> %llu bytes in %llu blocks (%llu stored), kernels %.3f ms (%.2f GB/s of text)\n", (unsigned long long)text_bytes,
+                    (unsigned long long)bytes, (unsigned long long)st.blocks, (unsigned long long)st.mode[0], 1e3 * st.seconds, st.seconds > 0 ? 1e-9 * (double)st.text / st.seconds : 0.0);
+        });
 }
 
 // ------------------------------------------------------------------------------------------------ unpacking
@@ -335,12 +281,15 @@ static int ip_parse_header(const char *who, const uint8_t *h, uint64_t n_bytes, 
     if (H->text < H->n || H->text > H->nb * (uint64_t)ID_MAX_BLOCK_TEXT) { harc_set_error("%s: the header announces %llu lines in %llu bytes of text", who, (unsigned long long)H->n, (unsigned long long)H->text); return HARC_AMD_EINVAL; }
     return HARC_AMD_OK;
 }
+// the prefix rule (the text bytes of a block stand behind its payload bytes)
+struct IdRule {
+    static __host__ __device__ int prefix(const PackHeader &, uint64_t, const uint8_t *q, uint64_t left, uint64_t text_left, uint64_t *pb, uint64_t *tb)
+    {
+        return id_prefix(q, left, text_left, pb, tb);
+    }
+};
 static const PackFormat ID_FORMAT = {
-    "id", "id", "HARC_AMD_IDPACK_PIECE", 8, ID_PREFIX, ip_parse_header,
-    [](const PackHeader &, uint64_t, const uint8_t *q, uint64_t left, uint64_t text_left, uint64_t *pb, uint64_t *tb) { return id_prefix(q, left, text_left, pb, tb); },
-    [](harc_amd_ctx *c, const uint8_t *d_packed, uint64_t n_bytes, const PackHeader &H, uint64_t *d_off, uint64_t *d_toff, unsigned long long *d_bad) {
-        hipLaunchKernelGGL(k_ip_walk, dim3(1), dim3(64), 0, c->stream, d_packed, n_bytes, H.nb, H.text, d_off, d_toff, d_bad);
-    },
+    "id", "id", "HARC_AMD_IDPACK_PIECE", 8, ID_PREFIX, ip_parse_header, IdRule::prefix, pack_walk_device<IdRule>,
     [](harc_amd_ctx *c, const uint8_t *d_blocks, const uint64_t *d_off, const uint64_t *d_toff, uint32_t nb, uint64_t n, const PackHeader &H, char *d_text, unsigned long long *d_errw) {
         hipLaunchKernelGGL(k_ip_decode, harc_fold256(nb), dim3(IP_T), 0, c->stream, d_blocks, d_off, d_toff, nb, n, H.rb, (uint8_t *)d_text, d_errw);
     },
@@ -382,20 +331,9 @@ extern "C" int harc_amd_idpack_host(const char *text, uint64_t text_bytes, uint3
 
 extern "C" int harc_amd_idunpack_host(const uint8_t *packed, uint64_t n_bytes, char *text, uint64_t cap, uint64_t *n_out)
 {
-    if (!packed || !n_out) { harc_set_error("idunpack_host: bad arguments"); return HARC_AMD_EINVAL; }
-    if (n_bytes < ID_FILE_HEADER) { harc_set_error("idunpack_host: %llu bytes are fewer than the %u of the header", (unsigned long long)n_bytes, ID_FILE_HEADER); return HARC_AMD_EINVAL; }
-    PackHeader H;
-    RC_TRY(ip_parse_header("idunpack_host", packed, n_bytes, &H));
-    *n_out = H.text;
-    if (!text) return HARC_AMD_OK;
-    if (cap < H.text) { harc_set_error("idunpack_host: the text takes %llu bytes, the buffer holds %llu", (unsigned long long)H.text, (unsigned long long)cap); return HARC_AMD_EINVAL; }
     std::vector<IdWork> W(1);
-    return pack_walk(ID_FORMAT, "idunpack_host", "the packed form", H, n_bytes,
-                     [&](uint64_t at, uint8_t *q, size_t k) { memcpy(q, packed + at, k); return HARC_AMD_OK; },
-                     [&](uint64_t b, uint64_t at, uint64_t pb, uint64_t tat) {
-                         const int e = id_block_decode(packed + at + 4, (uint32_t)pb, pack_block_lines(H, b), W[0], (uint8_t *)text + tat);
-                         return e ? pack_refuse_damaged(ID_FORMAT, b, at, (uint32_t)e) : HARC_AMD_OK;
-                     }, nullptr, nullptr);
+    return pack_unpack_host(ID_FORMAT, packed, n_bytes, (uint8_t *)text, cap, n_out,
+                            [&](const PackHeader &, const uint8_t *pl, uint32_t pb, uint32_t m, uint8_t *tx) { return id_block_decode(pl, pb, m, W[0], tx); });
 }
 
 // ------------------------------------------------------------------------------------------------ the files
@@ -427,7 +365,7 @@ extern "C" int harc_amd_idpack_files(const harc_amd_params *params, const char *
     CarriedText txt(c); DevBuf out{ c };
     const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
     double t_read = 0, t_write = 0;
-    IpStats st;
+    PackStats st;
     uint64_t at = ID_FILE_HEADER, n = 0, nb = 0; int npieces = 0;
     {
         FileDrain drain(c);
@@ -480,7 +418,7 @@ extern "C" int harc_amd_idpack_files(const harc_amd_params *params, const char *
         { const double t0 = mono_now(); RC_TRY(drain.finish()); t_write += mono_now() - t0; }
     }
     if (tlog) fprintf(stderr, "[idpack] %llu bytes of text -> %llu bytes in %llu blocks (%llu stored), %d pieces: %.3f s in the kernels, %.3f s waiting for the readers, %.3f s waiting for the writers\n",
-                      (unsigned long long)isz, (unsigned long long)at, (unsigned long long)nb, (unsigned long long)st.stored, npieces, st.seconds, t_read, t_write);
+                      (unsigned long long)isz, (unsigned long long)at, (unsigned long long)nb, (unsigned long long)st.mode[0], npieces, st.seconds, t_read, t_write);
     outguard.ok = true;
     return HARC_AMD_OK;
 }

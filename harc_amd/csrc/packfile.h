@@ -1,12 +1,17 @@
-// packfile.h -- the way back to text that the packed side files share (qpack.hip: X.quality.hq, idpack.hip: X.id.hi).  Such a file is a 32-byte header and then
-// self-delimiting blocks: a prefix says how many bytes a block holds, and a kernel with a workgroup per block turns the blocks into one contiguous text.  Here, once:
-// the walk over the prefixes on the host, the run of the decode kernel with its error word, the device call and the file call.  A format hands in a PackFormat.
+// packfile.h -- what the packed side files share (qpack.hip: X.quality.hq, idpack.hip: X.id.hi, spack.hip: X.hs).  Such a file is a 32-byte header and then
+// self-delimiting blocks: a prefix says how many bytes a block holds, and a kernel with a workgroup per block turns text into blocks or blocks into one contiguous text.
+// The way in, once: the coded branch of the gather kernels (pack_gather_coded), the run of encode, scan and gather with its error words and its capacity refusal
+// (pack_run) and the device call (pack_device); a format hands in its scratch, its launches and its messages as hooks.  The way back, once: the walk over the
+// prefixes on the host (pack_walk) and in one lane of the device (k_pack_walk), the run of the decode kernel with its error word, the host call, the device call
+// and the file call.  A format hands in a PackFormat.
 #pragma once
+#include "devutil.h"
+#include "qv_block.h"
 #include "fileio.h"
 
 #define PF_HEADER 32u
 struct PackHeader { uint32_t L = 0, rb = 0; uint64_t n = 0, nb = 0, text = 0; };      // lines of L (0: of any length) in blocks of rb: n lines, nb blocks, `text` bytes of text
-static inline uint32_t pack_block_lines(const PackHeader &H, uint64_t b) { const uint64_t line0 = b * (uint64_t)H.rb; return H.n - line0 < H.rb ? (uint32_t)(H.n - line0) : H.rb; }
+QV_HD uint32_t pack_block_lines(const PackHeader &H, uint64_t b) { const uint64_t line0 = b * (uint64_t)H.rb; return H.n - line0 < H.rb ? (uint32_t)(H.n - line0) : H.rb; }
 
 struct PackFormat {
     const char *tag;                                              // "q" / "id": <tag>unpack... in the messages, [<tag>pack] in the trace
@@ -16,8 +21,9 @@ struct PackFormat {
     int (*parse_header)(const char *who, const uint8_t *h, uint64_t n_bytes, PackHeader *H);
     // the format's prefix rule for block b: q and `left` as qv_prefix / id_prefix take them -> 1 with the bytes of its payload and of its text, or 0
     int (*prefix)(const PackHeader &H, uint64_t b, const uint8_t *q, uint64_t left, uint64_t text_left, uint64_t *payload_bytes, uint64_t *text_bytes);
-    // the one-lane walk kernel over a packed form in device memory: off / toff[0 .. nb] relative to the first block, bad[0]: 1 + the first block that the prefix rule
-    // refuses (nb + 1: bytes are left behind the last block, nb + 2: the text bytes of the blocks are not those of the header), bad[1]: its byte
+    // the one-lane walk kernel over a packed form in device memory, pack_walk_device<Rule> with the rule above: off / toff[0 .. nb] relative to the first block,
+    // bad[0]: 1 + the first block that the prefix rule refuses (nb + 1: bytes are left behind the last block, nb + 2: the text bytes of the blocks are not those of
+    // the header), bad[1]: its byte
     void (*walk)(harc_amd_ctx *c, const uint8_t *d_packed, uint64_t n_bytes, const PackHeader &H, uint64_t *d_off, uint64_t *d_toff, unsigned long long *d_bad);
     // the decode kernel over nb blocks with n lines: it lowers *d_errw to block << 8 | code for a block that is damaged
     void (*decode)(harc_amd_ctx *c, const uint8_t *d_blocks, const uint64_t *d_off, const uint64_t *d_toff, uint32_t nb, uint64_t n, const PackHeader &H, char *d_text, unsigned long long *d_errw);
@@ -62,6 +68,50 @@ static int pack_walk(const PackFormat &F, const char *who, const char *what, con
     }
     if (off) { off[nb] = at; toff[nb] = tat; }
     return nb == H.nb ? pack_check_ends(who, what, H, n_bytes, at, tat) : HARC_AMD_OK;
+}
+
+// The same walk by one lane over a packed form in device memory, what PackFormat::walk launches.  Rule::prefix is the format's prefix rule, PackFormat::prefix as
+// a __host__ __device__ function.  off and toff are filled for every format, also where the text of a block follows from its number alone, and both ends are
+// checked for every format: the drivers above allocate and read both
+template <class Rule>
+__global__ void k_pack_walk(const uint8_t *p, uint64_t n_bytes, PackHeader H, uint64_t *off, uint64_t *toff, unsigned long long *bad)
+{
+    if (threadIdx.x || blockIdx.x) return;
+    uint64_t at = PF_HEADER, tat = 0;
+    for (uint64_t b = 0; b < H.nb; b++) {
+        off[b] = at - PF_HEADER; toff[b] = tat;
+        uint64_t pb = 0, tb = 0;
+        if (!Rule::prefix(H, b, p + at, n_bytes - at, H.text - tat, &pb, &tb)) { bad[0] = b + 1; bad[1] = at; return; }
+        at += 4 + pb; tat += tb;
+    }
+    off[H.nb] = at - PF_HEADER; toff[H.nb] = tat;
+    if (at != n_bytes || tat != H.text) { bad[0] = H.nb + (at != n_bytes ? 1 : 2); bad[1] = at != n_bytes ? at : tat; }
+}
+template <class Rule>
+static void pack_walk_device(harc_amd_ctx *c, const uint8_t *d_packed, uint64_t n_bytes, const PackHeader &H, uint64_t *d_off, uint64_t *d_toff, unsigned long long *d_bad)
+{
+    hipLaunchKernelGGL(k_pack_walk<Rule>, dim3(1), dim3(64), 0, c->stream, d_packed, n_bytes, H, d_off, d_toff, d_bad);
+}
+
+// harc_amd_<tag>unpack_host: a packed form in host memory -> its text, block after block.  text == nullptr: the size alone.  decode(H, payload, payload_bytes,
+// lines, text) is the host's block rule: 0, or the format's code of what is damaged
+template <class Decode>
+static int pack_unpack_host(const PackFormat &F, const uint8_t *packed, uint64_t n_bytes, uint8_t *text, uint64_t cap, uint64_t *n_out, Decode decode)
+{
+    char who[32]; snprintf(who, sizeof who, "%sunpack_host", F.tag);
+    if (!packed || !n_out) { harc_set_error("%s: bad arguments", who); return HARC_AMD_EINVAL; }
+    if (n_bytes < PF_HEADER) { harc_set_error("%s: %llu bytes are fewer than the %u of the header", who, (unsigned long long)n_bytes, PF_HEADER); return HARC_AMD_EINVAL; }
+    PackHeader H;
+    RC_TRY(F.parse_header(who, packed, n_bytes, &H));
+    *n_out = H.text;
+    if (!text) return HARC_AMD_OK;
+    if (cap < H.text) { harc_set_error("%s: the text takes %llu bytes, the buffer holds %llu", who, (unsigned long long)H.text, (unsigned long long)cap); return HARC_AMD_EINVAL; }
+    return pack_walk(F, who, "the packed form", H, n_bytes,
+                     [&](uint64_t at, uint8_t *q, size_t k) { memcpy(q, packed + at, k); return HARC_AMD_OK; },
+                     [&](uint64_t b, uint64_t at, uint64_t pb, uint64_t tat) {
+                         const int e = decode(H, packed + at + 4, (uint32_t)pb, pack_block_lines(H, b), text + tat);
+                         return e ? pack_refuse_damaged(F, b, at, (uint32_t)e) : HARC_AMD_OK;
+                     }, nullptr, nullptr);
 }
 
 // nb blocks at d_blocks with their offsets d_off[0 .. nb] and text offsets d_toff[0 .. nb] -> the n lines at d_text.  block0 / base: number and file offset of the
@@ -208,5 +258,111 @@ static int pack_unpack_files(const PackFormat &F, const harc_amd_params *params,
     if (tlog) fprintf(stderr, "[%spack] unpacked %llu bytes of text from %llu bytes in %llu blocks, %d pieces: %.3f s in the kernels, %.3f s waiting for the readers, %.3f s waiting for the writers\n",
                       F.tag, (unsigned long long)H.text, (unsigned long long)fsz, (unsigned long long)H.nb, npieces, t_kernel, t_read, t_write);
     outguard.ok = true;
+    return HARC_AMD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the way in: text -> blocks
+// A format's encode kernel (a workgroup of PF_T per block, lane t owns strand t) codes every block into scratch: a head that holds the PF_T u32 strand lengths
+// somewhere, and the strands.  It leaves the block's size with its u32 prefix in bsize[b], its mode (0: stored) in bmode[b] and what went wrong in err[0 .. 3].
+#define PF_T 256
+struct PackGather { uint32_t scan[PF_T / 64 + 1], soff[PF_T], slen[PF_T]; };                // the LDS of a gather kernel
+struct PackStats { uint64_t text = 0, bytes = 0, blocks = 0, mode[3] = { 0, 0, 0 }; double seconds = 0; };      // mode[0]: stored blocks
+struct PackBlocks { uint32_t nb; uint32_t *bsize, *bmode; uint64_t *boff; unsigned int *err; };                 // what pack_run allocates for every format
+
+// The coded branch of a gather kernel, behind the u32 prefix that the kernel has written at dst: the head at hdr, whose strand lengths start at lens, and the
+// strands go to their byte-granular place behind dst + 4 -- whole dwords of the destination, the bytes in front of and behind them one by one, a wave per
+// strand.  payload: the bytes of head and strands together, so that the head is what the strands leave of it.  strand(s, n): where the n > 0 bytes of strand s lie
+template <class Strand>
+__device__ __forceinline__ void pack_gather_coded(PackGather &S, uint8_t *dst, uint32_t payload, const uint8_t *hdr, const uint8_t *lens, Strand strand)
+{
+    const uint32_t t = threadIdx.x;
+    const uint32_t len = qv_le32(lens + 4u * t);
+    uint32_t total;
+    const uint32_t off = block_excl_scan_u32<PF_T>(len, S.scan, &total);
+    const uint32_t h = payload - total;
+    S.soff[t] = off; S.slen[t] = len;
+    group_copy_bytes(dst + 4, hdr, h, t, PF_T);
+    __syncthreads();
+    const uint32_t wv = t >> 6, lane = t & 63u;
+    for (uint32_t s = wv; s < PF_T; s += PF_T / 64) {
+        const uint32_t n = S.slen[s];
+        if (n) group_copy_bytes(dst + 4 + h + S.soff[s], strand(s, n), n, lane, 64);
+    }
+}
+
+// The blocks alone (no file header) of nb64 <= max_blocks blocks of text_bytes bytes of text -> d_out[0 .. *n_out); d_out == nullptr: the size alone.  Sizes are
+// needed before bytes can be placed: encode into scratch, scan the sizes, gather.  tag: "qpack" / "idpack" / "spack" in the messages.  The hooks of the format:
+//   scratch(B)    allocates its own scratch from the pool (this function brackets it) and presets err where 0 is not its neutral value
+//   encode(B)     launches its encode kernel
+//   errors(e, st) reads the four error words: a refusal with its message, or OK with the blocks of each mode added to st->mode (st may be null)
+//   gather(B, o)  launches its gather kernel to o
+template <class Scratch, class Encode, class Errors, class Gather>
+static int pack_run(harc_amd_ctx *c, const char *tag, uint64_t nb64, uint64_t max_blocks, uint64_t text_bytes, uint8_t *d_out, uint64_t out_capacity, uint64_t *n_out, PackStats *st,
+                    Scratch scratch, Encode encode, Errors errors, Gather gather)
+{
+    *n_out = 0;
+    if (nb64 > max_blocks) { harc_set_error("%s: too many blocks for one call", tag); return HARC_AMD_EINVAL; }
+    PackBlocks B = { (uint32_t)nb64, nullptr, nullptr, nullptr, nullptr };
+    const size_t nb = B.nb;
+    if (!nb) return HARC_AMD_OK;
+    PoolScope scope(c);
+    RC_TRY(dalloc(c, &B.bsize, nb + 1)); RC_TRY(dalloc(c, &B.bmode, nb)); RC_TRY(dalloc(c, &B.boff, nb + 1)); RC_TRY(dalloc(c, &B.err, 4));
+    HIP_TRY(hipMemsetAsync(B.bsize + nb, 0, 4, c->stream));
+    HIP_TRY(hipMemsetAsync(B.err, 0, 16, c->stream));
+    RC_TRY(scratch(B));
+    KernelTimer timer(st ? &st->seconds : nullptr);
+    RC_TRY(timer.begin(c->stream));
+    encode(B);
+    HIP_TRY(hipGetLastError());
+    RC_TRY(prim_excl_scan_u32_to_u64(c, B.bsize, B.boff, nb + 1));
+    uint64_t total = 0; unsigned int err[4] = { 0, 0, 0, 0 };
+    HIP_TRY(hipMemcpyAsync(&total, B.boff + nb, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(err, B.err, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    RC_TRY(errors(err, st));
+    *n_out = total;
+    if (st) { st->text += text_bytes; st->bytes += total; st->blocks += nb; }
+    if (d_out) {
+        // the size first: a buffer that is too small is refused with both numbers before a byte of it is written
+        if (out_capacity < total) { harc_set_error("%s_device: the blocks take %llu bytes, the buffer holds %llu", tag, (unsigned long long)total, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
+        gather(B, d_out);
+        HIP_TRY(hipGetLastError());
+    }
+    RC_TRY(timer.end(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                     // the scratch goes back to the pool
+    return HARC_AMD_OK;
+}
+
+// harc_amd_<tag>_device: a text in device memory -> its packed form, `head` bytes of file header (0: none) and the blocks.  d_out == nullptr: the size alone.
+// args_ok: the format's own argument check.  The hooks of the format:
+//   geometry()                 refuses a block geometry that the format cannot hold, with its message
+//   run(o, cap, &nblk, st)     its run of pack_run, behind whatever it has to build first (its pool memory inside a scope of its own)
+//   header(h)                  the PF_HEADER bytes of the file header, after the run
+//   trace(st, n)               its line for HARC_AMD_TRACE, n the bytes of the packed form
+template <class Geometry, class Run, class Header, class Trace>
+static int pack_device(const char *tag, harc_amd_ctx *c, bool args_ok, uint64_t head, uint8_t *d_out, uint64_t out_capacity, uint64_t *n_out, Geometry geometry, Run run, Header header,
+                       Trace trace)
+{
+    if (!c || !args_ok || !n_out) { harc_set_error("%s_device: bad arguments", tag); return HARC_AMD_EINVAL; }
+    RC_TRY(geometry());
+    HIP_TRY(hipSetDevice(c->P.device));
+    const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
+    PackStats st; uint64_t nblk = 0;
+    *n_out = head;
+    // the size first: a buffer that is too small is refused with both numbers before a byte of it is written
+    if (d_out && out_capacity < head) { harc_set_error("%s_device: the blocks take at least %llu bytes, the buffer holds %llu", tag, (unsigned long long)head, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
+    const int rc = run(d_out ? d_out + head : nullptr, d_out ? out_capacity - head : 0, &nblk, tlog ? &st : nullptr);
+    *n_out = head + nblk;
+    if (rc != HARC_AMD_OK) {
+        if (d_out && nblk && out_capacity - head < nblk) harc_set_error("%s_device: the packed form takes %llu bytes, the buffer holds %llu", tag, (unsigned long long)(head + nblk), (unsigned long long)out_capacity);
+        return rc;
+    }
+    if (d_out && head) {
+        uint8_t h[PF_HEADER];
+        header(h);
+        HIP_TRY(hipMemcpyAsync(d_out, h, PF_HEADER, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (tlog) trace(st, *n_out);
     return HARC_AMD_OK;
 }

@@ -7,15 +7,16 @@
 //                 frequency | cumulative << 16.  Then every lane codes its strand downwards into its slab of scratch (qv_strand_encode); the strand lengths are
 //                 scanned over the workgroup, the header, table and lengths are written in front of the slabs, and the block's size, stored or coded, is decided.
 //   (scan of the block sizes, prims.hip)
-//   k_qp_gather   a workgroup per block copies u32 payload_bytes, header and strands -- or the stored lines -- to their byte-granular place: whole dwords of the
-//                 destination inside the block, the bytes in front of and behind them one by one.  Nothing outside the blocks is written.
+//   k_qp_gather   a workgroup per block writes u32 payload_bytes and the stored lines without their newlines -- or has head and strands copied to their
+//                 byte-granular place by pack_gather_coded (packfile.h).  Nothing outside the blocks is written.
 // The lanes of a wave read 64 neighbouring lines at a stride of L + 1 bytes in all three walks over the text: the same cache lines serve the next hundred symbols.
 //
-// Unpacking.  The block offsets follow from the payload_bytes prefixes (qv_prefix: k_qp_walk, one lane; on the host the walk of packfile.h).
+// Unpacking.  The block offsets follow from the payload_bytes prefixes (QvRule over qv_prefix, for the walks of packfile.h on the host and in one lane of the device).
 //   k_qp_decode   a workgroup per block validates head, table and strand lengths into LDS (qv_check_head, qv_load_row), then a lane per strand decodes forward
 //                 (qv_strand_decode) and writes its lines, a newline behind each.  Any violation raises the error word: block number << 8 | QV_E_*.
-// The plumbing of the file calls (probes, guards, ring split, device buffers, kernel timer) is fileio.h's; the drivers of the way back -- the run of k_qp_decode, the
-// device call and the file call -- are packfile.h's, shared with idpack.hip: this file hands them QV_FORMAT.
+// The plumbing of the file calls (probes, guards, ring split, device buffers, kernel timer) is fileio.h's.  The drivers are packfile.h's, shared with idpack.hip and
+// spack.hip: pack_run and pack_device on the way in, which harc_qpack_run and harc_amd_qpack_device hand their scratch, launches, error words and messages; the host
+// call, the run of k_qp_decode, the device call and the file call on the way back, which get QV_FORMAT.
 #include "devutil.h"
 #include "qv_block.h"
 #include "qm_block.h"
@@ -31,8 +32,6 @@ struct QpShared {
     unsigned long long sum;
     uint8_t sym_of[96], byte_of[96];
 };
-struct QpGather { uint32_t scan[QP_T / 64 + 1], soff[QV_STRANDS], slen[QV_STRANDS]; };
-struct QpStats { uint64_t text = 0, bytes = 0, blocks = 0, stored = 0; double seconds = 0; };
 
 // err[0]: stride positions that hold no newline; err[1]: newlines inside a line; err[2]: strands that did not fit their slab (never); err[3]: stored blocks
 __global__ __launch_bounds__(QP_T) void k_qp_encode(const uint8_t *text, uint64_t n_lines, uint32_t L, uint32_t RB, uint32_t nb, uint8_t *scratch, uint64_t stride,
@@ -105,7 +104,7 @@ __global__ __launch_bounds__(QP_T) void k_qp_encode(const uint8_t *text, uint64_
 __global__ __launch_bounds__(QP_T) void k_qp_gather(const uint8_t *text, uint64_t n_lines, uint32_t L, uint32_t RB, uint32_t nb, const uint8_t *scratch, uint64_t stride,
                                                     uint32_t slab, const uint32_t *bsize, const uint32_t *bmode, const uint64_t *boff, uint8_t *out)
 {
-    __shared__ QpGather S;
+    __shared__ PackGather S;
     const uint64_t b = harc_bid();
     if (b >= nb) return;
     const uint32_t t = threadIdx.x;
@@ -120,35 +119,8 @@ __global__ __launch_bounds__(QP_T) void k_qp_gather(const uint8_t *text, uint64_
         for (uint32_t j = t; j < m * L; j += QP_T) { const uint32_t i = j / L; dst[5 + j] = tx[(uint64_t)i * (L + 1u) + (j - i * L)]; }
         return;
     }
-    const uint8_t *hdr = scratch + b * stride;
-    const uint32_t A = hdr[1], h = qv_hdr1(A);
-    const uint32_t len = qv_le32(hdr + h - 4u * QV_STRANDS + 4u * t);
-    uint32_t total;
-    const uint32_t off = block_excl_scan_u32<QP_T>(len, S.scan, &total);
-    S.soff[t] = off; S.slen[t] = len;
-    group_copy_bytes(dst + 4, hdr, h, t, QP_T);
-    __syncthreads();
-    const uint32_t wv = t >> 6, lane = t & 63u;
-    for (uint32_t s = wv; s < QV_STRANDS; s += QP_T / 64) {
-        const uint32_t n = S.slen[s];
-        if (n) group_copy_bytes(dst + 4 + h + S.soff[s], hdr + QP_HDR + (uint64_t)(s + 1u) * slab - n, n, lane, 64);
-    }
-}
-
-// The offsets of the nb blocks behind the 32-byte header of p[0 .. n_bytes), relative to p + 32; off[nb] = their end.  bad[0]: 1 + the first block whose prefix
-// or payload leaves the bytes (nb + 1: bytes are left behind the last block), bad[1]: its offset
-__global__ void k_qp_walk(const uint8_t *p, uint64_t n_bytes, uint64_t nb, uint64_t *off, unsigned long long *bad)
-{
-    if (threadIdx.x || blockIdx.x) return;
-    uint64_t at = QV_FILE_HEADER;
-    for (uint64_t b = 0; b < nb; b++) {
-        off[b] = at - QV_FILE_HEADER;
-        uint64_t pb = 0;
-        if (!qv_prefix(p + at, n_bytes - at, &pb)) { bad[0] = b + 1; bad[1] = at; return; }
-        at += 4 + pb;
-    }
-    off[nb] = at - QV_FILE_HEADER;
-    if (at != n_bytes) { bad[0] = nb + 1; bad[1] = at; }
+    const uint8_t *hdr = scratch + b * stride, *slabs = hdr + QP_HDR;                     // the lengths end the head; strand s ends its slab
+    pack_gather_coded(S, dst, payload, hdr, hdr + qv_hdr1(hdr[1]) - 4u * QV_STRANDS, [=](uint32_t s, uint32_t n) { return slabs + (uint64_t)(s + 1u) * slab - n; });
 }
 
 // blocks: block b of this call at blocks + off[b], off[b + 1] - off[b] bytes with its u32; lines [b RB, ..) of the n_lines lines at text
@@ -217,47 +189,30 @@ static int qp_check_geometry(const char *who, int32_t readlen, uint32_t *rb)
     if ((uint64_t)*rb * (uint64_t)readlen > QV_MAX_BLOCK_SYMBOLS) { harc_set_error("%s: %u reads of %d per block are more than %u quality values", who, *rb, readlen, QV_MAX_BLOCK_SYMBOLS); return HARC_AMD_EINVAL; }
     return HARC_AMD_OK;
 }
-// the blocks alone (no file header) -> d_out[0 .. *n_out); d_out == nullptr: the size alone
-static int harc_qpack_run(harc_amd_ctx *c, const char *d_text, uint64_t n, uint32_t L, uint32_t RB, uint8_t *d_out, uint64_t out_capacity, uint64_t *n_out, QpStats *st)
+// the blocks alone (no file header) -> d_out[0 .. *n_out); d_out == nullptr: the size alone.  Scratch of block b at scratch + b * stride: QP_HDR bytes for the
+// head, then a slab per strand
+static int harc_qpack_run(harc_amd_ctx *c, const char *d_text, uint64_t n, uint32_t L, uint32_t RB, uint8_t *d_out, uint64_t out_capacity, uint64_t *n_out, PackStats *st)
 {
-    *n_out = 0;
-    const uint64_t nb64 = qv_blocks(n, RB);
-    if (nb64 > 0x7FFFFFF0ull) { harc_set_error("qpack: too many blocks for one call"); return HARC_AMD_EINVAL; }
-    const uint32_t nb = (uint32_t)nb64;
-    if (!nb) return HARC_AMD_OK;
-    PoolScope scope(c);
+    const uint8_t *text = (const uint8_t *)d_text;
     const uint32_t mmax = n < RB ? (uint32_t)n : RB, slab = qv_slab_bytes(qv_strand_lines(mmax, 0) * L);
     const uint64_t stride = (uint64_t)QP_HDR + (uint64_t)QV_STRANDS * slab;
-    uint8_t *scratch = nullptr; uint32_t *bsize = nullptr, *bmode = nullptr; uint64_t *boff = nullptr; unsigned int *d_err = nullptr;
-    RC_TRY(dalloc(c, &scratch, (size_t)(stride * nb))); RC_TRY(dalloc(c, &bsize, (size_t)nb + 1)); RC_TRY(dalloc(c, &bmode, (size_t)nb)); RC_TRY(dalloc(c, &boff, (size_t)nb + 1));
-    RC_TRY(dalloc(c, &d_err, 4));
-    HIP_TRY(hipMemsetAsync(bsize + nb, 0, 4, c->stream));
-    HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
-    KernelTimer timer(st ? &st->seconds : nullptr);
-    RC_TRY(timer.begin(c->stream));
-    hipLaunchKernelGGL(k_qp_encode, harc_fold256(nb), dim3(QP_T), 0, c->stream, (const uint8_t *)d_text, n, L, RB, nb, scratch, stride, slab, bsize, bmode, d_err);
-    HIP_TRY(hipGetLastError());
-    RC_TRY(prim_excl_scan_u32_to_u64(c, bsize, boff, (size_t)nb + 1));
-    uint64_t total = 0; unsigned int err[4] = { 0, 0, 0, 0 };
-    HIP_TRY(hipMemcpyAsync(&total, boff + nb, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(err, d_err, 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (err[0] || err[1]) {
-        harc_set_error("qpack: the text is not lines of %u quality values: %u positions on the %u-byte stride hold no newline and %u newlines are off it", L, err[0], L + 1, err[1]);
-        return HARC_AMD_EINVAL;
-    }
-    if (err[2]) { harc_set_error("qpack: %u strands did not fit their scratch", err[2]); return HARC_AMD_EINTERNAL; }
-    *n_out = total;
-    if (st) { st->text += n * (L + 1ull); st->bytes += total; st->blocks += nb; st->stored += err[3]; }
-    if (d_out) {
-        if (out_capacity < total) { harc_set_error("qpack_device: the blocks take %llu bytes, the buffer holds %llu", (unsigned long long)total, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
-        hipLaunchKernelGGL(k_qp_gather, harc_fold256(nb), dim3(QP_T), 0, c->stream, (const uint8_t *)d_text, n, L, RB, nb, (const uint8_t *)scratch, stride, slab,
-                           (const uint32_t *)bsize, (const uint32_t *)bmode, (const uint64_t *)boff, d_out);
-        HIP_TRY(hipGetLastError());
-    }
-    RC_TRY(timer.end(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));                     // the scratch goes back to the pool
-    return HARC_AMD_OK;
+    uint8_t *scratch = nullptr;
+    return pack_run(c, "qpack", qv_blocks(n, RB), 0x7FFFFFF0ull, n * (L + 1ull), d_out, out_capacity, n_out, st,
+        [&](const PackBlocks &B) { return dalloc(c, &scratch, (size_t)(stride * B.nb)); },
+        [&](const PackBlocks &B) { hipLaunchKernelGGL(k_qp_encode, harc_fold256(B.nb), dim3(QP_T), 0, c->stream, text, n, L, RB, B.nb, scratch, stride, slab, B.bsize, B.bmode, B.err); },
+        [&](const unsigned int *err, PackStats *stats) {
+            if (err[0] || err[1]) {
+                harc_set_error("qpack: the text is not lines of %u quality values: %u positions on the %u-byte stride hold no newline and %u newlines are off it", L, err[0], L + 1, err[1]);
+                return HARC_AMD_EINVAL;
+            }
+            if (err[2]) { harc_set_error("qpack: %u strands did not fit their scratch", err[2]); return HARC_AMD_EINTERNAL; }
+            if (stats) stats->mode[0] += err[3];
+            return HARC_AMD_OK;
+        },
+        [&](const PackBlocks &B, uint8_t *out) {
+            hipLaunchKernelGGL(k_qp_gather, harc_fold256(B.nb), dim3(QP_T), 0, c->stream, text, n, L, RB, B.nb, (const uint8_t *)scratch, stride, slab, (const uint32_t *)B.bsize,
+                               (const uint32_t *)B.bmode, (const uint64_t *)B.boff, out);
+        });
 }
 
 extern "C" uint64_t harc_amd_qpack_bound(uint64_t n_reads, int32_t readlen, uint32_t reads_per_block)
@@ -269,30 +224,15 @@ extern "C" uint64_t harc_amd_qpack_bound(uint64_t n_reads, int32_t readlen, uint
 extern "C" int harc_amd_qpack_device(harc_amd_ctx *c, const char *d_text, uint64_t n_reads, int32_t readlen, uint32_t reads_per_block, int32_t flags, uint8_t *d_out,
                                      uint64_t out_capacity, uint64_t *n_out)
 {
-    if (!c || (n_reads && !d_text) || !n_out) { harc_set_error("qpack_device: bad arguments"); return HARC_AMD_EINVAL; }
     uint32_t rb = reads_per_block;
-    RC_TRY(qp_check_geometry("qpack_device", readlen, &rb));
-    HIP_TRY(hipSetDevice(c->P.device));
-    const uint64_t head = (flags & 1) ? QV_FILE_HEADER : 0;
-    const bool trace = getenv("HARC_AMD_TRACE") != nullptr;
-    QpStats st; uint64_t nblk = 0;
-    // the size first: a buffer that is too small is refused with both numbers before a byte of it is written
-    if (d_out && out_capacity < head) { harc_set_error("qpack_device: the blocks take at least %llu bytes, the buffer holds %llu", (unsigned long long)head, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
-    const int rc = harc_qpack_run(c, d_text, n_reads, (uint32_t)readlen, rb, d_out ? d_out + head : nullptr, d_out ? out_capacity - head : 0, &nblk, trace ? &st : nullptr);
-    *n_out = head + nblk;
-    if (rc != HARC_AMD_OK) {
-        if (d_out && nblk && out_capacity - head < nblk) harc_set_error("qpack_device: the packed form takes %llu bytes, the buffer holds %llu", (unsigned long long)(head + nblk), (unsigned long long)out_capacity);
-        return rc;
-    }
-    if (d_out && head) {
-        uint8_t h[QV_FILE_HEADER];
-        if (n_reads) qv_file_header(h, (uint32_t)readlen, rb, n_reads); else qv_file_header(h, 0, 0, 0);
-        HIP_TRY(hipMemcpyAsync(d_out, h, QV_FILE_HEADER, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    if (trace) fprintf(stderr, "[qpack] device call: %llu bytes of text -> %llu bytes in %llu blocks (%llu stored), kernels %.3f ms (%.1f GB/s of text)\n", (unsigned long long)st.text,
-                       (unsigned long long)*n_out, (unsigned long long)st.blocks, (unsigned long long)st.stored, 1e3 * st.seconds, st.seconds > 0 ? 1e-9 * (double)st.text / st.seconds : 0.0);
-    return HARC_AMD_OK;
+    return pack_device("qpack", c, !n_reads || d_text, (flags & 1) ? QV_FILE_HEADER : 0, d_out, out_capacity, n_out,
+        [&] { return qp_check_geometry("qpack_device", readlen, &rb); },
+        [&](uint8_t *o, uint64_t cap, uint64_t *nblk, PackStats *st) { return harc_qpack_run(c, d_text, n_reads, (uint32_t)readlen, rb, o, cap, nblk, st); },
+        [&](uint8_t *h) { if (n_reads) qv_file_header(h, (uint32_t)readlen, rb, n_reads); else qv_file_header(h, 0, 0, 0); },
+        [&](const PackStats &st, uint64_t bytes) {
+            fprintf(stderr, "[qpack] device call: %llu bytes of text -> %llu bytes in %llu blocks (%llu stored), kernels %.3f ms (%.1f GB/s of text)\n", (unsigned long long)st.text,
+                    (unsigned long long)bytes, (unsigned long long)st.blocks, (unsigned long long)st.mode[0], 1e3 * st.seconds, st.seconds > 0 ? 1e-9 * (double)st.text / st.seconds : 0.0);
+        });
 }
 
 // ------------------------------------------------------------------------------------------------ unpacking
@@ -313,13 +253,16 @@ static int qp_parse_header(const char *who, const uint8_t *h, uint64_t n_bytes, 
     H->text = H->n * (H->L + 1ull);
     return HARC_AMD_OK;
 }
-// (the text bytes of a block follow from its number, lines of H.L and their newlines, not from its prefix)
+// the prefix rule (the text bytes of a block follow from its number, lines of H.L and their newlines, not from its prefix)
+struct QvRule {
+    static __host__ __device__ int prefix(const PackHeader &H, uint64_t b, const uint8_t *q, uint64_t left, uint64_t, uint64_t *pb, uint64_t *tb)
+    {
+        *tb = pack_block_lines(H, b) * (H.L + 1ull);
+        return qv_prefix(q, left, pb);
+    }
+};
 static const PackFormat QV_FORMAT = {
-    "q", "quality", "HARC_AMD_QPACK_PIECE", 64, QV_PREFIX, qp_parse_header,
-    [](const PackHeader &H, uint64_t b, const uint8_t *q, uint64_t left, uint64_t, uint64_t *pb, uint64_t *tb) { *tb = pack_block_lines(H, b) * (H.L + 1ull); return qv_prefix(q, left, pb); },
-    [](harc_amd_ctx *c, const uint8_t *d_packed, uint64_t n_bytes, const PackHeader &H, uint64_t *d_off, uint64_t *, unsigned long long *d_bad) {
-        hipLaunchKernelGGL(k_qp_walk, dim3(1), dim3(64), 0, c->stream, d_packed, n_bytes, H.nb, d_off, d_bad);
-    },
+    "q", "quality", "HARC_AMD_QPACK_PIECE", 64, QV_PREFIX, qp_parse_header, QvRule::prefix, pack_walk_device<QvRule>,
     [](harc_amd_ctx *c, const uint8_t *d_blocks, const uint64_t *d_off, const uint64_t *, uint32_t nb, uint64_t n, const PackHeader &H, char *d_text, unsigned long long *d_errw) {
         hipLaunchKernelGGL(k_qp_decode, harc_fold256(nb), dim3(QP_T), 0, c->stream, d_blocks, d_off, nb, n, H.L, H.rb, (uint8_t *)d_text, d_errw);
     },
@@ -376,20 +319,9 @@ extern "C" int harc_amd_qpack_host(const char *text, uint64_t n_reads, int32_t r
 
 extern "C" int harc_amd_qunpack_host(const uint8_t *packed, uint64_t n_bytes, char *text, uint64_t cap, uint64_t *n_out)
 {
-    if (!packed || !n_out) { harc_set_error("qunpack_host: bad arguments"); return HARC_AMD_EINVAL; }
-    if (n_bytes < QV_FILE_HEADER) { harc_set_error("qunpack_host: %llu bytes are fewer than the %u of the header", (unsigned long long)n_bytes, QV_FILE_HEADER); return HARC_AMD_EINVAL; }
-    PackHeader H;
-    RC_TRY(qp_parse_header("qunpack_host", packed, n_bytes, &H));
-    *n_out = H.text;
-    if (!text) return HARC_AMD_OK;
-    if (cap < H.text) { harc_set_error("qunpack_host: the text takes %llu bytes, the buffer holds %llu", (unsigned long long)H.text, (unsigned long long)cap); return HARC_AMD_EINVAL; }
     std::vector<QvWork> W(1);
-    return pack_walk(QV_FORMAT, "qunpack_host", "the packed form", H, n_bytes,
-                     [&](uint64_t at, uint8_t *q, size_t k) { memcpy(q, packed + at, k); return HARC_AMD_OK; },
-                     [&](uint64_t b, uint64_t at, uint64_t pb, uint64_t tat) {
-                         const int e = qv_block_decode(packed + at + 4, (uint32_t)pb, pack_block_lines(H, b), H.L, W[0], (uint8_t *)text + tat);
-                         return e ? pack_refuse_damaged(QV_FORMAT, b, at, (uint32_t)e) : HARC_AMD_OK;
-                     }, nullptr, nullptr);
+    return pack_unpack_host(QV_FORMAT, packed, n_bytes, (uint8_t *)text, cap, n_out,
+                            [&](const PackHeader &H, const uint8_t *pl, uint32_t pb, uint32_t m, uint8_t *tx) { return qv_block_decode(pl, pb, m, H.L, W[0], tx); });
 }
 
 // ------------------------------------------------------------------------------------------------ the files
@@ -418,7 +350,7 @@ extern "C" int harc_amd_qpack_files_ex(const harc_amd_params *params, const char
     DevBuf txt{ c }, out{ c };
     const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
     double t_read = 0, t_write = 0;
-    QpStats st;
+    PackStats st;
     QmAcc acc; qm_acc_zero(&acc);
     double t_map = 0;
     uint8_t h[QV_FILE_HEADER];
@@ -451,7 +383,7 @@ extern "C" int harc_amd_qpack_files_ex(const harc_amd_params *params, const char
         char mapped[64] = "";
         if (map) snprintf(mapped, sizeof mapped, ", %.3f s in the kernels of the map", t_map);
         fprintf(stderr, "[qpack] %llu bytes of text -> %llu bytes in %llu blocks (%llu stored), %d pieces: %.3f s in the kernels, %.3f s waiting for the readers, %.3f s waiting for the writers%s\n",
-                (unsigned long long)qsz, (unsigned long long)at, (unsigned long long)nb, (unsigned long long)st.stored, npieces, st.seconds, t_read, t_write, mapped);
+                (unsigned long long)qsz, (unsigned long long)at, (unsigned long long)nb, (unsigned long long)st.mode[0], npieces, st.seconds, t_read, t_write, mapped);
     }
     outguard.ok = true;
     return HARC_AMD_OK;

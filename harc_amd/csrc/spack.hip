@@ -9,15 +9,16 @@
 //                 row, lane r row r of the order-1 table; both heads are written into scratch, the rows of mode 2 at their scanned offsets.  Then every lane
 //                 codes its strand backwards twice, with either table, into two slabs; the two sums of strand lengths are scanned and sv_choose decides.
 //   (scan of the block sizes, prims.hip)
-//   k_sp_gather   a workgroup per block copies u32 payload_bytes, the head of the chosen mode and its strands -- or the stored text -- to their
-//                 byte-granular place: whole dwords of the destination inside the block, the bytes in front of and behind them one by one.
+//   k_sp_gather   a workgroup per block writes u32 payload_bytes and the stored text behind its 9 head bytes -- or has the head of the chosen mode and its
+//                 strands copied to their byte-granular place by pack_gather_coded (packfile.h).  Nothing outside the blocks is written.
 // A lane's walk over its own strand is byte-serial and not coalesced: neighbouring lanes read text q bytes apart, as in idpack.hip (NOTES.md has the rate).
 //
-// Unpacking.  The block offsets follow from the payload_bytes prefixes (sv_prefix: k_sp_walk, one lane; on the host the walk of packfile.h).
+// Unpacking.  The block offsets follow from the payload_bytes prefixes (SvRule over sv_prefix, for the walks of packfile.h on the host and in one lane of the device).
 //   k_sp_decode   lane 0 validates the head and finds the rows (sv_check_head); a lane per row loads it (mode 1: into LDS, mode 2: into the block's 256 KiB of
 //                 scratch), a lane per strand checks its size, decodes forward (sv_strand_decode), writes its bytes and takes their CRC-32.  Any violation
 //                 raises the error word: block number << 8 | SV_E_*.
-// The drivers of the way back -- the run of k_sp_decode, the device call and the file call -- are packfile.h's: this file hands them SV_FORMAT.
+// The drivers are packfile.h's, shared with qpack.hip and idpack.hip: pack_run and pack_device on the way in, which harc_spack_run and harc_amd_spack_device hand
+// their scratch, launches, error words and messages; the host call, the run of k_sp_decode, the device call and the file call on the way back, which get SV_FORMAT.
 #include "devutil.h"
 #include "sv_block.h"
 #include "packfile.h"
@@ -33,8 +34,6 @@ struct SpShared {
     uint32_t crc, want_crc, err, verr, mode, hdr;
     unsigned long long lsum;
 };
-struct SpGather { uint32_t scan[SP_T / 64 + 1], soff[SV_STRANDS], slen[SV_STRANDS]; };
-struct SpStats { uint64_t text = 0, bytes = 0, blocks = 0, mode[3] = { 0, 0, 0 }; double seconds = 0; };
 
 // scratch of block b at scratch + b * stride: the order-1 table, the head of mode 2, the head of mode 1, 256 slabs of mode 1, 256 of mode 2.
 // err[0]: strands that did not fit their slab (never); err[1 + k]: blocks of mode k
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(SP_T) void k_sp_encode(const uint8_t *text, uint64_
 __global__ __launch_bounds__(SP_T) void k_sp_gather(const uint8_t *text, uint64_t n, uint32_t B, uint32_t nb, const uint8_t *scratch, uint64_t stride, uint32_t slab,
                                                     const uint32_t *bsize, const uint32_t *bmode, const uint32_t *bhead, const uint64_t *boff, uint8_t *out)
 {
-    __shared__ SpGather S;
+    __shared__ PackGather S;
     const uint64_t b = harc_bid();
     if (b >= nb) return;
     const uint32_t t = threadIdx.x;
@@ -121,36 +120,9 @@ __global__ __launch_bounds__(SP_T) void k_sp_gather(const uint8_t *text, uint64_
         for (uint32_t j = t; j < m; j += SP_T) dst[4u + SV_HEAD0 + j] = tx[j];
         return;
     }
+    // the head and the slabs of the chosen mode; the lengths end the head, strand s ends its slab
     const uint8_t *hdr = md == 1u ? head1 : head2, *sl = slabs + (md == 1u ? 0ull : (uint64_t)SV_STRANDS * slab);
-    const uint32_t h = bhead[b];
-    const uint32_t len = qv_le32(hdr + h - SV_LENS + 4u * t);
-    uint32_t total;
-    const uint32_t off = block_excl_scan_u32<SP_T>(len, S.scan, &total);
-    S.soff[t] = off; S.slen[t] = len;
-    group_copy_bytes(dst + 4, hdr, h, t, SP_T);
-    __syncthreads();
-    const uint32_t wv = t >> 6, lane = t & 63u;
-    for (uint32_t s = wv; s < SV_STRANDS; s += SP_T / 64) {
-        const uint32_t k = S.slen[s];
-        if (k) group_copy_bytes(dst + 4 + h + S.soff[s], sl + (uint64_t)(s + 1u) * slab - k, k, lane, 64);
-    }
-}
-
-// The offsets of the nb blocks behind the 32-byte header of p[0 .. n_bytes), relative to p + 32, and of their text; off[nb] / toff[nb] = their ends.
-// bad[0]: 1 + the first block whose prefix or payload leaves the bytes or whose text bytes are not its share of the n text bytes (nb + 1: bytes are left behind
-// the last block), bad[1]: its offset
-__global__ void k_sp_walk(const uint8_t *p, uint64_t n_bytes, uint64_t nb, uint64_t n, uint32_t B, uint64_t *off, uint64_t *toff, unsigned long long *bad)
-{
-    if (threadIdx.x || blockIdx.x) return;
-    uint64_t at = SV_FILE_HEADER, tat = 0;
-    for (uint64_t b = 0; b < nb; b++) {
-        off[b] = at - SV_FILE_HEADER; toff[b] = tat;
-        uint64_t pb = 0, tb = 0;
-        if (!sv_prefix(p + at, n_bytes - at, sv_block_text(n, B, b), &pb, &tb)) { bad[0] = b + 1; bad[1] = at; return; }
-        at += 4 + pb; tat += tb;
-    }
-    off[nb] = at - SV_FILE_HEADER; toff[nb] = tat;
-    if (at != n_bytes) { bad[0] = nb + 1; bad[1] = at; }
+    pack_gather_coded(S, dst, payload, hdr, hdr + bhead[b] - SV_LENS, [=](uint32_t s, uint32_t k) { return sl + (uint64_t)(s + 1u) * slab - k; });
 }
 
 // blocks: block b of this call at blocks + off[b], off[b + 1] - off[b] bytes with its u32; its text at text + toff[b], toff[b + 1] - toff[b] bytes (the walk has
@@ -231,42 +203,23 @@ static int sp_check_block(const char *who, uint32_t *B)
     return HARC_AMD_OK;
 }
 // the blocks alone (no file header) -> d_out[0 .. *n_out); d_out == nullptr: the size alone
-static int harc_spack_run(harc_amd_ctx *c, const uint8_t *d_text, uint64_t n, uint32_t B, uint8_t *d_out, uint64_t out_capacity, uint64_t *n_out, SpStats *st)
+static int harc_spack_run(harc_amd_ctx *c, const uint8_t *d_text, uint64_t n, uint32_t B, uint8_t *d_out, uint64_t out_capacity, uint64_t *n_out, PackStats *st)
 {
-    *n_out = 0;
-    const uint64_t nb64 = sv_blocks(n, B);
-    if (nb64 > 0x7FFFFFF0ull) { harc_set_error("spack: too many blocks for one call"); return HARC_AMD_EINVAL; }
-    const uint32_t nb = (uint32_t)nb64;
-    if (!nb) return HARC_AMD_OK;
-    PoolScope scope(c);
     const uint32_t mmax = n < B ? (uint32_t)n : B, slab = sv_slab_bytes(mmax);
     const uint64_t stride = (uint64_t)SP_TAB + SP_HEAD2 + SP_HEAD1 + 2ull * SV_STRANDS * slab;
-    uint8_t *scratch = nullptr; uint32_t *bsize = nullptr, *bmode = nullptr, *bhead = nullptr; uint64_t *boff = nullptr; unsigned int *d_err = nullptr;
-    RC_TRY(dalloc(c, &scratch, (size_t)(stride * nb))); RC_TRY(dalloc(c, &bsize, (size_t)nb + 1)); RC_TRY(dalloc(c, &bmode, (size_t)nb)); RC_TRY(dalloc(c, &bhead, (size_t)nb));
-    RC_TRY(dalloc(c, &boff, (size_t)nb + 1)); RC_TRY(dalloc(c, &d_err, 4));
-    HIP_TRY(hipMemsetAsync(bsize + nb, 0, 4, c->stream));
-    HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
-    KernelTimer timer(st ? &st->seconds : nullptr);
-    RC_TRY(timer.begin(c->stream));
-    hipLaunchKernelGGL(k_sp_encode, harc_fold256(nb), dim3(SP_T), 0, c->stream, d_text, n, B, nb, scratch, stride, slab, bsize, bmode, bhead, d_err);
-    HIP_TRY(hipGetLastError());
-    RC_TRY(prim_excl_scan_u32_to_u64(c, bsize, boff, (size_t)nb + 1));
-    uint64_t total = 0; unsigned int err[4] = { 0, 0, 0, 0 };
-    HIP_TRY(hipMemcpyAsync(&total, boff + nb, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(err, d_err, 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (err[0]) { harc_set_error("spack: %u strands did not fit their scratch", err[0]); return HARC_AMD_EINTERNAL; }
-    *n_out = total;
-    if (st) { st->text += n; st->bytes += total; st->blocks += nb; for (int k = 0; k < 3; k++) st->mode[k] += err[1 + k]; }
-    if (d_out) {
-        if (out_capacity < total) { harc_set_error("spack_device: the blocks take %llu bytes, the buffer holds %llu", (unsigned long long)total, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
-        hipLaunchKernelGGL(k_sp_gather, harc_fold256(nb), dim3(SP_T), 0, c->stream, d_text, n, B, nb, (const uint8_t *)scratch, stride, slab, (const uint32_t *)bsize,
-                           (const uint32_t *)bmode, (const uint32_t *)bhead, (const uint64_t *)boff, d_out);
-        HIP_TRY(hipGetLastError());
-    }
-    RC_TRY(timer.end(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));                     // the scratch goes back to the pool
-    return HARC_AMD_OK;
+    uint8_t *scratch = nullptr; uint32_t *bhead = nullptr;
+    return pack_run(c, "spack", sv_blocks(n, B), 0x7FFFFFF0ull, n, d_out, out_capacity, n_out, st,
+        [&](const PackBlocks &P) -> int { RC_TRY(dalloc(c, &scratch, (size_t)(stride * P.nb))); return dalloc(c, &bhead, (size_t)P.nb); },
+        [&](const PackBlocks &P) { hipLaunchKernelGGL(k_sp_encode, harc_fold256(P.nb), dim3(SP_T), 0, c->stream, d_text, n, B, P.nb, scratch, stride, slab, P.bsize, P.bmode, bhead, P.err); },
+        [&](const unsigned int *err, PackStats *stats) {
+            if (err[0]) { harc_set_error("spack: %u strands did not fit their scratch", err[0]); return HARC_AMD_EINTERNAL; }
+            if (stats) for (int k = 0; k < 3; k++) stats->mode[k] += err[1 + k];
+            return HARC_AMD_OK;
+        },
+        [&](const PackBlocks &P, uint8_t *out) {
+            hipLaunchKernelGGL(k_sp_gather, harc_fold256(P.nb), dim3(SP_T), 0, c->stream, d_text, n, B, P.nb, (const uint8_t *)scratch, stride, slab, (const uint32_t *)P.bsize,
+                               (const uint32_t *)P.bmode, (const uint32_t *)bhead, (const uint64_t *)P.boff, out);
+        });
 }
 
 extern "C" uint64_t harc_amd_spack_bound(uint64_t text_bytes, uint32_t block_bytes) { return sv_bound(text_bytes, block_bytes ? block_bytes : SV_DEFAULT_B); }
@@ -274,31 +227,16 @@ extern "C" uint64_t harc_amd_spack_bound(uint64_t text_bytes, uint32_t block_byt
 extern "C" int harc_amd_spack_device(harc_amd_ctx *c, const uint8_t *d_text, uint64_t text_bytes, uint32_t block_bytes, int32_t flags, uint8_t *d_out, uint64_t out_capacity,
                                      uint64_t *n_out)
 {
-    if (!c || (text_bytes && !d_text) || !n_out) { harc_set_error("spack_device: bad arguments"); return HARC_AMD_EINVAL; }
     uint32_t B = block_bytes;
-    RC_TRY(sp_check_block("spack_device", &B));
-    HIP_TRY(hipSetDevice(c->P.device));
-    const uint64_t head = (flags & 1) ? SV_FILE_HEADER : 0;
-    const bool trace = getenv("HARC_AMD_TRACE") != nullptr;
-    SpStats st; uint64_t nblk = 0;
-    // the size first: a buffer that is too small is refused with both numbers before a byte of it is written
-    if (d_out && out_capacity < head) { harc_set_error("spack_device: the blocks take at least %llu bytes, the buffer holds %llu", (unsigned long long)head, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
-    const int rc = harc_spack_run(c, d_text, text_bytes, B, d_out ? d_out + head : nullptr, d_out ? out_capacity - head : 0, &nblk, trace ? &st : nullptr);
-    *n_out = head + nblk;
-    if (rc != HARC_AMD_OK) {
-        if (d_out && nblk && out_capacity - head < nblk) harc_set_error("spack_device: the packed form takes %llu bytes, the buffer holds %llu", (unsigned long long)(head + nblk), (unsigned long long)out_capacity);
-        return rc;
-    }
-    if (d_out && head) {
-        uint8_t h[SV_FILE_HEADER];
-        sv_file_header(h, B, text_bytes);
-        HIP_TRY(hipMemcpyAsync(d_out, h, SV_FILE_HEADER, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    if (trace) fprintf(stderr, "[spack] device call: %llu bytes of text -> %llu bytes in %llu blocks (%llu stored, %llu order 0, %llu order 1), kernels %.3f ms (%.2f GB/s of text)\n",
-                       (unsigned long long)text_bytes, (unsigned long long)*n_out, (unsigned long long)st.blocks, (unsigned long long)st.mode[0], (unsigned long long)st.mode[1],
-                       (unsigned long long)st.mode[2], 1e3 * st.seconds, st.seconds > 0 ? 1e-9 * (double)st.text / st.seconds : 0.0);
-    return HARC_AMD_OK;
+    return pack_device("spack", c, !text_bytes || d_text, (flags & 1) ? SV_FILE_HEADER : 0, d_out, out_capacity, n_out,
+        [&] { return sp_check_block("spack_device", &B); },
+        [&](uint8_t *o, uint64_t cap, uint64_t *nblk, PackStats *st) { return harc_spack_run(c, d_text, text_bytes, B, o, cap, nblk, st); },
+        [&](uint8_t *h) { sv_file_header(h, B, text_bytes); },
+        [&](const PackStats &st, uint64_t bytes) {
+            fprintf(stderr, "[spack] device call: %llu bytes of text -> %llu bytes in %llu blocks (%llu stored, %llu order 0, %llu order 1), kernels %.3f ms (%.2f GB/s of text)\n",
+                    (unsigned long long)text_bytes, (unsigned long long)bytes, (unsigned long long)st.blocks, (unsigned long long)st.mode[0], (unsigned long long)st.mode[1],
+                    (unsigned long long)st.mode[2], 1e3 * st.seconds, st.seconds > 0 ? 1e-9 * (double)st.text / st.seconds : 0.0);
+        });
 }
 
 // ------------------------------------------------------------------------------------------------ unpacking
@@ -318,12 +256,15 @@ static int sp_parse_header(const char *who, const uint8_t *h, uint64_t n_bytes, 
     if (H->nb > (n_bytes - SV_FILE_HEADER) / SV_PREFIX) { harc_set_error("%s: the header announces %llu blocks, %llu bytes cannot hold them", who, (unsigned long long)H->nb, (unsigned long long)n_bytes); return HARC_AMD_EINVAL; }
     return HARC_AMD_OK;
 }
+// the prefix rule (the text bytes behind the payload bytes of a block are held to its share of the text)
+struct SvRule {
+    static __host__ __device__ int prefix(const PackHeader &H, uint64_t b, const uint8_t *q, uint64_t left, uint64_t, uint64_t *pb, uint64_t *tb)
+    {
+        return sv_prefix(q, left, pack_block_lines(H, b), pb, tb);
+    }
+};
 static const PackFormat SV_FORMAT = {
-    "s", "stream", "HARC_AMD_SPACK_PIECE", 64, SV_PREFIX, sp_parse_header,
-    [](const PackHeader &H, uint64_t b, const uint8_t *q, uint64_t left, uint64_t, uint64_t *pb, uint64_t *tb) { return sv_prefix(q, left, pack_block_lines(H, b), pb, tb); },
-    [](harc_amd_ctx *c, const uint8_t *d_packed, uint64_t n_bytes, const PackHeader &H, uint64_t *d_off, uint64_t *d_toff, unsigned long long *d_bad) {
-        hipLaunchKernelGGL(k_sp_walk, dim3(1), dim3(64), 0, c->stream, d_packed, n_bytes, H.nb, H.n, H.rb, d_off, d_toff, d_bad);
-    },
+    "s", "stream", "HARC_AMD_SPACK_PIECE", 64, SV_PREFIX, sp_parse_header, SvRule::prefix, pack_walk_device<SvRule>,
     [](harc_amd_ctx *c, const uint8_t *d_blocks, const uint64_t *d_off, const uint64_t *d_toff, uint32_t nb, uint64_t, const PackHeader &, char *d_text, unsigned long long *d_errw) {
         uint8_t *tabs = nullptr;                                   // (inside the pool scope of pack_unpack_run)
         if (dalloc(c, &tabs, (size_t)nb * SP_TAB) != HARC_AMD_OK) { (void)hipMemsetAsync(d_errw, 0, 8, c->stream); return; }      // block 0, code 0
@@ -365,20 +306,9 @@ extern "C" int harc_amd_spack_host(const uint8_t *text, uint64_t text_bytes, uin
 
 extern "C" int harc_amd_sunpack_host(const uint8_t *packed, uint64_t n_bytes, uint8_t *text, uint64_t cap, uint64_t *n_out)
 {
-    if (!packed || !n_out) { harc_set_error("sunpack_host: bad arguments"); return HARC_AMD_EINVAL; }
-    if (n_bytes < SV_FILE_HEADER) { harc_set_error("sunpack_host: %llu bytes are fewer than the %u of the header", (unsigned long long)n_bytes, SV_FILE_HEADER); return HARC_AMD_EINVAL; }
-    PackHeader H;
-    RC_TRY(sp_parse_header("sunpack_host", packed, n_bytes, &H));
-    *n_out = H.text;
-    if (!text) return HARC_AMD_OK;
-    if (cap < H.text) { harc_set_error("sunpack_host: the text takes %llu bytes, the buffer holds %llu", (unsigned long long)H.text, (unsigned long long)cap); return HARC_AMD_EINVAL; }
     std::vector<SvWork> W(1);
-    return pack_walk(SV_FORMAT, "sunpack_host", "the packed form", H, n_bytes,
-                     [&](uint64_t at, uint8_t *q, size_t k) { memcpy(q, packed + at, k); return HARC_AMD_OK; },
-                     [&](uint64_t b, uint64_t at, uint64_t pb, uint64_t tat) {
-                         const int e = sv_block_decode(packed + at + 4, (uint32_t)pb, pack_block_lines(H, b), W[0], text + tat);
-                         return e ? pack_refuse_damaged(SV_FORMAT, b, at, (uint32_t)e) : HARC_AMD_OK;
-                     }, nullptr, nullptr);
+    return pack_unpack_host(SV_FORMAT, packed, n_bytes, text, cap, n_out,
+                            [&](const PackHeader &, const uint8_t *pl, uint32_t pb, uint32_t m, uint8_t *tx) { return sv_block_decode(pl, pb, m, W[0], tx); });
 }
 
 // ------------------------------------------------------------------------------------------------ the files
@@ -397,7 +327,7 @@ static int sp_pack_file(harc_amd_ctx *c, const char *in_path, const char *out_pa
     DevBuf txt{ c }, out{ c };
     const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
     double t_read = 0, t_write = 0;
-    SpStats st;
+    PackStats st;
     uint8_t h[SV_FILE_HEADER];
     sv_file_header(h, B, isz);
     uint64_t at = SV_FILE_HEADER; int npieces = 0;

@@ -1,5 +1,6 @@
 """BGZF input without a GPU: the member decoder of harc_amd/csrc/inflate_member.h built for the host with g++ and AddressSanitizer /
-UBSan and fuzzed against zlib (the same source the inflate kernel compiles), and the refusals that come before any device call."""
+UBSan and fuzzed against zlib (the same source the inflate kernel compiles), run on crafted members that zlib's encoder never writes
+(tests/foreign_deflate_cases.py), and the refusals that come before any device call."""
 import os
 import random
 import shutil
@@ -11,6 +12,8 @@ import gzip
 import pytest
 
 from tests import bgzf_util as bu
+from tests import deflate_craft as dc
+from tests import foreign_deflate_cases as fc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -78,9 +81,29 @@ def decoder(tmp_path_factory):
     return run
 
 
+def _specials():
+    """texts with matches at distance 1, of length 258 and as far back as zlib's encoder goes: within its window less 262 bytes (MAX_DIST), 32 506 at the most"""
+    specials = [b"A" * 65536, b"AC" * 32768, bytes(range(256)) * 128 + b"x" * 32768, os.urandom(32768)[:100] + b"\0" * 200 + b"Q" * 258,
+                (b"@" + os.urandom(16).hex().encode() + b"\n") * 1000]
+    half = bytes(random.Random(11).getrandbits(8) for _ in range(32768))
+    specials.append(b"ACGT" * 64 + half[:32000] + b"ACGT" * 64)                # a match 32 000+ back
+    specials.append(half[:20000] + b"\n" + half[:20000])                      # distance 20 001
+    specials.append(b"Z" + bytes(32767) + b"Z" + bytes(258))                   # a period of 32 768 that zlib codes at distance 1
+    out = []
+    for s in specials:
+        for level in (1, 6, 9):
+            for strat in ("default", "fixed", "rle"):
+                try:
+                    out.append((s, bu.member(s, level, strat, extra_before=b"XY\x03\x00abc" if level == 6 else b"")))
+                except ValueError:
+                    pass
+    return out
+
+
 def valid_corpus():
-    """(text, member bytes): FASTQ-like and random text, levels 0-9, every zlib strategy, sizes 0 / 1 / 65 280 / 65 536, matches at distance
-    1 and 32 768 and of length 258, extra subfields in front of BC"""
+    """(text, member bytes): FASTQ-like and random text, levels 0-9, every zlib strategy, sizes 0 / 1 / 65 280 / 65 536, matches at distance 1, up to
+    32 506 back (zlib's farthest) and of length 258, extra subfields in front of BC, and one member that zlib does not write: matches of length 258 at
+    distance 32 768 (far_32768 of tests/foreign_deflate_cases.py)"""
     rng = random.Random(7)
     fq = bu.fastq_text(1200, 100, seed=3)
     out = []
@@ -98,21 +121,18 @@ def valid_corpus():
                         out.append((text, bu.member(text, level, strat)))
                     except ValueError:                            # incompressible 64 KiB does not fit one member (bgzip uses 65 280)
                         pass
-    specials = [b"A" * 65536, b"AC" * 32768, bytes(range(256)) * 128 + b"x" * 32768, os.urandom(32768)[:100] + b"\0" * 200 + b"Q" * 258,
-                (b"@" + os.urandom(16).hex().encode() + b"\n") * 1000]
-    half = bytes(random.Random(11).getrandbits(8) for _ in range(32768))
-    specials.append(b"ACGT" * 64 + half[:32000] + b"ACGT" * 64)                # a match 32 000+ back
-    specials.append(half[:20000] + b"\n" + half[:20000])                      # distance 20 001
-    specials.append(b"Z" + bytes(32767) + b"Z" + bytes(258))                   # distance 32 768
-    for s in specials:
-        for level in (1, 6, 9):
-            for strat in ("default", "fixed", "rle"):
-                try:
-                    out.append((s, bu.member(s, level, strat, extra_before=b"XY\x03\x00abc" if level == 6 else b"")))
-                except ValueError:
-                    pass
+    out += _specials()
+    m, text = fc.bgzf_members()["far_32768"]
+    out.append((text, m))
     out.append((b"", bu.EOF_MARKER))
     return out
+
+
+def test_the_corpus_reaches_32768_only_in_its_crafted_member():
+    far = [dc.max_distance(blocks) for _, m in _specials() for blocks in dc.gz_tokens(m)]
+    assert max(far) <= 32506, max(far)
+    (blocks,) = dc.gz_tokens(valid_corpus()[-2][1])
+    assert (258, 32768) in [t for blk in blocks for t in blk["tokens"]]
 
 
 def test_host_decoder_equals_zlib_on_valid_members(decoder):
@@ -200,6 +220,21 @@ def test_host_decoder_accepts_a_block_without_distance_codes(decoder):
     texts = [b"A", b"AC" * 300, b"CCCA" * 1000, b""]
     res = decoder([_literal_only_member(t) for t in texts])
     assert [r for r in res] == [(0, t) for t in texts]
+
+
+def test_host_decoder_on_crafted_members_under_sanitizers(decoder):
+    """streams that zlib does not write, each as the CDATA of one member: full tables with 15-bit codes and a run of code 16 that crosses from one tree into
+    the other, runs of zeros that cross, a single distance code, no distance code, a block of end-of-block alone, empty blocks of every type, distance
+    32 768; and the headers and symbols that zlib refuses, each with the code of its kind"""
+    good = fc.bgzf_members()
+    (blocks,) = dc.gz_tokens(good["full_tables"][0])
+    assert all((b["hlit"], b["hdist"], b["maxbits"], b["cross"]) == (29, 29, (15, 15), 16) for b in blocks[:4]) and {b["cross_at"] for b in blocks[:4]} == {-1, 0}
+    assert {b["cross"] for b in dc.gz_tokens(good["far_32768"][0])[0]} == {None, 17, 18}
+    bad = fc.bgzf_refused_members()
+    res = decoder([m for m, _ in good.values()] + list(bad.values()))
+    assert res[:len(good)] == [(0, text) for _, text in good.values()], [(n, rc) for n, (rc, _) in zip(good, res) if rc]
+    want = {"hlit": 4, "hdis": 4, "repe": 4, "run_": 4, "litl": 4, "fixe": 5, "stor": 3, "dist": 6}     # IM_E_CODES, IM_E_SYMBOL, IM_E_STORED, IM_E_DIST
+    assert [rc for rc, _ in res[len(good):]] == [want[n[:4]] for n in bad], list(zip(bad, res[len(good):]))
 
 
 def test_host_decoder_rejects_mutations_under_sanitizers(decoder):

@@ -1,6 +1,8 @@
 """Plain gzip input without a GPU: the chunked inflate of harc_amd/csrc/inflate_stream.h built for the host with g++ and AddressSanitizer / UBSan into a
 stand-alone driver and fuzzed against zlib (the same source the kernels compile), harc_amd_gunzip_host (the restatement that the device is held to) on every
-case of tests/gunzip_cases.py, the paths it takes (starts found in parallel, repairs, dropped starts), the refusals, and ./harc with stand-in stage programs."""
+case of tests/gunzip_cases.py, the paths it takes (starts found in parallel, repairs, dropped starts), the refusals, and ./harc with stand-in stage programs.
+Both the driver and harc_amd_gunzip_host also run the streams of tests/foreign_deflate_cases.py, which zlib's encoder never writes, and the facts that give those
+streams their names are stated here with the token reader of tests/deflate_craft.py."""
 import gzip
 import os
 import random
@@ -16,6 +18,8 @@ import zlib
 import pytest
 
 from tests import bgzf_util as bu
+from tests import deflate_craft as dc
+from tests import foreign_deflate_cases as fc
 from tests import gunzip_cases as gc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -197,6 +201,154 @@ def test_driver_refuses_bit_flips_under_sanitizers(decoder):
         if not free:
             strict += 1; refused += rc != 0
     assert refused >= 0.95 * strict, (refused, strict)
+
+
+# ---------------------------------------------------------------------------------------------------------------- streams that zlib never writes
+FOREIGN_CHUNKS = (64, 257, 1000, 4099, 32768, 1 << 18)
+HOST_CHUNKS = (64, 1000, 32768, 0)
+
+
+def _all_tokens(blocks):
+    return [t for blk in blocks for t in blk["tokens"]]
+
+
+def test_zlib_streams_stop_at_distance_32506():
+    """what the crafted streams are for: zlib's encoder keeps a match within its window less 262 bytes (MAX_DIST), so no case of tests/gunzip_cases.py reaches
+    indices 0 to 261 of the window in front of a walk"""
+    far = {name: max(dc.max_distance(blocks) for blocks in dc.gz_tokens(blob)) for name, (blob, _) in gc.valid_cases().items()}
+    assert max(far.values()) <= 32506, far
+
+
+def test_foreign_families_hold_what_their_names_say():
+    """facts about the streams of tests/foreign_deflate_cases.py, read back with the token reader"""
+    got = {name: dc.gz_tokens(blob) for name, (blob, _) in fc.valid_cases().items()}
+    for name, ms in got.items():                                    # the reader sees the text that zlib sees
+        assert b"".join(dc.expand(_all_tokens(blocks)) for blocks in ms) == fc.valid_cases()[name][1], name
+    for D in fc.FAR:
+        (blocks,) = got[f"far_{D}"]
+        lit, rest = [b for b in blocks if not any(isinstance(t, tuple) for t in b["tokens"])], blocks[-6:]
+        assert len(lit) + 6 == len(blocks) and all(b["type"] == 2 and not b["final"] and 200 <= len(b["tokens"]) <= 900 for b in lit), D
+        assert sum(len(b["tokens"]) for b in lit) == D + 3000
+        assert {b["maxbits"][0] == 15 for b in lit} == {True, False} and {b["cross"] for b in lit} == {None, 17, 18}
+        assert {b["ncodes"][1] for b in lit} >= {0, 2}              # no distance code at all, and codes that nothing uses
+        assert [b["tokens"] for b in rest] == [[(L, D)] for L in (3, 258, 4, 257, 130)] + [[(258, D), (258, 1), (258, D), (3, D)]]
+        assert all(b["ncodes"] == (2, 1) for b in rest[:5]) and rest[-1]["final"]
+        assert dc.max_distance(blocks) == D
+    (blocks,) = got["full_tables"]
+    assert len(blocks) == 5 and all((b["hlit"], b["hdist"], b["maxbits"], b["ncodes"], b["cross"]) == (29, 29, (15, 15), (286, 30), 16) for b in blocks[:4])
+    assert [b["cross_at"] for b in blocks[:4]] == [-1, 0, -1, 0]    # a run of code 16 over the boundary, and one that starts on it and repeats the other tree's length
+    (blocks,) = got["one_dist_and_empties"]
+    assert [b["type"] for b in blocks] == [2, 2, 2, 0, 1, 2]
+    assert blocks[0]["ncodes"][1] == 1 and dc.max_distance(blocks[:1]) == 3
+    assert blocks[1]["ncodes"][1] == 0 and len(blocks[1]["tokens"]) > 100
+    assert blocks[2]["ncodes"] == (1, 0) and blocks[2]["maxbits"] == (1, 0)
+    assert [blocks[k]["tokens"] for k in (2, 3, 4)] == [[], [], []]
+    assert blocks[5]["tokens"] == [88] + [(258, 1)] * 300 and blocks[5]["ncodes"] == (3, 1)
+    (blocks,) = got["pigz_like"]
+    assert [b["type"] for b in blocks] == [2, 0, 0] * 5 + [1] and all(not b["tokens"] for b in blocks if b["type"] != 2) and blocks[-1]["final"]
+    (blocks,) = got["empty_walks"]
+    runs, k = [], 0
+    while k < len(blocks):
+        j = k
+        while j < len(blocks) and blocks[j]["type"] == 0 and not blocks[j]["tokens"]:
+            j += 1
+        if j > k:
+            runs.append((k, j)); k = j
+        else:
+            k += 1
+    assert [j - k for k, j in runs] == [60, 60]
+    for k, j in runs:                                               # longer than a chunk of 64 or 100 bytes, and the match behind them reaches over them
+        assert blocks[j]["bit"] - blocks[k]["bit"] >= 300 * 8 - 7
+        assert blocks[j]["tokens"][0][1] > 1
+    assert blocks[runs[0][1]]["tokens"][0] == (100, 1500) and blocks[runs[1][1]]["tokens"][0] == (258, 1800)
+    (blocks,) = got["stored_65535"]
+    assert [(b["type"], len(b["tokens"])) for b in blocks] == [(0, 65535), (2, 10), (0, 65535), (1, 2), (0, 0)] and blocks[-1]["final"]
+    assert blocks[1]["tokens"] == [(258, 32768)] * 10 and blocks[3]["tokens"] == [(258, 32768), (3, 32768)]
+    assert len(fc.valid_cases()["stored_65535"][0]) > 1024 * 64    # more chunks of 64 bytes than the finder has waves
+    (blocks,) = got["starts_behind_1024_chunks"]
+    assert [b["type"] for b in blocks] == [0, 0] + [2] * 7 and [b["final"] for b in blocks] == [0] * 8 + [1]
+    at = [(10 * 8 + b["bit"]) // 8 // 64 for b in blocks[2:]]       # the chunk of 64 bytes that holds each start
+    assert at[0] >= 2048 and all(y > x for x, y in zip(at, at[1:])), at      # chunk 0 has the member's start: the finder's wave for chunk k is k - 1
+    (blocks,) = got["fixed_only_far"]
+    assert all(b["type"] == 1 for b in blocks) and dc.max_distance(blocks) == 32768
+    first, second = got["two_members"]
+    assert dc.max_distance(first) <= 32506 and dc.max_distance(second) == 32768
+
+
+def test_driver_on_foreign_streams_under_sanitizers(decoder):
+    """every family of tests/foreign_deflate_cases.py at six chunk sizes: the text that zlib gives, or for a stream that zlib refuses a code other than 0"""
+    cases, want = [], []
+    for name, (blob, text) in fc.valid_cases().items():
+        for cb in FOREIGN_CHUNKS:
+            cases.append((blob, cb)); want.append((name, cb, text))
+    for name, (blob, _, _, _) in fc.refused_cases().items():
+        for cb in FOREIGN_CHUNKS:
+            cases.append((blob, cb)); want.append((name, cb, None))
+    res = decoder(cases)
+    bad = [(name, cb, rc) for (name, cb, text), (rc, got) in zip(want, res) if (rc != 0 or got != text) if text is not None]
+    assert not bad, bad[:8]
+    bad = [(name, cb) for (name, cb, text), (rc, got) in zip(want, res) if text is None and rc == 0]
+    assert not bad, bad[:8]
+
+
+def _stats_hold(st, blob, text, cb):
+    ms = dc.gz_tokens(blob)
+    assert st["members"] == len(ms) and st["text_bytes"] == len(text), st
+    assert st["starts_dropped"] <= st["starts_found"] <= st["chunks"], st
+    assert len(ms) <= st["chunks"] <= len(ms) * ((len(blob) + cb - 1) // cb), st     # a member's chunks are cut from its header to the end of the input
+    assert st["repair_walks"] <= sum(len(blocks) for blocks in ms), st              # a repair takes the chain over a block at least
+
+
+@pytest.mark.parametrize("name", sorted(fc.valid_cases()))
+def test_gunzip_host_returns_the_text_of_foreign_streams(name):
+    import harc_amd
+    blob, text = fc.valid_cases()[name]
+    for cb in HOST_CHUNKS:
+        got, st = harc_amd.gunzip_host(blob, cb)
+        assert got == text, (name, cb, st)
+        _stats_hold(st, blob, text, cb or 256 << 10)
+
+
+def test_the_chain_lands_on_starts_behind_1024_chunks():
+    """what makes the finder's stride visible in the statistics that the device is held to: of the six non-final dynamic blocks that start in chunks 2048 and up,
+    each alone in its chunk, at least five are found and used (a bit offset in front of one, in the same chunk, may parse as a header by accident)"""
+    import harc_amd
+    blob, text = fc.valid_cases()["starts_behind_1024_chunks"]
+    got, st = harc_amd.gunzip_host(blob, 64)
+    assert got == text and st["chunks"] > 2048 and st["starts_found"] - st["starts_dropped"] >= 5, st
+
+
+@pytest.mark.parametrize("name", sorted(fc.refused_cases()))
+def test_gunzip_host_refuses_what_zlib_refuses(name):
+    """every refusal names a compressed byte inside the input; with the whole input in one chunk it is a byte of the first block of the member that is refused: a
+    decode error is reported where it showed, a distance before the member's start at the first byte of the walk, and both lie in that block"""
+    import harc_amd
+    blob, lo, hi, _ = fc.refused_cases()[name]
+    for cb in HOST_CHUNKS:
+        with pytest.raises(harc_amd.HarcAmdError) as e:
+            harc_amd.gunzip_host(blob, cb)
+        m = re.search(r"compressed byte (\d+)", str(e.value))
+        assert e.value.code == -1 and m and int(m.group(1)) <= len(blob), (cb, str(e.value))
+        if cb == 0:
+            assert lo <= int(m.group(1)) <= hi, (lo, hi, str(e.value))
+
+
+@pytest.mark.parametrize("D", fc.FAR)
+def test_gunzip_host_budget_turns_carry_the_window(D, monkeypatch):
+    """HARC_AMD_GUNZIP_BUDGET cuts a member's text into turns, and the window goes from turn to turn in GzState::win.  A cut shows in the statistics: the chunks
+    behind it are counted again.  At chunks of 1000 bytes and a budget of 41 000 the text of these streams (D + 4429 bytes, 37 197 at most) fits one turn.  35 000
+    cuts the longer ones inside their D + 3000 literals: a walk there holds the literals of less than 1000 compressed bytes and of one more block, some 2000, so
+    the first turn leaves a full window.  At chunks of 64 bytes a walk is one literal block, a budget of exactly the D + 3000 literals ends the first turn
+    behind the last of them, and the second turn's first token is (3, D): with D = 32 768 it reads byte 0 of the carried window"""
+    import harc_amd
+    blob, text = fc.valid_cases()[f"far_{D}"]
+    plain = {cb: harc_amd.gunzip_host(blob, cb)[1] for cb in (64, 1000)}
+    for cb, budget in ((1000, 41000), (1000, 35000), (64, D + 3000)):
+        monkeypatch.setenv("HARC_AMD_GUNZIP_BUDGET", str(budget))
+        got, st = harc_amd.gunzip_host(blob, cb)
+        assert got == text, (cb, budget)
+        assert (st["chunks"] > plain[cb]["chunks"]) == (len(text) > budget), (cb, budget, st, plain[cb])
+        assert (st["members"], st["text_bytes"]) == (1, len(text))
 
 
 @pytest.mark.parametrize("name", sorted(gc.valid_cases()))

@@ -12,7 +12,7 @@ from .api import (HarcAmd, HarcAmdError, Params, Counters, default_params, lib, 
                   idpack_bound, idpack_host, idunpack_host, idpack_files, idunpack_files,
                   spack_bound, spack_host, sunpack_host, spack_files, sunpack_files, spack_file_list, sunpack_file_list,
                   text_digest_host, text_digest_file, reads_check_file,
-                  compress_fastq_pair, IDMATE_RULES, idmate_rule_host, idmate_apply_host, idmate_rule_files, fastq_assemble_pair,
+                  compress_fastq_pair, IDMATE_RULES, idmate_rule_host, THIRD_RULES, third_rule_host, third_rule_of, third_rule_name, third_rule_parse, idmate_apply_host, idmate_rule_files, fastq_assemble_pair,
                   LINE_NONE, line_offset_host, line_range_file, qunpack_range_files, idunpack_range_files,
                   recovery_make_host, recovery_repair_host, recovery_make_files, recovery_check_files, recovery_repair_files, block_digests_host, gf_combine_host)
 from ._build import build
@@ -26,6 +26,6 @@ __all__ = ["HarcAmd", "HarcAmdError", "Params", "Counters", "default_params", "l
            "idpack_bound", "idpack_host", "idunpack_host", "idpack_files", "idunpack_files",
            "spack_bound", "spack_host", "sunpack_host", "spack_files", "sunpack_files", "spack_file_list", "sunpack_file_list",
            "text_digest_host", "text_digest_file", "reads_check_file",
-           "compress_fastq_pair", "IDMATE_RULES", "idmate_rule_host", "idmate_apply_host", "idmate_rule_files", "fastq_assemble_pair",
+           "compress_fastq_pair", "IDMATE_RULES", "idmate_rule_host", "THIRD_RULES", "third_rule_host", "third_rule_of", "third_rule_name", "third_rule_parse", "idmate_apply_host", "idmate_rule_files", "fastq_assemble_pair",
            "LINE_NONE", "line_offset_host", "line_range_file", "qunpack_range_files", "idunpack_range_files",
            "recovery_make_host", "recovery_repair_host", "recovery_make_files", "recovery_check_files", "recovery_repair_files", "block_digests_host", "gf_combine_host"]

@@ -198,6 +198,18 @@ def lib():
         l.harc_amd_idmate_apply_host.argtypes = [C.c_char_p, C.c_uint64, C.c_int32, U64P]
         l.harc_amd_compress_fastq_pair_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, U64P]
         l.harc_amd_fastq_assemble_pair_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32]
+    if hasattr(l, "harc_amd_third_rule_device"):         # (HARC_AMD_LIB may name a build from before the third lines were kept)
+        l.harc_amd_third_rule_device.argtypes = [ctx, C.c_void_p, C.c_uint64, U64P, U32P]
+        l.harc_amd_third_rule_host.argtypes = [C.c_char_p, C.c_uint64, U64P, U32P]
+        l.harc_amd_third_rule_of.argtypes = [C.c_uint32, C.c_uint64]
+        l.harc_amd_third_rule_of.restype = C.c_int32
+        l.harc_amd_third_rule_name.argtypes = [C.c_int32]
+        l.harc_amd_third_rule_name.restype = C.c_char_p
+        l.harc_amd_third_rule_parse.argtypes = [C.c_char_p]
+        l.harc_amd_third_rule_parse.restype = C.c_int32
+        l.harc_amd_fastq_assemble_third_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64, U64P, C.c_int32]
+        l.harc_amd_fastq_assemble_third_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32]
+        l.harc_amd_fastq_assemble_third_pair_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32]
     if hasattr(l, "harc_amd_line_offset_device"):        # (HARC_AMD_LIB may name a build from before range restore)
         l.harc_amd_line_offset_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_uint64, U64P]
         l.harc_amd_line_offset_host.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, U64P]
@@ -327,10 +339,43 @@ def idmate_rule_files(path_a, path_b, device=0):
     return IDMATE_RULES[r.value], n.value
 
 
-def fastq_assemble_pair(dna, ids, quality, out1, out2, records, rule, device=0, bgzf=False):
+THIRD_RULES = ("dropped", "bare", "same")              # HARC_AMD_THIRD_DROPPED .. HARC_AMD_THIRD_SAME
+
+
+def _third_number(third):
+    return THIRD_RULES.index(third) if isinstance(third, str) else int(third)
+
+
+def third_rule_of(flags, records):
+    """the rule of the third lines that a flag word over `records` records stands for (include/harc_amd.h: harc_amd_third_rule_of) -> its name"""
+    return THIRD_RULES[lib().harc_amd_third_rule_of(flags, records)]
+
+
+def third_rule_name(rule):
+    return lib().harc_amd_third_rule_name(int(rule)).decode()
+
+
+def third_rule_parse(name):
+    return lib().harc_amd_third_rule_parse(name.encode() if isinstance(name, str) else name)
+
+
+def third_rule_host(fastq):
+    """the rule of the third lines of the FASTQ text `fastq` (bytes) on the host (include/harc_amd.h: harc_amd_third_rule_host)
+    -> (rule name, records that took part, the AND of their flags: bit 0 bare, 1 same); no device"""
+    n, f = C.c_uint64(0), C.c_uint32(0)
+    _check(lib().harc_amd_third_rule_host(fastq, len(fastq), C.byref(n), C.byref(f)))
+    return third_rule_of(f.value, n.value), n.value, f.value
+
+
+def fastq_assemble_pair(dna, ids, quality, out1, out2, records, rule, device=0, bgzf=False, third=None):
     """fastq_assemble for a paired archive: records [0, records) -> out1, [records, 2 records) -> out2; rule none: `ids` holds the lines of both files, any other
-    rule: the first file's, and the second file's are made from them on the GPU (include/harc_amd.h: harc_amd_fastq_assemble_pair_files)"""
+    rule: the first file's, and the second file's are made from them on the GPU (include/harc_amd.h: harc_amd_fastq_assemble_pair_files).  third: the rule of
+    the third lines, a name or a number (harc_amd_fastq_assemble_third_pair_files)"""
     p = default_params(100, device=device)
+    if third is not None:
+        _check(lib().harc_amd_fastq_assemble_third_pair_files(C.byref(p), os.fsencode(dna), os.fsencode(ids), os.fsencode(quality), os.fsencode(out1), os.fsencode(out2),
+                                                              records, _rule_number(rule), 1 if bgzf else 0, _third_number(third)))
+        return
     _check(lib().harc_amd_fastq_assemble_pair_files(C.byref(p), os.fsencode(dna), os.fsencode(ids), os.fsencode(quality), os.fsencode(out1), os.fsencode(out2),
                                                     records, _rule_number(rule), 1 if bgzf else 0))
 
@@ -421,12 +466,16 @@ def idunpack_range_files(packed, out, first_line, n_lines, device=0):
     _check(lib().harc_amd_idunpack_range_files(C.byref(p), os.fsencode(packed), os.fsencode(out), first_line, n_lines))
 
 
-def fastq_assemble(dna, ids, quality, out, device=0, bgzf=False):
-    """line i of the files `dna` (fixed-length reads), `ids` and `quality` -> record i of the FASTQ file `out` (id, read, a bare '+', quality), assembled on
+def fastq_assemble(dna, ids, quality, out, device=0, bgzf=False, third=None):
+    """line i of the files `dna` (fixed-length reads), `ids` and `quality` -> record i of the FASTQ file `out` (id, read, the third line, quality), assembled on
     the GPU; the read length is that of the first read (include/harc_amd.h: harc_amd_fastq_assemble_files).  bgzf: `out` is that text as BGZF (a .fastq.gz),
-    deflated on the GPU as well (harc_amd_fastq_assemble_files_ex)"""
+    deflated on the GPU as well (harc_amd_fastq_assemble_files_ex).  third: the rule of the third lines, a name or a number; "same" writes '+' and the id
+    without its first byte (harc_amd_fastq_assemble_third_files)"""
     p = default_params(100, device=device)
-    if bgzf:
+    if third is not None:
+        _check(lib().harc_amd_fastq_assemble_third_files(C.byref(p), os.fsencode(dna), os.fsencode(ids), os.fsencode(quality), os.fsencode(out), 1 if bgzf else 0,
+                                                         _third_number(third)))
+    elif bgzf:
         _check(lib().harc_amd_fastq_assemble_files_ex(C.byref(p), os.fsencode(dna), os.fsencode(ids), os.fsencode(quality), os.fsencode(out), 1))
     else:
         _check(lib().harc_amd_fastq_assemble_files(C.byref(p), os.fsencode(dna), os.fsencode(ids), os.fsencode(quality), os.fsencode(out)))
@@ -778,10 +827,22 @@ class HarcAmd:
                                                   C.c_void_p(out_ptr) if out_ptr else None, out_capacity, C.byref(n)))
         return n.value
 
-    def fastq_assemble_device(self, d_ids, id_bytes, d_dna, d_quality, n, readlen, out_ptr=None, out_capacity=0):
+    def third_rule_device(self, d_fastq, nbytes):
+        """the rule of the third lines of a FASTQ text in device memory (include/harc_amd.h: harc_amd_third_rule_device)
+        -> (rule name, records that took part, the AND of their flags: bit 0 bare, 1 same)"""
+        n, f = C.c_uint64(0), C.c_uint32(0)
+        _check(lib().harc_amd_third_rule_device(self._ctx, C.c_void_p(d_fastq) if d_fastq else None, nbytes, C.byref(n), C.byref(f)))
+        return third_rule_of(f.value, n.value), n.value, f.value
+
+    def fastq_assemble_device(self, d_ids, id_bytes, d_dna, d_quality, n, readlen, out_ptr=None, out_capacity=0, third=None):
         """n ids (id_bytes of text, a line each), reads and quality values (n lines of readlen + 1 bytes each) in device memory -> the n FASTQ records at
-        out_ptr (device memory); without out_ptr the inputs are only validated. -> bytes of the records"""
+        out_ptr (device memory); without out_ptr the inputs are only validated.  third: the rule of the third lines, a name or a number. -> bytes of the records"""
         n_out = C.c_uint64(0)
+        if third is not None:
+            _check(lib().harc_amd_fastq_assemble_third_device(self._ctx, C.c_void_p(d_ids) if d_ids else None, id_bytes, C.c_void_p(d_dna) if d_dna else None,
+                                                              C.c_void_p(d_quality) if d_quality else None, n, readlen, C.c_void_p(out_ptr) if out_ptr else None,
+                                                              out_capacity, C.byref(n_out), _third_number(third)))
+            return n_out.value
         _check(lib().harc_amd_fastq_assemble_device(self._ctx, C.c_void_p(d_ids) if d_ids else None, id_bytes, C.c_void_p(d_dna) if d_dna else None,
                                                     C.c_void_p(d_quality) if d_quality else None, n, readlen, C.c_void_p(out_ptr) if out_ptr else None,
                                                     out_capacity, C.byref(n_out)))

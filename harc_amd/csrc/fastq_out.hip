@@ -1,7 +1,8 @@
 // fastq_out.hip -- the way back to FASTQ (./harc -d -q): the three files a -c -q run took the FASTQ apart into -- one id per line, one read per line, one
 // quality string per line -- become 4-line records again, on the GPU.  Record i of the output is
 //     id_i \n read_i \n + \n quality_i \n
-// The third line is a bare '+': preprocess drops whatever followed it in the input, so nothing else can be restored.
+// The third line is a bare '+', or -- under the rule `same` of third.h, which -c -q records in the archive member read.third when every third line of the input
+// repeated its id -- '+' followed by id_i[1..].  Any other text behind the '+' of the input is not kept and cannot be restored.
 //
 // A streaming kernel: B bytes in, B bytes out, its floor is a device-to-device copy.  It is OUTPUT-centric.  A workgroup owns one 16-byte-aligned tile of
 // FQ_TILE output bytes; it finds the first record that reaches into the tile by binary search on out_off[i] = id_start[i] + i * (2 * readlen + 4) (the line
@@ -17,6 +18,7 @@
 #include "fileio.h"
 #include "deflate_member.h"
 #include "idmate.h"
+#include "third.h"
 
 #define FQ_TILE 16384
 #define FQ_WAVES 4
@@ -60,14 +62,17 @@ __device__ __forceinline__ void fq_const(char ch, int64_t at, int64_t p, uint32_
 
 // Tile t holds the output bytes whose ADDRESS, counted from the 16-byte boundary at or below out, lies in [t * FQ_TILE, (t + 1) * FQ_TILE): `mis` = out & 15.
 // nls: the line index of the id text (build_line_index; nls[-1] = -1).  err[0] / err[1]: stride errors of the reads / the quality values.
-__global__ __launch_bounds__(64 * FQ_WAVES) void k_fq_tiles(const char *ids, const uint64_t *nls, const char *dna, const char *qual, uint32_t n, int L,
+// SAME (the third lines repeat the ids): record i takes 2 * (idlen_i + 1) + 2 * readlen + 2 bytes and starts at 2 * id_start[i] + i * (2 * readlen + 2) -- still
+// closed-form; the second id is one more segment from the same source line, a byte further on, behind a constant '+'.  err[2]: id lines of length 0, which no
+// third line can repeat (counted where the record starts).  Without SAME the kernel is the code it was.
+template <bool SAME> __global__ __launch_bounds__(64 * FQ_WAVES) void k_fq_tiles(const char *ids, const uint64_t *nls, const char *dna, const char *qual, uint32_t n, int L,
                                                             char *out, uint64_t total, uint32_t mis, uint64_t ntiles, unsigned int *err)
 {
     __shared__ __attribute__((aligned(16))) uint32_t tile[FQ_TILE / 4];
     __shared__ uint32_t s_first;
     const uint64_t t = harc_bid();
     if (t >= ntiles) return;
-    const uint64_t K = 2ull * (uint64_t)L + 4, LL = (uint64_t)L + 1;
+    const uint64_t K = 2ull * (uint64_t)L + (SAME ? 2 : 4), LL = (uint64_t)L + 1, M = SAME ? 2 : 1;       // record i starts at M * id_start[i] + i * K
     const int64_t v0 = (int64_t)(t * FQ_TILE);                    // first byte of the tile, counted from the aligned boundary
     if (threadIdx.x == 0) {
         // the last record that starts at or in front of the tile's first output byte
@@ -75,22 +80,23 @@ __global__ __launch_bounds__(64 * FQ_WAVES) void k_fq_tiles(const char *ids, con
         uint64_t lo = 0, hi = (uint64_t)n - 1;
         while (lo < hi) {
             const uint64_t mid = (lo + hi + 1) >> 1;
-            if (nls[(int64_t)mid - 1] + 1 + mid * K <= o0) lo = mid; else hi = mid - 1;
+            if (M * (nls[(int64_t)mid - 1] + 1) + mid * K <= o0) lo = mid; else hi = mid - 1;
         }
         s_first = (uint32_t)lo;
     }
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    uint32_t errR = 0, errQ = 0;
+    uint32_t errR = 0, errQ = 0, errI = 0;
     uint8_t *tile8 = (uint8_t *)tile;
     for (uint64_t i = (uint64_t)s_first + wave; i < (uint64_t)n; i += FQ_WAVES) {
         const uint64_t ids0 = nls[(int64_t)i - 1] + 1, idlen = nls[i] - ids0;
-        const int64_t b = (int64_t)(ids0 + i * K) + (int64_t)mis - v0;       // the record in the tile's coordinates: [b, e)
+        const int64_t b = (int64_t)(M * ids0 + i * K) + (int64_t)mis - v0;   // the record in the tile's coordinates: [b, e)
         if (b >= FQ_TILE) break;
-        const int64_t e = b + (int64_t)(idlen + 1 + K);              // id and its newline, then the 2 * readlen + 4 bytes every record has
+        const int64_t e = b + (int64_t)(M * (idlen + 1) + K);        // id and its newline (SAME: twice), then the bytes every record has
         const int64_t clo = b > 0 ? b : 0, chi = e < FQ_TILE ? e : FQ_TILE;
-        const int64_t d_read = b + (int64_t)idlen + 1, d_plus = d_read + (int64_t)LL, d_qual = d_plus + 2;
+        const int64_t d_read = b + (int64_t)idlen + 1, d_plus = d_read + (int64_t)LL, d_qual = d_plus + (SAME ? (int64_t)idlen + 1 : 2);
+        if (SAME && idlen == 0 && b >= 0 && lane == 0) errI++;
         const char *s_id = ids + ids0, *s_read = dna + i * LL, *s_qual = qual + i * LL;
         for (int64_t j = (clo >> 2) + lane; j < ((chi + 3) >> 2); j += 64) {
             const int64_t p = 4 * j;
@@ -104,7 +110,12 @@ __global__ __launch_bounds__(64 * FQ_WAVES) void k_fq_tiles(const char *ids, con
             uint32_t m = m0 | m1 | m2;
             fq_const('\n', d_read - 1, p, &v, &m);
             fq_const('+', d_plus, p, &v, &m);
-            fq_const('\n', d_plus + 1, p, &v, &m);
+            if (SAME) {                                           // id[1..] behind the '+'
+                uint32_t m3;
+                v |= fq_seg(s_id + 1, d_plus + 1, (int64_t)idlen - 1, p, &m3);
+                m |= m3;
+            }
+            fq_const('\n', d_qual - 1, p, &v, &m);
             if (m == 0xFFFFFFFFu) tile[j] = v;                    // p >= 0 and p + 4 <= FQ_TILE: all four bytes are this record's and inside the tile
             else {
 #pragma unroll
@@ -114,6 +125,7 @@ __global__ __launch_bounds__(64 * FQ_WAVES) void k_fq_tiles(const char *ids, con
     }
     if (errR) atomicAdd(&err[0], errR);
     if (errQ) atomicAdd(&err[1], errQ);
+    if (SAME && errI) atomicAdd(&err[2], errI);
     __syncthreads();
     char *gbase = out - mis;
     const int64_t vlo = (int64_t)mis, vhi = (int64_t)mis + (int64_t)total;       // the output's bytes, counted from the aligned boundary
@@ -156,22 +168,45 @@ int fq_index(harc_amd_ctx *c, const char *d_ids, uint64_t id_bytes, const uint64
     *open_tail = lastch != '\n';
     return HARC_AMD_OK;
 }
-// n records -> d_out[0 .. total), enqueued on the context's stream; d_err[0..1] count the stride errors
+// id lines of length 0 among lines [0, n) (the validating device call under the rule same)
+__global__ void k_fq_empty_ids(const uint64_t *nls, uint32_t n, unsigned int *err)
+{
+    const uint32_t i = harc_gid32();
+    if (i < n && nls[i] == nls[(int64_t)i - 1] + 1) atomicAdd(err, 1u);
+}
+// what n records behind `id_bytes` bytes of id text take (a last line without its newline already counted in)
+static inline uint64_t fq_text_bytes(int32_t third, uint64_t id_bytes, uint64_t n, int L)
+{
+    return third == TH_SAME ? 2 * id_bytes + n * (2ull * (uint64_t)L + 2) : id_bytes + n * (2ull * (uint64_t)L + 4);
+}
+static int fq_check_third(const char *who, int32_t third)
+{
+    if (third >= TH_DROPPED && third <= TH_SAME) return HARC_AMD_OK;
+    harc_set_error("%s: %d is no rule of the third lines (0 dropped, 1 bare, 2 same)", who, (int)third);
+    return HARC_AMD_EINVAL;
+}
+// n records -> d_out[0 .. total), enqueued on the context's stream; d_err[0..1] count the stride errors, d_err[2] the empty id lines under the rule same
+// (third: TH_SAME, or anything else for a bare '+')
 static int fq_run(harc_amd_ctx *c, const char *d_ids, const uint64_t *nls, const char *d_dna, const char *d_quality, uint32_t n, int L, char *d_out, uint64_t total,
-                  unsigned int *d_err)
+                  unsigned int *d_err, int32_t third)
 {
     if (n == 0 || total == 0) return HARC_AMD_OK;
     const uint32_t mis = (uint32_t)((uintptr_t)d_out & 15);
     const uint64_t ntiles = (mis + total + FQ_TILE - 1) / FQ_TILE;
-    hipLaunchKernelGGL(k_fq_tiles, harc_fold256(ntiles), dim3(64 * FQ_WAVES), 0, c->stream, d_ids, nls, d_dna, d_quality, n, L, d_out, total, mis, ntiles, d_err);
+    if (third == TH_SAME) hipLaunchKernelGGL(k_fq_tiles<true>, harc_fold256(ntiles), dim3(64 * FQ_WAVES), 0, c->stream, d_ids, nls, d_dna, d_quality, n, L, d_out, total, mis, ntiles, d_err);
+    else hipLaunchKernelGGL(k_fq_tiles<false>, harc_fold256(ntiles), dim3(64 * FQ_WAVES), 0, c->stream, d_ids, nls, d_dna, d_quality, n, L, d_out, total, mis, ntiles, d_err);
     HIP_TRY(hipGetLastError());
     return HARC_AMD_OK;
 }
 static int fq_check_errors(harc_amd_ctx *c, const unsigned int *d_err, int L)
 {
-    unsigned int err[2] = { 0, 0 };
-    HIP_TRY(hipMemcpyAsync(err, d_err, 8, hipMemcpyDeviceToHost, c->stream));
+    unsigned int err[3] = { 0, 0, 0 };
+    HIP_TRY(hipMemcpyAsync(err, d_err, 12, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    if (err[2]) {
+        harc_set_error("fastq_assemble: %u id lines are empty, and no third line can repeat an empty id: the id text is damaged or another rule of the third lines was recorded than the one that held", err[2]);
+        return HARC_AMD_EINVAL;
+    }
     if (err[0] || err[1]) {
         harc_set_error("fastq_assemble: the fixed-width inputs are not lines of %d characters: %u bytes of the reads and %u bytes of the quality values are a newline off the %d-byte stride or no newline on it",
                        L, err[0], err[1], L + 1);
@@ -183,13 +218,19 @@ static int fq_check_errors(harc_amd_ctx *c, const unsigned int *d_err, int L)
 extern "C" int harc_amd_fastq_assemble_device(harc_amd_ctx *c, const char *d_ids, uint64_t id_bytes, const char *d_dna, const char *d_quality, uint32_t n_records,
                                               int32_t readlen, char *d_out, uint64_t out_capacity, uint64_t *n_out)
 {
+    return harc_amd_fastq_assemble_third_device(c, d_ids, id_bytes, d_dna, d_quality, n_records, readlen, d_out, out_capacity, n_out, TH_BARE);
+}
+extern "C" int harc_amd_fastq_assemble_third_device(harc_amd_ctx *c, const char *d_ids, uint64_t id_bytes, const char *d_dna, const char *d_quality, uint32_t n_records,
+                                                    int32_t readlen, char *d_out, uint64_t out_capacity, uint64_t *n_out, int32_t third)
+{
+    RC_TRY(fq_check_third("fastq_assemble_device", third));
     if (!c || !n_out || readlen < 1 || readlen > 255 || (id_bytes && !d_ids) || (n_records && (!d_dna || !d_quality))) { harc_set_error("fastq_assemble_device: bad arguments"); return HARC_AMD_EINVAL; }
     HIP_TRY(hipSetDevice(c->P.device));
     PoolScope scope(c);
     const uint64_t *nls = nullptr; uint64_t lines = 0; bool open_tail = false;
     RC_TRY(fq_index(c, d_ids, id_bytes, &nls, &lines, &open_tail));
     if (lines != (uint64_t)n_records) { harc_set_error("fastq_assemble_device: the id text holds %llu lines, %u records were announced", (unsigned long long)lines, n_records); return HARC_AMD_EINVAL; }
-    const uint64_t total = id_bytes + (open_tail ? 1 : 0) + (uint64_t)n_records * (2ull * (uint64_t)readlen + 4);
+    const uint64_t total = fq_text_bytes(third, id_bytes + (open_tail ? 1 : 0), n_records, readlen);
     *n_out = total;
     unsigned int *d_err = nullptr; RC_TRY(dalloc(c, &d_err, 4));
     HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
@@ -198,19 +239,20 @@ extern "C" int harc_amd_fastq_assemble_device(harc_amd_ctx *c, const char *d_ids
         if (nb) {
             hipLaunchKernelGGL(k_fq_stride_check, harc_grid256((nb + 15) / 16), dim3(256), 0, c->stream, d_dna, nb, (int)readlen, d_err);
             hipLaunchKernelGGL(k_fq_stride_check, harc_grid256((nb + 15) / 16), dim3(256), 0, c->stream, d_quality, nb, (int)readlen, d_err + 1);
+            if (third == TH_SAME) hipLaunchKernelGGL(k_fq_empty_ids, harc_grid256(n_records), dim3(256), 0, c->stream, nls, n_records, d_err + 2);
             HIP_TRY(hipGetLastError());
         }
         return fq_check_errors(c, d_err, readlen);
     }
     if (out_capacity < total) { harc_set_error("fastq_assemble_device: the records take %llu bytes, the buffer holds %llu", (unsigned long long)total, (unsigned long long)out_capacity); return HARC_AMD_EINVAL; }
     if (!getenv("HARC_AMD_TRACE")) {
-        RC_TRY(fq_run(c, d_ids, nls, d_dna, d_quality, n_records, readlen, d_out, total, d_err));
+        RC_TRY(fq_run(c, d_ids, nls, d_dna, d_quality, n_records, readlen, d_out, total, d_err, third));
         return fq_check_errors(c, d_err, readlen);
     }
     double seconds = 0;                                           // the tile kernel alone, for tools/fastq_out_rate.py
     KernelTimer timer(&seconds);
     RC_TRY(timer.begin(c->stream));
-    RC_TRY(fq_run(c, d_ids, nls, d_dna, d_quality, n_records, readlen, d_out, total, d_err));
+    RC_TRY(fq_run(c, d_ids, nls, d_dna, d_quality, n_records, readlen, d_out, total, d_err, third));
     RC_TRY(timer.end_mark(c->stream));
     const int rc = fq_check_errors(c, d_err, readlen);
     RC_TRY(timer.end_wait());
@@ -256,12 +298,12 @@ static int fq_probe(const char *who, const char *dna_path, const char *id_path, 
 // Three feeders (ids, reads, quality values) and the drain are alive at the same time and the context has ONE pinned ring: gq[0 .. 4) are its four quarters --
 // 0: the id feeder, 1: the read feeder, 2: the quality feeder, 3: the drain.  The caller guards the output file (OutFileGuard) and owns the context.
 template <class M> static int fq_assemble_part(harc_amd_ctx *c, const RingGeom *gq, const FqInputs &in, uint64_t id_begin, uint64_t rec_base, uint64_t nrec, bool stop_at_nrec,
-                                               int32_t rule, const char *out_path, int32_t bgzf, uint64_t *id_end, M &&on_mismatch)
+                                               int32_t rule, int32_t third, const char *out_path, int32_t bgzf, uint64_t *id_end, M &&on_mismatch)
 {
     const int L = in.L; const uint64_t isz = in.isz;
-    const uint64_t LL = (uint64_t)L + 1, K = 2ull * (uint64_t)L + 4;
+    const uint64_t LL = (uint64_t)L + 1;
     const bool id_open_tail = in.id_open_tail && isz > id_begin;
-    const uint64_t out_size = (isz - id_begin) + (id_open_tail ? 1 : 0) + nrec * K;    // known before a byte is read: the output is sized and mapped up front (stop_at_nrec: a bound)
+    const uint64_t out_size = fq_text_bytes(third, (isz - id_begin) + (id_open_tail ? 1 : 0), nrec, L);    // known before a byte is read: the output is sized and mapped up front (stop_at_nrec: a bound)
     CarriedText ids(c); DevBuf dna{ c }, qual{ c }, out{ c }, gz{ c };
     const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
     double t_kernel = 0, t_read = 0, t_write = 0;
@@ -304,7 +346,7 @@ template <class M> static int fq_assemble_part(harc_amd_ctx *c, const RingGeom *
         lines_seen += m;
         if (r0 + m > nrec) over = true;                                                      // more ids than reads: the lines are still counted, for the message
         if (!over && m) {
-            const uint64_t nb = m * LL, out_bytes = cut + ((lastp && open_tail && !clip) ? 1 : 0) + m * K;
+            const uint64_t nb = m * LL, out_bytes = fq_text_bytes(third, cut + ((lastp && open_tail && !clip) ? 1 : 0), m, L);
             RC_TRY(dev_reserve(&dna, (size_t)nb)); RC_TRY(dev_reserve(&qual, (size_t)nb)); RC_TRY(dev_reserve(&out, (size_t)(tcarry + out_bytes), (size_t)tcarry));
             {   // lines [rec_base + r0, rec_base + r0 + m) of the two fixed-width files, by offset
                 const uint64_t f0 = (rec_base + r0) * LL, f1 = (rec_base + r0 + m) * LL;
@@ -315,7 +357,7 @@ template <class M> static int fq_assemble_part(harc_amd_ctx *c, const RingGeom *
                 t_read += mono_now() - t0;
                 RC_TRY(timer.begin(c->stream));
                 RC_TRY(harc_idmate_apply_lines(c, d_ids, nls, m, rule, d_bad));              // (nothing for the rules that patch nothing)
-                RC_TRY(fq_run(c, d_ids, nls, dna.p, qual.p, (uint32_t)m, L, out.p + tcarry, out_bytes, d_err));
+                RC_TRY(fq_run(c, d_ids, nls, dna.p, qual.p, (uint32_t)m, L, out.p + tcarry, out_bytes, d_err, third));
                 RC_TRY(timer.end_mark(c->stream));
                 if (!bgzf) { const double t0w = mono_now(); RC_TRY(drain.put(out.p, (size_t)out_bytes, out_at)); t_write += mono_now() - t0w; }
                 else {
@@ -374,6 +416,13 @@ template <class M> static int fq_assemble_part(harc_amd_ctx *c, const RingGeom *
 extern "C" int harc_amd_fastq_assemble_files_ex(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out_path,
                                                 int32_t bgzf)
 {
+    return harc_amd_fastq_assemble_third_files(params, dna_path, id_path, quality_path, out_path, bgzf, TH_BARE);
+}
+// third (third.h): TH_SAME writes '+' and id[1..] as the third line of every record, anything else a bare '+'
+extern "C" int harc_amd_fastq_assemble_third_files(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out_path,
+                                                   int32_t bgzf, int32_t third)
+{
+    RC_TRY(fq_check_third("fastq_assemble_files", third));
     if (!params || !dna_path || !id_path || !quality_path || !out_path) { harc_set_error("fastq_assemble_files: bad arguments"); return HARC_AMD_EINVAL; }
     FqInputs in;
     RC_TRY(fq_probe("fastq_assemble_files", dna_path, id_path, quality_path, &in));
@@ -386,7 +435,7 @@ extern "C" int harc_amd_fastq_assemble_files_ex(const harc_amd_params *params, c
     RC_TRY(ring_split(c, 4, 4, "FASTQ output", gq));
     OutFileGuard outguard{ out_path };
     uint64_t id_end = 0;
-    RC_TRY(fq_assemble_part(c, gq, in, 0, 0, in.n, false, IDM_NONE, out_path, bgzf, &id_end, [&](uint64_t seen) {
+    RC_TRY(fq_assemble_part(c, gq, in, 0, 0, in.n, false, IDM_NONE, third, out_path, bgzf, &id_end, [&](uint64_t seen) {
         harc_set_error("fastq_assemble_files: %s holds %llu lines, %s %llu reads", id_path, (unsigned long long)seen, dna_path, (unsigned long long)in.n);
     }));
     outguard.ok = true;
@@ -399,6 +448,13 @@ extern "C" int harc_amd_fastq_assemble_files_ex(const harc_amd_params *params, c
 extern "C" int harc_amd_fastq_assemble_pair_files(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out1_path,
                                                   const char *out2_path, uint64_t records_per_file, int32_t rule, int32_t bgzf)
 {
+    return harc_amd_fastq_assemble_third_pair_files(params, dna_path, id_path, quality_path, out1_path, out2_path, records_per_file, rule, bgzf, TH_BARE);
+}
+// ... under the rule same of the third lines, file 2's third lines carry file 2's ids: the patch kernel runs in front of the assembly
+extern "C" int harc_amd_fastq_assemble_third_pair_files(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out1_path,
+                                                        const char *out2_path, uint64_t records_per_file, int32_t rule, int32_t bgzf, int32_t third)
+{
+    RC_TRY(fq_check_third("fastq_assemble_pair_files", third));
     if (!params || !dna_path || !id_path || !quality_path || !out1_path || !out2_path) { harc_set_error("fastq_assemble_pair_files: bad arguments"); return HARC_AMD_EINVAL; }
     if (rule < IDM_NONE || rule > IDM_SPACE) { harc_set_error("fastq_assemble_pair_files: %d is no mate rule (0 none, 1 same, 2 slash, 3 space)", (int)rule); return HARC_AMD_EINVAL; }
     FqInputs in;
@@ -421,13 +477,13 @@ extern "C" int harc_amd_fastq_assemble_pair_files(const harc_amd_params *params,
                        (unsigned long long)(taken + seen), (unsigned long long)want, (unsigned long long)n, idm_rule_name(rule));
     };
     if (rule == IDM_NONE) {
-        RC_TRY(fq_assemble_part(c, gq, in, 0, 0, n, true, IDM_NONE, out1_path, bgzf, &id_end, refuse));
+        RC_TRY(fq_assemble_part(c, gq, in, 0, 0, n, true, IDM_NONE, third, out1_path, bgzf, &id_end, refuse));
         taken = n;
         const uint64_t from = id_end;
-        RC_TRY(fq_assemble_part(c, gq, in, from, n, n, false, IDM_NONE, out2_path, bgzf, &id_end, refuse));
+        RC_TRY(fq_assemble_part(c, gq, in, from, n, n, false, IDM_NONE, third, out2_path, bgzf, &id_end, refuse));
     } else {
-        RC_TRY(fq_assemble_part(c, gq, in, 0, 0, n, false, IDM_SAME, out1_path, bgzf, &id_end, refuse));
-        RC_TRY(fq_assemble_part(c, gq, in, 0, n, n, false, rule, out2_path, bgzf, &id_end, refuse));
+        RC_TRY(fq_assemble_part(c, gq, in, 0, 0, n, false, IDM_SAME, third, out1_path, bgzf, &id_end, refuse));
+        RC_TRY(fq_assemble_part(c, gq, in, 0, n, n, false, rule, third, out2_path, bgzf, &id_end, refuse));
     }
     guard1.ok = guard2.ok = true;
     return HARC_AMD_OK;

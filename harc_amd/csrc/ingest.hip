@@ -7,6 +7,7 @@
 #include "inflate_member.h"
 #include "fileio.h"
 #include "check_block.h"
+#include "third.h"
 
 // line index in two levels: newlines per 4096-byte tile -> scan of the tile counts -> positions written tile by tile
 #define NL_TILE 4096
@@ -81,6 +82,49 @@ __global__ void k_ingest_pack3(const char *txt, const uint64_t *nl, const uint32
     if (w == 0) orderN[rankN[r]] = r;                             // preprocess.cpp:102
 }
 
+// ---- the rule of the third lines (third.h), found while the piece is here anyway (-q only).  TH_G lanes per record; a lane takes 8 bytes of the id line and of
+// the third line per step, through aligned 8-byte loads funnelled into place: the two lines sit at unrelated alignments of the same text.  A third line of
+// length 1 is decided from the line index and its single byte, so that a file with bare third lines reads no id text at all.  Every lane holds the flags its own
+// bytes leave standing, the wave ANDs them with two ballots and issues at most one atomicAnd -- none once the word holds no bit that the wave would clear.
+#define TH_G 8
+// the k (1 .. 8) bytes at p, the others zero; only aligned words that hold one of them are read
+__device__ __forceinline__ uint64_t th_fetch8(const uint8_t *p, uint32_t k)
+{
+    const uintptr_t u = (uintptr_t)p;
+    const uint32_t sh = (uint32_t)(u & 7);
+    const uint64_t *w = (const uint64_t *)(u - sh);
+    uint64_t v = w[0] >> (8 * sh);
+    if (sh + k > 8) v |= w[1] << (64 - 8 * sh);                   // (sh > 0 here)
+    if (k < 8) v &= ((uint64_t)1 << (8 * k)) - 1;
+    return v;
+}
+// record r of the piece: id line (nl[4r-1], nl[4r]), third line (nl[4r+1], nl[4r+2]).  *flags &= the flags of every record
+__global__ __launch_bounds__(256) void k_third_rule(const uint8_t *txt, const uint64_t *nl, uint64_t nrec, unsigned int *flags)
+{
+    const uint64_t r = harc_gid() / TH_G;
+    const uint32_t g = threadIdx.x & (TH_G - 1);
+    uint32_t f = TH_F_ALL;
+    if (r < nrec) {
+        const uint64_t a0 = nl[4 * (int64_t)r - 1] + 1, la = nl[4 * r] - a0, t0 = nl[4 * r + 1] + 1, lt = nl[4 * r + 2] - t0;
+        if (lt == 1) { if (g == 0) f = th_flags_short(txt[t0], la); else f = TH_F_BARE | (la == 1 ? TH_F_SAME : 0u); }
+        else if (lt == 0 || lt != la) f = 0;
+        else {
+            f = TH_F_SAME;
+            const uint8_t *pa = txt + a0, *pt = txt + t0;
+            const uint32_t len = (uint32_t)la;
+            for (uint32_t off = 8 * g; off < len; off += 8 * TH_G) {
+                const uint32_t k = len - off < 8 ? len - off : 8;
+                const uint64_t vt = th_fetch8(pt + off, k);
+                uint64_t x = th_fetch8(pa + off, k) ^ vt;
+                if (off == 0) { x &= ~(uint64_t)0xFF; if ((vt & 0xFF) != (uint64_t)'+') f = 0; }     // a[0] is not looked at, t[0] is the '+'
+                if (x) f = 0;
+            }
+        }
+    }
+    const uint32_t fw = (__ballot(!(f & TH_F_BARE)) ? 0u : TH_F_BARE) | (__ballot(!(f & TH_F_SAME)) ? 0u : TH_F_SAME);
+    if ((threadIdx.x & 63u) == 0 && (*(volatile unsigned int *)flags & ~fw & TH_F_ALL) != 0) atomicAnd(flags, fw);
+}
+
 #define G256(n) harc_grid256((uint64_t)(n)), dim3(256), 0, c->stream
 
 // nls[k] = byte position of the newline that ends line k (a last line without one ends at nbytes); nls[-1] = (u64)-1 so that line k
@@ -110,6 +154,44 @@ int build_line_index(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const 
     return HARC_AMD_OK;
 }
 
+// the rule kernel over a FASTQ text in device memory, with a line index of its own
+extern "C" int harc_amd_third_rule_device(harc_amd_ctx *c, const char *d_fastq, uint64_t n_bytes, uint64_t *n_records, uint32_t *flags_and)
+{
+    if (!c || !n_records || !flags_and || (n_bytes && !d_fastq)) { harc_set_error("third_rule_device: bad arguments"); return HARC_AMD_EINVAL; }
+    *n_records = 0; *flags_and = TH_F_ALL;
+    if (n_bytes == 0) return HARC_AMD_OK;
+    HIP_TRY(hipSetDevice(c->P.device));
+    PoolScope scope(c);
+    const uint64_t *nls = nullptr; uint64_t total_lines = 0;
+    RC_TRY(build_line_index(c, d_fastq, n_bytes, &nls, &total_lines));
+    const uint64_t nrec = (total_lines + 1) / 4;
+    unsigned int *d_flags = nullptr; RC_TRY(dalloc(c, &d_flags, 4));
+    HIP_TRY(hipMemsetAsync(d_flags, 0xFF, 16, c->stream));
+    const bool trace = getenv("HARC_AMD_TRACE") != nullptr;
+    double seconds = 0;
+    KernelTimer timer(trace ? &seconds : nullptr);
+    RC_TRY(timer.begin(c->stream));
+    if (nrec) hipLaunchKernelGGL(k_third_rule, G256(nrec * TH_G), (const uint8_t *)d_fastq, nls, nrec, d_flags);
+    HIP_TRY(hipGetLastError());
+    RC_TRY(timer.end(c->stream));
+    unsigned int f = 0;
+    HIP_TRY(hipMemcpyAsync(&f, d_flags, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (trace) fprintf(stderr, "[third] device call: %llu records, %llu bytes of text, rule kernel %.3f ms (%.1f GB/s)\n", (unsigned long long)nrec, (unsigned long long)n_bytes,
+                       1e3 * seconds, seconds > 0 ? 1e-9 * (double)n_bytes / seconds : 0.0);
+    *n_records = nrec; *flags_and = f & TH_F_ALL;
+    return HARC_AMD_OK;
+}
+extern "C" int harc_amd_third_rule_host(const char *fastq, uint64_t n_bytes, uint64_t *n_records, uint32_t *flags_and)
+{
+    if (!n_records || !flags_and || (n_bytes && !fastq)) { harc_set_error("third_rule_host: bad arguments"); return HARC_AMD_EINVAL; }
+    *flags_and = th_text_flags_host((const uint8_t *)fastq, n_bytes, n_records);
+    return HARC_AMD_OK;
+}
+extern "C" int32_t harc_amd_third_rule_of(uint32_t flags_and, uint64_t n_records) { return th_rule_of(flags_and, n_records); }
+extern "C" const char *harc_amd_third_rule_name(int32_t rule) { return th_rule_name(rule); }
+extern "C" int32_t harc_amd_third_rule_parse(const char *name) { return name ? th_rule_parse(name) : -1; }
+
 // FASTQ text in device memory -> the context's clean reads (2-bit) and N reads (3-bit), a chunk of whole records at a time: a file
 // larger than HBM is ingested in pieces (harc_amd_compress_fastq_files_ex), the packed stores grow as the pieces arrive.
 struct IngestState {
@@ -119,6 +201,9 @@ struct IngestState {
     // -q without -p on a file that does not stay in HBM (emit_quality_and_ids_streamed): the length of every id line
     bool want_idlen = false;
     std::vector<uint32_t> idlen;
+    // -q: the rule of the third lines (third.h), the AND over every piece of every file of the job
+    bool want_third = false;
+    uint32_t third_and = TH_F_ALL; uint64_t third_n = 0;           // the flags left standing; the records that took part
 };
 __global__ void k_q_idlen(const uint64_t *nls, uint32_t nid, uint32_t *len)
 {
@@ -127,7 +212,7 @@ __global__ void k_q_idlen(const uint64_t *nls, uint32_t nid, uint32_t *len)
 }
 static int ingest_begin(harc_amd_ctx *c, IngestState &st)
 {
-    { const bool w = st.want_idlen; st = IngestState(); st.want_idlen = w; }
+    { const bool w = st.want_idlen, t = st.want_third; st = IngestState(); st.want_idlen = w; st.want_third = t; }
     // same effect as harc_amd_set_reads_* on an empty set: previous inputs and results go
     RC_TRY(harc_amd_set_reads_packed_device(c, nullptr, 0));
     RC_TRY(harc_amd_set_nreads_ascii_device(c, nullptr, 0, (uint32_t)c->P.readlen));
@@ -172,12 +257,20 @@ static int ingest_append(harc_amd_ctx *c, IngestState &st, const char *d_txt, ui
     HIP_TRY(hipMemsetAsync(d_err, 0, 16, c->stream));
     HIP_TRY(hipMemsetAsync(isN, 0, ((size_t)nrec + 1) * 4, c->stream)); HIP_TRY(hipMemsetAsync(isC, 0, ((size_t)nrec + 1) * 4, c->stream));
     if (nrec) hipLaunchKernelGGL(k_classify, G256(nrec), d_txt, nls, nrec, L, isN, isC, d_err);
+    // -q: the records whose third line is there; their flag word sits behind the error counter and comes back with it
+    const uint64_t nthird = st.want_third ? (total_lines + 1) / 4 : 0;
+    if (nthird) {
+        HIP_TRY(hipMemsetAsync(d_err + 1, 0xFF, 4, c->stream));
+        hipLaunchKernelGGL(k_third_rule, G256(nthird * TH_G), (const uint8_t *)d_txt, nls, nthird, d_err + 1);
+    }
     RC_TRY(prim_excl_scan_u32(c, isN, rkN, (size_t)nrec + 1)); RC_TRY(prim_excl_scan_u32(c, isC, rkC, (size_t)nrec + 1));
-    uint32_t nN = 0, nC = 0; unsigned int err = 0;
+    uint32_t nN = 0, nC = 0; unsigned int errs[2] = { 0, 0 };
     HIP_TRY(hipMemcpyAsync(&nN, rkN + nrec, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(&nC, rkC + nrec, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(errs, d_err, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    const unsigned int err = errs[0];
+    if (nthird) { st.third_and &= errs[1] & TH_F_ALL; st.third_n += nthird; }
     if (err) {
         printf("Read length not fixed. Found reads whose length is not %d\n", L);
         harc_set_error("read length not fixed (%u records differ from %d)", err, L); return HARC_AMD_EINVAL;
@@ -841,6 +934,7 @@ static int compress_fastq_job(const harc_amd_params *params, const char *fastq, 
     const std::string od = std::string(basedir) + "/output/";
     DevBuf d_txt{ c };                                            // -q without -p: the whole text stays in HBM until the orders are known
     IngestState st;
+    st.want_third = preserve_quality != 0;                        // every route below ends in ingest_append
     // -q without -p: the text stays in HBM until the orders are known when it fits next to everything else; a larger file is ingested in pieces
     // like any other and streamed again, once per bin of output, when the orders are there (emit_quality_and_ids_streamed)
     bool stream_q = false;
@@ -921,6 +1015,14 @@ static int compress_fastq_job(const harc_amd_params *params, const char *fastq, 
     if (fastq2) {                                                 // the record of a pair run; ./harc appends the line "ids <rule>" with -q
         char rec[64]; const int k = snprintf(rec, sizeof rec, "HARCP1\nrecords %llu\n", (unsigned long long)pair_records[0]);
         RC_TRY(spit_file(od + "read.pair", rec, (size_t)k));
+    }
+    if (preserve_quality) {                                       // the record of the third lines: only when they are not bare, so that such an archive is what it always was
+        const int32_t third = th_rule_of(st.third_and, st.third_n);
+        if (third != TH_BARE) {
+            char rec[64]; const int k = snprintf(rec, sizeof rec, "%s\nthird %s\n", TH_MAGIC, th_rule_name(third));
+            RC_TRY(spit_file(od + "read.third", rec, (size_t)k));
+        }
+        if (third == TH_DROPPED) printf("[third] the input's third lines carry text that is not their ids; it is not kept (-d -q writes a bare + in its place)\n");
     }
     RC_TRY(write_shard_family(c, od, 0));
     tm.lap("stream files");

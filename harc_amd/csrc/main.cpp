@@ -13,6 +13,8 @@
 //   harc_amd_stage merge_shards <basedir> <world>                          the whole-job files of the archive from the rank parts
 //   harc_amd_stage fastq_out <dna> <ignored> <id> <quality> <out> [bgzf]     lines i of the three files -> record i of the FASTQ file <out> (./harc -d -q);
 //                                                                          bgzf: <out> is that text as BGZF, deflated on the GPU (./harc -d -q -z)
+//                                                                          fastq_out and fastq_out_pair take one more trailing word, third (behind bgzf where both are given): the third
+//                                                                          line of every record is '+' and its id without the first byte (the archive's read.third names the rule same)
 //   harc_amd_stage quality_pack <quality> <device> <out> [<spec>]          the fixed-length lines of <quality> -> the packed quality file <out> (./harc -c -q -Q);
 //                                                                          <spec>: their values are mapped first, in device memory (./harc -c -q -Q -b <spec>)
 //   harc_amd_stage quality_spec <spec>                                     0 when <spec> names a mapping of quality values (ill8, bin:T:H:L, cap:M, pblock:R), else 2
@@ -61,6 +63,15 @@ static void print_qmap(const char *spec, const harc_amd_qmap_stats *st)
 {
     printf("[qmap] %s: %llu values, %llu changed, mean absolute change %.3f, max change %u, distinct values %u -> %u\n", spec, (unsigned long long)st->values,
            (unsigned long long)st->changed, st->values ? (double)st->sum_abs / (double)st->values : 0.0, st->max_abs, st->distinct_in, st->distinct_out);
+}
+
+// the optional words behind the fixed arguments of fastq_out and fastq_out_pair: [bgzf] [third], in that order and nothing else
+static bool trailing_words(int argc, char **argv, int at, int *bgzf, int *third)
+{
+    *bgzf = *third = 0;
+    if (at < argc && !strcmp(argv[at], "bgzf")) { *bgzf = 1; at++; }
+    if (at < argc && !strcmp(argv[at], "third")) { *third = 1; at++; }
+    return at == argc;
 }
 
 int main(int argc, char **argv)
@@ -133,17 +144,20 @@ int main(int argc, char **argv)
         return 0;
     }
     if (!strcmp(argv[1], "fastq_out")) {                          // the read length is the first line's of <dna>
-        if (argc < 7) { fprintf(stderr, "fastq_out needs <dna> <ignored> <id> <quality> <out> [bgzf]\n"); return 2; }
-        if (argc > 7 && strcmp(argv[7], "bgzf")) { fprintf(stderr, "fastq_out: the sixth argument can only be 'bgzf' (got '%s')\n", argv[7]); return 2; }
+        if (argc < 7) { fprintf(stderr, "fastq_out needs <dna> <ignored> <id> <quality> <out> [bgzf] [third]\n"); return 2; }
+        int bgzf = 0, third = 0;
+        if (!trailing_words(argc, argv, 7, &bgzf, &third)) { fprintf(stderr, "fastq_out: behind <out> only 'bgzf', 'third' or 'bgzf third' can follow (got '%s')\n", argv[argc - 1]); return 2; }
         harc_amd_params PF;
         if (harc_amd_default_params(100, &PF) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
-        const int rcf = argc > 7 ? harc_amd_fastq_assemble_files_ex(&PF, argv[2], argv[4], argv[5], argv[6], 1) : harc_amd_fastq_assemble_files(&PF, argv[2], argv[4], argv[5], argv[6]);
+        const int rcf = third ? harc_amd_fastq_assemble_third_files(&PF, argv[2], argv[4], argv[5], argv[6], bgzf, HARC_AMD_THIRD_SAME)
+                        : bgzf ? harc_amd_fastq_assemble_files_ex(&PF, argv[2], argv[4], argv[5], argv[6], 1) : harc_amd_fastq_assemble_files(&PF, argv[2], argv[4], argv[5], argv[6]);
         if (rcf != 0) { fprintf(stderr, "harc_amd_stage fastq_out failed (%d): %s\n", rcf, harc_amd_last_error()); return 1; }
         return 0;
     }
     if (!strcmp(argv[1], "fastq_out_pair")) {
-        if (argc < 10) { fprintf(stderr, "fastq_out_pair needs <dna> <ignored> <id> <quality> <out1> <out2> <records> <rule> [bgzf]\n"); return 2; }
-        if (argc > 10 && strcmp(argv[10], "bgzf")) { fprintf(stderr, "fastq_out_pair: the ninth argument can only be 'bgzf' (got '%s')\n", argv[10]); return 2; }
+        if (argc < 10) { fprintf(stderr, "fastq_out_pair needs <dna> <ignored> <id> <quality> <out1> <out2> <records> <rule> [bgzf] [third]\n"); return 2; }
+        int bgzf = 0, third = 0;
+        if (!trailing_words(argc, argv, 10, &bgzf, &third)) { fprintf(stderr, "fastq_out_pair: behind <rule> only 'bgzf', 'third' or 'bgzf third' can follow (got '%s')\n", argv[argc - 1]); return 2; }
         char *end = nullptr;
         const unsigned long long records = strtoull(argv[8], &end, 10);
         if (!*argv[8] || *end) { fprintf(stderr, "fastq_out_pair: <records> must be a decimal number (got '%s')\n", argv[8]); return 2; }
@@ -151,7 +165,8 @@ int main(int argc, char **argv)
         if (rule < 0) { fprintf(stderr, "fastq_out_pair: <rule> must be none, same, slash or space (got '%s')\n", argv[9]); return 2; }
         harc_amd_params PF;
         if (harc_amd_default_params(100, &PF) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
-        const int rcf = harc_amd_fastq_assemble_pair_files(&PF, argv[2], argv[4], argv[5], argv[6], argv[7], records, rule, argc > 10);
+        const int rcf = third ? harc_amd_fastq_assemble_third_pair_files(&PF, argv[2], argv[4], argv[5], argv[6], argv[7], records, rule, bgzf, HARC_AMD_THIRD_SAME)
+                              : harc_amd_fastq_assemble_pair_files(&PF, argv[2], argv[4], argv[5], argv[6], argv[7], records, rule, bgzf);
         if (rcf != 0) { fprintf(stderr, "harc_amd_stage fastq_out_pair failed (%d): %s\n", rcf, harc_amd_last_error()); return 1; }
         return 0;
     }

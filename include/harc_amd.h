@@ -208,8 +208,8 @@ int harc_amd_bgzf_deflate_device(harc_amd_ctx *ctx, const char *d_text, uint64_t
 int harc_amd_bgzf_deflate_host(const char *text, uint64_t n_bytes, int32_t flags, uint8_t *out, uint64_t out_capacity, uint64_t *n_out);
 /* The way back to FASTQ: n_records ids (d_ids: id_bytes of text, one id per line, any length, 0 included; a last line without its newline counts as a
    line), reads and quality values (d_dna, d_quality: n_records lines at a stride of readlen + 1, readlen 1..255 whatever the context's own read length
-   is), all in device memory -> the records  id_i \n read_i \n + \n quality_i \n  at d_out.  The third line is a bare '+': preprocess.cpp drops the rest
-   of it, so that is the only faithful choice.  *n_out = id_bytes (+ 1 if the last id lacks its newline) + n_records * (2 * readlen + 4).
+   is), all in device memory -> the records  id_i \n read_i \n + \n quality_i \n  at d_out.  The third line is a bare '+' in this call; where every third line of the
+   input repeated its id, harc_amd_fastq_assemble_third_device writes that form back (below, "Third lines").  *n_out = id_bytes (+ 1 if the last id lacks its newline) + n_records * (2 * readlen + 4).
    d_out == NULL: the inputs are validated and the size returned, nothing written; else out_capacity must be at least that.
    HARC_AMD_EINVAL, with the counts in harc_amd_last_error(): the id text does not hold exactly n_records lines; a byte at a (readlen + 1)-stride position
    of the reads or the quality values is no newline, or a newline sits anywhere else in them (counted on the device; what was written to d_out by
@@ -664,6 +664,40 @@ int harc_amd_recovery_repair_files(const harc_amd_params *params, const char *re
    to (tests).  block_bytes, span_blocks, group_blocks: 0 = the environment's or the default.  write = 0: check, else repair. */
 int harc_amd_recovery_make_host(int32_t n_files, const char *const *paths, uint32_t pct, uint32_t block_bytes, uint32_t span_blocks, uint32_t group_blocks, const char *out_path, uint64_t *stats);
 int harc_amd_recovery_repair_host(const char *record_path, int32_t write, char *report, uint64_t report_capacity, int32_t *status);
+
+/* ---- Third lines (./harc -c -q, ./harc -d -q; README.md, "Third lines and what is promised").
+   The rule.  Let a be the id line of a record and t its third line, without their newlines, any bytes (a '\r' is a byte like any other).  A record satisfies
+     bare    |t| = 1 and t[0] = '+'
+     same    |t| = |a| >= 1, t[0] = '+' and t[1..] = a[1..] byte for byte (a[0] is not looked at)
+   (a = "@" with t = "+" satisfies both).  The rule of a job is the one that EVERY record satisfies: no record gives bare, the bare bit left standing gives bare,
+   otherwise the same bit gives same, otherwise the third lines are dropped (mixed files are).  A record takes part when its third line is there: a last record
+   cut short behind its first or second line does not.  A record's flags: bit 0 bare, bit 1 same; a rule as a number: */
+#define HARC_AMD_THIRD_DROPPED 0
+#define HARC_AMD_THIRD_BARE 1
+#define HARC_AMD_THIRD_SAME 2
+/* *flags_and = the AND of the flags of all records of the FASTQ text in device memory (any alignment; no load leaves the 8-byte-aligned hull of the text), 3 when
+   no record takes part; *n_records = the records that did.  The call builds its own line index; a third line of length 1 is decided from the index and its one
+   byte, so a text with bare third lines has no id byte read.  harc_amd_compress_fastq_files_ex and its kin run the same kernel over every piece of the ingest
+   when preserve_quality is set and write <basedir>/output/read.third ("HARCT1", then "third same" or "third dropped") unless the rule is bare.
+   HARC_AMD_TRACE=1: one "[third] device call" line on stderr with the rule kernel's time. */
+int harc_amd_third_rule_device(harc_amd_ctx *ctx, const char *d_fastq, uint64_t n_bytes, uint64_t *n_records, uint32_t *flags_and);
+/* The same over host memory, serially: what the kernel is held to (tests).  Touches no device. */
+int harc_amd_third_rule_host(const char *fastq, uint64_t n_bytes, uint64_t *n_records, uint32_t *flags_and);
+/* The rule that a flag word over n_records records stands for; its name ("dropped", "bare", "same"; "?" for anything else); a name -> its number, or -1. */
+int32_t harc_amd_third_rule_of(uint32_t flags_and, uint64_t n_records);
+const char *harc_amd_third_rule_name(int32_t rule);
+int32_t harc_amd_third_rule_parse(const char *name);
+/* harc_amd_fastq_assemble_device, harc_amd_fastq_assemble_files_ex and harc_amd_fastq_assemble_pair_files with the rule of the third lines; those calls are these
+   with HARC_AMD_THIRD_BARE.  HARC_AMD_THIRD_SAME: record i is  id_i \n read_i \n '+' id_i[1..] \n quality_i \n, the output holds 2 * size(id) + n * (2 * readlen + 2)
+   bytes (still known before a byte is read), and in a pair the second file's third lines carry the second file's ids.  An id line of length 0 cannot be repeated
+   behind a '+': such lines are counted on the device, the call fails with HARC_AMD_EINVAL naming the count and out_path is removed.  HARC_AMD_THIRD_DROPPED writes
+   what bare writes.  Any other number: HARC_AMD_EINVAL. */
+int harc_amd_fastq_assemble_third_device(harc_amd_ctx *ctx, const char *d_ids, uint64_t id_bytes, const char *d_dna, const char *d_quality, uint32_t n_records,
+                                         int32_t readlen, char *d_out, uint64_t out_capacity, uint64_t *n_out, int32_t third);
+int harc_amd_fastq_assemble_third_files(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out_path,
+                                        int32_t bgzf, int32_t third);
+int harc_amd_fastq_assemble_third_pair_files(const harc_amd_params *params, const char *dna_path, const char *id_path, const char *quality_path, const char *out1_path,
+                                             const char *out2_path, uint64_t records_per_file, int32_t rule, int32_t bgzf, int32_t third);
 
 #ifdef __cplusplus
 }

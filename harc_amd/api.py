@@ -218,6 +218,14 @@ def lib():
         l.harc_amd_idunpack_range_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64]
         l.harc_amd_decoder_range_files.argtypes = [PP, C.c_char_p, C.c_int32, C.c_int32, U64P, U64P]
         l.harc_amd_decoder_preserve_range_files.argtypes = [PP, C.c_char_p, C.c_int32, C.c_int32, U64P, U64P]
+    if hasattr(l, "harc_amd_select_files"):              # (HARC_AMD_LIB may name a build from before selection by name)
+        U8P = C.POINTER(C.c_uint8)
+        l.harc_amd_name_key_host.argtypes = [C.c_char_p, C.c_uint64, U64P]
+        l.harc_amd_select_flags_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, U64P, U64P, U64P]
+        l.harc_amd_select_flags_host.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, U8P, U64P, U64P, U64P]
+        l.harc_amd_lines_gather_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, U64P]
+        l.harc_amd_lines_gather_host.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, U64P]
+        l.harc_amd_select_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_int32, U64P, C.c_char_p, C.c_uint64]
     if hasattr(l, "harc_amd_recovery_make_files"):       # (HARC_AMD_LIB may name a build from before the recovery record)
         CPP, VPP, I32P = C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)
         l.harc_amd_block_digests_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, U64P]
@@ -464,6 +472,47 @@ def idunpack_range_files(packed, out, first_line, n_lines, device=0):
     """idunpack_files for lines first_line .. first_line + n_lines - 1 (counted from 0) alone: only the blocks that hold them are read, decoded and checked"""
     p = default_params(100, device=device)
     _check(lib().harc_amd_idunpack_range_files(C.byref(p), os.fsencode(packed), os.fsencode(out), first_line, n_lines))
+
+
+def name_key(line):
+    """(offset, length) of the name of `line` (bytes, without its newline): a leading '@' skipped, up to the first space or tab, one trailing "/1" or "/2" of a name
+    of at least 3 bytes dropped (include/harc_amd.h: harc_amd_name_key_host); no device"""
+    out = (C.c_uint64 * 2)()
+    line = bytes(line)
+    _check(lib().harc_amd_name_key_host(line, len(line), out))
+    return int(out[0]), int(out[1])
+
+
+def select_flags_host(names, ids):
+    """(flags, distinct names, names found): flags[i] = 1 when the name of line i of the id text `ids` is the name of a line of the list `names` (both bytes), on
+    the host: what HarcAmd.select_flags_device is held to (include/harc_amd.h: harc_amd_select_flags_host); no device"""
+    names, ids = bytes(names), bytes(ids)
+    room = ids.count(b"\n") + 1
+    flags = (C.c_uint8 * room)()
+    n, k, f = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _check(lib().harc_amd_select_flags_host(names, len(names), ids, len(ids), flags, C.byref(n), C.byref(k), C.byref(f)))
+    return bytes(flags[:n.value]), k.value, f.value
+
+
+def lines_gather_host(text, flags, stride=0):
+    """the lines of `text` whose flag byte is not zero, one behind the other: lines of `stride` bytes each, or (stride 0) lines of any length with their newlines
+    (include/harc_amd.h: harc_amd_lines_gather_host); no device"""
+    text, flags = bytes(text), bytes(flags)
+    out = C.create_string_buffer(len(text) + 1)
+    n = C.c_uint64(0)
+    _check(lib().harc_amd_lines_gather_host(text, len(text), stride, flags, len(flags), out, len(text), C.byref(n)))
+    return out.raw[:n.value]
+
+
+def select_files(names, ids, dna, quality, out_ids, out_dna, out_quality, pair_records=0, pair_rule="none", device=0):
+    """the records of the three texts of an archive whose id line carries a name of the list file `names` -> the three out files, selected and gathered on the GPU
+    in one call (include/harc_amd.h: harc_amd_select_files) -> (distinct names, names found, records selected, records, [up to ten names not found])"""
+    p = default_params(100, device=device)
+    st = (C.c_uint64 * 4)()
+    missing = C.create_string_buffer(1 << 16)
+    _check(lib().harc_amd_select_files(C.byref(p), os.fsencode(names), os.fsencode(ids), os.fsencode(dna), os.fsencode(quality), os.fsencode(out_ids), os.fsencode(out_dna),
+                                       os.fsencode(out_quality), pair_records, _rule_number(pair_rule) if pair_records else 0, st, missing, len(missing)))
+    return int(st[0]), int(st[1]), int(st[2]), int(st[3]), [m for m in missing.value.split(b"\n") if m]
 
 
 def fastq_assemble(dna, ids, quality, out, device=0, bgzf=False, third=None):
@@ -1000,6 +1049,21 @@ class HarcAmd:
         out = (C.c_uint64 * 2)()
         _check(lib().harc_amd_line_offset_device(self._ctx, C.c_void_p(ptr) if ptr else None, nbytes, k, out))
         return int(out[0]), int(out[1])
+
+    def select_flags_device(self, d_names, names_bytes, d_ids, id_bytes, d_flags):
+        """select_flags_host on the GPU: both texts in device memory at any alignment, one flag byte per id line written to d_flags -> (id lines, distinct names,
+        names found)"""
+        n, k, f = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().harc_amd_select_flags_device(self._ctx, C.c_void_p(d_names) if d_names else None, names_bytes, C.c_void_p(d_ids) if d_ids else None, id_bytes,
+                                                  C.c_void_p(d_flags) if d_flags else None, C.byref(n), C.byref(k), C.byref(f)))
+        return n.value, k.value, f.value
+
+    def lines_gather_device(self, d_text, nbytes, stride, d_flags, n_lines, d_out, capacity):
+        """lines_gather_host on the GPU: the flagged lines of the text at d_text -> d_out (device memory, any alignment) -> the bytes written"""
+        n = C.c_uint64(0)
+        _check(lib().harc_amd_lines_gather_device(self._ctx, C.c_void_p(d_text) if d_text else None, nbytes, stride, C.c_void_p(d_flags) if d_flags else None, n_lines,
+                                                  C.c_void_p(d_out) if d_out else None, capacity, C.byref(n)))
+        return n.value
 
     def idmate_rule_device(self, d_a, a_bytes, d_b, b_bytes):
         """the mate rule of two id texts in device memory (any alignment) -> (rule name, pairs, the AND of the pairs' flags)"""

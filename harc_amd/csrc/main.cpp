@@ -50,6 +50,11 @@
 //   harc_amd_stage recovery_check <record> [<device>]                      the files the record names, next to it, held against it; one "[recovery]" line per file; 0 when nothing
 //                                                                          is damaged (./harc -R -n)
 //   harc_amd_stage recovery_repair <record> [<device>]                     ... and the damaged blocks rebuilt in place; 0 when every file verifies in the end (./harc -R)
+//   harc_amd_stage records_select <names> <device> <ids> <dna> <quality> <out_ids> <out_dna> <out_quality> [pair <records> <rule>]
+//                                                                          the records whose id line carries a name of the list <names> -> the three <out_*> texts, selected and
+//                                                                          gathered on the GPU in one process (./harc -d -q -L); "[select] <names> names, <found> found, <selected>
+//                                                                          of <records> records" on stdout, then up to ten "[select] not found: <name>" lines; 0 also when nothing
+//                                                                          was selected
 // (every <first> above counts lines from 0; ./harc -r counts from 1)
 // compressfq takes one more trailing argument, "check" (./harc -c -V): the streams are decoded once before they are written, and output/read.check is written.
 // readlen / num_thr arrive as arguments instead of the compile-time macros of src/config.h (harc:52-63).
@@ -244,6 +249,23 @@ int main(int argc, char **argv)
         const int rcl = harc_amd_line_range_files(&PL, argv[2], first, count, r);
         if (rcl != 0) { fprintf(stderr, "harc_amd_stage line_range failed (%d): %s\n", rcl, harc_amd_last_error()); return 1; }
         printf("%llu %llu\n", (unsigned long long)r[0], (unsigned long long)r[1]);
+        return 0;
+    }
+    if (!strcmp(argv[1], "records_select")) {
+        // records_select <names> <device> <ids> <dna> <quality> <out_ids> <out_dna> <out_quality> [pair <records> <rule>]
+        uint64_t records = 0; int32_t rule = 0;
+        bool ok = argc == 10 || argc == 13;
+        if (ok && argc == 13) { ok = !strcmp(argv[10], "pair") && number(argv[11], &records) && records >= 1; rule = ok ? harc_amd_idmate_rule_parse(argv[12]) : -1; ok = ok && rule >= 0; }
+        if (!ok) { fprintf(stderr, "records_select needs <names> <device> <ids> <dna> <quality> <out_ids> <out_dna> <out_quality> [pair <records> <none|same|slash|space>]\n"); return 2; }
+        harc_amd_params PS;
+        if (harc_amd_default_params(100, &PS) != 0) { fprintf(stderr, "%s\n", harc_amd_last_error()); return 1; }
+        PS.device = atoi(argv[3]);
+        uint64_t st[4] = { 0, 0, 0, 0 };
+        static char missing[1 << 16];
+        const int rcs = harc_amd_select_files(&PS, argv[2], argv[4], argv[5], argv[6], argv[7], argv[8], argv[9], records, rule, st, missing, sizeof missing);
+        if (rcs != 0) { fprintf(stderr, "harc_amd_stage records_select failed (%d): %s\n", rcs, harc_amd_last_error()); return 1; }
+        printf("[select] %llu names, %llu found, %llu of %llu records\n", (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[2], (unsigned long long)st[3]);
+        for (const char *p = missing; *p;) { const char *e = strchr(p, '\n'); if (!e) break; printf("[select] not found: %.*s\n", (int)(e - p), p); p = e + 1; }
         return 0;
     }
     if (!strcmp(argv[1], "quality_unpack_range") || !strcmp(argv[1], "id_unpack_range")) {

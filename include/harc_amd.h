@@ -627,6 +627,52 @@ int harc_amd_idunpack_range_files(const harc_amd_params *params, const char *pac
 int harc_amd_decoder_range_files(const harc_amd_params *params, const char *basedir, int32_t num_thr_e, int32_t n_ranges, const uint64_t *first, const uint64_t *count);
 int harc_amd_decoder_preserve_range_files(const harc_amd_params *params, const char *basedir, int32_t num_thr_e, int32_t n_ranges, const uint64_t *first, const uint64_t *count);
 
+/* ---- Selection by name (./harc -d -q -L NAMES; README.md, "-L and what it promises").  The name of a line (harc_amd/csrc/namekey.h, once for host and device;
+   the line without its newline, any bytes): a leading '@' is skipped, the name runs up to the first space or tab or to the line's end, and a name of at least
+   3 bytes that ends in "/1" or "/2" loses those two bytes, once.  An empty name never matches.  A last line without its newline counts as a line in both texts.
+   out[0] = where the name of line[0 .. n) starts, out[1] = its length.  Touches no device. */
+int harc_amd_name_key_host(const void *line, uint64_t n, uint64_t out[2]);
+/* d_flags[i] = 1 when the name of line i of the id text is the name of a line of the list, else 0: one byte per id line, room for every line of the text.
+   Both texts lie in device memory at any alignment; no load leaves their 16-byte hulls.  The list's names go into an open-addressing table (the smallest power
+   of two >= 2 x list lines slots, at least 64; a slot holds the 64-bit hash of namekey.h and a list line; claimed with one 32-bit atomicCAS, linear probing,
+   equal names told from equal hashes by their bytes; the hashes are filled in by a launch behind the claims), then k_name_probe streams the id text, eight
+   lanes a line and eight bytes a lane and step, without atomics.  *n_lines = the id lines, *n_names = the distinct names of the list that are not empty,
+   *n_found = those of them that at least one id line carries.  All outputs are functions of the two texts alone.  names_bytes: at most 2^30; id_bytes: at most
+   2^32 - 1 (HARC_AMD_EINVAL beyond: harc_amd_select_files walks a longer text in pieces).  HARC_AMD_SELECT_HASH_BITS=b (1 .. 64, tests) keeps the low b bits of
+   every hash, table and probe alike: the outputs do not change.  HARC_AMD_TRACE=1: one "[select] device call" line on stderr with the probe kernel's time. */
+int harc_amd_select_flags_device(harc_amd_ctx *ctx, const void *d_names, uint64_t names_bytes, const void *d_ids, uint64_t id_bytes, uint8_t *d_flags,
+                                 uint64_t *n_lines, uint64_t *n_names, uint64_t *n_found);
+/* The same over host memory, serially: what the kernels are held to (tests).  Touches no device. */
+int harc_amd_select_flags_host(const void *names, uint64_t names_bytes, const void *ids, uint64_t id_bytes, uint8_t *flags, uint64_t *n_lines, uint64_t *n_names,
+                               uint64_t *n_found);
+/* The lines of a text whose flag byte is not zero, one behind the other at d_out (device memory, any alignment, room for `capacity` bytes; nothing outside
+   the result's bytes is written).  stride > 0: line i is bytes [i stride, (i + 1) stride) and nbytes = n_lines x stride (HARC_AMD_EINVAL otherwise); every lane
+   owns 16 bytes of the output and writes them with one aligned store where the output allows.  stride 0: lines of any length, n_lines the text's lines
+   (HARC_AMD_EINVAL naming both otherwise), each copied with its newline, a last line without one as it is.  nbytes at most 2^32 - 1.  The offsets come from the
+   library's scan over the flags.  *out_bytes = the bytes of the result; more than capacity: HARC_AMD_EINVAL naming both, nothing written. */
+int harc_amd_lines_gather_device(harc_amd_ctx *ctx, const void *d_text, uint64_t nbytes, uint64_t stride, const uint8_t *d_flags, uint64_t n_lines, void *d_out,
+                                 uint64_t capacity, uint64_t *out_bytes);
+/* The same over host memory, serially (tests).  Touches no device. */
+int harc_amd_lines_gather_host(const void *text, uint64_t nbytes, uint64_t stride, const uint8_t *flags, uint64_t n_lines, void *out, uint64_t capacity, uint64_t *out_bytes);
+/* The records of an archive's three texts whose id line carries a name of the list at names_path, in one call on one context: ids_path (lines of any length),
+   dna_path and quality_path (lines of one length, the first line's of dna_path) -> out_ids_path, out_dna_path, out_quality_path, in their order.
+   Phase A: the list is loaded whole, the id file walks through the pinned ring in pieces of HARC_AMD_SELECT_PIECE bytes (default 256 MiB; tests: a few bytes), what
+   lies behind a piece's last whole line is carried, the probe runs on every piece's whole lines, the flags of the whole job stay resident at one byte a line.
+   Phase B: each file goes through the ring in pieces of whole lines (the fixed-length files HARC_AMD_SELECT_LINES lines a piece), every piece is gathered and
+   drained into an output file whose size is known from the selection.
+   pair_records = 0: record i is selected when the name of id line i is listed; the id file holds as many lines as dna_path.  pair_records = n > 0, an archive of a
+   pair (dna_path and quality_path hold 2 n lines, file 1's records first): with a pair_rule other than HARC_AMD_IDMATE_NONE the id file holds n lines, line i
+   selects records i and n + i, and out_ids holds the selected lines once; with HARC_AMD_IDMATE_NONE it holds 2 n lines, pair i is selected when line i or line
+   n + i is listed, and out_ids holds both halves' selected lines.  out_dna / out_quality hold the selected records of [0, n), then of [n, 2 n).
+   stats = { distinct names, names found, records selected, records } (for a pair: of each file).  missing (may be null) receives up to ten listed names that
+   no record carries, in list order, a newline behind each, zero-terminated, cut to missing_cap bytes.  Nothing selected is a success with stats[2] = 0 and three
+   empty files.  HARC_AMD_EINVAL naming both counts, and no output file left, for: id lines that are not the reads' lines (for a pair with a rule: half of them), a
+   quality file whose size is not the reads' file's, a pair_records that is not the id file's lines (under none: half of them), a list of more than 2^30 bytes or
+   without a name.  Only `device` is taken from params. */
+int harc_amd_select_files(const harc_amd_params *params, const char *names_path, const char *ids_path, const char *dna_path, const char *quality_path,
+                          const char *out_ids_path, const char *out_dna_path, const char *out_quality_path, uint64_t pair_records, int32_t pair_rule,
+                          uint64_t stats[4], char *missing, uint64_t missing_cap);
+
 /* ---- The recovery record (./harc -c -P PCT writes X.hr, ./harc -R repairs from it; README: "-P and what it promises", "The recovery record (X.hr)").  Files are cut
    into blocks of B bytes, blocks into spans, spans into interleaved groups of at most 128 members; a group of k members gets m = min(128, max(1, ceil(k PCT / 100)))
    recovery blocks, recovery block i = XOR_j inverse(i ^ (128 + j)) * member_j over GF(2^8) with the polynomial 0x11D (a Cauchy matrix: any e <= m lost members of a

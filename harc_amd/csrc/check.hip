@@ -155,16 +155,6 @@ extern "C" int harc_amd_input_order_digest(harc_amd_ctx *c, uint64_t *out)
 }
 
 // ------------------------------------------------------------------------------------------------ the files
-// a slice for the ring of a file of fsz bytes: files of a few MB do not pin a ring of 1 GiB
-static size_t ck_slice(uint64_t fsz)
-{
-    const uint64_t full = (uint64_t)64 << 20;
-    if (fsz >= 16 * full) return 0;
-    uint64_t s = (fsz + 15) / 16;
-    s = (s + 4095) & ~(uint64_t)4095;
-    return (size_t)(s < 65536 ? 65536 : s);
-}
-
 extern "C" int harc_amd_text_digest_files(const harc_amd_params *params, const char *path, uint64_t *out)
 {
     if (!params || !path || !out) { harc_set_error("text_digest_files: bad arguments"); return HARC_AMD_EINVAL; }
@@ -176,10 +166,9 @@ extern "C" int harc_amd_text_digest_files(const harc_amd_params *params, const c
     RC_TRY(side_context(params, 100, &guard.c));
     harc_amd_ctx *c = guard.c;
     RingGeom g;
-    RC_TRY(ring_split(c, 1, 16, "check", &g, ck_slice(fsz)));
+    RC_TRY(ring_split(c, 1, 16, "check", &g, ring_slice_for(fsz, 16)));
     const uint64_t piece = (uint64_t)64 << 20;
-    std::vector<std::pair<uint64_t, uint64_t>> pieces;
-    for (uint64_t a = 0; a < fsz; a += piece) pieces.emplace_back(a, fsz - a < piece ? fsz : a + piece);
+    const Pieces pieces = byte_pieces(0, fsz, piece);
     DevBuf txt{ c };
     RC_TRY(dev_reserve(&txt, (size_t)(fsz < piece ? fsz : piece)));
     PoolScope scope(c);
@@ -220,10 +209,9 @@ extern "C" int harc_amd_reads_check_files(const harc_amd_params *params, const c
     RC_TRY(side_context(params, (int)L, &guard.c));
     harc_amd_ctx *c = guard.c;
     RingGeom g;
-    RC_TRY(ring_split(c, 1, 16, "check", &g, ck_slice(fsz)));
+    RC_TRY(ring_split(c, 1, 16, "check", &g, ring_slice_for(fsz, 16)));
     const uint64_t dflt = ((uint64_t)64 << 20) / LL, piece_lines = dflt ? dflt : 1;
-    std::vector<std::pair<uint64_t, uint64_t>> pieces;
-    for (uint64_t a = 0; a < n; a += piece_lines) pieces.emplace_back(a * LL, (n - a < piece_lines ? n : a + piece_lines) * LL);
+    const Pieces pieces = line_pieces(n, LL, piece_lines);
     DevBuf txt{ c };
     RC_TRY(dev_reserve(&txt, (size_t)(pieces[0].second - pieces[0].first)));
     PoolScope scope(c);

@@ -13,7 +13,7 @@
 // longer than a tile (an id of 40 000 bytes) is simply clipped to the tile by every workgroup it reaches into.  The first and the last 16 bytes of the whole
 // output, where the caller's buffer is not aligned or does not end on a 16-byte boundary, are stored byte by byte by the lanes that hold them.
 // The same lanes check the fixed-width inputs on the way -- a newline at every (readlen + 1)-stride position and nowhere else -- into an error counter.
-// The plumbing of the file call (probes, guards, ring split, device buffers, kernel timer, the carried tail of the id text) is fileio.h's.
+// The plumbing of the file call (probes, guards, ring split, device buffers, kernel timer, the walk over the id file in whole lines) is fileio.h's.
 #include "devutil.h"
 #include "fileio.h"
 #include "deflate_member.h"
@@ -151,23 +151,6 @@ __global__ void k_fq_stride_check(const char *txt, uint64_t nbytes, int L, unsig
     if (bad) atomicAdd(err, bad);
 }
 
-// the line index of an id text and whether its last line lacks the newline.  Pool memory: the caller brackets it
-int fq_index(harc_amd_ctx *c, const char *d_ids, uint64_t id_bytes, const uint64_t **nls, uint64_t *lines, bool *open_tail)
-{
-    *lines = 0; *open_tail = false;
-    if (id_bytes == 0) {                                          // no text, no line; the kernel still reads nls[-1]
-        uint64_t *z = nullptr; RC_TRY(dalloc(c, &z, 2));
-        HIP_TRY(hipMemsetAsync(z, 0xFF, 16, c->stream));
-        *nls = z + 1;
-        return HARC_AMD_OK;
-    }
-    RC_TRY(build_line_index(c, d_ids, id_bytes, nls, lines));
-    char lastch = 0;
-    HIP_TRY(hipMemcpyAsync(&lastch, d_ids + id_bytes - 1, 1, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *open_tail = lastch != '\n';
-    return HARC_AMD_OK;
-}
 // id lines of length 0 among lines [0, n) (the validating device call under the rule same)
 __global__ void k_fq_empty_ids(const uint64_t *nls, uint32_t n, unsigned int *err)
 {
@@ -228,7 +211,7 @@ extern "C" int harc_amd_fastq_assemble_third_device(harc_amd_ctx *c, const char 
     HIP_TRY(hipSetDevice(c->P.device));
     PoolScope scope(c);
     const uint64_t *nls = nullptr; uint64_t lines = 0; bool open_tail = false;
-    RC_TRY(fq_index(c, d_ids, id_bytes, &nls, &lines, &open_tail));
+    RC_TRY(text_line_index(c, d_ids, id_bytes, &nls, &lines, &open_tail));
     if (lines != (uint64_t)n_records) { harc_set_error("fastq_assemble_device: the id text holds %llu lines, %u records were announced", (unsigned long long)lines, n_records); return HARC_AMD_EINVAL; }
     const uint64_t total = fq_text_bytes(third, id_bytes + (open_tail ? 1 : 0), n_records, readlen);
     *n_out = total;
@@ -304,7 +287,7 @@ template <class M> static int fq_assemble_part(harc_amd_ctx *c, const RingGeom *
     const uint64_t LL = (uint64_t)L + 1;
     const bool id_open_tail = in.id_open_tail && isz > id_begin;
     const uint64_t out_size = fq_text_bytes(third, (isz - id_begin) + (id_open_tail ? 1 : 0), nrec, L);    // known before a byte is read: the output is sized and mapped up front (stop_at_nrec: a bound)
-    CarriedText ids(c); DevBuf dna{ c }, qual{ c }, out{ c }, gz{ c };
+    DevBuf dna{ c }, qual{ c }, out{ c }, gz{ c };
     const bool tlog = getenv("HARC_AMD_TRACE") != nullptr;
     double t_kernel = 0, t_read = 0, t_write = 0;
     KernelTimer timer(&t_kernel);
@@ -315,75 +298,45 @@ template <class M> static int fq_assemble_part(harc_amd_ctx *c, const RingGeom *
     FileDrain drain(c);
     RC_TRY(drain.start(out_path, bgzf ? (size_t)dm_bound(out_size) : (size_t)out_size, &gq[3], bgzf != 0 || stop_at_nrec));
     BgzfOutStats gst; uint64_t gz_at = 0, tcarry = 0;                  // bgzf: bytes of the file so far; text in front of `out` that no member holds yet
-    // the job is driven by the id file: a piece is a byte range of it; what follows the piece's last newline is carried into the next piece
-    const uint64_t piece = env_u64("HARC_AMD_FQOUT_PIECE", (uint64_t)256 << 20);
-    std::vector<std::pair<uint64_t, uint64_t>> pieces;
-    if (!(stop_at_nrec && nrec == 0)) for (uint64_t a = id_begin; a < isz; a += piece) pieces.emplace_back(a, isz - a < piece ? isz : a + piece);
-    FileFeeder idf(c, in.id_path);
-    if (!pieces.empty()) RC_TRY(idf.start(pieces, gq[0]));
-    uint64_t r0 = 0, lines_seen = 0, out_at = 0; int npieces = 0; bool over = false;
-    *id_end = id_begin;
-    for (size_t p = 0; p < pieces.size(); p++) {
-        const uint64_t len = pieces[p].second - pieces[p].first, total = ids.carry + len, origin = pieces[p].first - ids.carry; const bool lastp = p + 1 == pieces.size();
-        RC_TRY(ids.take(idf, p, len, &t_read));                                              // the carried bytes sit at its front
-        char *d_ids = ids.text();
-        PoolScope piece_scope(c);
-        const uint64_t *nls = nullptr; uint64_t lines = 0; bool open_tail = false;
-        RC_TRY(fq_index(c, d_ids, total, &nls, &lines, &open_tail));
-        uint64_t m = lines - ((open_tail && !lastp) ? 1 : 0);                              // whole lines; a last line of the FILE without its newline is one
-        if (m == 0 && !lastp) { ids.carry = total; continue; }                               // not one whole line yet: the piece grows by the next one
-        const bool clip = stop_at_nrec && r0 + m > nrec;                                     // the lines of this output end inside the piece
-        if (clip) m = nrec - r0;
-        uint64_t cut = total;
-        if ((open_tail && !lastp) || clip) {
-            cut = 0;
-            if (m) {
-                HIP_TRY(hipMemcpyAsync(&cut, nls + (m - 1), 8, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(hipStreamSynchronize(c->stream));
-                cut += 1;
-            }
-        }
-        lines_seen += m;
+    // the job is driven by the id file (walk_lines of fileio.h): a turn assembles the records of the whole id lines at hand
+    LineWalk w; w.begin = w.end = id_begin; w.piece = env_u64("HARC_AMD_FQOUT_PIECE", (uint64_t)256 << 20); w.geom = gq[0];
+    uint64_t r0 = 0, out_at = 0; int npieces = 0; bool over = false;
+    if (!(stop_at_nrec && nrec == 0)) RC_TRY(walk_lines(c, in.id_path, isz, &w, [&](CarriedText &ids, LineTurn &t) -> int {
+        if (stop_at_nrec && r0 + t.whole >= nrec) RC_TRY(ids.end_at(&t, nrec - r0));         // the lines of this output end in the piece: what follows belongs to the next output
+        const uint64_t m = t.whole;
         if (r0 + m > nrec) over = true;                                                      // more ids than reads: the lines are still counted, for the message
-        if (!over && m) {
-            const uint64_t nb = m * LL, out_bytes = fq_text_bytes(third, cut + ((lastp && open_tail && !clip) ? 1 : 0), m, L);
-            RC_TRY(dev_reserve(&dna, (size_t)nb)); RC_TRY(dev_reserve(&qual, (size_t)nb)); RC_TRY(dev_reserve(&out, (size_t)(tcarry + out_bytes), (size_t)tcarry));
-            {   // lines [rec_base + r0, rec_base + r0 + m) of the two fixed-width files, by offset
-                const uint64_t f0 = (rec_base + r0) * LL, f1 = (rec_base + r0 + m) * LL;
-                FileFeeder fd(c, in.dna_path), fq(c, in.quality_path);
-                RC_TRY(fd.start({ { f0, f1 } }, gq[1])); RC_TRY(fq.start({ { f0, f1 } }, gq[2]));
-                const double t0 = mono_now();
-                RC_TRY(fd.upload_piece(0, dna.p, nullptr)); RC_TRY(fq.upload_piece(0, qual.p, nullptr));
-                t_read += mono_now() - t0;
-                RC_TRY(timer.begin(c->stream));
-                RC_TRY(harc_idmate_apply_lines(c, d_ids, nls, m, rule, d_bad));              // (nothing for the rules that patch nothing)
-                RC_TRY(fq_run(c, d_ids, nls, dna.p, qual.p, (uint32_t)m, L, out.p + tcarry, out_bytes, d_err, third));
-                RC_TRY(timer.end_mark(c->stream));
-                if (!bgzf) { const double t0w = mono_now(); RC_TRY(drain.put(out.p, (size_t)out_bytes, out_at)); t_write += mono_now() - t0w; }
-                else {
-                    const uint64_t have = tcarry + out_bytes, full = have / DM_TEXT * DM_TEXT;
-                    if (full) {
-                        uint64_t ngz = 0;
-                        RC_TRY(dev_reserve(&gz, (size_t)dm_bound(full)));
-                        RC_TRY(harc_bgzf_deflate(c, out.p, full, 0, (uint8_t *)gz.p, gz.cap, &ngz, &gst));
-                        { const double t0w = mono_now(); RC_TRY(drain.put(gz.p, (size_t)ngz, gz_at)); t_write += mono_now() - t0w; }
-                        gz_at += ngz;
-                        if (have > full) HIP_TRY(hipMemcpyAsync(out.p, out.p + full, (size_t)(have - full), hipMemcpyDeviceToDevice, c->stream));     // (less than a member: no overlap)
-                    }
-                    tcarry = have - full;
-                }
-                out_at += out_bytes; npieces++;
-                RC_TRY(timer.end_wait());
-            }                                                                                // (the feeders wait for the stream when they go)
+        if (over) return HARC_AMD_OK;
+        const uint64_t nb = m * LL, out_bytes = fq_text_bytes(third, t.cut + ((t.open && m == t.lines) ? 1 : 0), m, L);      // (a last line of the FILE without its newline is one)
+        RC_TRY(dev_reserve(&dna, (size_t)nb)); RC_TRY(dev_reserve(&qual, (size_t)nb)); RC_TRY(dev_reserve(&out, (size_t)(tcarry + out_bytes), (size_t)tcarry));
+        // lines [rec_base + r0, rec_base + r0 + m) of the two fixed-width files, by offset
+        const uint64_t f0 = (rec_base + r0) * LL, f1 = (rec_base + r0 + m) * LL;
+        FileFeeder fd(c, in.dna_path), fq(c, in.quality_path);                               // (the feeders wait for the stream when they go)
+        RC_TRY(fd.start({ { f0, f1 } }, gq[1])); RC_TRY(fq.start({ { f0, f1 } }, gq[2]));
+        const double t0 = mono_now();
+        RC_TRY(fd.upload_piece(0, dna.p, nullptr)); RC_TRY(fq.upload_piece(0, qual.p, nullptr));
+        t_read += mono_now() - t0;
+        RC_TRY(timer.begin(c->stream));
+        RC_TRY(harc_idmate_apply_lines(c, t.text, t.nls, m, rule, d_bad));                   // (nothing for the rules that patch nothing)
+        RC_TRY(fq_run(c, t.text, t.nls, dna.p, qual.p, (uint32_t)m, L, out.p + tcarry, out_bytes, d_err, third));
+        RC_TRY(timer.end_mark(c->stream));
+        if (!bgzf) { const double t0w = mono_now(); RC_TRY(drain.put(out.p, (size_t)out_bytes, out_at)); t_write += mono_now() - t0w; }
+        else {
+            const uint64_t have = tcarry + out_bytes, full = have / DM_TEXT * DM_TEXT;
+            if (full) {
+                uint64_t ngz = 0;
+                RC_TRY(dev_reserve(&gz, (size_t)dm_bound(full)));
+                RC_TRY(harc_bgzf_deflate(c, out.p, full, 0, (uint8_t *)gz.p, gz.cap, &ngz, &gst));
+                { const double t0w = mono_now(); RC_TRY(drain.put(gz.p, (size_t)ngz, gz_at)); t_write += mono_now() - t0w; }
+                gz_at += ngz;
+                if (have > full) HIP_TRY(hipMemcpyAsync(out.p, out.p + full, (size_t)(have - full), hipMemcpyDeviceToDevice, c->stream));     // (less than a member: no overlap)
+            }
+            tcarry = have - full;
         }
-        if (!over) r0 += m;
-        *id_end = origin + cut;
-        if (stop_at_nrec && r0 == nrec) break;                                               // what follows belongs to the next output
-        const uint64_t rest = total - cut;
-        if (rest) RC_TRY(ids.carry_from(cut, rest));
-        else ids.carry = 0;
-    }
-    if (over || r0 != nrec) { on_mismatch(lines_seen); return HARC_AMD_EINVAL; }
+        out_at += out_bytes; npieces++; r0 += m;
+        return timer.end_wait();
+    }));
+    *id_end = w.end; t_read += w.t_read;
+    if (over || r0 != nrec) { on_mismatch(w.lines); return HARC_AMD_EINVAL; }
     if (!stop_at_nrec && out_at != out_size) { harc_set_error("fastq_assemble_files: %llu bytes assembled, the file sizes announce %llu", (unsigned long long)out_at, (unsigned long long)out_size); return HARC_AMD_EINTERNAL; }
     RC_TRY(fq_check_errors(c, d_err, L));
     {

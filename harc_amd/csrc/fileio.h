@@ -1,7 +1,9 @@
 // fileio.h -- the two file <-> HBM movers of the library, shared by ingest.hip (FASTQ in), verify.hip (decoded reads out), fastq_out.hip (both at once) and, through
 // packfile.h, qpack.hip and idpack.hip: FileFeeder reads a file into device memory, FileDrain writes device memory into a file, each through pinned slices of the
 // context's ring (c->feed_ring) worked by a few host threads.  Around them, once each, what every file-level call needs: the probes of a file (size, first line, last
-// byte), whole files read and written, the guards of an output file and of a context, the split of the ring, an owning device buffer, a kernel timer, and a text whose cut tail is carried on.
+// byte), whole files read and written, the guards of an output file and of a context, the split of the ring and the slice of a short file's ring, the list of pieces
+// a file is fed in (bytes, fixed-stride lines), an owning device buffer, a kernel timer, a text whose cut tail is carried on (CarriedText) with the steps of a turn
+// over its whole lines (idmate.hip and idpack.hip loop over them their own way), and walk_lines: the one walk over a file of lines of any length (select.hip, fastq_out.hip).
 #pragma once
 #include "internal.h"
 #include <string>
@@ -124,6 +126,27 @@ static inline int ring_split(harc_amd_ctx *c, int parts, int slices_each, const 
     harc_ring_geom_env(&base);
     for (int k = 0; k < parts; k++) { out[k].slice = base.slice; out[k].nslices = slices_each; out[k].nthr = base.nthr / parts > 0 ? base.nthr / parts : 1; out[k].ring_off = (size_t)k * slices_each * base.slice; }
     return harc_ring_reserve(c, (size_t)parts * slices_each * base.slice, what);
+}
+// the `slice` of ring_split for a mover of `slices` slices whose largest piece of work holds `most` bytes: a file of a few MB does not pin a ring of 1 GiB
+static inline size_t ring_slice_for(uint64_t most, uint64_t slices)
+{
+    if (most >= ((uint64_t)16 * 64 << 20)) return 0;
+    const uint64_t s = ((most + slices - 1) / slices + 4095) & ~(uint64_t)4095;
+    return (size_t)(s < 65536 ? 65536 : s);
+}
+// What FileFeeder::start takes: the bytes [lo, hi) of a file in pieces of `piece` bytes; n lines of LL bytes each in pieces of `piece_lines` lines
+typedef std::vector<std::pair<uint64_t, uint64_t>> Pieces;
+static inline Pieces byte_pieces(uint64_t lo, uint64_t hi, uint64_t piece)
+{
+    Pieces pieces;
+    for (uint64_t a = lo; a < hi; a += piece) pieces.emplace_back(a, hi - a < piece ? hi : a + piece);
+    return pieces;
+}
+static inline Pieces line_pieces(uint64_t n, uint64_t LL, uint64_t piece_lines)
+{
+    Pieces pieces;
+    for (uint64_t a = 0; a < n; a += piece_lines) pieces.emplace_back(a * LL, (n - a < piece_lines ? n : a + piece_lines) * LL);
+    return pieces;
 }
 
 // A device buffer that a file-level call owns and grows piece by piece
@@ -448,6 +471,9 @@ struct FileDrain {
 
 // A text that arrives in pieces and is worked in whole units (lines, blocks): what lies behind the last whole unit of a piece is carried to the front of the next.
 // Two buffers take turns: the carried bytes are copied device to device on the stream, behind the kernels that still read the piece they are cut from.
+// One turn over the lines of the text at hand: text[0 .. total) holds `lines` lines by the index nls, the last of them without its newline when `open`; the first
+// `whole` of them are worked in this turn and end in front of byte `cut`.  line0: whole lines of the turns before (walk_lines); stop: end_at() was called
+struct LineTurn { char *text; const uint64_t *nls; uint64_t total, lines, whole, cut, line0; bool open, stop; };
 struct CarriedText {
     DevBuf buf[2]; int cur = 0; uint64_t carry = 0;               // carry: bytes at the front of text() that the last piece left
     explicit CarriedText(harc_amd_ctx *c) : buf{ { c }, { c } } {}
@@ -469,4 +495,73 @@ struct CarriedText {
         cur ^= 1; carry = rest;
         return HARC_AMD_OK;
     }
+    // ---- the steps of a turn over whole lines
+    // the lines of text()[0 .. total).  An open last line is a whole line only where the file ends (`last`).  Pool memory: the caller brackets the turn
+    int index(uint64_t total, bool last, LineTurn *t)
+    {
+        t->text = text(); t->total = t->cut = total; t->line0 = 0; t->stop = false;
+        RC_TRY(text_line_index(buf[0].c, t->text, total, &t->nls, &t->lines, &t->open));
+        t->whole = t->lines - ((t->open && !last) ? 1 : 0);
+        return HARC_AMD_OK;
+    }
+    // *at: the byte behind line k - 1, where line k starts (of lines that have their newline)
+    int line_end(const uint64_t *nls, uint64_t k, uint64_t *at)
+    {
+        *at = 0;
+        if (!k) return HARC_AMD_OK;
+        hipStream_t s = buf[0].c->stream;
+        HIP_TRY(hipMemcpyAsync(at, nls + (k - 1), 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        *at += 1;
+        return HARC_AMD_OK;
+    }
+    // a walk's callable takes the first m <= whole lines of the turn only, and the walk ends behind them
+    int end_at(LineTurn *t, uint64_t m)
+    {
+        t->stop = true;
+        if (m == t->whole) return HARC_AMD_OK;
+        t->whole = m;
+        return line_end(t->nls, m, &t->cut);
+    }
+    // what lies behind byte `cut` of the `total` at hand is carried; with no whole unit in front of it the text stays where it is and grows by the next piece
+    int carry_behind(uint64_t cut, uint64_t total)
+    {
+        if (total - cut && cut) return carry_from(cut, total - cut);
+        carry = total - cut;
+        return HARC_AMD_OK;
+    }
 };
+
+// How walk_lines goes through the bytes [begin, fsz) of a file of lines of any length in pieces of `piece` bytes, and what it found.  text_limit: a text at hand
+// (what is carried and the piece) of more bytes is refused (0: any); sync_turn: the stream is waited for before a turn's line index goes
+struct LineWalk {
+    uint64_t begin = 0, piece = 0; RingGeom geom; uint64_t text_limit = 0; bool sync_turn = false;
+    uint64_t lines = 0, end = 0; double t_read = 0;               // out: the whole lines of all turns, the byte of the file behind the last of them, seconds in the uploads
+};
+// Every turn hands the whole lines of the text at hand to work(txt, turn): what lies behind a piece's last whole line is carried, a piece without a whole line grows
+// by the next one, and the last line of the file counts as a line with or without its newline.  work may cut the walk short (CarriedText::end_at)
+template <class F> static int walk_lines(harc_amd_ctx *c, const char *path, uint64_t fsz, LineWalk *w, F work)
+{
+    w->lines = 0; w->end = w->begin;
+    const Pieces pieces = byte_pieces(w->begin, fsz, w->piece);
+    if (pieces.empty()) return HARC_AMD_OK;
+    CarriedText txt(c);
+    FileFeeder feed(c, path);                                     // (goes first, and waits for the stream: nothing reads the text any more when its buffers go)
+    RC_TRY(feed.start(pieces, w->geom));
+    for (size_t p = 0; p < pieces.size(); p++) {
+        const uint64_t len = pieces[p].second - pieces[p].first, total = txt.carry + len, origin = pieces[p].first - txt.carry;
+        if (w->text_limit && total > w->text_limit) { harc_set_error("%s: a line of more than %llu bytes", path, (unsigned long long)(total - len)); return HARC_AMD_EINVAL; }
+        RC_TRY(txt.take(feed, p, len, &w->t_read));
+        PoolScope turn(c);
+        LineTurn t;
+        RC_TRY(txt.index(total, p + 1 == pieces.size(), &t));
+        t.line0 = w->lines;
+        if (t.whole < t.lines) RC_TRY(txt.line_end(t.nls, t.whole, &t.cut));
+        if (t.whole) RC_TRY(work(txt, t));
+        w->lines += t.whole; w->end = origin + t.cut;
+        if (t.stop) break;
+        RC_TRY(txt.carry_behind(t.cut, total));
+        if (w->sync_turn) HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return HARC_AMD_OK;
+}

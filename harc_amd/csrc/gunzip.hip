@@ -533,8 +533,7 @@ extern "C" int harc_amd_gunzip_files(const harc_amd_params *params, const char *
         // DEFLATE gives at most 1032 bytes of text per compressed byte: the file is mapped that long, its blocks are allocated as the text arrives, and it is cut at the end
         FileDrain drain(c);
         RC_TRY(drain.start(out_path, (size_t)(gsz * 1032 + 4096), &g[1], true));
-        std::vector<std::pair<uint64_t, uint64_t>> pieces;
-        for (uint64_t a = 0; a < gsz; a += piece) pieces.emplace_back(a, gsz - a < piece ? gsz : a + piece);
+        const Pieces pieces = byte_pieces(0, gsz, piece);
         FileFeeder feed(c, gz_path);
         RC_TRY(feed.start(pieces, g[0]));
         CarriedText in(c);

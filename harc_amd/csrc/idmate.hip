@@ -139,7 +139,7 @@ extern "C" int harc_amd_idmate_rule_device(harc_amd_ctx *c, const char *d_a, uin
     HIP_TRY(hipSetDevice(c->P.device));
     PoolScope scope(c);
     const uint64_t *nla = nullptr, *nlb = nullptr; uint64_t la = 0, lb = 0; bool oa = false, ob = false;
-    RC_TRY(fq_index(c, d_a, a_bytes, &nla, &la, &oa)); RC_TRY(fq_index(c, d_b, b_bytes, &nlb, &lb, &ob));
+    RC_TRY(text_line_index(c, d_a, a_bytes, &nla, &la, &oa)); RC_TRY(text_line_index(c, d_b, b_bytes, &nlb, &lb, &ob));
     RC_TRY(idm_refuse_counts("idmate_rule_device", la - (oa ? 1 : 0), oa, lb - (ob ? 1 : 0), ob));
     unsigned int *d_flags = nullptr; RC_TRY(dalloc(c, &d_flags, 4));
     HIP_TRY(hipMemsetAsync(d_flags, 0xFF, 16, c->stream));
@@ -167,7 +167,7 @@ extern "C" int harc_amd_idmate_apply_device(harc_amd_ctx *c, char *d_ids, uint64
     HIP_TRY(hipSetDevice(c->P.device));
     PoolScope scope(c);
     const uint64_t *nls = nullptr; uint64_t lines = 0; bool open = false;
-    RC_TRY(fq_index(c, d_ids, id_bytes, &nls, &lines, &open));
+    RC_TRY(text_line_index(c, d_ids, id_bytes, &nls, &lines, &open));
     unsigned long long *d_bad = nullptr; RC_TRY(dalloc(c, &d_bad, 2));
     HIP_TRY(hipMemsetAsync(d_bad, 0, 16, c->stream));
     RC_TRY(harc_idmate_apply_lines(c, d_ids, nls, lines - (open ? 1 : 0), rule, d_bad));      // whole lines only
@@ -200,13 +200,14 @@ extern "C" const char *harc_amd_idmate_rule_name(int32_t rule) { return idm_rule
 extern "C" int32_t harc_amd_idmate_rule_parse(const char *name) { return name ? idm_rule_parse(name) : -1; }
 
 // ------------------------------------------------------------------------------------------------ the files
-// one of the two id files on its way through the GPU: its pieces, its feeder, its text with what the last turn left
+// one of the two id files on its way through the GPU: its pieces, its feeder, its text with what the last turn left.  The steps of a turn (index, cut, carry) are
+// CarriedText's (fileio.h); the lockstep of the two files is this file's
 struct IdmSide {
     const char *path; uint64_t fsz = 0;
-    std::vector<std::pair<uint64_t, uint64_t>> pieces; size_t next = 0;
+    Pieces pieces; size_t next = 0;
     FileFeeder feed; CarriedText txt;
-    uint64_t total = 0, whole = 0, carry_lines = 0, lines_total = 0;      // bytes and whole lines of this turn's text; whole lines carried into it; whole lines seen in all
-    const uint64_t *nls = nullptr;
+    uint64_t total = 0, carry_lines = 0, lines_total = 0;         // bytes of this turn's text; whole lines carried into it; whole lines seen in all
+    LineTurn t;                                                   // its line index and its whole lines: those that have their newline
     IdmSide(harc_amd_ctx *c, const char *p) : path(p), feed(c, p), txt(c) {}
     bool done() const { return next == pieces.size(); }
 };
@@ -221,16 +222,13 @@ extern "C" int harc_amd_idmate_rule_files(const harc_amd_params *params, const c
     RC_TRY(side_context(params, 100, &guard.c));
     harc_amd_ctx *c = guard.c;
     // two feeders alive at the same time: half of the ring each; files of a few MB do not pin a ring of 1 GiB
-    const uint64_t big = asz > bsz ? asz : bsz;
-    size_t slice = 0;
-    if (big < ((uint64_t)16 * 64 << 20)) { uint64_t s = ((big + 7) / 8 + 4095) & ~(uint64_t)4095; slice = (size_t)(s < 65536 ? 65536 : s); }
     RingGeom g[2];
-    RC_TRY(ring_split(c, 2, 8, "id mates", g, slice));
+    RC_TRY(ring_split(c, 2, 8, "id mates", g, ring_slice_for(asz > bsz ? asz : bsz, 8)));
     const uint64_t piece = env_u64("HARC_AMD_IDMATE_PIECE", (uint64_t)256 << 20);
     IdmSide A(c, path_a), B(c, path_b); A.fsz = asz; B.fsz = bsz;
     IdmSide *S[2] = { &A, &B };
     for (int k = 0; k < 2; k++) {
-        for (uint64_t a = 0; a < S[k]->fsz; a += piece) S[k]->pieces.emplace_back(a, S[k]->fsz - a < piece ? S[k]->fsz : a + piece);
+        S[k]->pieces = byte_pieces(0, S[k]->fsz, piece);
         if (!S[k]->pieces.empty()) RC_TRY(S[k]->feed.start(S[k]->pieces, g[k]));
     }
     PoolScope scope(c);
@@ -253,27 +251,20 @@ extern "C" int harc_amd_idmate_rule_files(const harc_amd_params *params, const c
         PoolScope turn_scope(c);
         for (int k = 0; k < 2; k++) {
             IdmSide &s = *S[k];
-            uint64_t lines = 0; bool open = false;
-            RC_TRY(fq_index(c, s.txt.text(), s.total, &s.nls, &lines, &open));
-            s.whole = lines - (open ? 1 : 0);
-            s.lines_total += s.whole - s.carry_lines;
+            RC_TRY(s.txt.index(s.total, false, &s.t));
+            s.lines_total += s.t.whole - s.carry_lines;
         }
-        const uint64_t m = A.whole < B.whole ? A.whole : B.whole;
-        RC_TRY(idm_rule_launch(c, A.txt.text(), A.nls, B.txt.text(), B.nls, m, d_flags));
+        const uint64_t m = A.t.whole < B.t.whole ? A.t.whole : B.t.whole;
+        RC_TRY(idm_rule_launch(c, A.t.text, A.t.nls, B.t.text, B.t.nls, m, d_flags));
         pairs += m; turns++;
         for (int k = 0; k < 2; k++) {
             IdmSide &s = *S[k], &o = *S[k ^ 1];
             // lines whose partner can no longer come (the other file has ended and all its lines are paired) are counted and dropped
-            const uint64_t use = (o.done() && o.whole == m) ? s.whole : m;
+            const uint64_t use = (o.done() && o.t.whole == m) ? s.t.whole : m;
             uint64_t cut = 0;
-            if (use) {
-                HIP_TRY(hipMemcpyAsync(&cut, s.nls + (use - 1), 8, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(hipStreamSynchronize(c->stream));
-                cut += 1;
-            }
-            const uint64_t rest = s.total - cut;
-            if (rest) RC_TRY(s.txt.carry_from(cut, rest)); else s.txt.carry = 0;
-            s.carry_lines = s.whole - use;
+            RC_TRY(s.txt.line_end(s.t.nls, use, &cut));
+            RC_TRY(s.txt.carry_behind(cut, s.total));
+            s.carry_lines = s.t.whole - use;
         }
         HIP_TRY(hipStreamSynchronize(c->stream));                 // the line indexes go with the turn's scope
     }

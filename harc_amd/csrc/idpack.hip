@@ -339,7 +339,7 @@ extern "C" int harc_amd_idunpack_host(const uint8_t *packed, uint64_t n_bytes, c
 // ------------------------------------------------------------------------------------------------ the files
 // The text goes through the ring in byte ranges of about `piece_blocks` blocks of ids of 80 bytes (4 KiB .. 256 MiB).  The line index of what has arrived says how
 // many whole blocks it holds: they are packed, at most piece_blocks and at most IP_CALL_TEXT bytes of text a call (one block where a block alone is longer), and the
-// rest is carried to the front of the next range (CarriedText, as fastq_out.hip carries a cut line).  The event scratch and the slabs are five bytes per byte of text: 1.25 GiB a
+// rest is carried to the front of the next range (CarriedText of fileio.h, whose steps of a turn over whole lines this loop is made of).  The event scratch and the slabs are five bytes per byte of text: 1.25 GiB a
 // call with ids of any length, and 5 GiB in the one case that cannot be cut, a single block of the 2^30 bytes a block may hold
 extern "C" int harc_amd_idpack_files(const harc_amd_params *params, const char *id_path, const char *out_path)
 {
@@ -370,32 +370,23 @@ extern "C" int harc_amd_idpack_files(const harc_amd_params *params, const char *
     {
         FileDrain drain(c);
         RC_TRY(drain.start(out_path, (size_t)id_bound(isz, isz, rb), &g[1], true));      // (no more lines than bytes)
-        std::vector<std::pair<uint64_t, uint64_t>> pieces;
-        for (uint64_t a = 0; a < isz; a += piece) pieces.emplace_back(a, isz - a < piece ? isz : a + piece);
+        const Pieces pieces = byte_pieces(0, isz, piece);
         FileFeeder feed(c, id_path);
         if (!pieces.empty()) RC_TRY(feed.start(pieces, g[0]));
         for (size_t p = 0; p < pieces.size(); p++) {
             const uint64_t len = pieces[p].second - pieces[p].first, total = txt.carry + len; const bool lastp = p + 1 == pieces.size();
             RC_TRY(txt.take(feed, p, len, &t_read));                                         // the carried bytes sit at its front
-            const char *d_ids = txt.text();
             PoolScope piece_scope(c);
-            const uint64_t *nls = nullptr; uint64_t lines = 0;
-            RC_TRY(build_line_index(c, d_ids, total, &nls, &lines));
-            if (!lastp) {                                                                    // an open last line counts as one: whole lines, then whole blocks
-                char lastch = 0;
-                HIP_TRY(hipMemcpyAsync(&lastch, d_ids + total - 1, 1, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(hipStreamSynchronize(c->stream));
-                if (lastch != '\n') lines--;
-                lines = lines / rb * rb;
-            }
+            LineTurn t;
+            RC_TRY(txt.index(total, lastp, &t));
+            const char *d_ids = t.text; const uint64_t *nls = t.nls;
+            const uint64_t lines = lastp ? t.whole : t.whole / rb * rb;                      // whole lines, then whole blocks
             uint64_t cut = 0;
             for (uint64_t l0 = 0; l0 < lines;) {
                 // at most piece_blocks blocks a call and, by the line index, no more than IP_CALL_TEXT bytes of text unless one block alone is longer
                 uint64_t m = lines - l0 < piece_blocks * rb ? lines - l0 : piece_blocks * rb, end = 0;
                 for (;;) {
-                    HIP_TRY(hipMemcpyAsync(&end, nls + (l0 + m - 1), 8, hipMemcpyDeviceToHost, c->stream));
-                    HIP_TRY(hipStreamSynchronize(c->stream));
-                    end += 1;
+                    RC_TRY(txt.line_end(nls, l0 + m, &end));
                     if (end - cut <= call_text || m <= rb) break;
                     const uint64_t half = (id_blocks(m, rb) / 2) * rb;
                     m = half < rb ? rb : half;
@@ -407,9 +398,7 @@ extern "C" int harc_amd_idpack_files(const harc_amd_params *params, const char *
                 at += nblk; n += m; nb += id_blocks(m, rb); npieces++;
                 l0 += m; cut = end;
             }
-            const uint64_t rest = total - cut;
-            if (rest && cut) RC_TRY(txt.carry_from(cut, rest));
-            else txt.carry = rest;                                                           // nothing, or not one whole block yet: the piece grows by the next one
+            RC_TRY(txt.carry_behind(cut, total));                                            // (nothing, or not one whole block yet: the piece grows by the next one)
         }
         uint8_t h[ID_FILE_HEADER];
         id_file_header(h, rb, n, isz);

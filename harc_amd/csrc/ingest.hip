@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void k_third_rule(const uint8_t *txt, const ui
 
 // nls[k] = byte position of the newline that ends line k (a last line without one ends at nbytes); nls[-1] = (u64)-1 so that line k
 // starts at nls[k-1]+1 for every k.  Pool memory: the caller brackets it with a PoolScope.
-int build_line_index(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const uint64_t **nls_out, uint64_t *total_lines_out)
+int build_line_index(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const uint64_t **nls_out, uint64_t *total_lines_out, bool *open_tail)
 {
     const uint64_t ntiles = (nbytes + NL_TILE - 1) / NL_TILE;
     uint32_t *tilecnt = nullptr; uint64_t *tilebase = nullptr;
@@ -151,6 +151,16 @@ int build_line_index(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const 
         total_lines++;
     }
     *nls_out = nl + 1; *total_lines_out = total_lines;
+    if (open_tail) *open_tail = lastch != '\n';
+    return HARC_AMD_OK;
+}
+int text_line_index(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const uint64_t **nls, uint64_t *lines, bool *open_tail)
+{
+    if (nbytes) return build_line_index(c, d_txt, nbytes, nls, lines, open_tail);
+    *lines = 0; *open_tail = false;                               // no text, no line; a kernel still reads nls[-1]
+    uint64_t *z = nullptr; RC_TRY(dalloc(c, &z, 2));
+    HIP_TRY(hipMemsetAsync(z, 0xFF, 16, c->stream));
+    *nls = z + 1;
     return HARC_AMD_OK;
 }
 

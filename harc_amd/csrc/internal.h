@@ -248,9 +248,10 @@ int harc_d2h(harc_amd_ctx *c, std::vector<uint8_t> &dst, const void *d_src, size
 
 // ---- line index of a text in device memory (ingest.hip): nls[k] = byte position of the newline that ends line k (a last line without one ends at
 // nbytes and counts as a line); nls[-1] = (u64)-1, so that line k starts at nls[k-1] + 1 for every k.  nbytes > 0.  Pool memory: the caller brackets it
-int build_line_index(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const uint64_t **nls_out, uint64_t *total_lines_out);
-// ... of an id text that may be empty (fastq_out.hip), and whether its last line lacks the newline.  Pool memory: the caller brackets it
-int fq_index(harc_amd_ctx *c, const char *d_ids, uint64_t id_bytes, const uint64_t **nls, uint64_t *lines, bool *open_tail);
+// *open_tail (may be null): the last line lacks its newline
+int build_line_index(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const uint64_t **nls_out, uint64_t *total_lines_out, bool *open_tail = nullptr);
+// ... of a text that may be empty (no line; nls[-1] can still be read).  Pool memory: the caller brackets it
+int text_line_index(harc_amd_ctx *c, const char *d_txt, uint64_t nbytes, const uint64_t **nls, uint64_t *lines, bool *open_tail);
 // ---- the mate rule (idmate.hip) applied in place to lines [0, m) of an id text with its line index, on the stream; *d_bad += the lines that do not carry the '1'
 int harc_idmate_apply_lines(harc_amd_ctx *c, char *d_ids, const uint64_t *nls, uint64_t m, int32_t rule, unsigned long long *d_bad);
 

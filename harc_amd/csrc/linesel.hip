@@ -133,16 +133,6 @@ extern "C" int harc_amd_line_offset_host(const void *text, uint64_t nbytes, uint
 }
 
 // ------------------------------------------------------------------------------------------------ the file
-// a slice for the ring of a walk over pieces of `piece` bytes of a file of fsz bytes: a short file or short pieces do not pin a ring of 1 GiB
-static size_t ls_slice(uint64_t fsz, uint64_t piece)
-{
-    const uint64_t full = (uint64_t)64 << 20, most = fsz < piece ? fsz : piece;
-    if (most >= 16 * full) return 0;
-    uint64_t s = (most + 15) / 16;
-    s = (s + 4095) & ~(uint64_t)4095;
-    return (size_t)(s < 65536 ? 65536 : s);
-}
-
 extern "C" int harc_amd_line_range_files(const harc_amd_params *params, const char *path, uint64_t first_line, uint64_t n_lines, uint64_t out[2])
 {
     if (!params || !path || !out) { harc_set_error("line_range_files: bad arguments"); return HARC_AMD_EINVAL; }
@@ -158,9 +148,8 @@ extern "C" int harc_amd_line_range_files(const harc_amd_params *params, const ch
         RC_TRY(side_context(params, 100, &guard.c));
         harc_amd_ctx *c = guard.c;
         RingGeom g;
-        RC_TRY(ring_split(c, 1, 16, "line select", &g, ls_slice(fsz, piece)));
-        std::vector<std::pair<uint64_t, uint64_t>> pieces;
-        for (uint64_t a = 0; a < fsz; a += piece) pieces.emplace_back(a, fsz - a < piece ? fsz : a + piece);
+        RC_TRY(ring_split(c, 1, 16, "line select", &g, ring_slice_for(fsz < piece ? fsz : piece, 16)));      // a short file or short pieces do not pin a ring of 1 GiB
+        const Pieces pieces = byte_pieces(0, fsz, piece);
         DevBuf txt{ c };
         RC_TRY(dev_reserve(&txt, (size_t)(fsz < piece ? fsz : piece)));
         FileFeeder feed(c, path);

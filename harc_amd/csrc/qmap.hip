@@ -277,8 +277,7 @@ extern "C" int harc_amd_qmap_files(const harc_amd_params *params, const char *qu
     {
         FileDrain drain(c);
         RC_TRY(drain.start(out_path, (size_t)qsz, &g[1], true));
-        std::vector<std::pair<uint64_t, uint64_t>> pieces;
-        for (uint64_t a = 0; a < n; a += piece_lines) pieces.emplace_back(a * LL, (n - a < piece_lines ? n : a + piece_lines) * LL);
+        const Pieces pieces = line_pieces(n, LL, piece_lines);
         FileFeeder feed(c, quality_path);
         if (!pieces.empty()) RC_TRY(feed.start(pieces, g[0]));
         for (size_t p = 0; p < pieces.size(); p++) {

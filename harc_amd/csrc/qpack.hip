@@ -360,8 +360,7 @@ extern "C" int harc_amd_qpack_files_ex(const harc_amd_params *params, const char
         FileDrain drain(c);
         RC_TRY(drain.start(out_path, (size_t)(n ? qv_bound(n, L, rb) : QV_FILE_HEADER), &g[1], true));
         RC_TRY(drain.put_host(h, QV_FILE_HEADER, 0));
-        std::vector<std::pair<uint64_t, uint64_t>> pieces;
-        for (uint64_t a = 0; a < n; a += piece_lines) pieces.emplace_back(a * LL, (n - a < piece_lines ? n : a + piece_lines) * LL);
+        const Pieces pieces = line_pieces(n, LL, piece_lines);
         FileFeeder feed(c, quality_path);
         if (!pieces.empty()) RC_TRY(feed.start(pieces, g[0]));
         for (size_t p = 0; p < pieces.size(); p++) {

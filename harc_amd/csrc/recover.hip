@@ -269,10 +269,7 @@ struct DevBackend : RcBackend {
     {
         RC_TRY(side_context(params, 100, &guard.c));
         c = guard.c; A.c = c; O.c = c;
-        const uint64_t full = (uint64_t)64 << 20;                 // files of a few MB do not pin a ring of 1 GiB
-        uint64_t s = largest_file >= 16 * full ? full : (largest_file + 15) / 16;
-        s = (s + 4095) & ~(uint64_t)4095;
-        return ring_split(c, 1, 16, "recovery", &g, (size_t)(s < 65536 ? 65536 : s));
+        return ring_split(c, 1, 16, "recovery", &g, ring_slice_for(largest_file, 16));
     }
     int reserve(size_t a, size_t o) override { RC_TRY(dev_reserve(&A, a + 16)); return dev_reserve(&O, o + 16); }
     int open(const std::string &path, const std::vector<std::pair<uint64_t, uint64_t>> &pieces) override

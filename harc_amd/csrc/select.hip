@@ -243,7 +243,7 @@ static int nk_build_set(harc_amd_ctx *c, const char *d_names, uint64_t names_byt
 {
     const uint64_t *nls = nullptr; bool open = false;
     S->names = (const uint8_t *)d_names; S->hmask = nk_env_hmask();
-    RC_TRY(fq_index(c, d_names, names_bytes, &nls, &S->lines, &open));
+    RC_TRY(text_line_index(c, d_names, names_bytes, &nls, &S->lines, &open));
     const uint64_t slots = nk_table_slots(S->lines);
     S->mask = slots - 1;
     RC_TRY(dalloc(c, &S->rec, (size_t)S->lines + 1)); RC_TRY(dalloc(c, &S->slots, (size_t)slots));
@@ -309,7 +309,7 @@ extern "C" int harc_amd_select_flags_device(harc_amd_ctx *c, const void *d_names
     NkSet S;
     RC_TRY(nk_build_set(c, (const char *)d_names, names_bytes, &S));
     const uint64_t *nls = nullptr; uint64_t lines = 0; bool open = false;
-    RC_TRY(fq_index(c, (const char *)d_ids, id_bytes, &nls, &lines, &open));
+    RC_TRY(text_line_index(c, (const char *)d_ids, id_bytes, &nls, &lines, &open));
     const bool trace = getenv("HARC_AMD_TRACE") != nullptr;
     double seconds = 0;
     KernelTimer timer(trace ? &seconds : nullptr);
@@ -407,7 +407,7 @@ extern "C" int harc_amd_lines_gather_device(harc_amd_ctx *c, const void *d_text,
     const uint64_t *nls = nullptr;
     if (!stride) {
         uint64_t lines = 0; bool open = false;
-        RC_TRY(fq_index(c, (const char *)d_text, nbytes, &nls, &lines, &open));
+        RC_TRY(text_line_index(c, (const char *)d_text, nbytes, &nls, &lines, &open));
         if (lines != n_lines) { harc_set_error("lines_gather_device: the text holds %llu lines, the flags are those of %llu", (unsigned long long)lines, (unsigned long long)n_lines); return HARC_AMD_EINVAL; }
     }
     if (!n_lines) return HARC_AMD_OK;
@@ -441,46 +441,7 @@ extern "C" int harc_amd_lines_gather_host(const void *text, uint64_t nbytes, uin
 }
 
 // ------------------------------------------------------------------------------------------------ the files
-static size_t nk_slice(uint64_t big)
-{
-    if (big >= ((uint64_t)16 * 64 << 20)) return 0;
-    const uint64_t s = ((big + 7) / 8 + 4095) & ~(uint64_t)4095;
-    return (size_t)(s < 65536 ? 65536 : s);
-}
-// A file of lines of any length, walked in pieces of `piece` bytes; every turn hands the whole lines of the text at hand to `work(text, bytes, nls, lines, first_line)`.
-// What lies behind a piece's last whole line is carried; the last line of the file counts as a line with or without its newline.  *lines_total: the file's lines
-template <class F> static int nk_walk_lines(harc_amd_ctx *c, const char *path, uint64_t fsz, uint64_t piece, const RingGeom &g, uint64_t *lines_total, F work)
-{
-    *lines_total = 0;
-    if (!fsz) return HARC_AMD_OK;
-    std::vector<std::pair<uint64_t, uint64_t>> pieces;
-    for (uint64_t a = 0; a < fsz; a += piece) pieces.emplace_back(a, fsz - a < piece ? fsz : a + piece);
-    FileFeeder feed(c, path);
-    RC_TRY(feed.start(pieces, g));
-    CarriedText txt(c);
-    double t_read = 0;
-    for (size_t p = 0; p < pieces.size(); p++) {
-        const uint64_t len = pieces[p].second - pieces[p].first, total = txt.carry + len;
-        const bool last_piece = p + 1 == pieces.size();
-        if (total > 0xFFFFFFFFull) { harc_set_error("%s: a line of more than %llu bytes", path, (unsigned long long)(total - len)); return HARC_AMD_EINVAL; }
-        RC_TRY(txt.take(feed, p, len, &t_read));
-        PoolScope turn(c);
-        const uint64_t *nls = nullptr; uint64_t lines = 0; bool open = false;
-        RC_TRY(fq_index(c, txt.text(), total, &nls, &lines, &open));
-        const uint64_t whole = lines - ((open && !last_piece) ? 1 : 0);
-        uint64_t cut = total;
-        if (open && !last_piece) {
-            cut = 0;
-            if (whole) { HIP_TRY(hipMemcpyAsync(&cut, nls + (whole - 1), 8, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream)); cut += 1; }
-        }
-        if (whole) RC_TRY(work(txt.text(), cut, nls, whole, *lines_total));
-        *lines_total += whole;
-        if (total - cut) RC_TRY(txt.carry_from(cut, total - cut)); else txt.carry = 0;
-        HIP_TRY(hipStreamSynchronize(c->stream));                 // the line index goes with the turn's scope
-    }
-    return HARC_AMD_OK;
-}
-
+// (the ids are walked in whole lines by walk_lines of fileio.h, twice: for the flags, then for the gather)
 extern "C" int harc_amd_select_files(const harc_amd_params *params, const char *names_path, const char *ids_path, const char *dna_path, const char *quality_path,
                                      const char *out_ids_path, const char *out_dna_path, const char *out_quality_path, uint64_t pair_records, int32_t pair_rule,
                                      uint64_t stats[4], char *missing, uint64_t missing_cap)
@@ -514,7 +475,7 @@ extern "C" int harc_amd_select_files(const harc_amd_params *params, const char *
     harc_amd_ctx *c = guard.c;
     const uint64_t big = isz > dsz ? isz : dsz;
     RingGeom g[2];                                                // a feeder and a drain are alive together
-    RC_TRY(ring_split(c, 2, 8, "select", g, nk_slice(big)));
+    RC_TRY(ring_split(c, 2, 8, "select", g, ring_slice_for(big, 8)));
     LapTimer lap{ "[select]" };
     PoolScope scope(c);
     DevBuf names{ c }, flags{ c };
@@ -528,19 +489,21 @@ extern "C" int harc_amd_select_files(const harc_amd_params *params, const char *
     // ---- phase A: the flags of the whole job, one byte a line (a second half for the second file's records of a pair)
     RC_TRY(dev_reserve(&flags, (size_t)reads + 1));
     HIP_TRY(hipMemsetAsync(flags.p, 0, (size_t)reads + 1, c->stream));
-    uint64_t piece = env_u64("HARC_AMD_SELECT_PIECE", (uint64_t)256 << 20);
-    if (piece > ((uint64_t)1 << 30)) piece = (uint64_t)1 << 30;
-    uint64_t id_lines = 0; double probe_s = 0;
+    // a text at hand of more than 2^32 - 1 bytes is refused; the stream is waited for before a turn's line index goes
+    LineWalk w; w.piece = env_u64("HARC_AMD_SELECT_PIECE", (uint64_t)256 << 20); w.geom = g[0]; w.text_limit = 0xFFFFFFFFull; w.sync_turn = true;
+    if (w.piece > ((uint64_t)1 << 30)) w.piece = (uint64_t)1 << 30;
+    double probe_s = 0;
     const bool trace = getenv("HARC_AMD_TRACE") != nullptr;
     {
         KernelTimer timer(trace ? &probe_s : nullptr);
-        RC_TRY(nk_walk_lines(c, ids_path, isz, piece, g[0], &id_lines, [&](char *text, uint64_t, const uint64_t *nls, uint64_t whole, uint64_t line0) -> int {
-            if (line0 + whole > want_ids) return HARC_AMD_OK;    // (more id lines than records: counted on, refused below)
+        RC_TRY(walk_lines(c, ids_path, isz, &w, [&](CarriedText &, LineTurn &t) -> int {
+            if (t.line0 + t.whole > want_ids) return HARC_AMD_OK;    // (more id lines than records: counted on, refused below)
             RC_TRY(timer.begin(c->stream));
-            RC_TRY(nk_probe_launch(c, set, text, nls, whole, (uint8_t *)flags.p + line0));
+            RC_TRY(nk_probe_launch(c, set, t.text, t.nls, t.whole, (uint8_t *)flags.p + t.line0));
             return timer.end(c->stream);
         }));
     }
+    const uint64_t id_lines = w.lines;
     if (id_lines != want_ids) {
         if (pair) harc_set_error("select_files: %s holds %llu lines, a pair of %llu records under the rule %s has %llu", ids_path, (unsigned long long)id_lines, (unsigned long long)pair_records, idm_rule_name(pair_rule), (unsigned long long)want_ids);
         else harc_set_error("select_files: %s holds %llu lines, %s %llu reads: an id line per read is wanted", ids_path, (unsigned long long)id_lines, dna_path, (unsigned long long)reads);
@@ -582,11 +545,11 @@ extern "C" int harc_amd_select_files(const harc_amd_params *params, const char *
         // the ids: the size of the result is bounded by the file's; the drain cuts the file to what the pieces gave
         FileDrain drain(c);
         RC_TRY(drain.start(guards[0].path, (size_t)isz, &g[1], true));
-        uint64_t at = 0, lines_again = 0;
-        RC_TRY(nk_walk_lines(c, ids_path, isz, piece, g[0], &lines_again, [&](char *text, uint64_t bytes, const uint64_t *nls, uint64_t whole, uint64_t line0) -> int {
-            RC_TRY(dev_reserve(&out, (size_t)bytes));
+        uint64_t at = 0;
+        RC_TRY(walk_lines(c, ids_path, isz, &w, [&](CarriedText &, LineTurn &t) -> int {
+            RC_TRY(dev_reserve(&out, (size_t)t.cut));
             uint64_t got = 0;
-            RC_TRY(nk_gather(c, "select_files", text, bytes, 0, nls, (const uint8_t *)flags.p + line0, whole, out.p, bytes, &got));
+            RC_TRY(nk_gather(c, "select_files", t.text, t.cut, 0, t.nls, (const uint8_t *)flags.p + t.line0, t.whole, out.p, t.cut, &got));
             if (got) RC_TRY(drain.put(out.p, (size_t)got, at));
             at += got;
             return HARC_AMD_OK;
@@ -594,7 +557,7 @@ extern "C" int harc_amd_select_files(const harc_amd_params *params, const char *
         HIP_TRY(hipStreamSynchronize(c->stream));
         drain.set_final_size(at);
         RC_TRY(drain.finish());
-        if (lines_again != id_lines) { harc_set_error("select_files: %s changed while it was read (%llu lines, then %llu)", ids_path, (unsigned long long)id_lines, (unsigned long long)lines_again); return HARC_AMD_EIO; }
+        if (w.lines != id_lines) { harc_set_error("select_files: %s changed while it was read (%llu lines, then %llu)", ids_path, (unsigned long long)id_lines, (unsigned long long)w.lines); return HARC_AMD_EIO; }
     }
     lap.lap("ids gathered");
     uint64_t PL = env_u64("HARC_AMD_SELECT_LINES", ((uint64_t)256 << 20) / S);
@@ -607,8 +570,7 @@ extern "C" int harc_amd_select_files(const harc_amd_params *params, const char *
     for (int k = 0; k < 2; k++) {
         FileDrain drain(c);
         RC_TRY(drain.start(guards[1 + k].path, (size_t)(out_lines * S), &g[1]));
-        std::vector<std::pair<uint64_t, uint64_t>> pieces;
-        for (uint64_t a = 0; a < reads; a += PL) pieces.emplace_back(a * S, (reads - a < PL ? reads : a + PL) * S);
+        const Pieces pieces = line_pieces(reads, S, PL);
         FileFeeder feed(c, in_path[k]);
         RC_TRY(feed.start(pieces, g[0]));
         uint64_t at = 0;

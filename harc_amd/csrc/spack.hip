@@ -335,8 +335,7 @@ static int sp_pack_file(harc_amd_ctx *c, const char *in_path, const char *out_pa
         FileDrain drain(c);
         RC_TRY(drain.start(out_path, (size_t)sv_bound(isz, B), &g[1], true));
         RC_TRY(drain.put_host(h, SV_FILE_HEADER, 0));
-        std::vector<std::pair<uint64_t, uint64_t>> pieces;
-        for (uint64_t a = 0; a < isz; a += piece) pieces.emplace_back(a, isz - a < piece ? isz : a + piece);
+        const Pieces pieces = byte_pieces(0, isz, piece);
         FileFeeder feed(c, in_path);
         if (!pieces.empty()) RC_TRY(feed.start(pieces, g[0]));
         for (size_t p = 0; p < pieces.size(); p++) {

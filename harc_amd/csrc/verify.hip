@@ -68,18 +68,20 @@ __device__ __forceinline__ bool decode_read(const uint8_t *seqb, uint64_t seqlen
     for (int j = 0; j < L; j++) buf[j] = seqb[start + j];
     const uint64_t n0 = i ? nlpos[i - 1] + 1 : 0, n1 = nlpos[i];
     uint64_t np = n0 - i;                                                     // noisepos bytes consumed by earlier reads
-    int p = 0; bool anyN = false;
+    int p = 0; bool wroteN = false;
     for (uint64_t k = n0; k < n1; k++) {                                      // decoder.cpp:100-108
         if (p < L) p += noisepos[np];                                         // (a position past the read stays there: p never exceeds L + 254, buf is never indexed with it)
         np++;
         const int code = noise[k] - '0';
         if (p >= L || (unsigned)code > 3u) { atomicAdd(err, 1u); continue; }
-        const int ref = buf[p] & 3;
+        const int ref = seqb[start + p] & 3;                                  // the row of the CONSENSUS base (dec_noise[ref[noisepos]], :106), also where a position is named twice
         // dec_noise (decoder.cpp setglobalarrays): A:{C,G,T,N} C:{A,G,T,N} G:{T,A,C,N} T:{G,C,A,N}
         const unsigned tab = ref == 0 ? 0x4321u : ref == 1 ? 0x4320u : ref == 2 ? 0x4103u : 0x4012u;
-        buf[p] = (uint8_t)((tab >> (4 * code)) & 0xF); anyN |= buf[p] == 4;
+        buf[p] = (uint8_t)((tab >> (4 * code)) & 0xF); wroteN |= code == 3;
     }
     *rev = i < 8 * nrevb ? ((revb[i >> 3] >> (i & 7)) & 1) : (revtail[i - 8 * nrevb] == 'r');
+    bool anyN = false;                                                        // strchr(currentread, 'N') on the finished read (:110): a later entry may have taken an N away again
+    if (wroteN) for (int j = 0; j < L; j++) anyN |= buf[j] == 4;
     *hasN = anyN;
     return true;
 }

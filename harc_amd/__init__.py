@@ -14,7 +14,7 @@ from .api import (HarcAmd, HarcAmdError, Params, Counters, default_params, lib, 
                   text_digest_host, text_digest_file, reads_check_file,
                   compress_fastq_pair, IDMATE_RULES, idmate_rule_host, THIRD_RULES, third_rule_host, third_rule_of, third_rule_name, third_rule_parse, idmate_apply_host, idmate_rule_files, fastq_assemble_pair,
                   LINE_NONE, line_offset_host, line_range_file, qunpack_range_files, idunpack_range_files,
-                  name_key, select_flags_host, lines_gather_host, select_files,
+                  name_key, select_flags_host, lines_gather_host, select_files, motifs_check_host, motif_flags_host, match_files,
                   recovery_make_host, recovery_repair_host, recovery_make_files, recovery_check_files, recovery_repair_files, block_digests_host, gf_combine_host)
 from ._build import build
 
@@ -29,5 +29,5 @@ __all__ = ["HarcAmd", "HarcAmdError", "Params", "Counters", "default_params", "l
            "text_digest_host", "text_digest_file", "reads_check_file",
            "compress_fastq_pair", "IDMATE_RULES", "idmate_rule_host", "THIRD_RULES", "third_rule_host", "third_rule_of", "third_rule_name", "third_rule_parse", "idmate_apply_host", "idmate_rule_files", "fastq_assemble_pair",
            "LINE_NONE", "line_offset_host", "line_range_file", "qunpack_range_files", "idunpack_range_files",
-           "name_key", "select_flags_host", "lines_gather_host", "select_files",
+           "name_key", "select_flags_host", "lines_gather_host", "select_files", "motifs_check_host", "motif_flags_host", "match_files",
            "recovery_make_host", "recovery_repair_host", "recovery_make_files", "recovery_check_files", "recovery_repair_files", "block_digests_host", "gf_combine_host"]

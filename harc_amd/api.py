@@ -226,6 +226,12 @@ def lib():
         l.harc_amd_lines_gather_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, U64P]
         l.harc_amd_lines_gather_host.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, U64P]
         l.harc_amd_select_files.argtypes = [PP, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_int32, U64P, C.c_char_p, C.c_uint64]
+    if hasattr(l, "harc_amd_match_files"):               # (HARC_AMD_LIB may name a build from before the match by sequence)
+        U8P = C.POINTER(C.c_uint8)
+        l.harc_amd_motifs_check_host.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, U64P]
+        l.harc_amd_motif_flags_host.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_char_p, C.c_uint64, C.c_uint32, U8P, U8P, U64P, U64P]
+        l.harc_amd_motif_flags_device.argtypes = [ctx, C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, U8P, U64P, U64P]
+        l.harc_amd_match_files.argtypes = [PP, C.c_char_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_int32, U64P, C.c_char_p, C.c_uint64]
     if hasattr(l, "harc_amd_recovery_make_files"):       # (HARC_AMD_LIB may name a build from before the recovery record)
         CPP, VPP, I32P = C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)
         l.harc_amd_block_digests_device.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, U64P]
@@ -502,6 +508,39 @@ def lines_gather_host(text, flags, stride=0):
     n = C.c_uint64(0)
     _check(lib().harc_amd_lines_gather_host(text, len(text), stride, flags, len(flags), out, len(text), C.byref(n)))
     return out.raw[:n.value]
+
+
+def motifs_check_host(motifs, k=0):
+    """the distinct motifs of the list `motifs` (bytes) under `k` mismatches; HarcAmdError with the reason, which names the line, when the rule refuses the list
+    (include/harc_amd.h: harc_amd_motifs_check_host); no device"""
+    motifs = bytes(motifs)
+    n = C.c_uint64(0)
+    _check(lib().harc_amd_motifs_check_host(motifs, len(motifs), k, C.byref(n)))
+    return n.value
+
+
+def motif_flags_host(motifs, dna, readlen, k=0):
+    """(flags, hits, found): flags[i] = 1 when a motif of the list matches line i of `dna` (lines of readlen + 1 bytes), hits[j] = 1 when distinct motif j matches a
+    line, on the host with byte comparisons: what HarcAmd.motif_flags_device is held to (include/harc_amd.h: harc_amd_motif_flags_host); no device"""
+    motifs, dna = bytes(motifs), bytes(dna)
+    n_lines = len(dna) // (readlen + 1)
+    flags, hit = (C.c_uint8 * (n_lines + 1))(), (C.c_uint8 * 1024)()
+    n, f = C.c_uint64(0), C.c_uint64(0)
+    _check(lib().harc_amd_motif_flags_host(motifs, len(motifs), k, dna, n_lines, readlen, flags, hit, C.byref(n), C.byref(f)))
+    return bytes(flags[:n_lines]), bytes(hit[:n.value]), f.value
+
+
+def match_files(motifs, dna, out_dna, ids=None, quality=None, out_ids=None, out_quality=None, k=0, pair_records=0, pair_rule="none", device=0):
+    """the lines of `dna` whose read matches a motif of the list file `motifs` -> out_dna, with ids and quality the same records of those texts -> out_ids and
+    out_quality, matched and gathered on the GPU in one call (include/harc_amd.h: harc_amd_match_files) -> (distinct motifs, motifs found, records selected,
+    records, [up to ten motifs not found])"""
+    p = default_params(100, device=device)
+    st = (C.c_uint64 * 4)()
+    missing = C.create_string_buffer(1 << 12)
+    enc = lambda x: os.fsencode(x) if x is not None else None
+    _check(lib().harc_amd_match_files(C.byref(p), enc(motifs), k, enc(dna), enc(ids), enc(quality), enc(out_dna), enc(out_ids), enc(out_quality), pair_records,
+                                      _rule_number(pair_rule) if pair_records else 0, st, missing, len(missing)))
+    return int(st[0]), int(st[1]), int(st[2]), int(st[3]), [m for m in missing.value.split(b"\n") if m]
 
 
 def select_files(names, ids, dna, quality, out_ids, out_dna, out_quality, pair_records=0, pair_rule="none", device=0):
@@ -1057,6 +1096,16 @@ class HarcAmd:
         _check(lib().harc_amd_select_flags_device(self._ctx, C.c_void_p(d_names) if d_names else None, names_bytes, C.c_void_p(d_ids) if d_ids else None, id_bytes,
                                                   C.c_void_p(d_flags) if d_flags else None, C.byref(n), C.byref(k), C.byref(f)))
         return n.value, k.value, f.value
+
+    def motif_flags_device(self, motifs, d_dna, n_lines, readlen, d_flags, k=0):
+        """motif_flags_host on the GPU: n_lines lines of readlen + 1 bytes in device memory at any alignment, one flag byte per line written to d_flags; the list
+        `motifs` is host bytes -> (hits, found)"""
+        motifs = bytes(motifs)
+        hit = (C.c_uint8 * 1024)()
+        n, f = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().harc_amd_motif_flags_device(self._ctx, motifs, len(motifs), k, C.c_void_p(d_dna) if d_dna else None, n_lines, readlen,
+                                                 C.c_void_p(d_flags) if d_flags else None, hit, C.byref(n), C.byref(f)))
+        return bytes(hit[:n.value]), f.value
 
     def lines_gather_device(self, d_text, nbytes, stride, d_flags, n_lines, d_out, capacity):
         """lines_gather_host on the GPU: the flagged lines of the text at d_text -> d_out (device memory, any alignment) -> the bytes written"""

@@ -532,6 +532,18 @@ struct CarriedText {
     }
 };
 
+// The gather of a selection's files (select.hip: harc_gather_files; -L and -M share it).  flags: device memory, 0 or 1 a line of the reads' file, and where there is
+// an id file the first id_lines of them are the id lines' flags.  ids_path / quality_path may be null: that text is not part of the job and its output is not written.
+// out_lines: the flagged lines of the reads' file.  feed, drain: disjoint parts of the context's ring
+struct GatherFiles {
+    const char *who = "", *ids_path = nullptr, *dna_path = nullptr, *quality_path = nullptr, *out_ids_path = nullptr, *out_dna_path = nullptr, *out_quality_path = nullptr;
+    uint64_t isz = 0, id_lines = 0, reads = 0, S = 0, out_lines = 0; const uint8_t *flags = nullptr; RingGeom feed, drain; LapTimer *lap = nullptr;
+    bool ids_counted = true;                                      // the caller has walked the id file and found id_lines lines; false: the gather's walk is the first to count them
+};
+int harc_gather_files(harc_amd_ctx *c, const GatherFiles &J);
+int harc_flags_or_halves(harc_amd_ctx *c, uint8_t *f, uint64_t n);
+int harc_flags_count(harc_amd_ctx *c, const uint8_t *p, uint64_t n, uint64_t *out);
+
 // How walk_lines goes through the bytes [begin, fsz) of a file of lines of any length in pieces of `piece` bytes, and what it found.  text_limit: a text at hand
 // (what is carried and the piece) of more bytes is refused (0: any); sync_turn: the stream is waited for before a turn's line index goes
 struct LineWalk {

@@ -206,6 +206,48 @@ static int do_records_select(int argc, char **argv, harc_amd_params *P)
     return 0;
 }
 
+static int do_motifs_check(int argc, char **argv, harc_amd_params *)                // no device is touched
+{
+    uint64_t K = 0, n = 0;
+    if (argc != 4 || !number(argv[3], &K) || K > 8) return NEEDS;
+    FILE *f = fopen(argv[2], "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", argv[2]); return REFUSED; }
+    static char list[(1 << 20) + 1];
+    const size_t got = fread(list, 1, sizeof list, f);
+    fclose(f);
+    if (got > (size_t)1 << 20) { fprintf(stderr, "the list holds more than the 1048576 bytes of a list of motifs\n"); return REFUSED; }
+    if (harc_amd_motifs_check_host(list, got, (uint32_t)K, &n) != 0) {
+        const char *why = harc_amd_last_error(), *cut = strstr(why, ": ");      // (behind the call's own name)
+        fprintf(stderr, "%s\n", cut ? cut + 2 : why);
+        return REFUSED;
+    }
+    printf("%llu motifs\n", (ull)n);
+    return 0;
+}
+
+static int do_records_match(int argc, char **argv, harc_amd_params *P)
+{
+    uint64_t K = 0, records = 0, st[4] = { 0, 0, 0, 0 }; int32_t rule = 0;
+    static char missing[1 << 12];
+    const char *ids = nullptr, *quality = nullptr, *out_ids = nullptr, *out_quality = nullptr;
+    int at = 7;
+    if (!number(argv[4], &K) || K > 8) return NEEDS;
+    if (at < argc && !strcmp(argv[at], "q")) {
+        if (argc < at + 5) return NEEDS;
+        ids = argv[at + 1]; quality = argv[at + 2]; out_ids = argv[at + 3]; out_quality = argv[at + 4]; at += 5;
+    }
+    if (at < argc && !strcmp(argv[at], "pair")) {
+        if (argc != at + 3 || !ids || !number(argv[at + 1], &records) || records < 1 || (rule = harc_amd_idmate_rule_parse(argv[at + 2])) < 0) return NEEDS;
+        at += 3;
+    }
+    if (at != argc) return NEEDS;
+    const int rc = harc_amd_match_files(P, argv[2], (uint32_t)K, argv[5], ids, quality, argv[6], out_ids, out_quality, records, rule, st, missing, sizeof missing);
+    if (rc != 0) return rc;
+    printf("[match] %llu motifs, %llu found, %llu of %llu records\n", (ull)st[0], (ull)st[1], (ull)st[2], (ull)st[3]);
+    for (const char *p = missing; *p;) { const char *e = strchr(p, '\n'); if (!e) break; printf("[match] not found: %.*s\n", (int)(e - p), p); p = e + 1; }
+    return 0;
+}
+
 static int do_unpack_range(int, char **argv, harc_amd_params *P)                    // quality_unpack_range, id_unpack_range
 {
     uint64_t first = 0, count = 0;
@@ -327,6 +369,12 @@ static const command commands[] = {
     // the records whose id line carries a name of the list <names> -> the three <out_*> texts, selected and gathered on the GPU in one process (./harc -d -q -L); "[select] <names>
     // names, <found> found, <selected> of <records> records" on stdout, then up to ten "[select] not found: <name>" lines; 0 also when nothing was selected
     { "records_select", 10, RL_100, 3, "<names> <device> <ids> <dna> <quality> <out_ids> <out_dna> <out_quality> [pair <records> <none|same|slash|space>]", do_records_select },
+    // 0 and "<n> motifs" when the rule of harc_amd/csrc/motif.h takes the list <file> with <K> mismatches (0 .. 8), else 2 and the reason, which names the line; no device
+    { "motifs_check", 4, RL_100, 0, "<file> <K 0..8>", do_motifs_check },
+    // the lines of <dna> whose read matches a motif of the list <motifs>, on either strand, with up to <K> mismatches -> <out_dna>, matched and gathered on the GPU in one
+    // process (./harc -d -M); behind q the same records of the two side texts; "[match] <motifs> motifs, <found> found, <selected> of <records> records" on stdout, then up
+    // to ten "[match] not found: <motif>" lines; 0 also when nothing was selected
+    { "records_match", 7, RL_100, 3, "<motifs> <device> <K 0..8> <dna> <out_dna> [q <ids> <quality> <out_ids> <out_quality>] [pair <records> <none|same|slash|space>]", do_records_match },
     // ---- the streams of the archive: every <in> -> the packed stream file <out>, one after the other on one context (./harc -c -S), and back (./harc -d on .hs members)
     { "streams_pack", 5, RL_100, 2, "<device> <in> <out> [<in> <out> ...]", do_streams },
     { "streams_unpack", 5, RL_100, 2, "<device> <in> <out> [<in> <out> ...]", do_streams },

@@ -441,6 +441,87 @@ extern "C" int harc_amd_lines_gather_host(const void *text, uint64_t nbytes, uin
 }
 
 // ------------------------------------------------------------------------------------------------ the files
+// Phase B of harc_amd_select_files and of harc_amd_match_files (match.hip): every file of the job goes through the ring in pieces of whole lines, each piece is
+// gathered by the resident flags and drained.  The id file (lines of any length; HARC_AMD_SELECT_PIECE bytes a piece) is walked by walk_lines of fileio.h, the
+// files of lines of one length go HARC_AMD_SELECT_LINES lines a piece.  A job without an id file or without a quality file writes the others alone; a selection
+// of nothing writes empty files.  An output file is removed unless the call reaches its end
+int harc_gather_files(harc_amd_ctx *c, const GatherFiles &J)
+{
+    const bool have_ids = J.ids_path != nullptr, have_q = J.quality_path != nullptr;
+    const uint64_t S = J.S, reads = J.reads, out_lines = J.out_lines;
+    OutFileGuard guards[3] = { { have_ids ? J.out_ids_path : "" }, { J.out_dna_path }, { have_q ? J.out_quality_path : "" } };
+    const bool have[3] = { have_ids, true, have_q };
+    if (!have_ids) guards[0].ok = true;
+    if (!have_q) guards[2].ok = true;
+    if (!out_lines) {
+        for (int k = 0; k < 3; k++) if (have[k]) RC_TRY(spit_file(guards[k].path, nullptr, 0));
+        for (int k = 0; k < 3; k++) guards[k].ok = true;
+        return HARC_AMD_OK;
+    }
+    DevBuf out{ c };
+    if (have_ids) {
+        // the ids: the size of the result is bounded by the file's; the drain cuts the file to what the pieces gave
+        LineWalk w; w.piece = env_u64("HARC_AMD_SELECT_PIECE", (uint64_t)256 << 20); w.geom = J.feed; w.text_limit = 0xFFFFFFFFull; w.sync_turn = true;
+        if (w.piece > ((uint64_t)1 << 30)) w.piece = (uint64_t)1 << 30;
+        FileDrain drain(c);
+        RC_TRY(drain.start(guards[0].path, (size_t)J.isz, &J.drain, true));
+        uint64_t at = 0;
+        RC_TRY(walk_lines(c, J.ids_path, J.isz, &w, [&](CarriedText &, LineTurn &t) -> int {
+            if (t.line0 + t.whole > J.id_lines) return HARC_AMD_OK;  // (the file grew: refused below)
+            RC_TRY(dev_reserve(&out, (size_t)t.cut));
+            uint64_t got = 0;
+            RC_TRY(nk_gather(c, J.who, t.text, t.cut, 0, t.nls, J.flags + t.line0, t.whole, out.p, t.cut, &got));
+            if (got) RC_TRY(drain.put(out.p, (size_t)got, at));
+            at += got;
+            return HARC_AMD_OK;
+        }));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        drain.set_final_size(at);
+        RC_TRY(drain.finish());
+        if (w.lines != J.id_lines && !J.ids_counted) { harc_set_error("%s: %s holds %llu lines, %llu are wanted: an id line per record", J.who, J.ids_path, (unsigned long long)w.lines, (unsigned long long)J.id_lines); return HARC_AMD_EINVAL; }
+        if (w.lines != J.id_lines) { harc_set_error("%s: %s changed while it was read (%llu lines, then %llu)", J.who, J.ids_path, (unsigned long long)J.id_lines, (unsigned long long)w.lines); return HARC_AMD_EIO; }
+        if (J.lap) J.lap->lap("ids gathered");
+    }
+    uint64_t PL = env_u64("HARC_AMD_SELECT_LINES", ((uint64_t)256 << 20) / S);
+    if (PL * S > 0x7FFFFFFFull) PL = 0x7FFFFFFFull / S;
+    const char *in_path[2] = { J.dna_path, J.quality_path };
+    DevBuf txt{ c };
+    RC_TRY(dev_reserve(&txt, (size_t)((reads < PL ? reads : PL) * S)));
+    RC_TRY(dev_reserve(&out, (size_t)((reads < PL ? reads : PL) * S)));
+    for (int k = 0; k < (have_q ? 2 : 1); k++) {
+        FileDrain drain(c);
+        RC_TRY(drain.start(guards[1 + k].path, (size_t)(out_lines * S), &J.drain));
+        const Pieces pieces = line_pieces(reads, S, PL);
+        FileFeeder feed(c, in_path[k]);
+        RC_TRY(feed.start(pieces, J.feed));
+        uint64_t at = 0;
+        for (size_t p = 0; p < pieces.size(); p++) {
+            const uint64_t bytes = pieces[p].second - pieces[p].first, line0 = pieces[p].first / S;
+            RC_TRY(feed.upload_piece(p, txt.p, nullptr));
+            uint64_t got = 0;
+            RC_TRY(nk_gather(c, J.who, txt.p, bytes, S, nullptr, J.flags + line0, bytes / S, out.p, bytes, &got));
+            if (at + got > out_lines * S) { harc_set_error("%s: %s gives more than the %llu selected lines", J.who, in_path[k], (unsigned long long)out_lines); return HARC_AMD_EINTERNAL; }
+            if (got) RC_TRY(drain.put(out.p, (size_t)got, at));
+            at += got;
+            HIP_TRY(hipStreamSynchronize(c->stream));             // out and txt are written again by the next piece's upload and gather
+        }
+        RC_TRY(drain.finish());
+        if (at != out_lines * S) { harc_set_error("%s: %s gave %llu bytes of selected lines, %llu were expected", J.who, in_path[k], (unsigned long long)at, (unsigned long long)(out_lines * S)); return HARC_AMD_EINTERNAL; }
+        if (J.lap) J.lap->lap(k ? "quality gathered" : "reads gathered");
+    }
+    for (int k = 0; k < 3; k++) guards[k].ok = true;
+    return HARC_AMD_OK;
+}
+// f[i] |= f[n + i], both ways, on the stream; the bytes of p[0 .. n) that are not zero (the stream is waited for): for match.hip
+int harc_flags_or_halves(harc_amd_ctx *c, uint8_t *f, uint64_t n)
+{
+    if (!n) return HARC_AMD_OK;
+    hipLaunchKernelGGL(k_nk_or_halves, harc_grid256(n), dim3(256), 0, c->stream, f, n);
+    HIP_TRY(hipGetLastError());
+    return HARC_AMD_OK;
+}
+int harc_flags_count(harc_amd_ctx *c, const uint8_t *p, uint64_t n, uint64_t *out) { return nk_count(c, p, n, out); }
+
 // (the ids are walked in whole lines by walk_lines of fileio.h, twice: for the flags, then for the gather)
 extern "C" int harc_amd_select_files(const harc_amd_params *params, const char *names_path, const char *ids_path, const char *dna_path, const char *quality_path,
                                      const char *out_ids_path, const char *out_dna_path, const char *out_quality_path, uint64_t pair_records, int32_t pair_rule,
@@ -534,60 +615,10 @@ extern "C" int harc_amd_select_files(const harc_amd_params *params, const char *
     lap.lap("phase A");
 
     // ---- phase B: every file in pieces of whole lines, each piece gathered and drained
-    OutFileGuard guards[3] = { { out_ids_path }, { out_dna_path }, { out_quality_path } };
-    if (!selected) {
-        for (int k = 0; k < 3; k++) RC_TRY(spit_file(guards[k].path, nullptr, 0));
-        for (int k = 0; k < 3; k++) guards[k].ok = true;
-        return HARC_AMD_OK;
-    }
-    DevBuf out{ c };
-    {
-        // the ids: the size of the result is bounded by the file's; the drain cuts the file to what the pieces gave
-        FileDrain drain(c);
-        RC_TRY(drain.start(guards[0].path, (size_t)isz, &g[1], true));
-        uint64_t at = 0;
-        RC_TRY(walk_lines(c, ids_path, isz, &w, [&](CarriedText &, LineTurn &t) -> int {
-            RC_TRY(dev_reserve(&out, (size_t)t.cut));
-            uint64_t got = 0;
-            RC_TRY(nk_gather(c, "select_files", t.text, t.cut, 0, t.nls, (const uint8_t *)flags.p + t.line0, t.whole, out.p, t.cut, &got));
-            if (got) RC_TRY(drain.put(out.p, (size_t)got, at));
-            at += got;
-            return HARC_AMD_OK;
-        }));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        drain.set_final_size(at);
-        RC_TRY(drain.finish());
-        if (w.lines != id_lines) { harc_set_error("select_files: %s changed while it was read (%llu lines, then %llu)", ids_path, (unsigned long long)id_lines, (unsigned long long)w.lines); return HARC_AMD_EIO; }
-    }
-    lap.lap("ids gathered");
-    uint64_t PL = env_u64("HARC_AMD_SELECT_LINES", ((uint64_t)256 << 20) / S);
-    if (PL * S > 0x7FFFFFFFull) PL = 0x7FFFFFFFull / S;
-    const uint64_t out_lines = pair ? 2 * selected : selected;
-    const char *in_path[2] = { dna_path, quality_path };
-    DevBuf txt{ c };
-    RC_TRY(dev_reserve(&txt, (size_t)((reads < PL ? reads : PL) * S)));
-    RC_TRY(dev_reserve(&out, (size_t)((reads < PL ? reads : PL) * S)));
-    for (int k = 0; k < 2; k++) {
-        FileDrain drain(c);
-        RC_TRY(drain.start(guards[1 + k].path, (size_t)(out_lines * S), &g[1]));
-        const Pieces pieces = line_pieces(reads, S, PL);
-        FileFeeder feed(c, in_path[k]);
-        RC_TRY(feed.start(pieces, g[0]));
-        uint64_t at = 0;
-        for (size_t p = 0; p < pieces.size(); p++) {
-            const uint64_t bytes = pieces[p].second - pieces[p].first, line0 = pieces[p].first / S;
-            RC_TRY(feed.upload_piece(p, txt.p, nullptr));
-            uint64_t got = 0;
-            RC_TRY(nk_gather(c, "select_files", txt.p, bytes, S, nullptr, (const uint8_t *)flags.p + line0, bytes / S, out.p, bytes, &got));
-            if (at + got > out_lines * S) { harc_set_error("select_files: %s gives more than the %llu selected lines", in_path[k], (unsigned long long)out_lines); return HARC_AMD_EINTERNAL; }
-            if (got) RC_TRY(drain.put(out.p, (size_t)got, at));
-            at += got;
-            HIP_TRY(hipStreamSynchronize(c->stream));             // out and txt are written again by the next piece's upload and gather
-        }
-        RC_TRY(drain.finish());
-        if (at != out_lines * S) { harc_set_error("select_files: %s gave %llu bytes of selected lines, %llu were expected", in_path[k], (unsigned long long)at, (unsigned long long)(out_lines * S)); return HARC_AMD_EINTERNAL; }
-        lap.lap(k ? "quality gathered" : "reads gathered");
-    }
-    for (int k = 0; k < 3; k++) guards[k].ok = true;
-    return HARC_AMD_OK;
+    GatherFiles J;
+    J.who = "select_files"; J.ids_path = ids_path; J.dna_path = dna_path; J.quality_path = quality_path;
+    J.out_ids_path = out_ids_path; J.out_dna_path = out_dna_path; J.out_quality_path = out_quality_path;
+    J.isz = isz; J.id_lines = id_lines; J.reads = reads; J.S = S; J.out_lines = pair ? 2 * selected : selected; J.flags = (const uint8_t *)flags.p;
+    J.feed = g[0]; J.drain = g[1]; J.lap = &lap;
+    return harc_gather_files(c, J);
 }

@@ -673,6 +673,38 @@ int harc_amd_select_files(const harc_amd_params *params, const char *names_path,
                           const char *out_ids_path, const char *out_dna_path, const char *out_quality_path, uint64_t pair_records, int32_t pair_rule,
                           uint64_t stats[4], char *missing, uint64_t missing_cap);
 
+/* ---- Match by sequence (./harc -d -M MOTIFS [-e K]; README.md, "-M and what it promises").  The rule (harc_amd/csrc/motif.h, once for host and device):
+   the list is split at '\n' (a last line without its newline counts); a line that is empty or begins with '>' is skipped; every other line is a motif of 1 to 255
+   bytes from ACGTNacgtn, folded to upper case, whose bases that are not N number more than K; equal motifs count once; at most 1024 distinct motifs and 2^20
+   bytes.  Motif p of m bases matches read r of L bases when, for q = p or its reverse complement and some offset 0 <= o <= L - m, at most K of the positions j
+   with q[j] != 'N' have r[o + j] != q[j]; a read byte that is not one of A C G T equals no motif base.  0 <= K <= 8.
+   *n_motifs = the distinct motifs of the list.  HARC_AMD_EINVAL with the reason, naming the line, for a list the rule refuses.  Touches no device. */
+int harc_amd_motifs_check_host(const void *list, uint64_t list_bytes, uint32_t K, uint64_t *n_motifs);
+/* flags[i] = 1 when some motif of the list matches line i of the n_lines lines of readlen + 1 bytes at dna (a read and its newline), else 0; hit (may be NULL, room
+   for 1024 bytes) receives per distinct motif, in list order, 1 when it matches at least one line; *n_found = their number.  Plain C++ from the rule, with byte
+   comparisons: what the kernel is held to (tests).  Touches no device. */
+int harc_amd_motif_flags_host(const void *list, uint64_t list_bytes, uint32_t K, const void *dna, uint64_t n_lines, uint32_t readlen, uint8_t *flags, uint8_t *hit,
+                              uint64_t *n_motifs, uint64_t *n_found);
+/* The same on the GPU over resident reads: d_dna and d_flags are device memory at any alignment, list and hit host memory.  The list is parsed on the host and
+   goes to the device as a table of entries, every motif and its reverse complement as bit planes; k_motif_match turns every line into the planes lo, hi and bad
+   with aligned 16-byte loads that do not leave the 16-byte hull of the text, eight lanes a read, and counts mismatches with XOR and popcount.  No atomics; flags
+   and hits are a function of the two texts and K alone.  HARC_AMD_TRACE=1: one "[match] device call" line on stderr with the kernel's time. */
+int harc_amd_motif_flags_device(harc_amd_ctx *ctx, const void *list, uint64_t list_bytes, uint32_t K, const void *d_dna, uint64_t n_lines, uint32_t readlen,
+                                uint8_t *d_flags, uint8_t *hit, uint64_t *n_motifs, uint64_t *n_found);
+/* The lines of dna_path (lines of one length, the first line's) whose read matches a motif of the list at motifs_path -> out_dna_path, in their order, in one call
+   on one context.  ids_path and quality_path, both or neither (NULL): the lines of the same records of those texts -> out_ids_path, out_quality_path.
+   Phase A: the table is loaded, dna_path walks through the pinned ring in pieces of HARC_AMD_MATCH_LINES whole lines (default 256 MiB worth; tests: a few), the
+   flags of the whole job stay resident at one byte a line.  Phase B is the gather of harc_amd_select_files (HARC_AMD_SELECT_PIECE, HARC_AMD_SELECT_LINES).
+   pair_records = n > 0 (only with the id and quality files): dna_path and quality_path hold 2 n lines, pair i is selected when read i or read n + i matches, and
+   the layouts of the id file under pair_rule are those of harc_amd_select_files.
+   stats = { distinct motifs, motifs found, records selected, records } (for a pair: of each file; without the side files: lines).  missing (may be NULL) receives up
+   to ten motifs that no read matches, in list order, a newline behind each, zero-terminated, cut to missing_cap bytes.  Nothing selected is a success with
+   stats[2] = 0 and empty files.  HARC_AMD_EINVAL / HARC_AMD_EIO with the reason, and no output file left, for a list the rule refuses, files that do not fit each
+   other, or a file that cannot be read.  Only `device` is taken from params. */
+int harc_amd_match_files(const harc_amd_params *params, const char *motifs_path, uint32_t K, const char *dna_path, const char *ids_path, const char *quality_path,
+                         const char *out_dna_path, const char *out_ids_path, const char *out_quality_path, uint64_t pair_records, int32_t pair_rule,
+                         uint64_t stats[4], char *missing, uint64_t missing_cap);
+
 /* ---- The recovery record (./harc -c -P PCT writes X.hr, ./harc -R repairs from it; README: "-P and what it promises", "The recovery record (X.hr)").  Files are cut
    into blocks of B bytes, blocks into spans, spans into interleaved groups of at most 128 members; a group of k members gets m = min(128, max(1, ceil(k PCT / 100)))
    recovery blocks, recovery block i = XOR_j inverse(i ^ (128 + j)) * member_j over GF(2^8) with the polynomial 0x11D (a Cauchy matrix: any e <= m lost members of a

@@ -13,7 +13,7 @@
 //
 // Unpacking.  The block offsets follow from the payload_bytes prefixes (QvRule over qv_prefix, for the walks of packfile.h on the host and in one lane of the device).
 //   k_qp_decode   a workgroup per block validates head, table and strand lengths into LDS (qv_check_head, qv_load_row), then a lane per strand decodes forward
-//                 (qv_strand_decode) and writes its lines, a newline behind each.  Any violation raises the error word: block number << 8 | QV_E_*.
+//                 (qv_strand_decode) and writes its lines, a newline behind each.  A violation lowers the error word to block number << 8 | the smallest QV_E_* of the block.
 // The plumbing of the file calls (probes, guards, ring split, device buffers, kernel timer) is fileio.h's.  The drivers are packfile.h's, shared with idpack.hip and
 // spack.hip: pack_run and pack_device on the way in, which harc_qpack_run and harc_amd_qpack_device hand their scratch, launches, error words and messages; the host
 // call, the run of k_qp_decode, the device call and the file call on the way back, which get QV_FORMAT.
@@ -27,7 +27,7 @@
 
 struct QpShared {
     uint32_t fc[QV_TABLE];
-    uint32_t bm[3], bad, A, err, mode;
+    uint32_t bm[3], bad, A, err, verr, mode;
     uint32_t scan[QP_T / 64 + 1];
     unsigned long long sum;
     uint8_t sym_of[96], byte_of[96];
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(QP_T) void k_qp_decode(const uint8_t *blocks, const
     const uint8_t *pl = blocks + off[b] + 4;
     const uint32_t pbytes = (uint32_t)(off[b + 1] - off[b] - 4);
     uint8_t *tx = text + line0 * (L + 1u);
-    if (t == 0) { S.sum = 0; S.A = 0; S.mode = 0; S.err = (uint32_t)qv_check_head(pl, pbytes, m, L, &S.mode, &S.A, S.bm); }
+    if (t == 0) { S.sum = 0; S.A = 0; S.mode = 0; S.verr = QV_E_NONE; S.err = (uint32_t)qv_check_head(pl, pbytes, m, L, &S.mode, &S.A, S.bm); }
     __syncthreads();
     if (S.err) { if (t == 0) atomicMin(errw, ((unsigned long long)b << 8) | S.err); return; }
     if (S.mode == 0) {
@@ -146,23 +146,24 @@ __global__ __launch_bounds__(QP_T) void k_qp_decode(const uint8_t *blocks, const
     }
     const uint32_t A = S.A, h = qv_hdr1(A), rest = pbytes - h;
     if (t < QV_MAXA) qv_map_entry(S.bm, t, S.sym_of, S.byte_of);
-    uint32_t e = 0;
-    if (t <= A) e = (uint32_t)qv_load_row(pl + 14, t, A, S.fc + t * A);
+    // the smallest code of what is wrong, as qv_block_decode answers (a length above the rest of the payload is one that the sum will not meet)
+    uint32_t e = QV_E_NONE;
+    if (t <= A) e = qv_code(qv_load_row(pl + 14, t, A, S.fc + t * A));
     uint32_t len = qv_le32(pl + h - 4u * QV_STRANDS + 4u * t);
-    if (!e && (qv_strand_lines(m, t) ? len < 4 : len != 0)) e = QV_E_SHORT;
-    if (!e && len > rest) e = QV_E_LENGTHS;
-    if (e) { atomicMax(&S.err, e); len = 0; }
+    if (qv_strand_lines(m, t) ? len < 4 : len != 0) e = qv_min(e, QV_E_SHORT);
+    if (len > rest) { e = qv_min(e, QV_E_LENGTHS); len = 0; }
+    if (e != QV_E_NONE) atomicMin(&S.verr, e);
     atomicAdd(&S.sum, (unsigned long long)len);
     __syncthreads();
-    if (t == 0 && !S.err && S.sum != rest) S.err = QV_E_LENGTHS;
+    if (t == 0 && S.sum != rest) S.verr = qv_min(S.verr, QV_E_LENGTHS);
     __syncthreads();
-    if (S.err) { if (t == 0) atomicMin(errw, ((unsigned long long)b << 8) | S.err); return; }
+    if (S.verr != QV_E_NONE) { if (t == 0) atomicMin(errw, ((unsigned long long)b << 8) | S.verr); return; }
     uint32_t total;
     const uint32_t at = block_excl_scan_u32<QP_T>(len, S.scan, &total);
-    e = (uint32_t)qv_strand_decode(pl + h + at, len, S.fc, A, S.byte_of, tx, L, m, t);
-    if (e) atomicMax(&S.err, e);
+    e = qv_code(qv_strand_decode(pl + h + at, len, S.fc, A, S.byte_of, tx, L, m, t));
+    if (e != QV_E_NONE) atomicMin(&S.verr, e);
     __syncthreads();
-    if (t == 0 && S.err) atomicMin(errw, ((unsigned long long)b << 8) | S.err);
+    if (t == 0 && S.verr != QV_E_NONE) atomicMin(errw, ((unsigned long long)b << 8) | S.verr);
 }
 
 static const char *qv_error_text(uint32_t e)

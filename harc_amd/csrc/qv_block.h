@@ -48,6 +48,7 @@ enum {
 #define QV_FILE_HEADER 32u
 #define QV_MAX_BLOCK_SYMBOLS (1u << 30)                // reads per block x read length: the payload size is a u32
 #define QV_SLAB_OVERFLOW 0xFFFFFFFFu
+#define QV_E_NONE 0xFFFFFFFFu                          // qv_code(QV_OK): what a minimum over codes starts from
 
 QV_HD uint32_t qv_default_rb(uint32_t L) { const uint32_t r = (1u << 22) / L; return r < 256u ? 256u : r; }
 QV_HD uint64_t qv_blocks(uint64_t n, uint32_t rb) { return rb ? (n + rb - 1) / rb : 0; }
@@ -56,6 +57,8 @@ QV_HD uint32_t qv_hdr1(uint32_t A) { return 14u + 2u * (A + 1u) * A + 4u * QV_ST
 QV_HD uint32_t qv_strand_lines(uint32_t m, uint32_t s) { return s < m ? (m - s + QV_STRANDS - 1u) / QV_STRANDS : 0u; }
 // scratch for one strand of nsym symbols, a multiple of 16
 QV_HD uint32_t qv_slab_bytes(uint32_t nsym) { return ((3u * (nsym >> 1)) + (nsym >> 10) + 2u + 16u + 15u) & ~15u; }
+QV_HD uint32_t qv_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
+QV_HD uint32_t qv_code(int e) { return e ? (uint32_t)e : QV_E_NONE; }
 QV_HD uint32_t qv_le32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 QV_HD void qv_put32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
 QV_HD void qv_put64(uint8_t *p, uint64_t v) { qv_put32(p, (uint32_t)v); qv_put32(p + 4, (uint32_t)(v >> 32)); }
@@ -282,7 +285,9 @@ QV_HD uint32_t qv_block_encode(const uint8_t *text, uint32_t m, uint32_t L, QvWo
     return size;
 }
 
-// the payload of a block (pbytes bytes, behind its u32) -> the m * (L + 1) bytes of its lines at text.  Reads only the payload, writes only the lines
+// the payload of a block (pbytes bytes, behind its u32) -> the m * (L + 1) bytes of its lines at text.  Reads only the payload, writes only the lines.  Of
+// everything that is wrong in the rows and the strand lengths, and then in the strands, the smallest code is the answer: the lanes of a workgroup agree on it
+// in any order
 QV_HD int qv_block_decode(const uint8_t *pl, uint32_t pbytes, uint32_t m, uint32_t L, QvWork &W, uint8_t *text)
 {
     uint32_t mode = 0, A = 0;
@@ -294,21 +299,22 @@ QV_HD int qv_block_decode(const uint8_t *pl, uint32_t pbytes, uint32_t m, uint32
         return QV_OK;
     }
     for (uint32_t k = 0; k < QV_MAXA; k++) qv_map_entry(W.bm, k, W.sym_of, W.byte_of);
-    for (uint32_t r = 0; r <= A; r++) { const int er = qv_load_row(pl + 14, r, A, W.fc + r * A); if (er) return er; }
+    uint32_t bad = QV_E_NONE;
+    for (uint32_t r = 0; r <= A; r++) bad = qv_min(bad, qv_code(qv_load_row(pl + 14, r, A, W.fc + r * A)));
     const uint32_t h = qv_hdr1(A), rest = pbytes - h;
     const uint8_t *lens = pl + h - 4u * QV_STRANDS;
     uint64_t sum = 0;
     for (uint32_t s = 0; s < QV_STRANDS; s++) {
         const uint32_t n = qv_le32(lens + 4u * s);
-        if (qv_strand_lines(m, s) ? n < 4 : n != 0) return QV_E_SHORT;
+        if (qv_strand_lines(m, s) ? n < 4 : n != 0) bad = qv_min(bad, QV_E_SHORT);
         W.len[s] = n; sum += n;
     }
-    if (sum != rest) return QV_E_LENGTHS;
+    if (sum != rest) bad = qv_min(bad, QV_E_LENGTHS);
+    if (bad != QV_E_NONE) return (int)bad;
     const uint8_t *src = pl + h;
     for (uint32_t s = 0; s < QV_STRANDS; s++) {
-        const int es = qv_strand_decode(src, W.len[s], W.fc, A, W.byte_of, text, L, m, s);
-        if (es) return es;
+        bad = qv_min(bad, qv_code(qv_strand_decode(src, W.len[s], W.fc, A, W.byte_of, text, L, m, s)));
         src += W.len[s];
     }
-    return QV_OK;
+    return bad == QV_E_NONE ? QV_OK : (int)bad;
 }

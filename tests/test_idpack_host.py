@@ -4,7 +4,6 @@ stored / coded mode of every block; damaged files refused; the size against bz2 
 import bz2
 import lzma
 import os
-import re
 import shutil
 import struct
 import subprocess
@@ -12,6 +11,7 @@ import subprocess
 import pytest
 
 from tests import id_cases as ic
+from tests.readme_decoders import id_decode as readme_decode
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
@@ -25,7 +25,7 @@ DRIVER = r"""
 // enc: cases [u32 text bytes][u32 rb][text] -> [u32 status][u32 bytes][the blocks, no file header].  Every buffer is a heap block of exactly its size: a read or
 // write past it is an AddressSanitizer report.  status: 1 a second run into a block of the exact size differs, 2 id_block_decode does not return the text
 // dec: files [u32 bytes][the file] -> [u32 code][u32 block][u32 text bytes][text]; code 0, an ID_E_* of the first bad block, 100 a prefix that leaves the file or
-// the text, 101 the header
+// the text, 101 the header, 200 the strands decoded one by one answer otherwise
 static uint32_t one_block(const uint8_t *lines, uint32_t tb, uint32_t m, FILE *o, uint32_t *total)
 {
     uint32_t st = 0;
@@ -48,6 +48,27 @@ static uint32_t one_block(const uint8_t *lines, uint32_t tb, uint32_t m, FILE *o
     fwrite(exact, 1, size, o); *total += size;
     free(back); free(payload); free(exact); free(big); free(slabs); free(events); free(W); free(text);
     return st;
+}
+// a coded block that id_block_decode has taken as far as its strands with the answer `code` (W holds its table): strand after strand on its own, from a heap block of
+// exactly its coded bytes into one of exactly its text bytes -- a strand that wrote into its neighbour's text is an AddressSanitizer report here
+static uint32_t strands_alone(const uint8_t *pl, uint32_t pbytes, uint32_t m, IdWork &W, const uint8_t *text, uint32_t code)
+{
+    uint32_t mode = 0, tbytes = 0, hdr1 = 0, bm[4], bad = ID_E_NONE, differs = 0, tat = 0;
+    if (id_check_head(pl, pbytes, &mode, &tbytes, bm, &hdr1)) return 200;
+    const uint8_t *src = pl + hdr1;
+    for (uint32_t s = 0; s < ID_STRANDS; s++) {
+        uint32_t st, sl;
+        if (id_check_strand(pl, m, s, &st, &sl)) return 200;
+        uint8_t *in = (uint8_t *)malloc(sl ? sl : 1), *out = (uint8_t *)malloc(st ? st : 1);
+        memcpy(in, src, sl);
+        const uint32_t e = id_code(id_strand_decode(in, sl, W.fc, out, st, id_strand_lines(m, s)));
+        bad = id_min(bad, e);
+        if (e == ID_E_NONE && memcmp(out, text + tat, st)) differs = 1;
+        free(out); free(in);
+        src += sl; tat += st;
+    }
+    if (differs || (bad == ID_E_NONE ? code != 0 : code != bad)) return 200;
+    return code;
 }
 static void one_file(const uint8_t *f, uint32_t nbytes, FILE *o)
 {
@@ -73,6 +94,7 @@ static void one_file(const uint8_t *f, uint32_t nbytes, FILE *o)
                 memcpy(payload, f + at + 4, pb);
                 memset(lines, 0, t);
                 code = (uint32_t)id_block_decode(payload, pb, m, *W, lines);
+                if (payload[0] && (code == 0 || code >= ID_E_TRUNC)) code = strands_alone(payload, pb, m, *W, lines, code);
                 memcpy(text + tat, lines, t);
                 free(lines); free(payload);
                 if (code) break;
@@ -157,117 +179,6 @@ def cases():
 def _header(text, rb):
     n = text.count(b"\n")
     return MAGIC + (struct.pack("<IIQQ", rb or 1 << 18, 0, n, len(text)) if n else bytes(24))
-
-
-# ------------------------------------------------------------------------------------------------ the decoder of the README, in plain Python
-def _width(r):
-    return 5 if r < 16 else 256 if r < 28 else 96
-
-
-class _Rans:
-    def __init__(self, data):
-        assert len(data) >= 4
-        self.d, self.x, self.k = data, int.from_bytes(data[:4], "big"), 4
-        assert self.x >= 1 << 23
-
-    def get(self, row):
-        assert row is not None                                     # a symbol from an absent row
-        freq, cum, lut = row
-        slot = self.x & 4095
-        y = lut[slot]
-        assert freq[y] >= 1
-        self.x = freq[y] * (self.x >> 12) + slot - cum[y]
-        while self.x < 1 << 23:
-            self.x, self.k = self.x << 8 | self.d[self.k], self.k + 1
-        return y
-
-
-def readme_decode(f):
-    """-> (text, modes).  Asserts the constraints the format text states"""
-    assert f[:8] == MAGIC
-    RB, zero, n, tbytes = struct.unpack_from("<IIQQ", f, 8)
-    assert zero == 0
-    if n == 0:
-        assert RB == 0 and tbytes == 0 and len(f) == 32
-    at, out, modes = 32, [], []
-    for b0 in range(0, n, RB) if n else []:
-        m = min(n, b0 + RB) - b0
-        size, = struct.unpack_from("<I", f, at)
-        p = f[at + 4:at + 4 + size]
-        assert len(p) == size
-        at += 4 + size
-        mode, T = p[0], struct.unpack_from("<I", p, 1)[0]
-        modes.append(mode)
-        if mode == 0:
-            assert size == 5 + T and p.count(b"\n", 5) == m and p.endswith(b"\n")
-            out.append(p[5:])
-            continue
-        assert mode == 1
-        stext = struct.unpack_from("<256I", p, 5)
-        slen = struct.unpack_from("<256I", p, 5 + 1024)
-        bits = int.from_bytes(p[5 + 2048:5 + 2048 + 16], "little")
-        assert bits >> 124 == 0
-        pos, rows = 5 + 2048 + 16, []
-        for r in range(124):
-            if not bits >> r & 1:
-                rows.append(None)
-                continue
-            freq = struct.unpack_from("<%dH" % _width(r), p, pos)
-            pos += 2 * _width(r)
-            assert sum(freq) == 4096
-            cum, lut = [], []
-            for y, v in enumerate(freq):
-                cum.append(len(lut))
-                lut += [y] * v
-            rows.append((freq, cum, lut))
-        assert sum(stext) == T and pos + sum(slen) == size
-        q = -(-m // 256)
-        for s in range(256):
-            nl = min(m, (s + 1) * q) - min(m, s * q)
-            data, pos = p[pos:pos + slen[s]], pos + slen[s]
-            if nl == 0:
-                assert not data and stext[s] == 0
-                continue
-            dec, prev, strand = _Rans(data), b"", []
-            for _ in range(nl):
-                ptok, cur, t = re.findall(rb"[0-9]+|[^0-9]+", prev), bytearray(), 0
-                while True:
-                    op = dec.get(rows[min(t, 15)])
-                    if op == 4:
-                        break
-                    pt = ptok[t] if t < len(ptok) else None
-                    if op == 0:
-                        assert pt is not None
-                        cur += pt
-                    elif op == 1:
-                        assert pt is not None and re.fullmatch(rb"0|[1-9][0-9]{0,8}", pt)
-                        d = dec.get(rows[16 + min(t, 7)])
-                        assert 1 <= d <= 255 and int(pt) + d <= 999999999
-                        cur += b"%d" % (int(pt) + d)
-                    elif op == 2:
-                        v = sum(dec.get(rows[24 + k]) << 8 * k for k in range(4))
-                        assert v <= 999999999
-                        cur += b"%d" % v
-                    else:
-                        ctx = 0
-                        while True:
-                            y = dec.get(rows[28 + ctx])
-                            if y == 0:
-                                break
-                            cur.append(y + 31)
-                            ctx = y
-                        assert ctx
-                    t += 1
-                strand.append(bytes(cur) + b"\n")
-                prev = bytes(cur)
-            strand = b"".join(strand)
-            assert len(strand) == stext[s]
-            assert dec.x == 1 << 23 and dec.k == len(data)         # the integrity check of the format
-            out.append(strand)
-    assert at == len(f)
-    text = b"".join(out)
-    assert len(text) == tbytes
-    return text, modes
 
 
 def test_every_case_round_trips_in_the_sanitizer_build(driver, cases):

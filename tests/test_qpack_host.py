@@ -12,6 +12,7 @@ import subprocess
 import pytest
 
 from tests import quality_cases as qc
+from tests.readme_decoders import quality_decode as readme_decode
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
@@ -24,7 +25,8 @@ DRIVER = r"""
 #include <string.h>
 // enc: cases [u32 n][u32 L][u32 rb][n * (L + 1) bytes] -> [u32 status][u32 bytes][the blocks, no file header].  Every buffer is a heap block of exactly its size:
 // a read or write past it is an AddressSanitizer report.  status: 1 a second run into a block of the exact size differs, 2 qv_block_decode does not return the text
-// dec: files [u32 bytes][the file] -> [u32 code][u32 text bytes][text]; code 0, a QV_E_* of the first bad block, 100 a prefix that leaves the file, 101 the header
+// dec: files [u32 bytes][the file] -> [u32 code][u32 block][u32 text bytes][text]; code 0, a QV_E_* of the first bad block, 100 a prefix that leaves the file, 101 the
+// header.  The payload and the lines of every block are heap blocks of exactly their declared sizes
 static uint32_t one_block(const uint8_t *lines, uint32_t m, uint32_t L, FILE *o, uint32_t *total)
 {
     uint32_t st = 0;
@@ -50,7 +52,7 @@ static uint32_t one_block(const uint8_t *lines, uint32_t m, uint32_t L, FILE *o,
 }
 static uint32_t one_file(const uint8_t *f, uint32_t nbytes, FILE *o)
 {
-    uint32_t code = 0, tb = 0;
+    uint32_t code = 0, tb = 0, block = 0;
     uint8_t *text = NULL;
     if (nbytes < 32 || !qv_magic_ok(f)) code = 101;
     else {
@@ -63,7 +65,7 @@ static uint32_t one_file(const uint8_t *f, uint32_t nbytes, FILE *o)
             memset(text, 0, tb);
             QvWork *W = (QvWork *)malloc(sizeof(QvWork));
             uint64_t at = 32;
-            for (uint64_t a = 0; a < n && !code; a += rb) {
+            for (uint64_t a = 0; a < n; a += rb, block++) {
                 const uint32_t m = n - a < rb ? (uint32_t)(n - a) : rb;
                 if (nbytes - at < 4) { code = 100; break; }
                 const uint32_t pb = qv_le32(f + at);
@@ -74,13 +76,14 @@ static uint32_t one_file(const uint8_t *f, uint32_t nbytes, FILE *o)
                 code = (uint32_t)qv_block_decode(payload, pb, m, L, *W, lines);
                 memcpy(text + a * (L + 1), lines, (size_t)m * (L + 1));
                 free(lines); free(payload);
+                if (code) break;
                 at += 4 + (uint64_t)pb;
             }
-            if (!code && at != nbytes) code = 100;
+            if (!code && at != nbytes) { code = 100; block--; }
             free(W);
         }
     }
-    fwrite(&code, 4, 1, o); fwrite(&tb, 4, 1, o);
+    fwrite(&code, 4, 1, o); fwrite(&block, 4, 1, o); fwrite(&tb, 4, 1, o);
     if (tb) fwrite(text, 1, tb, o);
     free(text);
     return code;
@@ -155,64 +158,6 @@ def _header(text, L, rb):
     return MAGIC + (struct.pack("<IIQQ", L, rb or _default_rb(L), n, 0) if n else bytes(24))
 
 
-# ------------------------------------------------------------------------------------------------ the decoder of the README, in plain Python
-def readme_decode(f):
-    """-> (text, modes).  Asserts the constraints the format text states: the table's, and every strand's end"""
-    assert f[:8] == MAGIC
-    L, RB, n, zero = struct.unpack_from("<IIQQ", f, 8)
-    assert zero == 0
-    at, out, modes = 32, [], []
-    for b0 in range(0, n, RB) if n else []:
-        m = min(n, b0 + RB) - b0
-        size, = struct.unpack_from("<I", f, at)
-        p = f[at + 4:at + 4 + size]
-        assert len(p) == size
-        at += 4 + size
-        modes.append(p[0])
-        if p[0] == 0:
-            assert size == 1 + m * L
-            out += [p[1 + i * L:1 + (i + 1) * L] + b"\n" for i in range(m)]
-            continue
-        assert p[0] == 1
-        A = p[1]
-        bits = int.from_bytes(p[2:14], "little")
-        syms = [33 + k for k in range(96) if bits >> k & 1]
-        assert len(syms) == A and 1 <= A <= 94 and syms[-1] <= 126
-        freq = [struct.unpack_from("<%dH" % A, p, 14 + 2 * A * r) for r in range(A + 1)]
-        cum = []
-        for row in freq:
-            assert sum(row) in (0, 4096)
-            c = [0]
-            for v in row:
-                c.append(c[-1] + v)
-            cum.append(c)
-        lens = struct.unpack_from("<256I", p, 14 + 2 * A * (A + 1))
-        pos = 14 + 2 * A * (A + 1) + 1024
-        assert pos + sum(lens) == size
-        lines = [None] * m
-        for s in range(256):
-            data, pos = p[pos:pos + lens[s]], pos + lens[s]
-            if s >= m:
-                assert not data
-                continue
-            x, k = int.from_bytes(data[:4], "big"), 4
-            for i in range(s, m, 256):
-                ctx, ln = A, bytearray()
-                for _ in range(L):
-                    slot = x & 4095
-                    y = next(y for y in range(A) if cum[ctx][y] <= slot < cum[ctx][y] + freq[ctx][y])
-                    assert freq[ctx][y] >= 1                       # an occurring pair
-                    x = freq[ctx][y] * (x >> 12) + slot - cum[ctx][y]
-                    while x < 1 << 23:
-                        x, k = x << 8 | data[k], k + 1
-                    ln.append(syms[y]); ctx = y
-                lines[i] = bytes(ln) + b"\n"
-            assert x == 1 << 23 and k == len(data)                 # the integrity check of the format
-        out += lines
-    assert at == len(f)
-    return b"".join(out), modes
-
-
 def test_every_case_round_trips_in_the_sanitizer_build(driver, cases):
     names = sorted(cases)
     out = driver("enc", b"".join(struct.pack("<III", len(cases[k][0]) // (cases[k][1] + 1), cases[k][1], cases[k][2]) + cases[k][0] for k in names))
@@ -257,8 +202,8 @@ def test_corruption_is_refused(driver):
     out = driver("dec", b"".join(struct.pack("<I", len(bad[k])) + bad[k] for k in names))          # the sanitizer build reports nothing on any of them
     at, undetected = 0, 0
     for k in names:
-        code, tb = struct.unpack_from("<II", out, at)
-        got, at = out[at + 8:at + 8 + tb], at + 8 + tb
+        code, block, tb = struct.unpack_from("<III", out, at)
+        got, at = out[at + 12:at + 12 + tb], at + 12 + tb
         try:
             back = harc_amd.qunpack_host(bad[k])
         except harc_amd.HarcAmdError as e:

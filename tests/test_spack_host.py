@@ -6,11 +6,11 @@ import os
 import shutil
 import struct
 import subprocess
-import zlib
 
 import pytest
 
 from tests import stream_cases as sc
+from tests.readme_decoders import stream_decode as readme_decode
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
@@ -24,7 +24,9 @@ DRIVER = r"""
 // enc: cases [u32 n][u32 B][n bytes] -> [u32 status][u32 bytes][the blocks, no file header].  Every buffer is a heap block of exactly its size: a read or write
 // past it is an AddressSanitizer report.  status: 1 a second run into a block of the exact size differs or a capacity one byte short is not refused,
 // 2 sv_block_decode does not return the text
-// dec: files [u32 bytes][the file] -> [u32 code][u32 text bytes][text]; code 0, an SV_E_* of the first bad block, 100 a prefix that leaves the file, 101 the header
+// dec: files [u32 bytes][the file] -> [u32 code][u32 block][u32 text bytes][text]; code 0, an SV_E_* of the first bad block, 100 a prefix that leaves the file, 101 the
+// header, 200 the strands decoded one by one answer otherwise.  The payload and the text of every block are heap blocks of exactly their declared sizes; once a coded
+// block's head, rows and strand sizes have passed, every strand is decoded again from a heap block of exactly its coded bytes into one of exactly its text bytes
 static uint32_t one_block(const uint8_t *bytes, uint32_t m, FILE *o, uint32_t *total)
 {
     uint32_t st = 0;
@@ -47,9 +49,29 @@ static uint32_t one_block(const uint8_t *bytes, uint32_t m, FILE *o, uint32_t *t
     free(back); free(payload); free(exact); free(big); free(slabs); free(W); free(text);
     return st;
 }
+// a coded block that sv_block_decode has taken as far as its strands with the answer `code` (W holds its rows and strand sizes): strand after strand on its own
+static uint32_t strands_alone(const uint8_t *pl, uint32_t pbytes, uint32_t m, SvWork &W, const uint8_t *text, uint32_t code)
+{
+    uint32_t hdr = 0, mode = 0, crc = 0, bad = SV_E_NONE, differs = 0;
+    if (sv_check_head(pl, pbytes, m, &mode, &crc, &hdr, W.rowoff)) return 200;
+    const uint8_t *src = pl + hdr;
+    for (uint32_t s = 0; s < SV_STRANDS; s++) {
+        const uint32_t n = sv_strand_bytes(m, s), len = W.len1[s];
+        uint8_t *in = (uint8_t *)malloc(len ? len : 1), *out = (uint8_t *)malloc(n ? n : 1);
+        memcpy(in, src, len);
+        uint32_t c;
+        const uint32_t e = sv_code(sv_strand_decode(in, len, mode == 1u ? W.t0 : W.t1, mode == 2u, out, n, W.crctab, &c));
+        bad = id_min(bad, e);
+        if (e == SV_E_NONE && memcmp(out, text + sv_strand_at(m, s), n)) differs = 1;
+        free(out); free(in);
+        src += len;
+    }
+    if (differs || (bad == SV_E_NONE ? code != 0 && code != SV_E_CRC : code != bad)) return 200;
+    return code;
+}
 static uint32_t one_file(const uint8_t *f, uint32_t nbytes, FILE *o)
 {
-    uint32_t code = 0, tb = 0;
+    uint32_t code = 0, tb = 0, block = 0;
     uint8_t *text = NULL;
     if (nbytes < 32 || !sv_magic_ok(f) || qv_le32(f + 12) || qv_le64(f + 24)) code = 101;
     else {
@@ -62,7 +84,7 @@ static uint32_t one_file(const uint8_t *f, uint32_t nbytes, FILE *o)
             memset(text, 0, tb);
             SvWork *W = (SvWork *)malloc(sizeof(SvWork));
             uint64_t at = 32;
-            for (uint64_t b = 0; b < sv_blocks(n, B) && !code; b++) {
+            for (uint64_t b = 0; b < sv_blocks(n, B); b++, block++) {
                 const uint32_t m = sv_block_text(n, B, b);
                 uint64_t pb = 0, t = 0;
                 uint8_t q[SV_PREFIX];
@@ -72,15 +94,17 @@ static uint32_t one_file(const uint8_t *f, uint32_t nbytes, FILE *o)
                 memcpy(payload, f + at + 4, pb);
                 memset(out, 0, m);
                 code = (uint32_t)sv_block_decode(payload, (uint32_t)pb, m, *W, out);
+                if (payload[0] && (code == 0 || code >= SV_E_TRUNC)) code = strands_alone(payload, (uint32_t)pb, m, *W, out, code);
                 memcpy(text + b * B, out, m);
                 free(out); free(payload);
+                if (code) break;
                 at += 4 + pb;
             }
-            if (!code && at != nbytes) code = 100;
+            if (!code && at != nbytes) { code = 100; block--; }
             free(W);
         }
     }
-    fwrite(&code, 4, 1, o); fwrite(&tb, 4, 1, o);
+    fwrite(&code, 4, 1, o); fwrite(&block, 4, 1, o); fwrite(&tb, 4, 1, o);
     if (tb) fwrite(text, 1, tb, o);
     free(text);
     return code;
@@ -149,87 +173,6 @@ def _header(text, B):
     return MAGIC + (struct.pack("<IIQQ", B or 1 << 22, 0, len(text), 0) if text else bytes(24))
 
 
-# ------------------------------------------------------------------------------------------------ the decoder of the README, in plain Python
-def _row(p, at):
-    """the row at p[at:]: 32 bytes of bitmap, the u16 frequencies of its symbols -> (freq[256], cum[256], the bytes it takes)"""
-    bits = int.from_bytes(p[at:at + 32], "little")
-    syms = [y for y in range(256) if bits >> y & 1]
-    assert syms
-    f = struct.unpack_from("<%dH" % len(syms), p, at + 32)
-    assert all(v >= 1 for v in f) and sum(f) == 4096
-    freq, cum, c = [0] * 256, [0] * 256, 0
-    for y in range(256):
-        cum[y] = c
-        if bits >> y & 1:
-            freq[y] = f[syms.index(y)]
-            c += freq[y]
-    return freq, cum, 32 + 2 * len(syms)
-
-
-def readme_decode(f):
-    """-> (text, modes).  Asserts the constraints the format text states"""
-    assert f[:8] == MAGIC
-    B, zero, n, zero2 = struct.unpack_from("<IIQQ", f, 8)
-    assert zero == 0 and zero2 == 0
-    if n == 0:
-        assert B == 0 and len(f) == 32
-        return b"", []
-    assert 1 <= B <= 1 << 30
-    at, out, modes = 32, [], []
-    for b0 in range(0, n, B):
-        m = min(n, b0 + B) - b0
-        size, = struct.unpack_from("<I", f, at)
-        p = f[at + 4:at + 4 + size]
-        assert len(p) == size
-        at += 4 + size
-        mode, tb, crc = struct.unpack_from("<BII", p, 0)
-        assert tb == m and mode in (0, 1, 2)
-        modes.append(mode)
-        if mode == 0:
-            assert size == 9 + m
-            text = p[9:]
-        else:
-            rows, pos = {}, 9
-            if mode == 1:
-                fr, cu, k = _row(p, pos)
-                rows, pos = {r: (fr, cu) for r in range(256)}, pos + k
-            else:
-                present = int.from_bytes(p[9:41], "little")
-                pos = 41
-                for r in range(256):
-                    if present >> r & 1:
-                        fr, cu, k = _row(p, pos)
-                        rows[r], pos = (fr, cu), pos + k
-            lens = struct.unpack_from("<256I", p, pos)
-            pos += 1024
-            assert pos + sum(lens) == size
-            q = (m + 255) // 256
-            text = bytearray()
-            for s in range(256):
-                data, pos = p[pos:pos + lens[s]], pos + lens[s]
-                ns = min(m, (s + 1) * q) - min(m, s * q)
-                if ns == 0:
-                    assert not data
-                    continue
-                assert len(data) >= 4
-                x, k, ctx = int.from_bytes(data[:4], "big"), 4, 0
-                for _ in range(ns):
-                    freq, cum = rows[ctx]                          # an absent row: a KeyError
-                    slot = x & 4095
-                    y = next(y for y in range(256) if freq[y] and cum[y] <= slot < cum[y] + freq[y])
-                    x = freq[y] * (x >> 12) + slot - cum[y]
-                    while x < 1 << 23:
-                        x, k = x << 8 | data[k], k + 1
-                    text.append(y)
-                    ctx = y if mode == 2 else 0
-                assert x == 1 << 23 and k == len(data)             # the end of a strand
-            text = bytes(text)
-        assert len(text) == m and zlib.crc32(text) == crc
-        out.append(text)
-    assert at == len(f)
-    return b"".join(out), modes
-
-
 def test_every_case_round_trips_in_the_sanitizer_build(driver, cases):
     import harc_amd
     names = sorted(cases)
@@ -278,8 +221,8 @@ def test_corruption_is_refused(driver):
     out = driver("dec", b"".join(struct.pack("<I", len(blobs[k])) + blobs[k] for k in names))       # the sanitizer build reports nothing on any of them
     at = 0
     for k in names:
-        code, tb = struct.unpack_from("<II", out, at)
-        at += 8 + tb
+        code, block, tb = struct.unpack_from("<III", out, at)
+        at += 12 + tb
         assert code != 0, k                                        # every single-bit flip too: the CRC-32 leaves none undetected
         with pytest.raises(harc_amd.HarcAmdError) as e:
             harc_amd.sunpack_host(blobs[k])
